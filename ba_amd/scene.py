@@ -12,6 +12,9 @@ trajectory at height -1.5 m, pixel noise sigma 1.5, and the IMU noise constants 
 Poses are 7-vectors [tx,ty,tz,qx,qy,qz,qw]; the camera looks along +z of the pose
 frame (T_vs = identity), x right, y down; world z points down.
 """
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 
 CAM_PARAMS = np.array([198.969, 198.1284, 329.9368, 240.1017])
@@ -131,9 +134,33 @@ class Scene:
     pass
 
 
+def random_order_head(rng, m, ncol, k, block=8192):
+    """np.argsort(rng.random((m, ncol)), axis=1)[:, :k] — the first k columns of a random order
+    per row — with the same draws from `rng`, without sorting whole rows.  Rows are drawn in
+    blocks (row-major, so the stream is the same as one (m, ncol) draw); the k smallest values
+    of a row are partitioned out and sorted.  A row in which two of them are equal, or the
+    k-th equals the next, takes np.argsort of the whole row, so ties order exactly as before."""
+    if k >= ncol:
+        return np.argsort(rng.random((m, ncol)), axis=1)[:, :k]
+    out = np.empty((m, k), dtype=np.intp)
+    for r0 in range(0, m, block):
+        r = rng.random((min(block, m - r0), ncol))
+        part = np.argpartition(r, k, axis=1)[:, :k + 1]
+        val = np.take_along_axis(r, part, 1)
+        o = np.argsort(val[:, :k], axis=1)
+        head = np.take_along_axis(part[:, :k], o, 1)
+        hv = np.take_along_axis(val[:, :k], o, 1)
+        tie = (hv[:, 1:] == hv[:, :-1]).any(1) | (hv[:, -1] == val[:, k])
+        if tie.any():
+            head[tie] = np.argsort(r[tie], axis=1)[:, :k]
+        out[r0:r0 + len(r)] = head
+    return out
+
+
 def make_scene(num_poses, num_landmarks, obs_per_landmark=10, lm_dim=1, seed=0,
                pixel_sigma=1.5, outlier_frac=0.02, trans_sigma=0.05, rot_sigma=0.01,
-               depth_sigma=0.05, lm_range=None, window=None, chunk=200000, anchors=None, roll_amp=0.0):
+               depth_sigma=0.05, lm_range=None, window=None, chunk=200000, anchors=None, roll_amp=0.0,
+               threads=None):
     """Build a scene with exactly `obs_per_landmark` ACCEPTED projection residuals per landmark.
 
     lm_dim == 1 (inverse depth): the first chosen pose is the landmark's reference pose; its
@@ -144,6 +171,9 @@ def make_scene(num_poses, num_landmarks, obs_per_landmark=10, lm_dim=1, seed=0,
     `lm_range` restricts generation to landmark ids [lo, hi) of the same global scene —
     every landmark is drawn from its own counter-based stream, so shards of one scene can
     be generated independently (multi-GPU landmark sharding).
+
+    Chunks of `chunk` landmarks have streams of their own and are generated on up to `threads`
+    threads (default: one per chunk, at most 8); the scene does not depend on the count.
     """
     P, Ltot, k = int(num_poses), int(num_landmarks), int(obs_per_landmark)
     lo, hi = (0, Ltot) if lm_range is None else lm_range
@@ -180,7 +210,8 @@ def make_scene(num_poses, num_landmarks, obs_per_landmark=10, lm_dim=1, seed=0,
     ref_pose = np.empty(L, dtype=np.uint32)
     sel_poses = np.empty((L, nsel), dtype=np.uint32)
     z_all = np.empty((L, nsel, 2))
-    for c0 in range(0, L, chunk):
+
+    def gen_chunk(c0):
         c1 = min(L, c0 + chunk)
         n = c1 - c0
         # one stream per chunk start (chunks are aligned to the global landmark index)
@@ -197,7 +228,7 @@ def make_scene(num_poses, num_landmarks, obs_per_landmark=10, lm_dim=1, seed=0,
                             (uv[:, 1] - CAM_PARAMS[3]) / CAM_PARAMS[1], np.ones(m)], -1)
             pts = ap[:, :3] + np.einsum('nij,nj->ni', quat_to_rot(ap[:, 3:7]), ray * depth[:, None])
             # candidate poses: distinct offsets around the anchor
-            offs = np.argsort(rng.random((m, 2 * window)), axis=1)[:, :ncand] - window
+            offs = random_order_head(rng, m, 2 * window, ncand) - window
             offs = np.where(offs >= 0, offs + 1, offs)  # skip 0 (the anchor itself)
             cand = (anchor[:, None] + offs) % P
             cuv, cz = project(gt_poses[cand], pts[:, None, :])
@@ -229,6 +260,17 @@ def make_scene(num_poses, num_landmarks, obs_per_landmark=10, lm_dim=1, seed=0,
             attempt += 1
             if attempt > 200:
                 raise RuntimeError("scene generation did not converge")
+
+    # every chunk writes its own rows of x_w, ref_pose, sel_poses and z_all; numpy releases the
+    # GIL in the random draws, the partitions and the array arithmetic
+    starts = range(0, L, chunk)
+    nthr = min(len(starts), threads or 8, os.cpu_count() or 1)
+    if nthr > 1:
+        with ThreadPoolExecutor(nthr) as ex:
+            list(ex.map(gen_chunk, starts))
+    else:
+        for c0 in starts:
+            gen_chunk(c0)
     # measurement noise + gross outliers
     rng_n = np.random.Generator(np.random.PCG64([seed, 0xBA5E, 3, lo]))
     z_all += rng_n.normal(0.0, pixel_sigma, z_all.shape)

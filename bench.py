@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Gauss-Newton iterations/sec of the MI355X BundleAdjuster path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4]
+    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--full] [--dump-outputs DIR]
 
 A "step" is one full iteration of ba::BundleAdjuster::Solve
 (/root/reference/src/BundleAdjuster.cpp:298-663) on a synthetic scene already resident in
@@ -27,9 +27,17 @@ owners of S's column panels, every panel is factorised by its owner and broadcas
 applies the trailing updates to the panels it owns; the right-hand side and a few
 scalars/histograms are all-reduced ("scaling": "strong").
 
-Rank 0 prints one JSON line with the driver's contract keys plus `roofline` (dominant kernel,
-measured live with HIP events on the stream it runs on) and `cpu_baseline` (the oracle — a CPU
-restatement of the reference — timed on the host cores on a bounded sample of the workload).
+Rank 0 prints one JSON line with the driver's contract keys.  A plain run sets up, warms up, times
+the steps and prints; everything else the benchmark measures is behind `--full`: `roofline` and
+the per-kernel figures (dominant kernel, measured live with HIP events on the stream it runs on,
+during the timed steps), the `api_solve_ms` pass of configs 1 / 3, and `cpu_baseline` (the
+oracle — a CPU restatement of the reference — timed on the host cores on a bounded sample of the
+workload).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step left for a caller as
+float64 `DIR/<name>.npy`: poses, landmarks, the step of the last iteration and its error (rank 0:
+all poses, its own landmark shard).  The scene is seeded, so the same arguments give the same
+inputs in every run.  Above 64 MB in all, every array keeps the same fixed, seeded sample of rows.
 """
 import argparse
 import glob
@@ -252,6 +260,21 @@ def newest_pmc(config):
         return {}, None
 
 
+def dump_outputs(out_dir, arrays, budget=63 << 20):
+    """Write every array as out_dir/<name>.npy (float64).  Above `budget` bytes in all (64 MB less
+    room for the headers), every array with more than one row keeps the same fraction of its rows:
+    a fixed, seeded, sorted sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * budget // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs written to %s" % out_dir)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -271,7 +294,16 @@ def main():
                     help="after the timed region, run the two rocprofv3 --pmc passes of this configuration as child "
                          "processes (scratch/pmc_traffic.py; minutes) and report THEIR traffic instead of the committed summary")
     ap.add_argument("--no-api", action="store_true", help="skip the api_solve_ms pass of configs 1 / 3")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel and roofline figures "
+                         "(profiling of the timed steps), the api_solve_ms pass and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.live_pmc:
+        args.full = True   # the live PMC traffic goes into the --full figures
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
     if args.poses is None:
         args.poses = cfg["P"]
@@ -329,6 +361,7 @@ def main():
         t_setup = time.perf_counter()
         eng, _ = build_engine(sc, lm_dim, lo, hi, local_rank if world > 1 else 0, ids=ids)
         t_setup = time.perf_counter() - t_setup  # host -> device uploads + structure build (once per graph)
+        n_lm = hi - lo if ids is None else len(ids)   # this engine's landmarks
         if world > 1 and comm_mode == "native":
             # native RCCL inside the engine: all-reduce, reduce-scatter of S to the panel owners,
             # per-panel broadcast in stream order (BA_HIP_NO_DIST_SOLVE=1 keeps the replicated solve)
@@ -345,7 +378,8 @@ def main():
         for _ in range(args.warmup):
             gn_step(eng)
         log("warmup done")
-        eng.set_profiling(True)
+        if args.full:
+            eng.set_profiling(True)
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -354,18 +388,24 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         log("timed region done: %.1f ms / step" % (1e3 * elapsed / args.steps))
-        ks = eng.kernel_stats()
-        timers = eng.get_timers()
-        stats = eng.structure_stats() if world == 1 else {}
-        eng.set_profiling(False)
+        if args.full:
+            ks = eng.kernel_stats()
+            timers = eng.get_timers()
+            stats = eng.structure_stats() if world == 1 else {}
+            eng.set_profiling(False)
         n = eng.num_pose_params()
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        eng.end_solve()
+        eng.end_solve()   # landmarks back in world coordinates, as a caller reads them
+        if args.dump_outputs and rank == 0:
+            step_p, step_l = eng.get_step()
+            dump_outputs(args.dump_outputs, {
+                "poses": eng.get_poses(P)[0], "landmarks": eng.get_landmarks(n_lm),
+                "step_poses": step_p[:n], "step_landmarks": step_l, "error": np.array([err])})
         eng.close()
-        if world == 1 and not args.no_api:
+        if world == 1 and args.full and not args.no_api:
             # the same scene through ba::BundleAdjuster::Solve(1): first call = upload + structure
             # build + one iteration; later calls on the warm object must not rebuild anything
             h = build_adjuster(cfg, sc, lm_dim)
@@ -409,7 +449,8 @@ def main():
         for _ in range(max(args.warmup - 1, 0)):
             h.Solve(1)
         ev = h.engine()
-        ev.set_profiling(True)
+        if args.full:
+            ev.set_profiling(True)
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -424,17 +465,60 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         log("timed region done: %.1f ms / step" % (1e3 * elapsed / args.steps))
-        ks = ev.kernel_stats()
-        timers = ev.get_timers()
-        stats = ev.structure_stats() if world == 1 else {}
-        ev.set_profiling(False)
+        if args.full:
+            ks = ev.kernel_stats()
+            timers = ev.get_timers()
+            stats = ev.structure_stats() if world == 1 else {}
+            ev.set_profiling(False)
         n = ev.num_pose_params()
+        if args.dump_outputs and rank == 0:
+            t_wp, v_w, b = h.poses()
+            dump_outputs(args.dump_outputs, {
+                "poses": t_wp, "velocities": v_w, "biases": b, "landmarks": h.landmarks(),
+                "step_poses": h.delta_p(), "step_landmarks": h.delta_l(), "error": np.array([err])})
         api_ms = 1e3 * elapsed / args.steps
         t_setup -= api_ms * 1e-3
 
     if rank == 0:
         O = L * K
         ms = 1e3 * elapsed / args.steps
+        out = {
+            "metric": "Gauss-Newton iterations/sec",
+            "value": args.steps / elapsed,
+            "unit": "iterations/sec",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": "BASELINE.json configs[%d]: %d poses / %d landmarks / %d reprojection residuals%s%s, "
+                                   "%s, LmSize=%d, PoseSize=%d, %s%s"
+                                   % (args.config, P, L, O, " + %d IMU pre-integration residuals" % (P - 1) if cfg["imu"] else "",
+                                      " + unary priors every 100th pose + %d binary odometry constraints" % (P - 1) if cfg["priors"] else "",
+                                      ("VARIANT: FOV camera w = %g" % args.fov_w) if args.fov_w else "pinhole",
+                                      lm_dim, cfg["D"], "dogleg trust region" if cfg["dogleg"] else "Gauss-Newton (no dogleg)",
+                                      "" if cfg["imu"] else ", 2 anchor poses inactive"),
+                       "poses": P, "landmarks": L, "residuals": O, "reduced_system_n": n,
+                       "driver": ("ba::BundleAdjuster::Solve(1) per step on a warm object (C++ API path, include/ba_capi.h)"
+                                  if api_driver else "phase calls of the C-ABI (include/ba_hip.h)"),
+                       "parallelism": ("landmark-sharded x%d (all poses on every rank%s), %s; collectives: %s"
+                                       % (world, ", pose-pose residuals on rank 0" if api_driver else "",
+                                          "replicated LDL^T (all-reduce of S)" if (os.environ.get("BA_BENCH_REPLICATED_SOLVE") or (api_driver and comm_mode != "native"))
+                                          else "sparse exchange of S onto tile-block owners (shards along the trajectory), distributed LDL^T (square broadcast + point-to-point block rows, DESIGN.md 6a)",
+                                          "engine-owned RCCL communicator" + (" (ba::BundleAdjuster::SetCommunicator)" if api_driver else "")
+                                          if comm_mode == "native" else "torch.distributed hooks (%s)" % backend))
+                       if world > 1 else "single GPU"},
+            # one-off per graph: PCIe uploads of the scene + host-side structure build (gather
+            # lists, tile pattern); NOT part of `value` (inputs are resident when the timed region starts)
+            "setup_s_rank0": round(t_setup, 3),
+            "accepted_steps": accepted,
+            "final_error": err,
+        }
+    if rank == 0 and args.full:
         # dominant kernel: the trailing update of the dense LDL^T factorisation (FP64 MFMA);
         # timed with HIP events on the stream it is launched on (the engine's second stream)
         syrk_tf = ks.syrk_flops / (ks.syrk_ms * 1e-3) / 1e12 if ks.syrk_ms > 0 else 0.0
@@ -500,36 +584,7 @@ def main():
         def pmc_raw(name):
             e = pmc_entry(name)
             return (e.get("FETCH_SIZE_KB_per_launch", 0.0) + e.get("WRITE_SIZE_KB_per_launch", 0.0)) * 1024.0 if e else None
-        out = {
-            "metric": "Gauss-Newton iterations/sec",
-            "value": args.steps / elapsed,
-            "unit": "iterations/sec",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE.json configs[%d]: %d poses / %d landmarks / %d reprojection residuals%s%s, "
-                                   "%s, LmSize=%d, PoseSize=%d, %s%s"
-                                   % (args.config, P, L, O, " + %d IMU pre-integration residuals" % (P - 1) if cfg["imu"] else "",
-                                      " + unary priors every 100th pose + %d binary odometry constraints" % (P - 1) if cfg["priors"] else "",
-                                      ("VARIANT: FOV camera w = %g" % args.fov_w) if args.fov_w else "pinhole",
-                                      lm_dim, cfg["D"], "dogleg trust region" if cfg["dogleg"] else "Gauss-Newton (no dogleg)",
-                                      "" if cfg["imu"] else ", 2 anchor poses inactive"),
-                       "poses": P, "landmarks": L, "residuals": O, "reduced_system_n": n,
-                       "driver": ("ba::BundleAdjuster::Solve(1) per step on a warm object (C++ API path, include/ba_capi.h)"
-                                  if api_driver else "phase calls of the C-ABI (include/ba_hip.h)"),
-                       "parallelism": ("landmark-sharded x%d (all poses on every rank%s), %s; collectives: %s"
-                                       % (world, ", pose-pose residuals on rank 0" if api_driver else "",
-                                          "replicated LDL^T (all-reduce of S)" if (os.environ.get("BA_BENCH_REPLICATED_SOLVE") or (api_driver and comm_mode != "native"))
-                                          else "sparse exchange of S onto tile-block owners (shards along the trajectory), distributed LDL^T (square broadcast + point-to-point block rows, DESIGN.md 6a)",
-                                          "engine-owned RCCL communicator" + (" (ba::BundleAdjuster::SetCommunicator)" if api_driver else "")
-                                          if comm_mode == "native" else "torch.distributed hooks (%s)" % backend))
-                       if world > 1 else "single GPU"},
+        out.update({
             "roofline": {"bound": "mfma", "kernel": "%s (dense LDL^T trailing update, v_mfma_f64_16x16x4_f64; the look-ahead's bulk launches)" % bulk_kernel,
                          "achieved": syrk_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
                          "frac": syrk_tf / FP64_MFMA_PEAK_TF, "traffic": pmc_bytes("bae::" + bulk_kernel),
@@ -565,12 +620,7 @@ def main():
                                   "pmc_raw_bytes": pmc_raw("bae::k_pose_blocks")}},
             "phase_ms_last_step": {k: round(v, 4) for k, v in timers.items()},
             "structure": stats,
-            # one-off per graph: PCIe uploads of the scene + host-side structure build (gather
-            # lists, tile pattern); NOT part of `value` (inputs are resident when the timed region starts)
-            "setup_s_rank0": round(t_setup, 3),
-            "accepted_steps": accepted,
-            "final_error": err,
-        }
+        })
         if cfg["imu"] and ks.imu_launches:
             # per residual: two pose states and the samples in; 3 blocks of 15x15, two gradients, two
             # Jacobians, the information matrix out (one lane per residual: latency-bound, not HBM-bound)
@@ -634,6 +684,7 @@ def main():
                 out["cpu_baseline"]["nproc"] = ncpu
             except OSError:
                 pass
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -10,7 +10,7 @@ cfgs=${@:-3 1 2 4}
 for c in $cfgs; do
   case $mode in
     bench)
-      timeout -k 10 420 python $ROOT/bench.py --config $c > $OUT/r03_bench_cfg$c.json 2> $OUT/r03_bench_cfg$c.err || exit 1
+      timeout -k 10 420 python $ROOT/bench.py --full --config $c > $OUT/r03_bench_cfg$c.json 2> $OUT/r03_bench_cfg$c.err || exit 1
       tail -2 $OUT/r03_bench_cfg$c.err ;;
     stats)
       (cd /tmp && export TMPDIR=/tmp && rm -rf $OUT/prof_cfg$c && timeout -k 10 420 rocprofv3 --kernel-trace --stats -d $OUT/prof_cfg$c -o cfg$c -- \

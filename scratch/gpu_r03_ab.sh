@@ -14,7 +14,7 @@ for round in 1 2; do
       p6) lib=scratch/ab/p6/libba_hip.so; dbg=;;
       new_nofillskip) lib=ba_amd/lib/libba_hip.so; dbg=1;;
     esac
-    BA_AMD_LIB=$lib BA_BENCH_NO_FILL_SKIP=$dbg timeout -k 10 200 python bench.py --config 3 --no-cpu-baseline --no-api --steps 4 > $OUT/r03_ab_${v}_$round.json 2> $OUT/r03_ab_${v}_$round.err || { tail -5 $OUT/r03_ab_${v}_$round.err; exit 1; }
+    BA_AMD_LIB=$lib BA_BENCH_NO_FILL_SKIP=$dbg timeout -k 10 200 python bench.py --full --config 3 --no-cpu-baseline --no-api --steps 4 > $OUT/r03_ab_${v}_$round.json 2> $OUT/r03_ab_${v}_$round.err || { tail -5 $OUT/r03_ab_${v}_$round.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$OUT/r03_ab_${v}_$round.json')); p=d['phase_ms_last_step']; print('$v $round', round(d['ms_per_step'],1), 'solve', round(p['solve'],1), 'j_eval', round(p['j_evaluation'],2), 'jtj', round(p['jtj_schur'],2), 'bulk TF', round(d['roofline']['achieved'],2), {k: round(x['avg_launch_us']) for k,x in d['hbm_kernels'].items()})"
   done

@@ -14,7 +14,7 @@ for v in cur fake cur_nolook fake_nolook; do
     fake_nolook) lib=scratch/ab/fake/libba_hip.so; nl=1;;
   esac
   if [ -n "$nl" ]; then export BA_HIP_NO_LOOKAHEAD=1; else unset BA_HIP_NO_LOOKAHEAD; fi
-  BA_BENCH_IGNORE_RC=1 BA_AMD_LIB=$lib timeout -k 10 200 python bench.py --config 3 --no-cpu-baseline --no-api --steps 3 > $OUT/r03_ceil_$v.json 2> $OUT/r03_ceil_$v.err || { tail -5 $OUT/r03_ceil_$v.err; exit 1; }
+  BA_BENCH_IGNORE_RC=1 BA_AMD_LIB=$lib timeout -k 10 200 python bench.py --full --config 3 --no-cpu-baseline --no-api --steps 3 > $OUT/r03_ceil_$v.json 2> $OUT/r03_ceil_$v.err || { tail -5 $OUT/r03_ceil_$v.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/r03_ceil_$v.json')); p=d['phase_ms_last_step']; print('$v', round(d['ms_per_step'],1), 'solve', round(p['solve'],1), 'bulk TF', round(d['roofline']['achieved'],2), 'avg launch us', round(d['roofline']['avg_launch_us']))"
 done

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 for m in look nolook; do
   if [ $m = nolook ]; then export BA_HIP_NO_LOOKAHEAD=1; fi
-  (cd $ROOT && timeout -k 10 200 python bench.py --config 1 --no-cpu-baseline --no-api --steps 20 > $OUT/r03_c1_$m.json 2> $OUT/r03_c1_$m.err) || exit 1
+  (cd $ROOT && timeout -k 10 200 python bench.py --full --config 1 --no-cpu-baseline --no-api --steps 20 > $OUT/r03_c1_$m.json 2> $OUT/r03_c1_$m.err) || exit 1
   python3 -c "
 import json; d=json.loads(open('$OUT/r03_c1_$m.json').read().strip().splitlines()[-1]); p=d['phase_ms_last_step']; print('$m', round(d['ms_per_step'],3), 'solve', round(p['solve'],3))"
   (cd /tmp && export TMPDIR=/tmp && rm -rf $OUT/c1prof_$m && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/c1prof_$m -o f -- \

@@ -6,8 +6,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 for c in 2 4; do
-  timeout -k 10 300 python $ROOT/bench.py --config $c --no-cpu-baseline --steps 2 > $OUT/r03_imu_ab_cfg${c}_concurrent.json 2> $OUT/r03_imu_ab_cfg${c}_concurrent.err || exit 1
-  BA_HIP_IMU_SERIAL=1 timeout -k 10 300 python $ROOT/bench.py --config $c --no-cpu-baseline --steps 2 > $OUT/r03_imu_ab_cfg${c}_serial.json 2> $OUT/r03_imu_ab_cfg${c}_serial.err || exit 1
+  timeout -k 10 300 python $ROOT/bench.py --full --config $c --no-cpu-baseline --steps 2 > $OUT/r03_imu_ab_cfg${c}_concurrent.json 2> $OUT/r03_imu_ab_cfg${c}_concurrent.err || exit 1
+  BA_HIP_IMU_SERIAL=1 timeout -k 10 300 python $ROOT/bench.py --full --config $c --no-cpu-baseline --steps 2 > $OUT/r03_imu_ab_cfg${c}_serial.json 2> $OUT/r03_imu_ab_cfg${c}_serial.err || exit 1
 done
 python3 - <<PY
 import json

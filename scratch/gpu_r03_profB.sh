@@ -9,5 +9,5 @@ rc=$?
 tail -6 $OUT/r03_pytest_fullsize_dist.log
 [ $rc -eq 0 ] || exit $rc
 bash scratch/gpu_profile_round.sh bench 2 4 || exit 1
-timeout -k 10 300 python bench.py --config 3 --no-cpu-baseline > $OUT/r03_bench_cfg3_again.json 2> $OUT/r03_bench_cfg3_again.err || exit 1
+timeout -k 10 300 python bench.py --full --config 3 --no-cpu-baseline > $OUT/r03_bench_cfg3_again.json 2> $OUT/r03_bench_cfg3_again.err || exit 1
 tail -3 $OUT/r03_bench_cfg3_again.err

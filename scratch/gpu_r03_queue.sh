@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out
 cd $ROOT
 for round in 1 2; do
   for q in 0 1; do
-    BA_HIP_BULK_QUEUE=$q timeout -k 10 200 python bench.py --config 3 --no-cpu-baseline --no-api --steps 4 > $OUT/r03_queue_${q}_$round.json 2> $OUT/r03_queue_${q}_$round.err || { tail -5 $OUT/r03_queue_${q}_$round.err; exit 1; }
+    BA_HIP_BULK_QUEUE=$q timeout -k 10 200 python bench.py --full --config 3 --no-cpu-baseline --no-api --steps 4 > $OUT/r03_queue_${q}_$round.json 2> $OUT/r03_queue_${q}_$round.err || { tail -5 $OUT/r03_queue_${q}_$round.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$OUT/r03_queue_${q}_$round.json').read().strip().splitlines()[-1]); p=d['phase_ms_last_step']; print('queue=$q round $round', round(d['ms_per_step'],1), 'solve', round(p['solve'],1), 'bulk TF', round(d['roofline']['achieved'],2), 'final', d.get('final_error', d.get('error'))) "
   done

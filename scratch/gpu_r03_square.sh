@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $ROOT
 for round in 1 2; do
   for v in 0 1; do
-    BA_HIP_SQUARE=$v timeout -k 10 200 python bench.py --config 1 --no-cpu-baseline --no-api --steps 20 > $OUT/r03_sq_${v}_$round.json 2> $OUT/r03_sq_${v}_$round.err || { tail -5 $OUT/r03_sq_${v}_$round.err; exit 1; }
+    BA_HIP_SQUARE=$v timeout -k 10 200 python bench.py --full --config 1 --no-cpu-baseline --no-api --steps 20 > $OUT/r03_sq_${v}_$round.json 2> $OUT/r03_sq_${v}_$round.err || { tail -5 $OUT/r03_sq_${v}_$round.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$OUT/r03_sq_${v}_$round.json').read().strip().splitlines()[-1]); p=d['phase_ms_last_step']; print('square=$v round $round', round(d['ms_per_step'],3), 'solve', round(p['solve'],3))"
   done

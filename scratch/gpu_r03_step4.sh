@@ -10,7 +10,7 @@ rc=$?
 tail -6 $OUT/r03_pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
 for k in 16 24; do
-  BA_HIP_KOUT=$k timeout -k 10 300 python bench.py --config 3 --no-cpu-baseline --no-api --steps 4 > $OUT/r03_kout$k.json 2> $OUT/r03_kout$k.err || { tail -5 $OUT/r03_kout$k.err; exit 1; }
+  BA_HIP_KOUT=$k timeout -k 10 300 python bench.py --full --config 3 --no-cpu-baseline --no-api --steps 4 > $OUT/r03_kout$k.json 2> $OUT/r03_kout$k.err || { tail -5 $OUT/r03_kout$k.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/r03_kout$k.json')); print('KOUT $k', round(d['ms_per_step'],1), 'ms  bulk', round(d['roofline']['achieved'],2), 'TF', d['phase_ms_last_step'], d['hbm_group'])"
 done
