@@ -13,6 +13,7 @@
 //                                           BundleAdjuster.h:758-759) on a ba::FovCamera whose five parameters
 //                                           (fx, fy, u0, v0, w) start 2-4 % off
 //   visual_ba_demo --ranks N --rank R --comm-id-file F [--device D]
+//   visual_ba_demo --ordering auto          Options::pose_ordering = Auto: prints the ordering statistics
 //                                           one process per GPU: every process holds all poses and the landmarks
 //                                           l with l mod N == R; the class joins the engine-owned RCCL communicator
 //                                           (SetCommunicator; rank 0 writes the 128-byte id to F, the others wait for
@@ -28,7 +29,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -57,6 +58,7 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   ba::Options<double> options;  // reference defaults: dogleg, robust norm, auto regularisation
   options.error_change_threshold = 1e-5;
   options.device = shard.device;
+  if (shard.order_auto) options.pose_ordering = ba::PoseOrdering::Auto;
   if (!shard.id_file.empty()) {
     unsigned char id[128];
     if (!exchange_id(shard, id)) { std::printf("communicator id exchange failed\n"); return 3; }
@@ -172,6 +174,13 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   }
   std::printf("poses %u landmarks %u residuals %d\n", adjuster.GetNumPoses(), adjuster.GetNumLandmarks(), n_res);
   adjuster.Solve(1);
+  if (shard.order_auto) {
+    ba_hip_ordering_stats os;
+    if (ba_hip_get_pose_ordering(adjuster.engine(), nullptr, &os) != 0) { std::printf("no pose ordering\n"); return 2; }
+    std::printf("pose ordering: mode %d candidate %d group %u groups %u tile products %llu -> %llu (%.2f ms host, %.2f ms device)\n",
+                os.mode, os.candidate, os.group_size, os.num_groups, (unsigned long long)os.tile_products_natural,
+                (unsigned long long)os.tile_products_chosen, os.host_ms, os.device_ms);
+  }
   if (!shard.id_file.empty())
     std::printf("rank %d of %d on device %d: reduced solve %s\n", shard.rank, shard.ranks, shard.device,
                 adjuster.SolveIsDistributed() ? "distributed over the communicator" : "replicated");
@@ -222,6 +231,7 @@ int main(int argc, char** argv) {
     else if (std::strcmp(argv[i], "--rank") == 0) shard.rank = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--device") == 0) shard.device = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--comm-id-file") == 0) shard.id_file = argv[i + 1];
+    else if (std::strcmp(argv[i], "--ordering") == 0) shard.order_auto = std::strcmp(argv[i + 1], "auto") == 0;
   }
   if (shard.ranks < 1 || shard.rank < 0 || shard.rank >= shard.ranks) { std::printf("bad --rank / --ranks\n"); return 3; }
   return run<ba::BundleAdjuster<double, 1, 6, 0>>(0, shard);  // VisualBundleAdjuster<double>

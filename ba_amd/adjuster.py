@@ -39,7 +39,7 @@ class BaOptions(C.Structure):
                 ("use_robust_norm_for_inertial_residuals", C.c_int32),
                 ("write_reduced_camera_matrix", C.c_int32),
                 ("device", C.c_int32), ("factorization_pivot_tolerance", C.c_double),
-                ("calculate_calibration_marginals", C.c_int32), ("reserved", C.c_int32)]
+                ("calculate_calibration_marginals", C.c_int32), ("pose_ordering", C.c_int32)]
 
 
 class BaSummary(C.Structure):

@@ -75,6 +75,7 @@ struct Impl : Iface {
     opt.device = o->device;
     opt.factorization_pivot_tolerance = o->factorization_pivot_tolerance;
     opt.calculate_calibration_marginals = o->calculate_calibration_marginals != 0;
+    opt.pose_ordering = o->pose_ordering == 1 ? ba::PoseOrdering::Auto : ba::PoseOrdering::Natural;
     ba.Init(opt);
   }
   void set_gravity(const double* g) override { ba.SetGravity(ba::Vector3t({g[0], g[1], g[2]})); }
@@ -262,7 +263,7 @@ void ba_default_options(ba_options* o) {
   o->device = d.device;
   o->factorization_pivot_tolerance = d.factorization_pivot_tolerance;
   o->calculate_calibration_marginals = d.calculate_calibration_marginals;
-  o->reserved = 0;
+  o->pose_ordering = d.pose_ordering == ba::PoseOrdering::Auto ? 1 : 0;
 }
 ba_adjuster* ba_adjuster_create(int lm_dim, int pose_dim) { return ba_adjuster_create_calib(lm_dim, pose_dim, 0, 0); }
 ba_adjuster* ba_adjuster_create_calib(int lm_dim, int pose_dim, int calib_size, int do_tvs) {

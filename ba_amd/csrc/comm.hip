@@ -191,6 +191,8 @@ int ba_hip_comm_unique_id(void* id128) {
 int ba_hip_comm_init(ba_hip_engine* h, const void* id128, int rank, int nranks) {
   Engine* e = reinterpret_cast<Engine*>(h);
   if (!id128 || nranks < 1 || rank < 0 || rank >= nranks) return e->fail_msg("ba_hip_comm_init: bad arguments");
+  if (e->order_mode != kOrderNatural)
+    return e->fail_msg("the communicator needs natural pose order (ba_hip_set_pose_ordering is set)");
   RcclApi* a = rccl();
   if (!a) return e->fail_msg("ba_hip_comm_init: librccl could not be loaded");
   BAE_HIP(hipSetDevice(e->device));

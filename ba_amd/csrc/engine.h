@@ -7,6 +7,7 @@
 
 #include "../../include/ba_hip.h"
 #include "structure.h"
+#include "ordering.h"
 #include "dist_plan.h"
 
 namespace bae {
@@ -78,6 +79,15 @@ struct Engine {
   void* allreduce_ctx = nullptr;
   ba_hip_collective_fn coll = nullptr;   // broadcast / reduce-scatter: distributed reduced solve
   void* coll_ctx = nullptr;
+  // pose ordering (ba_hip_set_pose_ordering, ordering.h): mode for the next finalize, the caller's permutation
+  // (USER), and what the last finalize applied: opt_of_natural[natural opt index] = factorised index (empty:
+  // identity), the group graph it was chosen from, its statistics
+  int order_mode = kOrderNatural;
+  std::vector<uint32_t> order_user;
+  std::vector<uint32_t> opt_of_natural;
+  std::vector<uint32_t> group_ptr, group_adj;
+  ba_hip_ordering_stats order_stats = {};
+  bool ordering_refused() const { return allreduce || coll || comm; }
   int rank = 0, nranks = 1;
   // native RCCL communicator (ba_hip_comm_init, comm.hip); comm_force: run the sharded code paths
   // even with one rank (exercises the RCCL calls on a one-GPU box)
@@ -300,6 +310,11 @@ int build_tile_desc(Engine* e);   // k_reduce.hip
 int dist_assembly_tiles(Engine* e, std::vector<uint8_t>* need);  // k_chol.hip
 // the static lists built on the device (structure_dev.hip); same contents as structure.h's host builder
 int build_lists_device(Engine* e, const std::function<void(const char*)>& stage);
+// Pose ordering of ba_hip_finalize (engine.hip): with e->st.pose_opt holding the natural opt ids, builds the
+// group graph from `proj_edges` (group pairs that share a landmark, (a << 32 | b)) and the pose-pose residuals,
+// chooses the permutation (AUTO) or takes the caller's (USER), and rewrites e->st.pose_opt.
+int order_poses(Engine* e, std::vector<uint64_t>* proj_edges, double device_ms);
+bool ordering_wants_graph(const Engine* e);
 // broadcast of `count` doubles from `root`, ordered into `s`: native RCCL enqueues without a host
 // round trip; with a caller-supplied hook the stream is drained first (hook contract)
 int dist_broadcast(Engine* e, double* buf, size_t count, int root, hipStream_t s);

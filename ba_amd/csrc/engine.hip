@@ -115,6 +115,50 @@ static int upload_imu_consts(Engine* e) {
   return upload(e, e->imu_consts, c);
 }
 
+bool ordering_wants_graph(const Engine* e) { return e->order_mode == kOrderAuto; }
+
+int order_poses(Engine* e, std::vector<uint64_t>* proj_edges, double device_ms) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const Problem& pb = e->prob;
+  std::vector<int32_t> nat;
+  const uint32_t Pact = natural_pose_opt(pb, nat);
+  ba_hip_ordering_stats& os = e->order_stats;
+  os.mode = e->order_mode;
+  os.device_ms = device_ms;
+  if (e->order_mode == kOrderUser) {
+    const std::vector<uint32_t>& u = e->order_user;
+    if (u.size() != Pact) return e->fail_msg("ba_hip_set_pose_permutation: size differs from the active pose count");
+    std::vector<uint8_t> seen(Pact, 0);
+    for (uint32_t v : u) {
+      if (v >= Pact || seen[v]) return e->fail_msg("ba_hip_set_pose_permutation: not a permutation of the active poses");
+      seen[v] = 1;
+    }
+    e->opt_of_natural = u;
+  } else {
+    const int D = e->pose_dim;
+    const uint32_t G = pose_group_size(D), ng = (Pact + G - 1) / G;
+    // the pose-pose residuals couple their two poses (unary residuals couple none)
+    std::vector<uint64_t> edges(proj_edges ? *proj_edges : std::vector<uint64_t>());
+    auto pair = [&](uint32_t p1, uint32_t p2) {
+      if (p1 >= pb.num_poses || p2 >= pb.num_poses || nat[p1] < 0 || nat[p2] < 0) return;
+      const uint32_t a = (uint32_t)nat[p1] / G, b = (uint32_t)nat[p2] / G;
+      if (a != b) edges.push_back((uint64_t)std::min(a, b) << 32 | std::max(a, b));
+    };
+    for (uint32_t i = 0; i < pb.num_binary; ++i) pair(pb.bin_p1[i], pb.bin_p2[i]);
+    for (uint32_t i = 0; i < pb.num_imu; ++i) pair(pb.imu_p1[i], pb.imu_p2[i]);
+    group_graph_csr(ng, std::move(edges), e->group_ptr, e->group_adj);
+    OrderingResult r;
+    choose_pose_ordering(Pact, D, (uint32_t)e->calib_dim, e->group_ptr, e->group_adj, e->opt_of_natural, &r);
+    os.candidate = r.candidate;
+    os.group_size = r.G;
+    os.num_groups = ng;
+    os.tile_products_natural = r.products[0];
+    os.tile_products_chosen = r.products[r.candidate];
+  }
+  os.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
 // Build everything that depends only on the problem graph (not on the state): the lists of
 // structure.h on the host (threads), the pose-pose scatter lists, the tile pattern; then upload.
 static int build_structure(Engine* e) {
@@ -136,7 +180,18 @@ static int build_structure(Engine* e) {
   const bool host_build = env_host || e->dbg_host_structure;
   if (host_build) {
     std::string err;
-    if (!build_lists(pb, LM, e->pose_dim, st, err, stage, e->calib_dim)) {
+    if (e->order_mode != kOrderNatural) {
+      std::vector<uint64_t> edges;
+      if (ordering_wants_graph(e)) {
+        std::vector<int32_t> nat;
+        natural_pose_opt(pb, nat);
+        host_group_edges(pb, LM, nat, pose_group_size(e->pose_dim), edges);
+      }
+      const int orc = order_poses(e, &edges, 0.0);
+      if (orc) return orc;
+      stage("pose ordering");
+    }
+    if (!build_lists(pb, LM, e->pose_dim, st, err, stage, e->calib_dim, &e->opt_of_natural)) {
       e->err = err;
       return -1;
     }
@@ -859,6 +914,11 @@ int ba_hip_finalize(ba_hip_engine* h) {
   Problem& pb = e->prob;
   if (pb.pose_active.size() != pb.num_poses) pb.pose_active.assign(pb.num_poses, 1);
   if (pb.lm_active.size() != pb.num_lms) pb.lm_active.assign(pb.num_lms, 1);
+  if (e->order_mode != kOrderNatural && e->ordering_refused())
+    return e->fail_msg("pose ordering is not available on a sharded engine");
+  e->opt_of_natural.clear();
+  e->group_ptr.clear(); e->group_adj.clear();
+  e->order_stats = ba_hip_ordering_stats();
   int rc = build_structure(e);
   if (rc) return rc;
   e->finalized = true;
@@ -1270,6 +1330,19 @@ uint32_t ba_hip_num_lm_params(const ba_hip_engine* h) {
   return e->st.Lact * e->lm_dim;
 }
 
+// Public outputs are indexed by the NATURAL optimisation index: row r of the caller's numbering is row
+// int_row(r) of the engine's (the pose ordering of ba_hip_set_pose_ordering; the calibration border stays last).
+static inline uint32_t int_row(const Engine* e, uint32_t r) {
+  const uint32_t D = (uint32_t)e->pose_dim;
+  if (e->opt_of_natural.empty() || r >= e->st.np) return r;
+  return e->opt_of_natural[r / D] * D + r % D;
+}
+static void unpermute_vec(const Engine* e, double* v) {
+  if (e->opt_of_natural.empty() || !v) return;
+  std::vector<double> tmp(v, v + e->st.np);
+  for (uint32_t r = 0; r < e->st.np; ++r) v[r] = tmp[int_row(e, r)];
+}
+
 int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
   ENG(h);
   NEED_FINAL();
@@ -1284,13 +1357,16 @@ int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
   if (n) BAE_HIP(hipMemcpy(a.data(), src, a.size() * sizeof(double), hipMemcpyDeviceToHost));
   // lower storage -> the reference's s_: block (i,j) kept for i <= j only when
   // use_triangular_matrices (SparseBlockMatrixOps.h:236-238), full symmetric otherwise
+  // (r, c) in the caller's numbering, (ri, ci) in the engine's; the triangle kept is the caller's
   for (uint32_t r = 0; r < n; ++r)
     for (uint32_t c = 0; c < n; ++c) {
-      const uint32_t bi = block_of(r), bj = block_of(c);
+      const uint32_t ri = int_row(e, r), ci = int_row(e, c);
+      const uint32_t bi = block_of(ri), bj = block_of(ci);
       double v;
-      if (bi == bj) v = a[(size_t)r * ld + c];
-      else if (bi < bj) v = a[(size_t)c * ld + r];
-      else v = e->opt.use_triangular_matrices ? 0.0 : a[(size_t)r * ld + c];
+      if (bi == bj) v = a[(size_t)ri * ld + ci];
+      else if (bi < bj) v = a[(size_t)ci * ld + ri];
+      else v = a[(size_t)ri * ld + ci];
+      if (e->opt.use_triangular_matrices && block_of(r) > block_of(c)) v = 0.0;
       s_nxn[(size_t)r * n + c] = v;
     }
   return 0;
@@ -1303,6 +1379,8 @@ int ba_hip_get_rhs(ba_hip_engine* h, double* rhs_p_sc, double* rhs_p, double* rh
   BAE_HIP(hipStreamSynchronize(e->stream));
   if (rhs_p_sc && st.n) BAE_HIP(hipMemcpy(rhs_p_sc, e->rhs_sc.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
   if (rhs_p && st.n) BAE_HIP(hipMemcpy(rhs_p, e->rhs_p.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
+  unpermute_vec(e, st.n ? rhs_p_sc : nullptr);
+  unpermute_vec(e, st.n ? rhs_p : nullptr);
   if (rhs_l && st.Lact) {
     std::vector<double> bl((size_t)st.L * e->lm_dim);
     BAE_HIP(hipMemcpy(bl.data(), e->lm_bl.p, bl.size() * 8, hipMemcpyDeviceToHost));
@@ -1320,6 +1398,7 @@ int ba_hip_get_delta_gn(ba_hip_engine* h, double* delta_p, double* delta_l) {
   const Structure& st = e->st;
   BAE_HIP(hipStreamSynchronize(e->stream));
   if (delta_p && st.n) BAE_HIP(hipMemcpy(delta_p, e->gn_p.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
+  unpermute_vec(e, st.n ? delta_p : nullptr);
   if (delta_l && st.Lact) BAE_HIP(hipMemcpy(delta_l, e->gn_l.p, (size_t)st.Lact * e->lm_dim * 8, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -1330,6 +1409,7 @@ int ba_hip_get_step(ba_hip_engine* h, double* delta_p, double* delta_l) {
   const Structure& st = e->st;
   BAE_HIP(hipStreamSynchronize(e->stream));
   if (delta_p && st.n) BAE_HIP(hipMemcpy(delta_p, e->step_p.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
+  unpermute_vec(e, st.n ? delta_p : nullptr);
   if (delta_l && st.Lact) BAE_HIP(hipMemcpy(delta_l, e->step_l.p, (size_t)st.Lact * e->lm_dim * 8, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -1484,15 +1564,7 @@ int ba_hip_get_structure_stats(ba_hip_engine* h, ba_hip_structure_stats* out) {
         out->tiles_S += e->nzS_host[i * nt + k] ? 1 : 0;
         out->tiles_L += e->nzL_host[i * nt + k] ? 1 : 0;
       }
-  if (e->nzL_valid && e->nzL_host.size() == nt * nt) {
-    // column k with m_k structurally nonzero tiles below the diagonal: m_k (m_k + 1) / 2 update products, m_k / 2
-    // substitution products (a triangular 64x64 solve is half a product), + the rhs row (m_k + 1 products)
-    for (uint64_t k = 0; k < nt; ++k) {
-      uint64_t m = 0;
-      for (uint64_t i = k + 1; i < nt; ++i) m += e->nzL_host[i * nt + k] ? 1 : 0;
-      out->factor_tile_products += m * (m + 1) / 2 + (m + 1) / 2 + m + 1;
-    }
-  }
+  if (e->nzL_valid && e->nzL_host.size() == nt * nt) out->factor_tile_products = factor_tile_products(e->nzL_host, (uint32_t)nt);
   return 0;
 }
 
@@ -1597,8 +1669,47 @@ int ba_hip_solve_is_distributed(ba_hip_engine* h) {
   return dist_solve_enabled(reinterpret_cast<Engine*>(h)) ? 1 : 0;
 }
 
+int ba_hip_set_pose_ordering(ba_hip_engine* h, int mode) {
+  ENG(h);
+  if (mode != kOrderNatural && mode != kOrderAuto && mode != kOrderUser)
+    return e->fail_msg("ba_hip_set_pose_ordering: unknown mode");
+  if (mode != kOrderNatural && e->ordering_refused())
+    return e->fail_msg("pose ordering is not available on a sharded engine (all-reduce hook, collectives hook or communicator set)");
+  e->order_mode = mode;
+  return 0;
+}
+
+int ba_hip_set_pose_permutation(ba_hip_engine* h, const uint32_t* opt_of_natural, uint32_t n) {
+  ENG(h);
+  if (n && !opt_of_natural) return e->fail_msg("ba_hip_set_pose_permutation: NULL permutation");
+  e->order_user.assign(opt_of_natural, opt_of_natural + n);
+  return 0;
+}
+
+int ba_hip_get_pose_ordering(ba_hip_engine* h, uint32_t* opt_of_natural, ba_hip_ordering_stats* out) {
+  ENG(h);
+  NEED_FINAL();
+  if (opt_of_natural)
+    for (uint32_t i = 0; i < e->st.Pact; ++i) opt_of_natural[i] = e->opt_of_natural.empty() ? i : e->opt_of_natural[i];
+  if (out) *out = e->order_stats;
+  return 0;
+}
+
+int ba_hip_get_pose_group_graph(ba_hip_engine* h, uint32_t* ptr, uint32_t* adj, uint32_t* num_groups, uint32_t* num_edges) {
+  ENG(h);
+  NEED_FINAL();
+  const uint32_t ng = e->group_ptr.empty() ? 0 : (uint32_t)e->group_ptr.size() - 1;
+  if (num_groups) *num_groups = ng;
+  if (num_edges) *num_edges = (uint32_t)e->group_adj.size();
+  if (ptr && !e->group_ptr.empty()) memcpy(ptr, e->group_ptr.data(), e->group_ptr.size() * 4);
+  if (adj && !e->group_adj.empty()) memcpy(adj, e->group_adj.data(), e->group_adj.size() * 4);
+  return 0;
+}
+
 int ba_hip_set_collectives(ba_hip_engine* h, ba_hip_collective_fn fn, void* ctx) {
   ENG(h);
+  if (fn && e->order_mode != kOrderNatural)
+    return e->fail_msg("the collectives hook needs natural pose order (ba_hip_set_pose_ordering is set)");
   e->coll = fn; e->coll_ctx = ctx;
   e->dist_plan_version = ~0ull;
   return 0;
@@ -1606,6 +1717,8 @@ int ba_hip_set_collectives(ba_hip_engine* h, ba_hip_collective_fn fn, void* ctx)
 
 int ba_hip_set_allreduce(ba_hip_engine* h, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) {
   ENG(h);
+  if (fn && e->order_mode != kOrderNatural)
+    return e->fail_msg("the all-reduce hook needs natural pose order (ba_hip_set_pose_ordering is set)");
   e->allreduce = fn; e->allreduce_ctx = ctx; e->rank = rank; e->nranks = nranks < 1 ? 1 : nranks;
   e->nzL_valid = false;  // the tile pattern of S is the union over the shards
   e->dist_plan_version = ~0ull;

@@ -291,3 +291,38 @@ extern "C" int ba_hostcheck_schur_lists(
   }
   return 0;
 }
+
+// ---- pose ordering (ordering.h) -------------------------------------------------------------------------
+#include "ordering.h"
+
+// symbolic tile elimination in place (nt x nt symmetric pattern in, lower factor pattern out); returns the
+// factor's tile products
+extern "C" uint64_t ba_hostcheck_tile_factor(uint32_t nt, uint8_t* nz) {
+  std::vector<uint8_t> v(nz, nz + (size_t)nt * nt);
+  bae::tile_symbolic_factor(v, nt);
+  std::copy(v.begin(), v.end(), nz);
+  return bae::factor_tile_products(v, nt);
+}
+
+// choose_pose_ordering on a group graph (CSR over ceil(Pact / G) groups); products4: per candidate
+extern "C" int ba_hostcheck_pose_ordering(uint32_t Pact, int D, uint32_t K, const uint32_t* ptr, const uint32_t* adj,
+                                          uint32_t* opt_of_natural, int* candidate, uint32_t* group_size,
+                                          uint64_t* products4) {
+  const uint32_t G = bae::pose_group_size(D), ng = (Pact + G - 1) / G;
+  std::vector<uint32_t> p(ptr, ptr + ng + 1), a(adj, adj + (ng ? ptr[ng] : 0)), perm;
+  bae::OrderingResult r;
+  bae::choose_pose_ordering(Pact, D, K, p, a, perm, &r);
+  std::copy(perm.begin(), perm.end(), opt_of_natural);
+  *candidate = r.candidate;
+  *group_size = r.G;
+  for (int c = 0; c < bae::kOrderCandidates; ++c) products4[c] = r.products[c];
+  return 0;
+}
+
+// model tile products of a group order (order[position] = group)
+extern "C" uint64_t ba_hostcheck_group_order_products(uint32_t Pact, int D, uint32_t K, const uint32_t* ptr,
+                                                      const uint32_t* adj, const uint32_t* order) {
+  const uint32_t G = bae::pose_group_size(D), ng = (Pact + G - 1) / G;
+  std::vector<uint32_t> p(ptr, ptr + ng + 1), a(adj, adj + (ng ? ptr[ng] : 0)), o(order, order + ng);
+  return bae::group_order_products(Pact, D, K, p, a, o);
+}

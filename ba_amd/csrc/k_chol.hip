@@ -1534,7 +1534,8 @@ static void launch_backward(hipStream_t s, double* dA, uint32_t ld, uint32_t nbl
 }
 
 // Tile pattern of the factor L: the union of the shards' S patterns (all-reduce of the tile
-// map), then symbolic elimination in natural order at 64x64-tile granularity:
+// map), then symbolic elimination in the order of the optimisation indices (natural, or the pose
+// ordering of ba_hip_set_pose_ordering) at 64x64-tile granularity (ordering.h: tile_symbolic_factor):
 // L(i,j) becomes nonzero when L(i,k) and L(j,k) are, k < j <= i.  The trailing updates,
 // triangular solves and the look-ahead skip every tile product with a structurally zero
 // operand — the reference reaches the same saving through Eigen::SimplicialLDLT on
@@ -1557,23 +1558,7 @@ int factor_tile_pattern(Engine* e) {
     for (size_t i = 0; i < nz.size(); ++i) nz[i] = cnt[i] > 0.5 ? 1 : 0;
   }
   e->nzS_host = nz;
-  // symbolic right-looking elimination on the lower triangle; the working copy is column-major
-  // (c[k * nt + i] = L(i,k)) so that both the scan of column k and the fill of column j are
-  // contiguous
-  std::vector<uint8_t> c(nz);  // symmetric on input
-  std::vector<uint32_t> rows;
-  for (uint32_t k = 0; k < nt; ++k) {
-    rows.clear();
-    const uint8_t* ck = &c[(size_t)k * nt];
-    for (uint32_t i = k + 1; i < nt; ++i)
-      if (ck[i]) rows.push_back(i);
-    for (size_t a = 0; a < rows.size(); ++a) {
-      uint8_t* cj = &c[(size_t)rows[a] * nt];
-      for (size_t b = a; b < rows.size(); ++b) cj[rows[b]] = 1;
-    }
-  }
-  for (uint32_t i = 0; i < nt; ++i)
-    for (uint32_t k = 0; k < nt; ++k) nz[(size_t)i * nt + k] = (k <= i) ? c[(size_t)k * nt + i] : 0;
+  tile_symbolic_factor(nz, nt);  // ordering.h (shared with the ordering's candidate scores)
   BAE_HIP(e->nzL.alloc(nz.size()));
   BAE_HIP(hipMemcpy(e->nzL.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
   e->nzL_host = nz;

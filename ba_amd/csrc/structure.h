@@ -118,17 +118,67 @@ inline unsigned structure_threads() {
 }
 
 // Returns false and sets `err` on an inconsistent graph.
+// natural optimisation ids: running count of active items in id order (BundleAdjuster.h:309-316)
+inline uint32_t natural_pose_opt(const Problem& pb, std::vector<int32_t>& pose_opt) {
+  uint32_t n = 0;
+  pose_opt.assign(pb.num_poses, -1);
+  for (uint32_t p = 0; p < pb.num_poses; ++p)
+    if (pb.pose_active[p]) pose_opt[p] = (int32_t)n++;
+  return n;
+}
+
+// Group pairs (a << 32 | b, a < b) of the projection part of S: two active poses whose groups
+// (opt id / G) differ and that share an active landmark — through the incidences build_lists uses
+// (measuring poses of listed observations, and for LM == 1 the reference pose).  Duplicates removed.
+// The device builds the same list (structure_dev.hip: k_group_pairs).
+inline void host_group_edges(const Problem& pb, int LM, const std::vector<int32_t>& pose_opt, uint32_t G,
+                             std::vector<uint64_t>& edges) {
+  edges.clear();
+  if (LM == 0) return;
+  std::vector<uint32_t> ptr((size_t)pb.num_lms + 1, 0), obs(pb.num_proj);
+  for (uint32_t a = 0; a < pb.num_proj; ++a) ptr[pb.proj_lm[a] + 1]++;
+  for (uint32_t l = 0; l < pb.num_lms; ++l) ptr[l + 1] += ptr[l];
+  {
+    std::vector<uint32_t> cur(ptr.begin(), ptr.end() - 1);
+    for (uint32_t a = 0; a < pb.num_proj; ++a) obs[cur[pb.proj_lm[a]]++] = a;
+  }
+  std::vector<uint32_t> grp;
+  for (uint32_t l = 0; l < pb.num_lms; ++l) {
+    if (!pb.lm_active[l]) continue;
+    grp.clear();
+    bool any = false;
+    for (uint32_t q = ptr[l]; q < ptr[l + 1]; ++q) {
+      const uint32_t a = obs[q];
+      if (LM == 1 && pb.proj_pose[a] == pb.lm_ref_pose[l]) continue;
+      any = true;
+      if (pose_opt[pb.proj_pose[a]] >= 0) grp.push_back((uint32_t)pose_opt[pb.proj_pose[a]] / G);
+    }
+    if (LM == 1 && any && pose_opt[pb.lm_ref_pose[l]] >= 0) grp.push_back((uint32_t)pose_opt[pb.lm_ref_pose[l]] / G);
+    std::sort(grp.begin(), grp.end());
+    grp.erase(std::unique(grp.begin(), grp.end()), grp.end());
+    for (size_t x = 0; x < grp.size(); ++x)
+      for (size_t y = x + 1; y < grp.size(); ++y) edges.push_back((uint64_t)grp[x] << 32 | grp[y]);
+  }
+  std::sort(edges.begin(), edges.end());
+  edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+}
+
+// opt_of_natural (optional): the pose ordering — pose_opt[p] = opt_of_natural[natural opt id of p]
 inline bool build_lists(const Problem& pb, int LM, int D, Lists& st, std::string& err,
-                        const std::function<void(const char*)>& stage = nullptr, int K = 0) {
+                        const std::function<void(const char*)>& stage = nullptr, int K = 0,
+                        const std::vector<uint32_t>* opt_of_natural = nullptr) {
   auto mark_stage = [&](const char* s) { if (stage) stage(s); };
   st = Lists();
   st.P = pb.num_poses; st.L = pb.num_lms; st.O = pb.num_proj; st.C = pb.num_cams;
   if (st.O > 0 && st.C == 0) { err = "projection residuals without a camera"; return false; }
   if (st.O > 0 && LM == 0) { err = "projection residuals need LmSize 1 or 3"; return false; }
   // opt ids: running count of active items in id order (BundleAdjuster.h:309-316,353-360)
-  st.pose_opt.assign(st.P, -1);
-  for (uint32_t p = 0; p < st.P; ++p)
-    if (pb.pose_active[p]) st.pose_opt[p] = (int32_t)st.Pact++;
+  st.Pact = natural_pose_opt(pb, st.pose_opt);
+  if (opt_of_natural && !opt_of_natural->empty()) {
+    if (opt_of_natural->size() != st.Pact) { err = "pose permutation size differs from the active pose count"; return false; }
+    for (uint32_t p = 0; p < st.P; ++p)
+      if (st.pose_opt[p] >= 0) st.pose_opt[p] = (int32_t)(*opt_of_natural)[st.pose_opt[p]];
+  }
   st.lm_opt.assign(st.L, -1);
   for (uint32_t l = 0; l < st.L; ++l)
     if (pb.lm_active[l] && LM > 0) st.lm_opt[l] = (int32_t)st.Lact++;

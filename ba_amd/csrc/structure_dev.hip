@@ -17,6 +17,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 
 namespace bae {
@@ -106,6 +107,38 @@ __global__ void k_inc_fill(DevGraph g, const uint32_t* __restrict__ linc_ptr, ui
   if (g.LM == 1 && any) {
     const int ro = g.pose_opt[g.lm_ref_pose[l]];
     if (ro >= 0) { inc_pose[w] = (uint32_t)ro; inc_wrow[w] = g.lrow_base + 2 * l; ++w; }
+  }
+}
+
+// ---- group co-visibility graph of the pose ordering (ordering.h) -----------------------------------
+// Per landmark, every pair of its incidences on different tile-aligned groups (natural opt id / G) gives
+// the key min(g) << 32 | max(g); sorted and made unique these are the group edges of the projection part.
+__global__ void k_group_pair_count(uint32_t L, uint32_t G, const uint32_t* __restrict__ linc_ptr,
+                                   const uint32_t* __restrict__ inc_pose, uint32_t* __restrict__ cnt) {
+  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= L) return;
+  const uint32_t q0 = linc_ptr[l], q1 = linc_ptr[l + 1];
+  uint32_t c = 0;
+  for (uint32_t x = q0; x < q1; ++x) {
+    const uint32_t gx = inc_pose[x] / G;
+    for (uint32_t y = x + 1; y < q1; ++y) c += (inc_pose[y] / G != gx) ? 1u : 0u;
+  }
+  cnt[l] = c;
+}
+__global__ void k_group_pairs(uint32_t L, uint32_t G, const uint32_t* __restrict__ linc_ptr,
+                              const uint32_t* __restrict__ inc_pose, const uint32_t* __restrict__ off,
+                              unsigned long long* __restrict__ keys) {
+  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= L) return;
+  const uint32_t q0 = linc_ptr[l], q1 = linc_ptr[l + 1];
+  uint32_t w = off[l];
+  for (uint32_t x = q0; x < q1; ++x) {
+    const uint32_t gx = inc_pose[x] / G;
+    for (uint32_t y = x + 1; y < q1; ++y) {
+      const uint32_t gy = inc_pose[y] / G;
+      if (gy == gx) continue;
+      keys[w++] = (unsigned long long)min(gx, gy) << 32 | max(gx, gy);
+    }
   }
 }
 
@@ -461,6 +494,61 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   BAE_HIP(hipStreamSynchronize(e->stream));
   BAE_HIP(inc_pose.alloc(std::max<size_t>(st.n_inc, 1))); BAE_HIP(inc_wrow.alloc(std::max<size_t>(st.n_inc, 1)));
   if (L) hipLaunchKernelGGL(k_inc_fill, GRID(L), g, (const uint32_t*)linc_ptr.p, inc_pose.p, inc_wrow.p);
+
+  // ---- pose ordering: group graph from the natural incidences, then the permuted opt ids ------------------
+  if (e->order_mode != kOrderNatural) {
+    std::vector<uint64_t> edges;
+    double dev_ms = 0.0;
+    if (ordering_wants_graph(e) && L) {
+      const auto t0 = std::chrono::steady_clock::now();
+      const uint32_t G = pose_group_size(D), ng = (st.Pact + G - 1) / G;
+      TBuf<uint32_t> gp_cnt, gp_off, n_unique;
+      BAE_HIP(gp_cnt.alloc(L1)); BAE_HIP(gp_off.alloc(L1)); BAE_HIP(n_unique.alloc(1));
+      hipLaunchKernelGGL(k_group_pair_count, GRID(L), L, G, (const uint32_t*)linc_ptr.p, (const uint32_t*)inc_pose.p,
+                         gp_cnt.p);
+      BAE_HIP(hipGetLastError());
+      if ((rc = scan_exclusive(e, tmp, (const uint32_t*)gp_cnt.p, gp_off.p, L))) return rc;
+      uint32_t n_gp = 0;
+      if ((rc = total_of(e, gp_off.p, gp_cnt.p, L, &n_gp, "group pair list"))) return rc;
+      if (n_gp) {
+        TBuf<unsigned long long> gk0, gk1;
+        BAE_HIP(gk0.alloc(n_gp)); BAE_HIP(gk1.alloc(n_gp));
+        hipLaunchKernelGGL(k_group_pairs, GRID(L), L, G, (const uint32_t*)linc_ptr.p, (const uint32_t*)inc_pose.p,
+                           (const uint32_t*)gp_off.p, gk0.p);
+        BAE_HIP(hipGetLastError());
+        size_t bytes = 0;
+        const unsigned end_bit = 32u + (unsigned)bits_for(ng ? ng - 1 : 0);
+        BAE_HIP(rocprim::radix_sort_keys(nullptr, bytes, (const unsigned long long*)gk0.p, gk1.p, (size_t)n_gp, 0u, end_bit,
+                                         e->stream));
+        BAE_HIP(tmp.alloc(std::max<size_t>(bytes, 16)));
+        BAE_HIP(rocprim::radix_sort_keys(tmp.p, bytes, (const unsigned long long*)gk0.p, gk1.p, (size_t)n_gp, 0u, end_bit,
+                                         e->stream));
+        bytes = 0;
+        BAE_HIP(rocprim::unique(nullptr, bytes, (const unsigned long long*)gk1.p, gk0.p, n_unique.p, (size_t)n_gp,
+                                rocprim::equal_to<unsigned long long>(), e->stream));
+        BAE_HIP(tmp.alloc(std::max<size_t>(bytes, 16)));
+        BAE_HIP(rocprim::unique(tmp.p, bytes, (const unsigned long long*)gk1.p, gk0.p, n_unique.p, (size_t)n_gp,
+                                rocprim::equal_to<unsigned long long>(), e->stream));
+        uint32_t nu = 0;
+        BAE_HIP(hipMemcpyAsync(&nu, n_unique.p, 4, hipMemcpyDeviceToHost, e->stream));
+        BAE_HIP(hipStreamSynchronize(e->stream));
+        if (nu > n_gp) return e->fail_msg("group pair list: bad unique count");
+        edges.resize(nu);
+        if (nu) BAE_HIP(hipMemcpy(edges.data(), gk0.p, (size_t)nu * 8, hipMemcpyDeviceToHost));
+      }
+      dev_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if ((rc = order_poses(e, &edges, dev_ms))) return rc;
+    if (!e->opt_of_natural.empty()) {
+      for (uint32_t p = 0; p < st.P; ++p)
+        if (st.pose_opt[p] >= 0) st.pose_opt[p] = (int32_t)e->opt_of_natural[st.pose_opt[p]];
+      BAE_HIP(hipMemcpyAsync(e->pose_opt.p, st.pose_opt.data(), st.pose_opt.size() * 4, hipMemcpyHostToDevice, e->stream));
+      if (L) hipLaunchKernelGGL(k_inc_fill, GRID(L), g, (const uint32_t*)linc_ptr.p, inc_pose.p, inc_wrow.p);
+      BAE_HIP(hipGetLastError());
+      BAE_HIP(hipStreamSynchronize(e->stream));  // st.pose_opt is read by the copy
+    }
+    if (stage) stage("pose ordering");
+  }
 
   // ---- rank-1 terms of the off-diagonal blocks -----------------------------------------------------------
   TBuf<uint32_t> lrec_cnt, lrec_off, orec_cnt, orec_off, schur_cnt, schur_off, jt_cnt, jt_off;

@@ -97,6 +97,12 @@ def dist_plan_stats(nblk, nz_lower, nranks, layout="auto", kout=0):
     return {k: getattr(out, k) for k, _ in DistPlanStats._fields_}
 
 
+class OrderingStats(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("candidate", C.c_int32), ("group_size", C.c_uint32), ("num_groups", C.c_uint32),
+                ("tile_products_natural", C.c_uint64), ("tile_products_chosen", C.c_uint64),
+                ("host_ms", C.c_double), ("device_ms", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
 
@@ -119,7 +125,10 @@ SYMBOLS = [
     "ba_hip_set_camera_models", "ba_hip_get_camera_fov",
     "ba_hip_integrate_imu_jacobians", "ba_hip_imu_pose_derivative", "ba_hip_imu_integrate_pose", "ba_hip_lie",
     "ba_hip_get_comm_stats", "ba_hip_reset_comm_stats", "ba_hip_dist_plan_stats", "ba_hip_get_factor_tile_pattern",
+    "ba_hip_set_pose_ordering", "ba_hip_set_pose_permutation", "ba_hip_get_pose_ordering", "ba_hip_get_pose_group_graph",
 ]
+
+ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
 
 
 def build(force=False):
@@ -411,6 +420,32 @@ class Engine:
         st = StructureStats()
         self._chk(self.L.ba_hip_get_structure_stats(self.h, C.byref(st)))
         return {n: int(getattr(st, n)) for n, _ in StructureStats._fields_}
+
+    def set_pose_ordering(self, mode):
+        """ORDER_NATURAL / ORDER_AUTO / ORDER_USER, effective at the next finalize()."""
+        self._chk(self.L.ba_hip_set_pose_ordering(self.h, int(mode)))
+
+    def set_pose_permutation(self, opt_of_natural):
+        """The permutation of ORDER_USER: opt_of_natural[i] = factorised position of the i-th active pose."""
+        p = np.ascontiguousarray(opt_of_natural, dtype=np.uint32)
+        self._chk(self.L.ba_hip_set_pose_permutation(self.h, _p(p, u32p), len(p)))
+
+    def get_pose_ordering(self):
+        """(opt_of_natural, stats dict) of the last finalize."""
+        n = self.num_pose_params() // self.pose_dim
+        perm = np.zeros(max(n, 1), dtype=np.uint32)
+        st = OrderingStats()
+        self._chk(self.L.ba_hip_get_pose_ordering(self.h, _p(perm, u32p), C.byref(st)))
+        return perm[:n], {k: getattr(st, k) for k, _ in OrderingStats._fields_}
+
+    def get_pose_group_graph(self):
+        """(ptr, adj) CSR of the group graph the last AUTO ordering was chosen from."""
+        ng, ne = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.ba_hip_get_pose_group_graph(self.h, None, None, C.byref(ng), C.byref(ne)))
+        ptr = np.zeros(ng.value + 1, dtype=np.uint32)
+        adj = np.zeros(max(ne.value, 1), dtype=np.uint32)
+        self._chk(self.L.ba_hip_get_pose_group_graph(self.h, _p(ptr, u32p), _p(adj, u32p), C.byref(ng), C.byref(ne)))
+        return (ptr if ng.value else np.zeros(0, dtype=np.uint32)), adj[:ne.value]
 
     def debug_set(self, key, value):
         self._chk(self.L.ba_hip_debug_set(self.h, int(key), int(value)))

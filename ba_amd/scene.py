@@ -304,6 +304,134 @@ def make_scene(num_poses, num_landmarks, obs_per_landmark=10, lm_dim=1, seed=0,
     return sc
 
 
+def make_revisit_scene(num_poses, num_landmarks, laps, window, revisit_frac, obs_per_landmark=10, lm_dim=1,
+                       seed=0, pixel_sigma=1.5, trans_sigma=0.05, rot_sigma=0.01, depth_sigma=0.05,
+                       lap_offset=(0.04, -0.03, 0.05)):
+    """A route driven `laps` times: the closed curve of trajectory() with M = num_poses // laps places,
+    pose i at place i % M on lap i // M, every lap shifted by `lap_offset` metres.  A landmark is seen
+    from poses in its own window (at most `window` poses either side of its anchor along the pose ids);
+    with probability `revisit_frac` it is also seen from the poses at the same places on the other laps
+    (those it projects into).  In the pose graph a revisit couples pose i to pose i +- M: the graphs of
+    multi-session mapping, whose natural elimination order fills the band between the laps.
+
+    Observations are projected through the true poses (plus pixel noise, no outliers).  lm_dim == 1: the
+    first observation of a landmark is its reference frame (rejected by AddProjectionResidual).  The
+    observation count per landmark varies; sc.obs_per_landmark is the window part only.  Poses 0 and
+    P // 2 are the gauge anchors (left at ground truth)."""
+    P, L, k = int(num_poses), int(num_landmarks), int(obs_per_landmark)
+    laps = max(1, int(laps))
+    M = max(1, P // laps)
+    nsel = k + 1 if lm_dim == 1 else k
+    place_poses, vel = trajectory(M)
+    idx = np.arange(P)
+    gt_poses = place_poses[idx % M].copy()
+    gt_poses[:, :3] += (idx // M)[:, None] * np.asarray(lap_offset, dtype=np.float64)[None, :]
+    sc = Scene()
+    sc.lm_dim, sc.num_poses, sc.num_landmarks_total, sc.lm_lo = lm_dim, P, L, 0
+    sc.cam_params = CAM_PARAMS.copy()
+    sc.gt_poses = gt_poses
+    sc.gt_vel = vel[idx % M]
+    sc.laps, sc.places = laps, M
+    rng_p = np.random.Generator(np.random.PCG64([seed, 0xBA5E, 11]))
+    dt = rng_p.normal(0.0, trans_sigma, (P, 3))
+    dw = rng_p.normal(0.0, rot_sigma, (P, 3))
+    sc.anchor_poses = np.array((0, P // 2), dtype=np.int64)
+    dt[sc.anchor_poses] = 0
+    dw[sc.anchor_poses] = 0
+    init = gt_poses.copy()
+    init[:, :3] += dt
+    init[:, 3:7] = quat_mul(gt_poses[:, 3:7], quat_exp(dw))
+    init[:, 3:7] /= np.linalg.norm(init[:, 3:7], axis=-1, keepdims=True)
+    sc.poses = init
+
+    window = int(window)
+    ncand = min(2 * window, max(4 * nsel, 48))
+    x_w = np.zeros((L, 4))
+    x_w[:, 3] = 1.0
+    sel_all = np.empty((L, nsel), dtype=np.int64)
+    todo = np.arange(L)
+    attempt = 0
+    while todo.size:
+        rng = np.random.Generator(np.random.PCG64([seed, 0xBA5E, 12, attempt]))
+        m = todo.size
+        anchor = rng.integers(0, P, m)
+        uv = np.stack([rng.uniform(20, IMG_W - 20, m), rng.uniform(20, IMG_H - 20, m)], -1)
+        depth = rng.uniform(2.0, 40.0, m)
+        ap = gt_poses[anchor]
+        ray = np.stack([(uv[:, 0] - CAM_PARAMS[2]) / CAM_PARAMS[0],
+                        (uv[:, 1] - CAM_PARAMS[3]) / CAM_PARAMS[1], np.ones(m)], -1)
+        pts = ap[:, :3] + np.einsum('nij,nj->ni', quat_to_rot(ap[:, 3:7]), ray * depth[:, None])
+        offs = random_order_head(rng, m, 2 * window, ncand) - window
+        offs = np.where(offs >= 0, offs + 1, offs)
+        cand = anchor[:, None] + offs
+        inside = (cand >= 0) & (cand < P)
+        cand = np.clip(cand, 0, P - 1)
+        cuv, cz = project(gt_poses[cand], pts[:, None, :])
+        vis = inside & (cz > 0.5) & (cuv[..., 0] > 0) & (cuv[..., 0] < IMG_W) & (cuv[..., 1] > 0) & (cuv[..., 1] < IMG_H)
+        order = np.argsort(~vis, axis=1, kind='stable')
+        good = np.nonzero(vis.sum(1) >= nsel - 1)[0]
+        if good.size:
+            picks = np.take_along_axis(cand[good], order[good, :nsel - 1], 1)
+            sel = np.concatenate([anchor[good, None], picks], 1)
+            x_w[todo[good], :3] = pts[good]
+            sel_all[todo[good]] = sel
+            done = np.zeros(m, dtype=bool)
+            done[good] = True
+            todo = todo[~done]
+        attempt += 1
+        if attempt > 200:
+            raise RuntimeError("scene generation did not converge")
+    # revisits: the same places on the other laps
+    rng_r = np.random.Generator(np.random.PCG64([seed, 0xBA5E, 13]))
+    rev = rng_r.random(L) < revisit_frac
+    extra = [np.empty((L, 0), dtype=np.int64)]
+    for d in range(1, laps):
+        q = sel_all[:, 1:] + d * M
+        q = np.where(q >= laps * M, q - laps * M, q)
+        ok = rev[:, None] & (q < P)
+        qc = np.clip(q, 0, P - 1)
+        cuv, cz = project(gt_poses[qc], x_w[:, None, :3])
+        ok &= (cz > 0.5) & (cuv[..., 0] > 0) & (cuv[..., 0] < IMG_W) & (cuv[..., 1] > 0) & (cuv[..., 1] < IMG_H)
+        extra.append(np.where(ok, qc, -1))
+    allp = np.concatenate([sel_all] + extra, 1)
+    keep = allp >= 0
+    # drop a pose that occurs twice for one landmark (laps wrapping onto the window)
+    srt = np.sort(np.where(keep, allp, -1 - np.arange(allp.shape[1])[None, :]), 1)
+    if (srt[:, 1:] == srt[:, :-1]).any():
+        for l in np.nonzero((srt[:, 1:] == srt[:, :-1]).any(1))[0]:
+            seen = set()
+            for c in range(allp.shape[1]):
+                if keep[l, c]:
+                    if allp[l, c] in seen:
+                        keep[l, c] = False
+                    seen.add(allp[l, c])
+    obs_lm = np.repeat(np.arange(L), allp.shape[1]).reshape(L, -1)[keep].astype(np.uint32)
+    obs_pose = allp[keep].astype(np.uint32)
+    z, _ = project(gt_poses[obs_pose], x_w[obs_lm, :3])
+    rng_n = np.random.Generator(np.random.PCG64([seed, 0xBA5E, 14]))
+    z = z + rng_n.normal(0.0, pixel_sigma, z.shape)
+    ref_pose = sel_all[:, 0].astype(np.uint32)
+    first = np.zeros(len(obs_lm), dtype=bool)
+    first[np.r_[0, np.nonzero(np.diff(obs_lm))[0] + 1]] = True
+    z_ref = z[first]
+    ray = np.stack([(z_ref[:, 0] - CAM_PARAMS[2]) / CAM_PARAMS[0],
+                    (z_ref[:, 1] - CAM_PARAMS[3]) / CAM_PARAMS[1], np.ones(L)], -1)
+    gp = gt_poses[ref_pose]
+    dep = np.einsum('nij,nj->ni', np.transpose(quat_to_rot(gp[:, 3:7]), (0, 2, 1)), x_w[:, :3] - gp[:, :3])[:, 2]
+    scale = 1.0 / (1.0 + rng_n.normal(0.0, depth_sigma, L))
+    ip = init[ref_pose]
+    x_init = x_w.copy()
+    x_init[:, :3] = ip[:, :3] + np.einsum('nij,nj->ni', quat_to_rot(ip[:, 3:7]), ray * (dep * scale)[:, None])
+    sc.gt_landmarks = x_w
+    sc.landmarks = x_init
+    sc.lm_ref_pose = ref_pose
+    sc.num_landmarks = L
+    sc.obs_pose, sc.obs_lm, sc.obs_z = obs_pose, obs_lm, z
+    sc.obs_per_landmark = k
+    sc.revisited = rev
+    return sc
+
+
 def add_scene_to(ba, sc, pose_dim=6, active=None):
     """Feed a Scene through a reference-style API object (oracle or ba_amd adjuster)."""
     ba.AddCamera(sc.cam_params)

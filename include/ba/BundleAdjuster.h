@@ -63,6 +63,9 @@ struct SolutionSummary {  // reference BundleAdjuster.h:48-70
   bool IsResultGood() const { return (result != SolverError) && (result != FactorizationError); }
 };
 
+// values of Options::pose_ordering (extension)
+enum class PoseOrdering { Natural = 0, Auto = 1 };
+
 template <typename Scalar = double>
 struct Options {  // reference BundleAdjuster.h:72-107, same names and defaults
   Scalar trust_region_size = kTrustRegionAuto;
@@ -93,6 +96,11 @@ struct Options {  // reference BundleAdjuster.h:72-107, same names and defaults
   bool calculate_inertial_covariance_once = false;
   // engine placement (not in the reference): HIP device ordinal
   int device = 0;
+  // extension: fill-reducing ordering of the poses in the reduced camera solve (include/ba_hip.h:
+  // ba_hip_set_pose_ordering).  Natural = the reference's pose-id order; Auto lets the engine reorder
+  // tile-aligned groups of poses when that needs fewer tile products (multi-lap routes, loop closures).
+  // Results are the same either way; not available with a sharded engine.
+  PoseOrdering pose_ordering = PoseOrdering::Natural;
 };
 
 template <typename Scalar = double, int LmSize = 1, int PoseSize = 6, int CalibSize = 0,
@@ -745,6 +753,9 @@ bool BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::UploadProblem()
   if (!Check(ba_hip_set_imu_residuals(engine_, (uint32_t)imu_p1_.size(), imu_p1_.data(), imu_p2_.data(),
                                       imu_ptr_.data(), imu_meas_.data(), imu_w_.data()),
              "ba_hip_set_imu_residuals")) return false;
+  if (!Check(ba_hip_set_pose_ordering(engine_, options_.pose_ordering == PoseOrdering::Auto ? BA_HIP_ORDER_AUTO
+                                                                                          : BA_HIP_ORDER_NATURAL),
+             "ba_hip_set_pose_ordering")) return false;
   if (!Check(ba_hip_finalize(engine_), "ba_hip_finalize")) return false;
   structure_dirty_ = false;
   engine_per_pose_cam_ = options_.use_per_pose_cam_params;

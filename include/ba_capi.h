@@ -30,7 +30,7 @@ typedef struct { /* ba::Options<double>, reference BundleAdjuster.h:72-107 */
   int32_t device;
   double factorization_pivot_tolerance; /* extension, 0 = off: ba::Options::factorization_pivot_tolerance */
   int32_t calculate_calibration_marginals; /* reference BundleAdjuster.h:95 (do_tvs adjusters) */
-  int32_t reserved;
+  int32_t pose_ordering; /* extension: 0 natural, 1 auto (ba::Options::pose_ordering, ba_hip_set_pose_ordering) */
 } ba_options;
 
 typedef struct { /* ba::SolutionSummary<double> + GetErrors, reference :48-70,593-602 */

@@ -425,10 +425,49 @@ typedef struct {
 } ba_hip_dist_plan_stats_t;
 int ba_hip_dist_plan_stats(uint32_t nblk, const uint8_t* nz_lower, int nranks, const char* layout, uint32_t kout,
                            ba_hip_dist_plan_stats_t* out);
-/* Tile pattern of the factor as the engine holds it (nblk x nblk bytes, lower): for the accounting above. */
+/* Tile pattern of the factor as the engine holds it (nblk x nblk bytes, lower): for the accounting above.
+ * With a pose ordering (ba_hip_set_pose_ordering) the pattern is in the order actually factorised. */
 int ba_hip_get_factor_tile_pattern(ba_hip_engine* e, uint32_t nblk, uint8_t* nz_lower);
 /* 1 if the next ba_hip_solve_gn will run the distributed solve, 0 if replicated / single. */
 int ba_hip_solve_is_distributed(ba_hip_engine* e);
+
+/* ---- fill-reducing pose ordering of the reduced camera solve (extension) ------------
+ * The reference factorises S with Eigen's SimplicialLDLT, which applies an AMD ordering
+ * (BundleAdjuster.cpp:752-761).  The engine factorises in the order of the optimisation
+ * indices; with an ordering the poses are renumbered inside the engine at the next
+ * ba_hip_finalize.  Every output indexed by the optimisation index (get_S, get_rhs,
+ * get_delta_gn, get_step and the dumps built from them) stays in NATURAL order (active poses
+ * in pose-id order): the caller never sees the internal one.  AUTO permutes tile-aligned groups
+ * of G = lcm(PoseSize, 64) / PoseSize consecutive poses, keeps the partial last group and the
+ * calibration unknowns last, and keeps the candidate ordering with the fewest tile products
+ * (natural included).  Not available on sharded engines (all-reduce hook, collectives hook or
+ * communicator): a mode other than NATURAL fails there, whichever of the two calls comes second. */
+#define BA_HIP_ORDER_NATURAL 0 /* default: factorise in pose-id order */
+#define BA_HIP_ORDER_AUTO 1    /* tile-aligned group ordering chosen by the engine */
+#define BA_HIP_ORDER_USER 2    /* the permutation of ba_hip_set_pose_permutation */
+typedef struct {
+  int32_t mode;                    /* the mode the last finalize applied */
+  int32_t candidate;               /* AUTO: 0 natural, 1 minimum degree + postorder, 2 minimum degree on pairs of
+                                      groups + postorder, 3 nested dissection */
+  uint32_t group_size;             /* G: poses per tile-aligned group */
+  uint32_t num_groups;             /* ceil(active poses / G) */
+  uint64_t tile_products_natural;  /* AUTO: model tile products of natural order and of the chosen one (the group */
+  uint64_t tile_products_chosen;   /*       graph expanded to tiles; ba_hip_get_structure_stats has the exact count) */
+  double host_ms;                  /* choosing the order on the host */
+  double device_ms;                /* building the group graph on the device */
+} ba_hip_ordering_stats;
+/* Mode of the next ba_hip_finalize (one of BA_HIP_ORDER_*). */
+int ba_hip_set_pose_ordering(ba_hip_engine* e, int mode);
+/* The permutation of BA_HIP_ORDER_USER: opt_of_natural[i] = factorised position of the i-th active
+ * pose; n must equal the active pose count at the next finalize.  Any permutation, aligned or not. */
+int ba_hip_set_pose_permutation(ba_hip_engine* e, const uint32_t* opt_of_natural, uint32_t n);
+/* What the last finalize applied: opt_of_natural (active pose count entries; may be NULL) and the
+ * statistics (may be NULL). */
+int ba_hip_get_pose_ordering(ba_hip_engine* e, uint32_t* opt_of_natural, ba_hip_ordering_stats* st);
+/* The group graph AUTO chose from (CSR over the groups of natural order, symmetric, ascending): call with
+ * NULL arrays for the sizes, then with ptr[num_groups + 1] and adj[num_edges]. */
+int ba_hip_get_pose_group_graph(ba_hip_engine* e, uint32_t* ptr, uint32_t* adj, uint32_t* num_groups,
+                                uint32_t* num_edges);
 
 /* ---- stand-alone kernels exposed for tests and benchmarks ------------------------- */
 /* Dense Cholesky solve of an SPD system given by its LOWER triangle (row-major n x n,
