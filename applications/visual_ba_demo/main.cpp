@@ -13,13 +13,17 @@
 //                                           BundleAdjuster.h:758-759) on a ba::FovCamera whose five parameters
 //                                           (fx, fy, u0, v0, w) start 2-4 % off
 //   visual_ba_demo --ranks N --rank R --comm-id-file F [--device D]
-//   visual_ba_demo --ordering auto          Options::pose_ordering = Auto: prints the ordering statistics
 //                                           one process per GPU: every process holds all poses and the landmarks
 //                                           l with l mod N == R; the class joins the engine-owned RCCL communicator
 //                                           (SetCommunicator; rank 0 writes the 128-byte id to F, the others wait for
 //                                           it) and the reduced solve is distributed over the GPUs — no torch, no hooks
+//   visual_ba_demo --ordering auto          Options::pose_ordering = Auto: prints the ordering statistics
+//   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
+//                                           sigmas) and the median landmark sigma (GetPoseCovariance,
+//                                           GetLandmarkCovariance: selected inverse of the reduced system)
 #include <ba/BundleAdjuster.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -29,7 +33,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -218,6 +222,20 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
     const double before = std::sqrt(0.03 * 0.03 + 0.02 * 0.02 + 0.02 * 0.02);
     ok = ok && std::sqrt(m.t[0] * m.t[0] + m.t[1] * m.t[1] + m.t[2] * m.t[2]) < before;
   }
+  if (shard.covariances) {
+    const ba::MatX c = adjuster.GetPoseCovariance(kPoses - 1);
+    std::vector<double> sl;
+    for (uint32_t l = 0; l < adjuster.GetNumLandmarks(); ++l) {
+      const ba::MatX v = adjuster.GetLandmarkCovariance(l);
+      if (v.rows() == 1) sl.push_back(std::sqrt(v(0, 0)));
+    }
+    if (c.rows() != 6 || sl.empty()) { std::printf("covariances unavailable\n"); return 2; }
+    std::nth_element(sl.begin(), sl.begin() + sl.size() / 2, sl.end());
+    std::printf("pose %d sigma translation %.3e %.3e %.3e  rotation %.3e %.3e %.3e\n", kPoses - 1, std::sqrt(c(0, 0)),
+                std::sqrt(c(1, 1)), std::sqrt(c(2, 2)), std::sqrt(c(3, 3)), std::sqrt(c(4, 4)), std::sqrt(c(5, 5)));
+    std::printf("median landmark sigma (inverse depth) %.3e over %zu landmarks\n", sl[sl.size() / 2], sl.size());
+    ok = ok && std::isfinite(c(0, 0)) && c(0, 0) > 0 && sl[sl.size() / 2] > 0;
+  }
   return ok ? 0 : 1;
 }
 
@@ -226,7 +244,9 @@ int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "--calibrate-extrinsics") == 0) return run<ba::BundleAdjuster<double, 1, 6, 0, true>>(2);
   if (argc > 1 && std::strcmp(argv[1], "--calibrate-fov") == 0) return run<ba::SelfCalBundleAdjuster<double>>(3);
   Shard shard;
-  for (int i = 1; i + 1 < argc; i += 2) {
+  for (int i = 1; i < argc; i += 2) {
+    if (std::strcmp(argv[i], "--covariances") == 0) { shard.covariances = true; --i; continue; }
+    if (i + 1 >= argc) break;
     if (std::strcmp(argv[i], "--ranks") == 0) shard.ranks = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--rank") == 0) shard.rank = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--device") == 0) shard.device = std::atoi(argv[i + 1]);

@@ -68,6 +68,7 @@ SYMBOLS = [
     "ba_adjuster_set_allreduce", "ba_adjuster_set_communicator", "ba_adjuster_solve_is_distributed", "ba_adjuster_set_collectives", "ba_adjuster_create_calib", "ba_adjuster_get_camera_pose",
     "ba_adjuster_get_last_calib_step", "ba_adjuster_get_calibration_marginals", "ba_adjuster_get_camera_params",
     "ba_adjuster_add_camera_fov", "ba_adjuster_get_camera_fov",
+    "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
 ]
 
 _lib = None
@@ -358,6 +359,32 @@ class BundleAdjuster:
         self.L.ba_adjuster_get_calibration_marginals.restype = C.c_uint32
         k = self.L.ba_adjuster_get_calibration_marginals(self.h, c.ctypes.data_as(C.POINTER(C.c_double)))
         return c[:k * k].reshape(k, k)
+
+    def pose_covariance(self, pose_id, other=None):
+        """GetPoseCovariance (or GetPoseCrossCovariance with `other`): PoseSize x PoseSize; raises when
+        unavailable."""
+        D = self.pose_dim
+        c = np.zeros(D * D)
+        cp = c.ctypes.data_as(C.POINTER(C.c_double))
+        if other is None:
+            self.L.ba_adjuster_get_pose_covariance.restype = C.c_uint32
+            k = self.L.ba_adjuster_get_pose_covariance(self.h, int(pose_id), cp)
+        else:
+            self.L.ba_adjuster_get_pose_cross_covariance.restype = C.c_uint32
+            k = self.L.ba_adjuster_get_pose_cross_covariance(self.h, int(pose_id), int(other), cp)
+        if k != D:
+            raise RuntimeError("pose covariance of pose %d unavailable (see stderr)" % pose_id)
+        return c.reshape(D, D)
+
+    def landmark_covariance(self, landmark_id):
+        """GetLandmarkCovariance: LmSize x LmSize; raises when unavailable."""
+        m = self.lm_dim
+        c = np.zeros(m * m)
+        self.L.ba_adjuster_get_landmark_covariance.restype = C.c_uint32
+        k = self.L.ba_adjuster_get_landmark_covariance(self.h, int(landmark_id), c.ctypes.data_as(C.POINTER(C.c_double)))
+        if k != m:
+            raise RuntimeError("landmark covariance of landmark %d unavailable (see stderr)" % landmark_id)
+        return c.reshape(m, m)
 
     def camera_params(self, cam_id=0):
         """rig()->cameras_[cam_id]->GetParams()"""

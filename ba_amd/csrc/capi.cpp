@@ -48,6 +48,7 @@ struct Iface {
   virtual void camera_params(uint32_t cam, double* p4) const = 0;
   virtual void last_calib_step(double* d6) const = 0;
   virtual uint32_t marginals(double* cov) const = 0;
+  virtual uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) = 0;
 };
 
 template <int LM, int PD, bool TVS = false, int CS = 0>
@@ -208,6 +209,12 @@ struct Impl : Iface {
     for (int i = 0; i < m.rows() * m.cols(); ++i) cov[i] = m.data()[i];
     return (uint32_t)m.rows();
   }
+  uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) override {
+    const ba::MatX m = kind == 0 ? ba.GetPoseCovariance(a) : kind == 1 ? ba.GetPoseCrossCovariance(a, b)
+                                                                        : ba.GetLandmarkCovariance(a);
+    for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
+    return (uint32_t)m.rows();
+  }
   void last_calib_step(double* d6) const override {
     const auto& d = ba.GetLastStep().delta_k;
     for (size_t i = 0; i < 6; ++i) d6[i] = i < d.size() ? d[i] : 0.0;
@@ -337,6 +344,13 @@ void ba_adjuster_get_camera_pose(const ba_adjuster* a, uint32_t cam_id, double t
 void ba_adjuster_get_camera_params(const ba_adjuster* a, uint32_t cam_id, double params[4]) { a->p->camera_params(cam_id, params); }
 void ba_adjuster_get_last_calib_step(const ba_adjuster* a, double delta_k[6]) { a->p->last_calib_step(delta_k); }
 uint32_t ba_adjuster_get_calibration_marginals(const ba_adjuster* a, double cov[36]) { return a->p->marginals(cov); }
+uint32_t ba_adjuster_get_pose_covariance(ba_adjuster* a, uint32_t pose_id, double* cov) { return a->p->covariance(0, pose_id, 0, cov); }
+uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, uint32_t pose_b, double* cov) {
+  return a->p->covariance(1, pose_a, pose_b, cov);
+}
+uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov) {
+  return a->p->covariance(2, landmark_id, 0, cov);
+}
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) { a->p->set_allreduce(fn, ctx, rank, nranks); }
 void ba_adjuster_set_communicator(ba_adjuster* a, const void* id128, int rank, int nranks, int distributed_solve) { a->p->set_communicator(id128, rank, nranks, distributed_solve); }
 int ba_adjuster_solve_is_distributed(ba_adjuster* a) { return a->p->solve_is_distributed(); }

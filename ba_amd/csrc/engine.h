@@ -8,6 +8,7 @@
 #include "../../include/ba_hip.h"
 #include "structure.h"
 #include "ordering.h"
+#include "selinv.h"
 #include "dist_plan.h"
 
 namespace bae {
@@ -238,6 +239,16 @@ struct Engine {
   DBuf<int32_t> flags;                   // factorisation status block (k_chol.hip: setup_status_block)
   bool square_attr_set = false;          // k_square / k_rowpanel: dynamic LDS limit raised on this engine's device
   DBuf<double> pivot_floor;              // tol * |S_jj| per row (ba_hip_options::pivot_rel_tolerance)
+  // marginal covariances (ba_hip_compute_marginals, k_selinv.hip): the selected inverse of the last factor,
+  // computed on request only.  sig: one 64x64 slot per lower tile of nzL (selinv.h); the plan is rebuilt when
+  // the pattern changes; sig_valid: sig belongs to the factor currently in A (cleared by every linearisation
+  // and factorisation)
+  DBuf<double> sig;
+  DBuf<uint32_t> sig_slot, sig_col_ptr, sig_col_rows, sig_level_cols, sig_items;
+  SelinvPlan sig_plan;
+  uint64_t sig_plan_version = ~0ull;
+  bool sig_valid = false;
+  ba_hip_marginal_stats mstats = {};
 
   // optional per-kernel timing (ba_hip_set_profiling)
   bool profiling = false;
@@ -329,5 +340,13 @@ void comm_release(Engine* e);
 int check_solve_residual(Engine* e, const double* dS, const double* dx, const double* db, double* out2);
 int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* status, const uint8_t* nz);
 int trailing_marginals(Engine* e, const double* dA, uint32_t ld, uint32_t first, uint32_t K, double* cov);
+// marginal covariances (k_selinv.hip): the selected inverse of the factor in A (no-op while sig_valid); blocks
+// out of it (rows in engine order: out[q] = Sigma[ra[q] .. + Da, rb[q] .. + Db]); landmark blocks (ids: landmark
+// ids, or null for every active landmark by optimisation index); freeing the store
+int marginals_compute(Engine* e);
+int marginals_gather(Engine* e, uint32_t n, const std::vector<uint32_t>& ra, const std::vector<uint32_t>& rb, int Da,
+                     int Db, double* out);
+int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out);
+void marginals_release(Engine* e);
 
 }  // namespace bae

@@ -551,6 +551,7 @@ void ba_hip_destroy(ba_hip_engine* h) {
   REL(frow); REL(diag_blocks); REL(scal); REL(lm_vinv); REL(lm_bl); REL(A); REL(A_keep); REL(rhs_p); REL(rhs_sc); REL(gn_p);
   REL(gn_l); REL(step_p); REL(step_l); REL(invdiag); REL(partials); REL(scalars_out); REL(hist);
   REL(flags); REL(pivot_floor);
+  marginals_release(e);
   REL(pose_active); REL(un_pose); REL(un_t); REL(un_cov_inv); REL(un_scale); REL(un_rot);
   REL(bin_p1); REL(bin_p2); REL(bin_t); REL(bin_cov_inv); REL(bin_cov_inv_sqrt); REL(bin_w); REL(bin_rot);
   REL(imu_p1); REL(imu_p2); REL(imu_ptr); REL(imu_meas); REL(imu_consts); REL(imu_cov_inv);
@@ -1028,6 +1029,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   t_l.mark();
   EventTimer t_s(e);
   e->factored = false;
+  e->sig_valid = false;
   if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) { (void)defer_flush(e); return rc; }
   // copy the reduced rhs into the rhs row of A
   BAE_HIP(hipMemcpyAsync(e->A.p + (size_t)st.ld * st.ld, e->rhs_sc.p, (size_t)st.n * sizeof(double),
@@ -1081,6 +1083,7 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
   // CalculateGn runs only with active poses (BundleAdjuster.cpp:959-964, 1089-1094): with none, the
   // calibration unknowns are not solved for either (delta_k stays empty in the reference)
   const bool skip = st.K && st.Pact == 0;
+  e->sig_valid = false;
   if (skip) BAE_HIP(hipMemsetAsync(e->gn_p.p, 0, e->gn_p.bytes(), e->stream));
   if (st.n > 0 && !skip) {
     if (e->opt.keep_reduced_system) {
@@ -1369,6 +1372,90 @@ int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
       if (e->opt.use_triangular_matrices && block_of(r) > block_of(c)) v = 0.0;
       s_nxn[(size_t)r * n + c] = v;
     }
+  return 0;
+}
+
+// ---- marginal covariances (k_selinv.hip) ----------------------------------------------------------
+static int marginals_ready(Engine* e, const char* what, bool landmarks) {
+  std::string m = std::string(what) + ": ";
+  if (!e->finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
+  if (dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
+  if (landmarks && e->sharded())
+    return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
+  if (!e->factored)
+    return e->fail_msg((m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised "
+                            "since)").c_str());
+  BAE_HIP(hipSetDevice(e->device));
+  return marginals_compute(e);
+}
+static int pose_row(Engine* e, uint32_t id, uint32_t* row, const char* what) {
+  if (id >= e->st.P || e->st.pose_opt[id] < 0) {
+    e->err = std::string(what) + ": pose " + std::to_string(id) + " is not an active pose (it has no columns in S)";
+    return -1;
+  }
+  *row = (uint32_t)e->st.pose_opt[id] * (uint32_t)e->pose_dim;
+  return 0;
+}
+int ba_hip_compute_marginals(ba_hip_engine* h) {
+  ENG(h);
+  return marginals_ready(e, "ba_hip_compute_marginals", false);
+}
+int ba_hip_get_pose_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, double* out) {
+  ENG(h);
+  static const char* what = "ba_hip_get_pose_marginals";
+  int rc;
+  if ((rc = marginals_ready(e, what, false))) return rc;
+  if (n && (!pose_ids || !out)) return e->fail_msg("ba_hip_get_pose_marginals: NULL argument");
+  std::vector<uint32_t> r(n);
+  for (uint32_t i = 0; i < n; ++i)
+    if ((rc = pose_row(e, pose_ids[i], &r[i], what))) return rc;
+  return marginals_gather(e, n, r, r, e->pose_dim, e->pose_dim, out);
+}
+int ba_hip_get_pose_pair_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* a_ids, const uint32_t* b_ids, double* out) {
+  ENG(h);
+  static const char* what = "ba_hip_get_pose_pair_marginals";
+  int rc;
+  if ((rc = marginals_ready(e, what, false))) return rc;
+  if (n && (!a_ids || !b_ids || !out)) return e->fail_msg("ba_hip_get_pose_pair_marginals: NULL argument");
+  std::vector<uint32_t> ra(n), rb(n);
+  for (uint32_t i = 0; i < n; ++i)
+    if ((rc = pose_row(e, a_ids[i], &ra[i], what)) || (rc = pose_row(e, b_ids[i], &rb[i], what))) return rc;
+  return marginals_gather(e, n, ra, rb, e->pose_dim, e->pose_dim, out);
+}
+int ba_hip_get_calibration_block_marginals(ba_hip_engine* h, double* out) {
+  ENG(h);
+  if (!e->st.K) return e->fail_msg("no calibration columns (ba_hip_set_calibration)");
+  int rc;
+  if ((rc = marginals_ready(e, "ba_hip_get_calibration_block_marginals", false))) return rc;
+  std::vector<uint32_t> r(1, e->st.np);
+  return marginals_gather(e, 1, r, r, (int)e->st.K, (int)e->st.K, out);
+}
+int ba_hip_get_landmark_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* lm_ids, double* out) {
+  ENG(h);
+  int rc;
+  if ((rc = marginals_ready(e, "ba_hip_get_landmark_marginals", true))) return rc;
+  if (n && !out) return e->fail_msg("ba_hip_get_landmark_marginals: NULL argument");
+  if (!lm_ids && n != e->st.Lact)
+    return e->fail_msg("ba_hip_get_landmark_marginals: with NULL ids n must be the active landmark count");
+  if (lm_ids)
+    for (uint32_t i = 0; i < n; ++i)
+      if (lm_ids[i] >= e->st.L || e->st.lm_opt[lm_ids[i]] < 0) {
+        e->err = "ba_hip_get_landmark_marginals: landmark " + std::to_string(lm_ids[i]) + " is not an active landmark";
+        return -1;
+      }
+  return marginals_landmarks(e, n, lm_ids, out);
+}
+int ba_hip_get_marginal_stats(ba_hip_engine* h, ba_hip_marginal_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_marginal_stats: NULL argument");
+  *out = e->mstats;
+  return 0;
+}
+int ba_hip_release_marginals(ba_hip_engine* h) {
+  ENG(h);
+  (void)hipSetDevice(e->device);
+  (void)hipStreamSynchronize(e->stream);
+  marginals_release(e);
   return 0;
 }
 

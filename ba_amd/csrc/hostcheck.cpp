@@ -326,3 +326,68 @@ extern "C" uint64_t ba_hostcheck_group_order_products(uint32_t Pact, int D, uint
   std::vector<uint32_t> p(ptr, ptr + ng + 1), a(adj, adj + (ng ? ptr[ng] : 0)), o(order, order + ng);
   return bae::group_order_products(Pact, D, K, p, a, o);
 }
+
+// ---- selected inverse (selinv.h) ------------------------------------------------------------------------
+#include <cmath>
+#include "selinv.h"
+
+// The selected inverse on a dense symmetric n x n matrix S (row-major; n need not be a multiple of 64:
+// the last tile is padded with an identity, as the engine pads A).  The tile pattern is that of S
+// (diagonal tiles always), closed by tile_symbolic_factor.  S is factorised like the engine does —
+// un-pivoted L D L^T, L carrying sqrt|pivot|, D = diag(+-1) — and selinv_host runs on the factor.
+// Out: sigma (n x n, both halves, NaN outside the factor's pattern), nzL (nt x nt lower pattern), the
+// tile products of the plan and its number of levels.  Returns -1 on a zero pivot.
+extern "C" int ba_hostcheck_selinv(uint32_t n, const double* S, double* sigma, uint8_t* nzL_out, uint64_t* products,
+                                   uint32_t* levels) {
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  std::vector<uint8_t> nz((size_t)nt * nt, 0);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c < n; ++c)
+      if (S[(size_t)r * n + c] != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
+  for (uint32_t t = 0; t < nt; ++t) nz[(size_t)t * nt + t] = 1;
+  bae::tile_symbolic_factor(nz, nt);
+  std::vector<double> L((size_t)ld * ld, 0.0), d(ld, 1.0);
+  for (uint32_t r = 0; r < ld; ++r)
+    for (uint32_t c = 0; c <= r; ++c) L[(size_t)r * ld + c] = (r < n && c < n) ? S[(size_t)r * n + c] : (r == c ? 1.0 : 0.0);
+  for (uint32_t j = 0; j < ld; ++j) {
+    double p = L[(size_t)j * ld + j];
+    for (uint32_t k = 0; k < j; ++k) p -= L[(size_t)j * ld + k] * L[(size_t)j * ld + k] * d[k];
+    if (p == 0.0 || !std::isfinite(p)) return -1;
+    d[j] = p < 0.0 ? -1.0 : 1.0;
+    const double ljj = std::sqrt(std::fabs(p));
+    L[(size_t)j * ld + j] = ljj;
+    for (uint32_t i = j + 1; i < ld; ++i) {
+      double s = L[(size_t)i * ld + j];
+      for (uint32_t k = 0; k < j; ++k) s -= L[(size_t)i * ld + k] * d[k] * L[(size_t)j * ld + k];
+      L[(size_t)i * ld + j] = s / (d[j] * ljj);
+    }
+  }
+  // linvT[J] = L_JJ^-T: forward substitution on the identity, stored transposed
+  std::vector<double> linvT((size_t)nt * 4096, 0.0);
+  for (uint32_t J = 0; J < nt; ++J) {
+    const double* Ljj = &L[(size_t)J * 64 * ld + (size_t)J * 64];
+    double* G = &linvT[(size_t)J * 4096];
+    for (uint32_t c = 0; c < 64; ++c)      // column c of L_JJ^-1
+      for (uint32_t r = c; r < 64; ++r) {
+        double s = r == c ? 1.0 : 0.0;
+        for (uint32_t k = c; k < r; ++k) s -= Ljj[(size_t)r * ld + k] * G[(size_t)c * 64 + k];
+        G[(size_t)c * 64 + r] = s / Ljj[(size_t)r * ld + r];  // (L^-1)[r][c] at G[c][r]
+      }
+  }
+  bae::SelinvPlan plan;
+  bae::build_selinv_plan(nz, nt, plan);
+  std::vector<double> store((size_t)plan.n_slots * 4096, 0.0);
+  bae::selinv_host(plan, L.data(), ld, linvT.data(), d.data(), store.data());
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c < n; ++c) sigma[(size_t)r * n + c] = bae::selinv_element(plan, store.data(), r, c);
+  std::copy(nz.begin(), nz.end(), nzL_out);
+  *products = plan.products;
+  *levels = (uint32_t)plan.level_ptr.size() - 1;
+  return 0;
+}
+
+// the tile products formula of the plan on a lower factor pattern
+extern "C" uint64_t ba_hostcheck_selinv_products(uint32_t nt, const uint8_t* nzL) {
+  std::vector<uint8_t> v(nzL, nzL + (size_t)nt * nt);
+  return bae::selinv_tile_products(v, nt);
+}

@@ -103,6 +103,12 @@ class OrderingStats(C.Structure):
                 ("host_ms", C.c_double), ("device_ms", C.c_double)]
 
 
+class MarginalStats(C.Structure):
+    _fields_ = [("selinv_ms", C.c_double), ("landmark_ms", C.c_double), ("tile_products", C.c_uint64),
+                ("factor_tile_products", C.c_uint64), ("store_bytes", C.c_double), ("store_tiles", C.c_uint32),
+                ("levels", C.c_uint32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
 
@@ -126,6 +132,9 @@ SYMBOLS = [
     "ba_hip_integrate_imu_jacobians", "ba_hip_imu_pose_derivative", "ba_hip_imu_integrate_pose", "ba_hip_lie",
     "ba_hip_get_comm_stats", "ba_hip_reset_comm_stats", "ba_hip_dist_plan_stats", "ba_hip_get_factor_tile_pattern",
     "ba_hip_set_pose_ordering", "ba_hip_set_pose_permutation", "ba_hip_get_pose_ordering", "ba_hip_get_pose_group_graph",
+    "ba_hip_compute_marginals", "ba_hip_get_pose_marginals", "ba_hip_get_pose_pair_marginals",
+    "ba_hip_get_calibration_block_marginals", "ba_hip_get_landmark_marginals", "ba_hip_get_marginal_stats",
+    "ba_hip_release_marginals",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -347,6 +356,57 @@ class Engine:
         c = np.empty((k, k))
         self._chk(self.L.ba_hip_get_calibration_marginals(self.h, _p(c, dp)))
         return c
+
+    # ---- marginal covariances (selected inverse of the last factor; ba_hip.h) ----
+    def compute_marginals(self):
+        self._chk(self.L.ba_hip_compute_marginals(self.h))
+
+    def pose_marginals(self, ids):
+        """(n, D, D) covariances of the poses `ids` (caller's pose ids)."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32)
+        D = self.pose_dim
+        out = np.empty((len(ids), D, D))
+        self._chk(self.L.ba_hip_get_pose_marginals(self.h, len(ids), _p(ids, u32p), _p(out, dp)))
+        return out
+
+    def pose_pair_marginals(self, a, b):
+        """(n, D, D) cross covariances Cov(a_i, b_i)."""
+        a = np.ascontiguousarray(np.atleast_1d(a), dtype=np.uint32)
+        b = np.ascontiguousarray(np.atleast_1d(b), dtype=np.uint32)
+        if a.shape != b.shape:
+            raise ValueError("pose_pair_marginals: a and b differ in length")
+        D = self.pose_dim
+        out = np.empty((len(a), D, D))
+        self._chk(self.L.ba_hip_get_pose_pair_marginals(self.h, len(a), _p(a, u32p), _p(b, u32p), _p(out, dp)))
+        return out
+
+    def calibration_block_marginals(self):
+        """K x K calibration block read from the selected inverse."""
+        k = self.num_calib_params()
+        c = np.empty((k, k))
+        self._chk(self.L.ba_hip_get_calibration_block_marginals(self.h, _p(c, dp)))
+        return c
+
+    def landmark_marginals(self, ids=None):
+        """(n, LM, LM) landmark covariances; ids=None: every active landmark by optimisation index."""
+        lm = self.lm_dim
+        if ids is None:
+            n = self.num_lm_params() // max(lm, 1)
+            out = np.empty((n, lm, lm))
+            self._chk(self.L.ba_hip_get_landmark_marginals(self.h, n, None, _p(out, dp)))
+            return out
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32)
+        out = np.empty((len(ids), lm, lm))
+        self._chk(self.L.ba_hip_get_landmark_marginals(self.h, len(ids), _p(ids, u32p), _p(out, dp)))
+        return out
+
+    def marginal_stats(self):
+        st = MarginalStats()
+        self._chk(self.L.ba_hip_get_marginal_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in MarginalStats._fields_}
+
+    def release_marginals(self):
+        self._chk(self.L.ba_hip_release_marginals(self.h))
 
     def set_landmark_ref_pixels(self, z_ref):
         z = _d(z_ref).reshape(-1, 2)

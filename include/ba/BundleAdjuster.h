@@ -460,6 +460,31 @@ class BundleAdjuster {
     }
     return last_step_;
   }
+  // Marginal covariances of the system the last Solve() factorised (extension; selected inverse of the
+  // reduced system on the device, include/ba_hip.h ba_hip_get_pose_marginals): kPoseDim x kPoseDim /
+  // kLmDim x kLmDim in the tangent coordinates of the step.  Valid until the next linearisation; a 0 x 0
+  // matrix, reported through Check(), when unavailable (no solve yet, an inactive pose or landmark, the
+  // distributed solve, a cross covariance outside the factor's pattern).
+  MatX GetPoseCovariance(uint32_t pose_id) {
+    MatX m((int)kPoseDim, (int)kPoseDim);
+    if (!engine_ || !Check(ba_hip_get_pose_marginals(engine_, 1, &pose_id, m.data()), "ba_hip_get_pose_marginals"))
+      return MatX();
+    return m;
+  }
+  MatX GetPoseCrossCovariance(uint32_t pose_a, uint32_t pose_b) {
+    MatX m((int)kPoseDim, (int)kPoseDim);
+    if (!engine_ || !Check(ba_hip_get_pose_pair_marginals(engine_, 1, &pose_a, &pose_b, m.data()),
+                           "ba_hip_get_pose_pair_marginals"))
+      return MatX();
+    return m;
+  }
+  MatX GetLandmarkCovariance(uint32_t landmark_id) {
+    MatX m((int)kLmDim, (int)kLmDim);
+    if (!engine_ || !Check(ba_hip_get_landmark_marginals(engine_, 1, &landmark_id, m.data()),
+                           "ba_hip_get_landmark_marginals"))
+      return MatX();
+    return m;
+  }
   Scalar trust_region_size() const { return trust_region_size_; }
   const ba_hip_timers& GetLastTimers() const { return last_timers_; }
   uint32_t iterations_run() const { return iterations_run_; }

@@ -118,6 +118,12 @@ double ba_adjuster_get_camera_fov(const ba_adjuster* a, uint32_t cam_id);
 /* SolutionSummary::calibration_marginals (6 x 6, row-major) of the last iteration; returns its
  * dimension (0 when the option was off or the adjuster has no calibration unknowns) */
 uint32_t ba_adjuster_get_calibration_marginals(const ba_adjuster* a, double cov[36]);
+/* GetPoseCovariance / GetPoseCrossCovariance / GetLandmarkCovariance (extension): PoseSize^2 or LmSize^2
+ * values row-major into cov; returns the dimension, 0 when unavailable (the summary's result then reads
+ * SolverError) */
+uint32_t ba_adjuster_get_pose_covariance(ba_adjuster* a, uint32_t pose_id, double* cov);
+uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, uint32_t pose_b, double* cov);
+uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov);
 /* GetLastStep().delta_k (zeros without do_tvs) */
 void ba_adjuster_get_last_calib_step(const ba_adjuster* a, double delta_k[6]);
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks);

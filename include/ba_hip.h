@@ -469,6 +469,48 @@ int ba_hip_get_pose_ordering(ba_hip_engine* e, uint32_t* opt_of_natural, ba_hip_
 int ba_hip_get_pose_group_graph(ba_hip_engine* e, uint32_t* ptr, uint32_t* adj, uint32_t* num_groups,
                                 uint32_t* num_edges);
 
+/* ---- marginal covariances (selected inverse of the reduced system) ------------------ */
+/* Blocks of Sigma = S^-1 for the system the last ba_hip_solve_gn factorised (the last linearisation:
+ * Huber weights, masks and pose-pose terms included — the system ba_hip_get_calibration_marginals
+ * reads), in the tangent coordinates of the step, with a pose's layout of its entries of delta_p
+ * (ba_hip_get_step).  Computed on the device from the factor by a selected inversion (the tiles of
+ * S^-1 on the factor's tile pattern, kept in a store of their own; the factor, the kept S and the
+ * calibration marginals are untouched).  Nothing is computed or allocated before the first request.
+ *   - Pose ids and landmark ids are the caller's ids; an inactive pose or landmark is an error.
+ *   - Masked parameters carry 1e6 on the diagonal of S: their variance reads ~1e-6.
+ *   - Valid until the next ba_hip_linearize; after it every call is an error.
+ *   - Pose orderings (BA_HIP_ORDER_AUTO / USER) are invisible: results are those of natural order.
+ *   - Refused with the distributed solve; landmark blocks are also refused on sharded engines (each
+ *     rank holds only its landmark shard), pose blocks are not (every rank holds the whole factor). */
+typedef struct {
+  double selinv_ms;              /* device time of the last selected inversion */
+  double landmark_ms;            /* device time of the last landmark pass */
+  uint64_t tile_products;        /* 64x64x64 tile products of the selected inverse: sum_J |R_J|^2 + tiles */
+  uint64_t factor_tile_products; /* the factorisation's, for comparison (ba_hip_structure_stats) */
+  double store_bytes;            /* bytes of the Sigma store */
+  uint32_t store_tiles;          /* 64x64 tiles in it */
+  uint32_t levels;               /* launch pairs of the schedule (levels of the elimination tree) */
+} ba_hip_marginal_stats;
+/* The selected inverse of the current factor; a no-op when it is already there. */
+int ba_hip_compute_marginals(ba_hip_engine* e);
+/* out: n x D x D row-major (D = PoseSize), the covariance of each pose. */
+int ba_hip_get_pose_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* pose_ids, double* out);
+/* out: n x D x D, Cov(a_i, b_i) (rows: pose a_i, columns: pose b_i).  Available when all tiles of the
+ * block lie in the factor's pattern — always for poses that share a landmark or a pose-pose residual;
+ * otherwise an error. */
+int ba_hip_get_pose_pair_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* a_ids, const uint32_t* b_ids,
+                                   double* out);
+/* out: K x K, the calibration block of Sigma (K = ba_hip_set_calibration's unknowns), read from the store:
+ * the same block ba_hip_get_calibration_marginals computes from the diagonal tiles. */
+int ba_hip_get_calibration_block_marginals(ba_hip_engine* e, double* out);
+/* out: n x LmSize x LmSize, Sigma_ll = V^-1 + V^-1 W^T Sigma_pp W V^-1 (the (l, l) block of the inverse of
+ * the full poses + landmarks system) in the coordinates of delta_l (inverse depth for LmSize 1, x_w for
+ * LmSize 3).  lm_ids NULL: every active landmark, by optimisation index (n = active landmark count). */
+int ba_hip_get_landmark_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* lm_ids, double* out);
+int ba_hip_get_marginal_stats(ba_hip_engine* e, ba_hip_marginal_stats* out);
+/* Frees the Sigma store (also freed with the engine). */
+int ba_hip_release_marginals(ba_hip_engine* e);
+
 /* ---- stand-alone kernels exposed for tests and benchmarks ------------------------- */
 /* Dense Cholesky solve of an SPD system given by its LOWER triangle (row-major n x n,
  * host memory): x = A^-1 b.  Runs the same kernels ba_hip_solve_gn uses. */
