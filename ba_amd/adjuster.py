@@ -69,6 +69,7 @@ SYMBOLS = [
     "ba_adjuster_get_last_calib_step", "ba_adjuster_get_calibration_marginals", "ba_adjuster_get_camera_params",
     "ba_adjuster_add_camera_fov", "ba_adjuster_get_camera_fov",
     "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
+    "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
 ]
 
 _lib = None
@@ -359,6 +360,49 @@ class BundleAdjuster:
         self.L.ba_adjuster_get_calibration_marginals.restype = C.c_uint32
         k = self.L.ba_adjuster_get_calibration_marginals(self.h, c.ctypes.data_as(C.POINTER(C.c_double)))
         return c[:k * k].reshape(k, k)
+
+    def Marginalize(self, pose_ids, lm_ids=()):
+        """ba::BundleAdjuster::Marginalize after a Solve(): a dict with pose_ids (the blanket), x0 (|B| x 16), H, b,
+        c and dropped_projection.  Raises RuntimeError when refused."""
+        m = np.ascontiguousarray(pose_ids, dtype=np.uint32)
+        l = np.ascontiguousarray(lm_ids, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        nb = C.c_uint32(0)
+        rc = self.L.ba_adjuster_marginalize(self.h, len(m), m.ctypes.data_as(u32p) if len(m) else None, len(l),
+                                            l.ctypes.data_as(u32p) if len(l) else None, C.byref(nb))
+        if rc != 0:
+            raise RuntimeError("Marginalize refused (see stderr)")
+        n, D = nb.value, self.pose_dim
+        ids = np.zeros(max(n, 1), dtype=np.uint32)
+        x0 = np.zeros((max(n, 1), 16))
+        H = np.zeros((max(n * D, 1), max(n * D, 1)))
+        b = np.zeros(max(n * D, 1))
+        c = C.c_double(0.0)
+        dr = C.c_uint32(0)
+        dp = C.POINTER(C.c_double)
+        self.L.ba_adjuster_get_marginalization(self.h, ids.ctypes.data_as(u32p), x0.ctypes.data_as(dp),
+                                               H.ctypes.data_as(dp), b.ctypes.data_as(dp), C.byref(c), C.byref(dr))
+        return {"pose_ids": ids[:n], "x0": x0[:n], "H": H[:n * D, :n * D], "b": b[:n * D], "c": c.value,
+                "dropped_projection": dr.value}
+
+    def AddDensePrior(self, pose_ids, prior):
+        """ba::BundleAdjuster::AddDensePrior: pose_ids of this problem, in the order of prior["pose_ids"]."""
+        ids = np.ascontiguousarray(pose_ids, dtype=np.uint32)
+        x0 = np.ascontiguousarray(prior["x0"], dtype=np.float64)
+        H = np.ascontiguousarray(prior["H"], dtype=np.float64)
+        b = np.ascontiguousarray(prior["b"], dtype=np.float64)
+        k, D = len(ids), self.pose_dim
+        if (k == 0 or len(prior["pose_ids"]) != k or x0.size != 16 * k or H.size != (k * D) ** 2 or
+                b.size != k * D):
+            raise RuntimeError("AddDensePrior: the sizes of the prior do not match its %d poses" % k)
+        dp = C.POINTER(C.c_double)
+        self.L.ba_adjuster_add_dense_prior.restype = C.c_uint32
+        r = self.L.ba_adjuster_add_dense_prior(self.h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               x0.ctypes.data_as(dp), H.ctypes.data_as(dp), b.ctypes.data_as(dp),
+                                               C.c_double(float(prior["c"])))
+        if r == 0xFFFFFFFF:
+            raise RuntimeError("AddDensePrior refused (see stderr)")
+        return r
 
     def pose_covariance(self, pose_id, other=None):
         """GetPoseCovariance (or GetPoseCrossCovariance with `other`): PoseSize x PoseSize; raises when

@@ -49,6 +49,10 @@ struct Iface {
   virtual void last_calib_step(double* d6) const = 0;
   virtual uint32_t marginals(double* cov) const = 0;
   virtual uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) = 0;
+  virtual int marginalize(uint32_t nm, const uint32_t* m, uint32_t nl, const uint32_t* l, uint32_t* nb) = 0;
+  virtual void marginalization(uint32_t* ids, double* x0, double* H, double* b, double* c, uint32_t* dropped) const = 0;
+  virtual uint32_t add_dense_prior(uint32_t k, const uint32_t* ids, const double* x0, const double* H, const double* b,
+                                   double c) = 0;
 };
 
 template <int LM, int PD, bool TVS = false, int CS = 0>
@@ -209,6 +213,33 @@ struct Impl : Iface {
     for (int i = 0; i < m.rows() * m.cols(); ++i) cov[i] = m.data()[i];
     return (uint32_t)m.rows();
   }
+  ba::DensePosePrior marg;  // the last Marginalize() result
+  int marginalize(uint32_t nm, const uint32_t* m, uint32_t nl, const uint32_t* l, uint32_t* nb) override {
+    ba::DensePosePrior r;
+    if (!ba.Marginalize(std::vector<uint32_t>(m, m + nm), std::vector<uint32_t>(l, l + nl), &r)) return 1;
+    marg = std::move(r);
+    if (nb) *nb = (uint32_t)marg.pose_ids.size();
+    return 0;
+  }
+  void marginalization(uint32_t* ids, double* x0, double* H, double* b, double* c, uint32_t* dropped) const override {
+    if (ids) std::copy(marg.pose_ids.begin(), marg.pose_ids.end(), ids);
+    if (x0) std::copy(marg.x0.begin(), marg.x0.end(), x0);
+    if (H) std::copy(marg.H.begin(), marg.H.end(), H);
+    if (b) std::copy(marg.b.begin(), marg.b.end(), b);
+    if (c) *c = marg.c;
+    if (dropped) *dropped = marg.dropped_projection;
+  }
+  uint32_t add_dense_prior(uint32_t k, const uint32_t* ids, const double* x0, const double* H, const double* b,
+                           double c) override {
+    const size_t kD = (size_t)k * PD;
+    ba::DensePosePrior p;
+    p.pose_ids.assign(ids, ids + k);
+    p.x0.assign(x0, x0 + 16 * (size_t)k);
+    p.H.assign(H, H + kD * kD);
+    p.b.assign(b, b + kD);
+    p.c = c;
+    return ba.AddDensePrior(p.pose_ids, p);
+  }
   uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) override {
     const ba::MatX m = kind == 0 ? ba.GetPoseCovariance(a) : kind == 1 ? ba.GetPoseCrossCovariance(a, b)
                                                                         : ba.GetLandmarkCovariance(a);
@@ -350,6 +381,20 @@ uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, 
 }
 uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov) {
   return a->p->covariance(2, landmark_id, 0, cov);
+}
+int ba_adjuster_marginalize(ba_adjuster* a, uint32_t nm, const uint32_t* pose_ids, uint32_t nl,
+                            const uint32_t* landmark_ids, uint32_t* blanket_poses) {
+  if ((nm && !pose_ids) || (nl && !landmark_ids)) return 1;
+  return a->p->marginalize(nm, pose_ids, nl, landmark_ids, blanket_poses);
+}
+void ba_adjuster_get_marginalization(const ba_adjuster* a, uint32_t* pose_ids, double* x0_16, double* H, double* b,
+                                     double* c, uint32_t* dropped_projection) {
+  a->p->marginalization(pose_ids, x0_16, H, b, c, dropped_projection);
+}
+uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t* pose_ids, const double* x0_16,
+                                     const double* H, const double* b, double c) {
+  if (!k || !pose_ids || !x0_16 || !H || !b) return UINT32_MAX;
+  return a->p->add_dense_prior(k, pose_ids, x0_16, H, b, c);
 }
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) { a->p->set_allreduce(fn, ctx, rank, nranks); }
 void ba_adjuster_set_communicator(ba_adjuster* a, const void* id128, int rank, int nranks, int distributed_solve) { a->p->set_communicator(id128, rank, nranks, distributed_solve); }

@@ -9,6 +9,7 @@
 #include "structure.h"
 #include "ordering.h"
 #include "selinv.h"
+#include "marg.h"
 #include "dist_plan.h"
 
 namespace bae {
@@ -249,6 +250,27 @@ struct Engine {
   uint64_t sig_plan_version = ~0ull;
   bool sig_valid = false;
   ba_hip_marginal_stats mstats = {};
+  // dense pose priors (ba_hip_set_dense_priors, k_marg.hip): the caller's priors, their device copies (uploaded
+  // by ba_hip_finalize), the lower D x D blocks of every prior (dp_blk, prior q from dp_blk_first[q]) and the
+  // per-linearisation values: d, J_d, G = J_d^T H J_d, g = J_d^T (b - H d), w = b - H d, E_p
+  DensePriors dpri;
+  std::vector<uint32_t> dp_blk_first;
+  DBuf<uint32_t> dp_ptr, dp_pose;
+  DBuf<double> dp_x0, dp_H, dp_b, dp_c;
+  DBuf<unsigned long long> dp_hoff;
+  DBuf<uint2> dp_blk;
+  DBuf<double> dp_d, dp_J, dp_G, dp_g, dp_w, dp_E, dp_E_eval, dp_jr;
+  const double* dp_E_last = nullptr;    // E_p of the last linearisation or evaluation (ba_hip_get_prior_errors)
+  double prior_err_h = 0.0, prior_jrhs_h = 0.0;
+  // marginalisation (ba_hip_marginalize): lin_valid = the device holds the last linearisation at the current
+  // state (cleared by every step, rollback, new masks or solve); pp_err_lin: the pose-pose errors of it
+  bool lin_valid = false;
+  DBuf<double> pp_err_lin;
+  std::vector<uint16_t> mask_host;       // the masks of the last ba_hip_set_pose_masks, by pose id
+  bool marg_valid = false;
+  std::vector<uint32_t> marg_ids;        // the blanket, by pose id
+  std::vector<double> marg_x0, marg_H, marg_b;
+  double marg_c = 0.0;
 
   // optional per-kernel timing (ba_hip_set_profiling)
   bool profiling = false;
@@ -348,5 +370,11 @@ int marginals_gather(Engine* e, uint32_t n, const std::vector<uint32_t>& ra, con
                      int Db, double* out);
 int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out);
 void marginals_release(Engine* e);
+// dense priors and marginalisation (k_marg.hip): upload at finalize; linearise (mode 1: into A, rhs_p, rhs_p_sc) or
+// evaluate (mode 0) every prior at the current state, E_p summed into *err_host; the dogleg term; one marginalisation
+int priors_upload(Engine* e);
+int launch_priors(Engine* e, int mode, double* err_host);
+int launch_priors_jrhs(Engine* e, double* out);
+int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& lmask, double tol, double* dev_ms);
 
 }  // namespace bae

@@ -146,6 +146,11 @@ int order_poses(Engine* e, std::vector<uint64_t>* proj_edges, double device_ms) 
     };
     for (uint32_t i = 0; i < pb.num_binary; ++i) pair(pb.bin_p1[i], pb.bin_p2[i]);
     for (uint32_t i = 0; i < pb.num_imu; ++i) pair(pb.imu_p1[i], pb.imu_p2[i]);
+    // a dense prior couples every pair of its poses
+    const DensePriors& pr = e->dpri;
+    for (uint32_t q = 0; q < pr.count(); ++q)
+      for (uint32_t k = pr.ptr[q]; k < pr.ptr[q + 1]; ++k)
+        for (uint32_t k2 = pr.ptr[q]; k2 < k; ++k2) pair(pr.pose[k], pr.pose[k2]);
     group_graph_csr(ng, std::move(edges), e->group_ptr, e->group_adj);
     OrderingResult r;
     choose_pose_ordering(Pact, D, (uint32_t)e->calib_dim, e->group_ptr, e->group_adj, e->opt_of_natural, &r);
@@ -231,6 +236,8 @@ static int build_structure(Engine* e) {
   }
 
   stage("pose-pose lists");
+  int rc;
+  if ((rc = priors_upload(e))) return rc;
   // ---- 64x64-tile pattern of S (for the tile-sparse factorisation): build_lists marked the tiles
   // of the projection part and the diagonal; add the pose-pose residual blocks ------------------------
   {
@@ -246,6 +253,14 @@ static int build_structure(Engine* e) {
       const int32_t o2 = res_p2[s] != 0xffffffffu ? st.pose_opt[res_p2[s]] : -1;
       if (o1 >= 0 && o2 >= 0) mark((uint32_t)o1, (uint32_t)o2);
     }
+    // dense priors: every block of their clique
+    const DensePriors& pr = e->dpri;
+    for (uint32_t q = 0; q < pr.count(); ++q)
+      for (uint32_t k = pr.ptr[q]; k < pr.ptr[q + 1]; ++k)
+        for (uint32_t k2 = pr.ptr[q]; k2 <= k; ++k2) {
+          const int32_t o1 = st.pose_opt[pr.pose[k]], o2 = st.pose_opt[pr.pose[k2]];
+          if (o1 >= 0 && o2 >= 0) mark((uint32_t)o1, (uint32_t)o2);
+        }
     // calibration border: rows np .. np + K - 1 are dense (every pose with a projection residual
     // couples to T_vs, BundleAdjuster.cpp:501-518)
     if (st.K)
@@ -256,7 +271,6 @@ static int build_structure(Engine* e) {
 
   stage("tile pattern");
   // ---- upload ------------------------------------------------------------------------------
-  int rc;
 #define UP(buf, vec) if ((rc = upload(e, e->buf, vec))) return rc
   if (host_build) {
     UP(pose_opt, st.pose_opt); UP(lm_opt, st.lm_opt);
@@ -306,6 +320,7 @@ static int build_structure(Engine* e) {
     BAE_HIP(e->pp_h.alloc(nr1 * 3 * 225)); BAE_HIP(e->pp_g.alloc(nr1 * 30));
     BAE_HIP(e->pp_dz.alloc(nr1 * 2 * 225)); BAE_HIP(e->pp_info.alloc(nr1 * 225));
     BAE_HIP(e->pp_err.alloc(nr1));
+    BAE_HIP(e->pp_err_lin.alloc(nr1));
     BAE_HIP(e->imu_cov_inv.alloc(std::max<size_t>(ni, 1) * 225));
     BAE_HIP(hipMemsetAsync(e->imu_cov_inv.p, 0, e->imu_cov_inv.bytes(), e->stream));
   }
@@ -556,7 +571,9 @@ void ba_hip_destroy(ba_hip_engine* h) {
   REL(bin_p1); REL(bin_p2); REL(bin_t); REL(bin_cov_inv); REL(bin_cov_inv_sqrt); REL(bin_w); REL(bin_rot);
   REL(imu_p1); REL(imu_p2); REL(imu_ptr); REL(imu_meas); REL(imu_consts); REL(imu_cov_inv);
   REL(pp_h); REL(pp_g); REL(pp_dz); REL(pp_info); REL(pp_err); REL(pp_ptr); REL(pp_res_p1);
-  REL(pp_res_p2); REL(pp_ent);
+  REL(pp_res_p2); REL(pp_ent); REL(pp_err_lin);
+  REL(dp_ptr); REL(dp_pose); REL(dp_x0); REL(dp_H); REL(dp_b); REL(dp_c); REL(dp_hoff); REL(dp_blk);
+  REL(dp_d); REL(dp_J); REL(dp_G); REL(dp_g); REL(dp_w); REL(dp_E); REL(dp_E_eval); REL(dp_jr);
 #undef REL
   comm_release(e);
   if (e->ev_imu_done) { (void)hipEventDestroy(e->ev_imu_done); (void)hipEventDestroy(e->ev_imu_start); }
@@ -920,6 +937,8 @@ int ba_hip_finalize(ba_hip_engine* h) {
   e->opt_of_natural.clear();
   e->group_ptr.clear(); e->group_adj.clear();
   e->order_stats = ba_hip_ordering_stats();
+  e->lin_valid = false;
+  e->mask_host.assign(pb.num_poses, 0);
   int rc = build_structure(e);
   if (rc) return rc;
   e->finalized = true;
@@ -947,6 +966,7 @@ int ba_hip_begin_solve(ba_hip_engine* h) {
   e->dog_jrhs_valid = false;
   e->err_cache_clear();   // x_s is re-derived from x_w, the cameras may have been re-uploaded
   e->err_cache_off = getenv("BA_HIP_NO_ERR_CACHE") != nullptr;
+  e->lin_valid = false;
   BAE_HIP(hipSetDevice(e->device));
   if (!e->prob.pose_cam_params.empty() && e->prob.pose_cam_params.size() != 4 * (size_t)e->prob.num_poses)
     return e->fail_msg("per-pose camera parameters: one [fx,fy,u0,v0] per pose expected");
@@ -971,6 +991,8 @@ int ba_hip_set_pose_masks(ba_hip_engine* h, uint32_t n, const uint16_t* masks) {
   NEED_FINAL();
   if (n != e->st.P) return e->fail_msg("mask count != pose count");
   e->dog_jrhs_valid = false;
+  e->lin_valid = false;
+  e->mask_host.assign(masks, masks + n);
   return set_masks_device(e, std::vector<uint16_t>(masks, masks + n));
 }
 
@@ -1031,6 +1053,12 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   e->factored = false;
   e->sig_valid = false;
   if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) { (void)defer_flush(e); return rc; }
+  // dense priors after k_pp_scatter, in prior order; their E_p is folded into unary_error
+  e->lin_valid = false;
+  if ((rc = launch_priors(e, 1, &e->prior_err_h))) { (void)defer_flush(e); return rc; }
+  if (e->prob.num_unary + e->prob.num_binary + e->prob.num_imu)  // kept for ba_hip_marginalize (the dogleg reuses pp_err)
+    BAE_HIP(hipMemcpyAsync(e->pp_err_lin.p, e->pp_err.p, (size_t)(e->prob.num_unary + e->prob.num_binary + e->prob.num_imu) *
+                           sizeof(double), hipMemcpyDeviceToDevice, e->stream));
   // copy the reduced rhs into the rhs row of A
   BAE_HIP(hipMemcpyAsync(e->A.p + (size_t)st.ld * st.ld, e->rhs_sc.p, (size_t)st.n * sizeof(double),
                          hipMemcpyDeviceToDevice, e->stream));
@@ -1068,7 +1096,8 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   e->timers.j_evaluation = t_j.read_ms() + t_l.read_ms();
   e->timers.robust_weights = t_r.read_ms();
   e->timers.jtj_schur = t_s.read_ms();
-  errs.proj_error = hs[0]; errs.unary_error = hs[1]; errs.binary_error = hs[2]; errs.inertial_error = hs[3];
+  errs.proj_error = hs[0]; errs.unary_error = hs[1] + e->prior_err_h; errs.binary_error = hs[2]; errs.inertial_error = hs[3];
+  e->lin_valid = true;
   if (out) *out = errs;
   return 0;
 }
@@ -1117,12 +1146,13 @@ int ba_hip_dogleg_terms(ba_hip_engine* h, int gn_available, ba_hip_dogleg_scalar
   defer_begin(e);
   int rc = launch_dogleg(e, gn_available, dh, reuse);
   if (!rc && !reuse) rc = launch_posepose_jrhs(e, dh + 7);
+  if (!rc && !reuse) rc = launch_priors_jrhs(e, &e->prior_jrhs_h);
   const int rf = defer_flush(e);
   if (rc || rf) { e->dog_jrhs_valid = false; return rc ? rc : rf; }
   e->dog_jrhs_valid = true;
   out->rhs_p_sq = dh[0]; out->gn_p_sq = dh[1]; out->rhs_gn_p = dh[2];
   out->rhs_l_sq = dh[3]; out->gn_l_sq = dh[4]; out->rhs_gn_l = dh[5];
-  out->j_rhs_sq = dh[6] + dh[7];
+  out->j_rhs_sq = dh[6] + dh[7] + e->prior_jrhs_h;
   if (e->st.K && (rc = launch_calib_dogleg(e, gn_available, out))) return rc;
   return 0;
 }
@@ -1149,6 +1179,7 @@ int ba_hip_apply_step(ba_hip_engine* h) {
   if (rc) return rc;
   e->cur = 1 - e->cur;
   e->has_snapshot = true;
+  e->lin_valid = false;
   e->obs_e_valid[e->cur] = false;   // a new state in this buffer: no evaluation of it yet
   if (e->calib_dim && !e->calib_tvs && e->st.C > 0) {
     // BundleAdjuster.cpp:46-69: params of camera 0 -= delta_k, then every x_s ray is re-derived from
@@ -1193,6 +1224,7 @@ int ba_hip_rollback(ba_hip_engine* h) {
   BAE_HIP(hipSetDevice(e->device));
   e->cur = 1 - e->cur;
   e->has_snapshot = false;
+  e->lin_valid = false;
   int rc;
   if (e->calib_tvs) {
     // the reference restores the poses WITH their cached T_sw but not the rig (:1060-1068): the
@@ -1223,9 +1255,10 @@ int ba_hip_eval_residuals(ba_hip_engine* h, ba_hip_errors* out) {
   int rc = launch_residuals(e, 1);
   if (!rc) rc = sum_partials(e, (e->st.O + 255) / 256, 1, hs);
   if (!rc) rc = launch_posepose_eval(e, hs + 1);
+  if (!rc) rc = launch_priors(e, 0, &e->prior_err_h);
   const int rf = defer_flush(e);
   if (rc || rf) return rc ? rc : rf;
-  errs.proj_error = hs[0]; errs.unary_error = hs[1]; errs.binary_error = hs[2]; errs.inertial_error = hs[3];
+  errs.proj_error = hs[0]; errs.unary_error = hs[1] + e->prior_err_h; errs.binary_error = hs[2]; errs.inertial_error = hs[3];
   e->timers.evaluate_residuals = t.stop_ms();
   if (out) *out = errs;
   return 0;
@@ -1600,6 +1633,17 @@ int ba_hip_get_imu_errors(ba_hip_engine* h, double* mahalanobis) {
   return 0;
 }
 
+int ba_hip_set_unary_scales(ba_hip_engine* h, uint32_t n, const double* scale) {
+  ENG(h);
+  NEED_FINAL();
+  if (n != e->prob.num_unary || (n && !scale)) return e->fail_msg("ba_hip_set_unary_scales: one scale per unary residual expected");
+  if (!n) return 0;
+  BAE_HIP(hipSetDevice(e->device));
+  BAE_HIP(hipMemcpyAsync(e->un_scale.p, scale, n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 int ba_hip_get_unary_scales(ba_hip_engine* h, double* scale) {
   ENG(h);
   NEED_FINAL();
@@ -1810,6 +1854,126 @@ int ba_hip_set_allreduce(ba_hip_engine* h, ba_hip_allreduce_fn fn, void* ctx, in
   e->nzL_valid = false;  // the tile pattern of S is the union over the shards
   e->dist_plan_version = ~0ull;
   e->dog_jrhs_valid = false;  // a local sum may have become a cross-shard one
+  return 0;
+}
+
+// ---- dense pose priors and marginalisation (k_marg.hip, marg.h) --------------------------------------
+int ba_hip_set_dense_priors(ba_hip_engine* h, uint32_t n, const uint32_t* ptr, const uint32_t* pose_ids,
+                            const double* x0_16, const double* H, const double* b, const double* c) {
+  ENG(h);
+  const int D = e->pose_dim;
+  if (n && (!ptr || !pose_ids || !x0_16 || !H || !b || !c)) return e->fail_msg("ba_hip_set_dense_priors: NULL argument");
+  if (n == 0) {  // removes the priors
+    e->dpri = DensePriors();
+    e->finalized = false;
+    return 0;
+  }
+  if (ptr[0] != 0) return e->fail_msg("ba_hip_set_dense_priors: ptr[0] must be 0");
+  for (uint32_t q = 0; q < n; ++q)
+    if (ptr[q + 1] <= ptr[q]) return e->fail_msg("ba_hip_set_dense_priors: every prior needs at least one pose");
+  DensePriors pr;
+  pr.ptr.assign(ptr, ptr + n + 1);
+  const uint32_t ktot = pr.ptr.back();
+  for (uint32_t q = 0; q < n; ++q)
+    if ((uint64_t)(ptr[q + 1] - ptr[q]) * D > kMargMaxB)
+      return e->fail_msg("ba_hip_set_dense_priors: a prior exceeds 4096 unknowns");
+  pr.pose.assign(pose_ids, pose_ids + ktot);
+  pr.x0.assign(x0_16, x0_16 + (size_t)ktot * kPoseState);
+  pr.offsets(D);
+  pr.H.assign(H, H + pr.h_off[n]);
+  // E_p only sees the symmetric part of H: keep (H + H^T) / 2 (a symmetric H is kept bit for bit)
+  for (uint32_t q = 0; q < n; ++q) {
+    const size_t kD = (size_t)(pr.ptr[q + 1] - pr.ptr[q]) * D;
+    double* h = pr.H.data() + pr.h_off[q];
+    for (size_t r = 0; r < kD; ++r)
+      for (size_t c = 0; c < r; ++c) h[r * kD + c] = h[c * kD + r] = 0.5 * (h[r * kD + c] + h[c * kD + r]);
+  }
+  pr.b.assign(b, b + (size_t)ktot * D);
+  pr.c.assign(c, c + n);
+  e->dpri = std::move(pr);
+  e->finalized = false;  // part of the graph: takes effect at the next ba_hip_finalize
+  return 0;
+}
+
+int ba_hip_get_prior_errors(ba_hip_engine* h, uint32_t n, double* out) {
+  ENG(h);
+  NEED_FINAL();
+  if (n != e->dpri.count() || (n && !out)) return e->fail_msg("ba_hip_get_prior_errors: one entry per dense prior expected");
+  if (!n) return 0;
+  BAE_HIP(hipSetDevice(e->device));
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  if (!e->dp_E_last) { for (uint32_t q = 0; q < n; ++q) out[q] = 0.0; return 0; }
+  BAE_HIP(hipMemcpy(out, e->dp_E_last, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int ba_hip_marginalize(ba_hip_engine* h, uint32_t nm, const uint32_t* m_ids, uint32_t nl, const uint32_t* l_ids,
+                       ba_hip_marginalization_stats* stats) {
+  ENG(h);
+  NEED_FINAL();
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((nm && !m_ids) || (nl && !l_ids)) return e->fail_msg("marginalize: NULL argument");
+  if (e->st.K) return e->fail_msg("marginalize: not offered with calibration unknowns");
+  if (e->allreduce || e->coll || e->comm) return e->fail_msg("marginalize: not offered on sharded engines or with the distributed solve");
+  if (!e->lin_valid)
+    return e->fail_msg("marginalize: needs the linearisation of the current state (ba_hip_linearize, no step, rollback or "
+                       "new masks since)");
+  BAE_HIP(hipSetDevice(e->device));
+  const Structure& st = e->st;
+  MargPlan pl;
+  std::string err;
+  if (!marg_plan(e->prob, e->lm_dim, e->pose_dim, st.pose_opt, st.lm_ptr, st.obs_perm, st.R, st.lrow_base, e->dpri, m_ids, nm,
+                 l_ids, nl, pl, err)) {
+    e->err = err;
+    return -1;
+  }
+  std::vector<uint16_t> lmask(pl.local_pose.size());
+  for (size_t i = 0; i < lmask.size(); ++i) lmask[i] = e->mask_host.empty() ? 0 : e->mask_host[pl.local_pose[i]];
+  const double tol = e->opt.pivot_rel_tolerance > 0 ? e->opt.pivot_rel_tolerance : 1e-10;
+  double dev_ms = 0.0;
+  const int rc = marginalize_run(e, pl, lmask, tol, &dev_ms);
+  if (rc) {  // the store may hold a partial result
+    e->marg_valid = false;
+    return rc;
+  }
+  // x0: the state of the blanket poses at this linearisation
+  std::vector<double> state((size_t)st.P * kPoseState);
+  BAE_HIP(hipMemcpy(state.data(), e->pose_state[e->cur].p, state.size() * sizeof(double), hipMemcpyDeviceToHost));
+  e->marg_ids.assign(pl.local_pose.begin() + pl.nM, pl.local_pose.end());
+  e->marg_x0.resize(e->marg_ids.size() * kPoseState);
+  for (size_t i = 0; i < e->marg_ids.size(); ++i)
+    for (int k = 0; k < kPoseState; ++k) e->marg_x0[i * kPoseState + k] = state[(size_t)e->marg_ids[i] * kPoseState + k];
+  e->marg_valid = true;
+  if (stats) {
+    *stats = ba_hip_marginalization_stats();
+    stats->blanket_poses = pl.nB;
+    stats->absorbed_projection = pl.n_proj; stats->absorbed_unary = pl.n_unary; stats->absorbed_binary = pl.n_binary;
+    stats->absorbed_inertial = pl.n_imu; stats->absorbed_priors = pl.n_prior; stats->dropped_projection = pl.n_dropped;
+    stats->device_ms = dev_ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return 0;
+}
+
+int ba_hip_get_marginalization(ba_hip_engine* h, uint32_t* blanket_ids, double* x0_16, double* H, double* b, double* c) {
+  ENG(h);
+  if (!e->marg_valid) return e->fail_msg("ba_hip_get_marginalization: no marginalisation result (ba_hip_marginalize)");
+  if (blanket_ids) std::copy(e->marg_ids.begin(), e->marg_ids.end(), blanket_ids);
+  if (x0_16) std::copy(e->marg_x0.begin(), e->marg_x0.end(), x0_16);
+  if (H) std::copy(e->marg_H.begin(), e->marg_H.end(), H);
+  if (b) std::copy(e->marg_b.begin(), e->marg_b.end(), b);
+  if (c) *c = e->marg_c;
+  return 0;
+}
+
+int ba_hip_release_marginalization(ba_hip_engine* h) {
+  ENG(h);
+  e->marg_valid = false;
+  std::vector<uint32_t>().swap(e->marg_ids);
+  std::vector<double>().swap(e->marg_x0);
+  std::vector<double>().swap(e->marg_H);
+  std::vector<double>().swap(e->marg_b);
+  e->marg_c = 0.0;
   return 0;
 }
 

@@ -391,3 +391,58 @@ extern "C" uint64_t ba_hostcheck_selinv_products(uint32_t nt, const uint8_t* nzL
   std::vector<uint8_t> v(nzL, nzL + (size_t)nt * nt);
   return bae::selinv_tile_products(v, nt);
 }
+
+// ---- marginalisation plan and the dense prior's error state (marg.h) ----------------------------------
+#include <cstring>
+#include <string>
+#include "marg.h"
+
+extern "C" void ba_hostcheck_prior_delta(const double* x0_16, const double* x16, int D, double* d, double* J) {
+  bae::prior_delta(x0_16, x16, D, d, J);
+}
+
+// The plan of one marginalisation on a graph given by ids (natural pose order).  counts7: |B|, absorbed
+// projection, unary, binary, inertial, prior residuals, dropped projection residuals; blanket: |B| pose ids.
+// Returns 0, or -1 with the refusal in err (err_cap bytes).
+extern "C" int ba_hostcheck_marg_plan(int LM, int D, uint32_t P, const uint8_t* pose_active, uint32_t L,
+                                      const uint8_t* lm_active, const uint32_t* lm_ref_pose, uint32_t O,
+                                      const uint32_t* proj_pose, const uint32_t* proj_lm, uint32_t nu, const uint32_t* un_pose,
+                                      uint32_t nb, const uint32_t* bin_p1, const uint32_t* bin_p2, uint32_t ni,
+                                      const uint32_t* imu_p1, const uint32_t* imu_p2, uint32_t nq, const uint32_t* prior_ptr,
+                                      const uint32_t* prior_pose, uint32_t nm, const uint32_t* m_ids, uint32_t nl,
+                                      const uint32_t* l_ids, uint32_t* counts7, uint32_t* blanket, char* err, uint32_t err_cap) {
+  bae::Problem pb;
+  pb.num_poses = P; pb.num_lms = L; pb.num_proj = O; pb.num_unary = nu; pb.num_binary = nb; pb.num_imu = ni;
+  pb.pose_active.assign(pose_active, pose_active + P);
+  pb.lm_active.assign(lm_active, lm_active + L);
+  pb.lm_ref_pose.assign(lm_ref_pose, lm_ref_pose + L);
+  pb.proj_pose.assign(proj_pose, proj_pose + O);
+  pb.proj_lm.assign(proj_lm, proj_lm + O);
+  pb.un_pose.assign(un_pose, un_pose + nu);
+  pb.bin_p1.assign(bin_p1, bin_p1 + nb); pb.bin_p2.assign(bin_p2, bin_p2 + nb);
+  pb.imu_p1.assign(imu_p1, imu_p1 + ni); pb.imu_p2.assign(imu_p2, imu_p2 + ni);
+  std::vector<int32_t> pose_opt;
+  bae::natural_pose_opt(pb, pose_opt);
+  // observations sorted by landmark, stable in residual id (structure.h)
+  std::vector<uint32_t> lm_ptr((size_t)L + 1, 0), obs_perm(O);
+  for (uint32_t a = 0; a < O; ++a) lm_ptr[proj_lm[a] + 1]++;
+  for (uint32_t l = 0; l < L; ++l) lm_ptr[l + 1] += lm_ptr[l];
+  {
+    std::vector<uint32_t> cur(lm_ptr.begin(), lm_ptr.end() - 1);
+    for (uint32_t a = 0; a < O; ++a) obs_perm[cur[proj_lm[a]]++] = a;
+  }
+  bae::DensePriors pr;
+  pr.ptr.assign(prior_ptr, prior_ptr + nq + 1);
+  pr.pose.assign(prior_pose, prior_pose + pr.ptr.back());
+  const uint32_t R = (uint32_t)bae::rows_per_obs(LM);
+  bae::MargPlan pl;
+  std::string e;
+  if (!bae::marg_plan(pb, LM, D, pose_opt, lm_ptr, obs_perm, R, O * R, pr, m_ids, nm, l_ids, nl, pl, e)) {
+    if (err && err_cap) { strncpy(err, e.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
+    return -1;
+  }
+  const uint32_t c[7] = {pl.nB, pl.n_proj, pl.n_unary, pl.n_binary, pl.n_imu, pl.n_prior, pl.n_dropped};
+  for (int i = 0; i < 7; ++i) counts7[i] = c[i];
+  for (uint32_t i = 0; i < pl.nB; ++i) blanket[i] = pl.local_pose[pl.nM + i];
+  return 0;
+}

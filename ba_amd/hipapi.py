@@ -109,6 +109,12 @@ class MarginalStats(C.Structure):
                 ("levels", C.c_uint32)]
 
 
+class MarginalizationStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("blanket_poses", "absorbed_projection", "absorbed_unary", "absorbed_binary",
+                                          "absorbed_inertial", "absorbed_priors", "dropped_projection", "reserved")] + \
+               [("device_ms", C.c_double), ("host_ms", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
 
@@ -135,6 +141,8 @@ SYMBOLS = [
     "ba_hip_compute_marginals", "ba_hip_get_pose_marginals", "ba_hip_get_pose_pair_marginals",
     "ba_hip_get_calibration_block_marginals", "ba_hip_get_landmark_marginals", "ba_hip_get_marginal_stats",
     "ba_hip_release_marginals",
+    "ba_hip_set_dense_priors", "ba_hip_get_prior_errors", "ba_hip_marginalize", "ba_hip_get_marginalization",
+    "ba_hip_release_marginalization", "ba_hip_set_unary_scales",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -407,6 +415,55 @@ class Engine:
 
     def release_marginals(self):
         self._chk(self.L.ba_hip_release_marginals(self.h))
+
+    # ---- dense pose priors and marginalisation (ba_hip.h) ----
+    def set_dense_priors(self, priors):
+        """priors: list of dicts with pose_ids (k), x0 (k x 16), H (kD x kD), b (kD), c; before finalize."""
+        D = self.pose_dim
+        ptr = np.zeros(len(priors) + 1, dtype=np.uint32)
+        for q, p in enumerate(priors):
+            ptr[q + 1] = ptr[q] + len(p["pose_ids"])
+        cat = lambda key, shape: (np.ascontiguousarray(np.concatenate([np.asarray(p[key], dtype=np.float64).reshape(shape)
+                                                                       for p in priors]))
+                                  if priors else np.zeros(1))
+        ids = (np.ascontiguousarray(np.concatenate([np.asarray(p["pose_ids"], dtype=np.uint32) for p in priors]))
+               if priors else np.zeros(1, dtype=np.uint32))
+        x0 = cat("x0", (-1,))
+        H = cat("H", (-1,))
+        b = cat("b", (-1,))
+        c = np.ascontiguousarray([float(p["c"]) for p in priors] or [0.0])
+        for p in priors:
+            k = len(p["pose_ids"])
+            assert np.asarray(p["x0"]).size == 16 * k and np.asarray(p["H"]).size == (k * D) ** 2
+        self._chk(self.L.ba_hip_set_dense_priors(self.h, len(priors), _p(ptr, u32p), _p(ids, u32p), _p(x0, dp), _p(H, dp),
+                                                 _p(b, dp), _p(c, dp)))
+
+    def prior_errors(self, n):
+        out = np.zeros(max(n, 1))
+        self._chk(self.L.ba_hip_get_prior_errors(self.h, n, _p(out, dp)))
+        return out[:n]
+
+    def marginalize(self, pose_ids, lm_ids=()):
+        """ba_hip_marginalize + ba_hip_get_marginalization: a dict with pose_ids (the blanket), x0, H, b, c and the
+        statistics.  Raises HipError on a refusal (a non-PD S^a_MM included)."""
+        m = np.ascontiguousarray(pose_ids, dtype=np.uint32)
+        l = np.ascontiguousarray(lm_ids, dtype=np.uint32)
+        st = MarginalizationStats()
+        self._chk(self.L.ba_hip_marginalize(self.h, len(m), _p(m, u32p) if len(m) else None, len(l),
+                                            _p(l, u32p) if len(l) else None, C.byref(st)))
+        nb, D = st.blanket_poses, self.pose_dim
+        ids = np.zeros(max(nb, 1), dtype=np.uint32)
+        x0 = np.zeros((max(nb, 1), 16))
+        H = np.zeros((max(nb * D, 1), max(nb * D, 1)))
+        b = np.zeros(max(nb * D, 1))
+        c = C.c_double(0.0)
+        self._chk(self.L.ba_hip_get_marginalization(self.h, _p(ids, u32p), _p(x0, dp), _p(H, dp), _p(b, dp), C.byref(c)))
+        out = {"pose_ids": ids[:nb], "x0": x0[:nb], "H": H[:nb * D, :nb * D], "b": b[:nb * D], "c": c.value}
+        out.update({k: getattr(st, k) for k, _ in MarginalizationStats._fields_ if k != "reserved"})
+        return out
+
+    def release_marginalization(self):
+        self._chk(self.L.ba_hip_release_marginalization(self.h))
 
     def set_landmark_ref_pixels(self, z_ref):
         z = _d(z_ref).reshape(-1, 2)

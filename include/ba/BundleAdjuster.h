@@ -103,6 +103,16 @@ struct Options {  // reference BundleAdjuster.h:72-107, same names and defaults
   PoseOrdering pose_ordering = PoseOrdering::Natural;
 };
 
+// A dense Gaussian prior on poses (extension; include/ba_hip.h, ba_hip_marginalize): pose_ids (k), x0 (k x 16:
+// t(3) q(4) v(3) b(6)), H (kD x kD row-major), b (kD), c, and the projection residuals the marginalisation
+// dropped.  Marginalize() fills it; AddDensePrior() carries it into a later problem.
+struct DensePosePrior {
+  std::vector<uint32_t> pose_ids;
+  std::vector<double> x0, H, b;
+  double c = 0.0;
+  uint32_t dropped_projection = 0;
+};
+
 template <typename Scalar = double, int LmSize = 1, int PoseSize = 6, int CalibSize = 0,
           bool DoTvs = false>
 class BundleAdjuster {
@@ -185,6 +195,7 @@ class BundleAdjuster {
     bin_w_.clear(); bin_rot_.clear();
     imu_p1_.clear(); imu_p2_.clear(); imu_ptr_.assign(1, 0); imu_meas_.clear(); imu_w_.clear();
     conditioning_proj_residuals_.clear(); conditioning_inertial_residuals_.clear();
+    dp_ptr_.assign(1, 0); dp_pose_.clear(); dp_x0_.clear(); dp_H_.clear(); dp_b_.clear(); dp_c_.clear();
     proj_error_ = binary_error_ = unary_error_ = inertial_error_ = 0;
     summary_ = SolutionSummary<Scalar>();
     structure_dirty_ = true;
@@ -478,6 +489,71 @@ class BundleAdjuster {
       return MatX();
     return m;
   }
+  // Sliding-window marginalisation (extension; include/ba_hip.h).  Called after Solve():
+  // relinearises at the state Solve() left (masks as Solve() computes them) and eliminates pose_ids and
+  // landmark_ids into a dense prior on their blanket.  The unary Huber scales the extra linearisation compounds
+  // are put back, so a later Solve() computes what it would have computed without this call.  Refused (false,
+  // reported through Check()) with calibration unknowns, on sharded engines, before a Solve() of the current
+  // graph, and for every refusal of ba_hip_marginalize.
+  bool Marginalize(const std::vector<uint32_t>& pose_ids, const std::vector<uint32_t>& landmark_ids,
+                   DensePosePrior* out) {
+    if (kCalibDim > 0) { std::cerr << "ba::BundleAdjuster::Marginalize: not offered with calibration unknowns" << std::endl; return false; }
+    if (nranks_ > 1 || comm_set_ || allreduce_ || collectives_) {
+      std::cerr << "ba::BundleAdjuster::Marginalize: not offered on sharded engines" << std::endl;
+      return false;
+    }
+    if (!engine_ || !uploaded_once_ || structure_dirty_) {
+      std::cerr << "ba::BundleAdjuster::Marginalize: call Solve() on the current graph first" << std::endl;
+      return false;
+    }
+    std::vector<uint16_t> masks;
+    ComputeMasks(masks);
+    if (masks != masks_uploaded_) {
+      if (!Check(ba_hip_set_pose_masks(engine_, (uint32_t)masks.size(), masks.data()), "ba_hip_set_pose_masks")) return false;
+      masks_uploaded_ = masks;
+    }
+    std::vector<double> sc(un_pose_.size(), 1.0);
+    if (!sc.empty() && !Check(ba_hip_get_unary_scales(engine_, sc.data()), "ba_hip_get_unary_scales")) return false;
+    ba_hip_errors built;
+    const bool lin = Check(ba_hip_linearize(engine_, &built), "ba_hip_linearize");
+    if (!sc.empty() && !Check(ba_hip_set_unary_scales(engine_, (uint32_t)sc.size(), sc.data()), "ba_hip_set_unary_scales"))
+      return false;
+    if (!lin) return false;
+    ba_hip_marginalization_stats st;
+    if (!Check(ba_hip_marginalize(engine_, (uint32_t)pose_ids.size(), pose_ids.data(), (uint32_t)landmark_ids.size(),
+                                  landmark_ids.data(), &st), "ba_hip_marginalize"))
+      return false;
+    if (!out) return true;
+    const size_t nb = st.blanket_poses, nD = nb * kPoseDim;
+    out->pose_ids.assign(nb, 0); out->x0.assign(16 * nb, 0.0); out->H.assign(nD * nD, 0.0); out->b.assign(nD, 0.0);
+    out->dropped_projection = st.dropped_projection;
+    return Check(ba_hip_get_marginalization(engine_, out->pose_ids.data(), out->x0.data(), out->H.data(), out->b.data(),
+                                            &out->c), "ba_hip_get_marginalization");
+  }
+  // Carries a prior into this problem: pose_ids are ids of THIS problem, one per pose of the prior, in the
+  // prior's order.  Returns the prior's index, or UINT32_MAX when refused (calibration unknowns, sharded
+  // engines, sizes that do not match).
+  uint32_t AddDensePrior(const std::vector<uint32_t>& pose_ids, const DensePosePrior& prior) {
+    const size_t k = pose_ids.size(), kD = k * kPoseDim;
+    if (kCalibDim > 0 || nranks_ > 1 || comm_set_ || allreduce_ || collectives_ || k == 0 ||
+        prior.pose_ids.size() != k || prior.x0.size() != 16 * k || prior.H.size() != kD * kD || prior.b.size() != kD) {
+      std::cerr << "ba::BundleAdjuster::AddDensePrior: refused (calibration unknowns, a sharded engine, or sizes that "
+                   "do not match the prior)" << std::endl;
+      return UINT32_MAX;
+    }
+    for (uint32_t p : pose_ids)
+      if (p >= poses_.size()) { std::cerr << "ba::BundleAdjuster::AddDensePrior: unknown pose " << p << std::endl; return UINT32_MAX; }
+    dp_pose_.insert(dp_pose_.end(), pose_ids.begin(), pose_ids.end());
+    dp_ptr_.push_back((uint32_t)dp_pose_.size());
+    dp_x0_.insert(dp_x0_.end(), prior.x0.begin(), prior.x0.end());
+    dp_H_.insert(dp_H_.end(), prior.H.begin(), prior.H.end());
+    dp_b_.insert(dp_b_.end(), prior.b.begin(), prior.b.end());
+    dp_c_.push_back(prior.c);
+    structure_dirty_ = true;
+    mask_counts_dirty_ = true;
+    return (uint32_t)dp_c_.size() - 1;
+  }
+  uint32_t NumDensePriors() const { return (uint32_t)dp_c_.size(); }
   MatX GetLandmarkCovariance(uint32_t landmark_id) {
     MatX m((int)kLmDim, (int)kLmDim);
     if (!engine_ || !Check(ba_hip_get_landmark_marginals(engine_, 1, &landmark_id, m.data()),
@@ -598,6 +674,9 @@ class BundleAdjuster {
   bool host_state_stale_ = false;          // the device holds a newer state than poses_ / landmarks_
   uint32_t uploaded_poses_ = 0, uploaded_landmarks_ = 0;  // sizes of the engine's copy of the graph
   std::vector<double> un_scale_seen_;      // cumulative Huber scale already folded into un_cov_inv_
+  // dense pose priors (AddDensePrior): CSR over their poses, x0 / H / b / c concatenated in prior order
+  std::vector<uint32_t> dp_ptr_{0}, dp_pose_;
+  std::vector<double> dp_x0_, dp_H_, dp_b_, dp_c_;
   std::vector<uint64_t> mask_counts_;      // per pose: proj, binary, unary, inertial residual counts (global); + #unary
   bool mask_counts_dirty_ = true;
   std::vector<uint16_t> masks_uploaded_;   // what the engine currently holds
@@ -778,6 +857,8 @@ bool BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::UploadProblem()
   if (!Check(ba_hip_set_imu_residuals(engine_, (uint32_t)imu_p1_.size(), imu_p1_.data(), imu_p2_.data(),
                                       imu_ptr_.data(), imu_meas_.data(), imu_w_.data()),
              "ba_hip_set_imu_residuals")) return false;
+  if (!Check(ba_hip_set_dense_priors(engine_, (uint32_t)dp_c_.size(), dp_ptr_.data(), dp_pose_.data(), dp_x0_.data(),
+                                     dp_H_.data(), dp_b_.data(), dp_c_.data()), "ba_hip_set_dense_priors")) return false;
   if (!Check(ba_hip_set_pose_ordering(engine_, options_.pose_ordering == PoseOrdering::Auto ? BA_HIP_ORDER_AUTO
                                                                                           : BA_HIP_ORDER_NATURAL),
              "ba_hip_set_pose_ordering")) return false;
@@ -886,7 +967,9 @@ void BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::ComputeMasks(st
       mask_counts_[4 * p + 2] = poses_[p].num_unary_residuals;
       mask_counts_[4 * p + 3] = poses_[p].num_inertial_residuals;
     }
-    mask_counts_[4 * P] = un_pose_.size();
+    mask_counts_[4 * P] = un_pose_.size() + dp_c_.size();  // any dense prior counts like a unary residual
+    for (uint32_t p : dp_pose_)
+      if (p < P) { mask_counts_[4 * p + 2]++; mask_counts_[4 * p + 3]++; }  // it carries v and b as well
     if (nranks_ > 1 && engine_)
       Check(ba_hip_allreduce_host(engine_, mask_counts_.data(), mask_counts_.size(), 1), "ba_hip_allreduce_host");
     mask_counts_dirty_ = false;

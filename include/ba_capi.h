@@ -124,6 +124,18 @@ uint32_t ba_adjuster_get_calibration_marginals(const ba_adjuster* a, double cov[
 uint32_t ba_adjuster_get_pose_covariance(ba_adjuster* a, uint32_t pose_id, double* cov);
 uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, uint32_t pose_b, double* cov);
 uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov);
+/* Marginalize / AddDensePrior (extension; include/ba_hip.h).  ba_adjuster_marginalize:
+ * after a solve, eliminates the poses and landmarks into a dense prior kept by the adjuster; returns 0 and the
+ * blanket size, or 1 when refused.  ba_adjuster_get_marginalization reads it: |B| pose ids, |B| x 16 states,
+ * (|B| D)^2 H, |B| D b, c and the dropped projection residual count (any pointer may be NULL).
+ * ba_adjuster_add_dense_prior carries a prior of k poses into this problem (pose_ids of THIS problem, in the
+ * prior's order); returns its index or UINT32_MAX when refused. */
+int ba_adjuster_marginalize(ba_adjuster* a, uint32_t nm, const uint32_t* pose_ids, uint32_t nl,
+                            const uint32_t* landmark_ids, uint32_t* blanket_poses);
+void ba_adjuster_get_marginalization(const ba_adjuster* a, uint32_t* pose_ids, double* x0_16, double* H, double* b,
+                                     double* c, uint32_t* dropped_projection);
+uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t* pose_ids, const double* x0_16,
+                                     const double* H, const double* b, double c);
 /* GetLastStep().delta_k (zeros without do_tvs) */
 void ba_adjuster_get_last_calib_step(const ba_adjuster* a, double delta_k[6]);
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks);

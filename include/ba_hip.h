@@ -312,6 +312,9 @@ int ba_hip_get_imu_errors(ba_hip_engine* e, double* mahalanobis);
 /* cumulative Huber scale of every unary residual's cov^-1 (the reference multiplies
  * cov_inv in place every BuildProblem, BundleAdjuster.cpp:1469) */
 int ba_hip_get_unary_scales(ba_hip_engine* e, double* scale);
+/* restores them (n = the unary residual count): a caller that relinearises outside a Solve() (the host
+ * class's Marginalize) puts back what the extra BuildProblem compounded */
+int ba_hip_set_unary_scales(ba_hip_engine* e, uint32_t n, const double* scale);
 
 /* Per-kernel device time, accumulated since ba_hip_set_profiling(e, 1): HIP events on
  * the engine's stream around every launch of the three hot kernels (used by bench.py's
@@ -510,6 +513,64 @@ int ba_hip_get_landmark_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* 
 int ba_hip_get_marginal_stats(ba_hip_engine* e, ba_hip_marginal_stats* out);
 /* Frees the Sigma store (also freed with the engine). */
 int ba_hip_release_marginals(ba_hip_engine* e);
+
+/* ---- sliding-window marginalisation and dense pose priors (extension) ----------------
+ * Conventions are the engine's: S delta = rhs (rhs_p_sc), ApplyUpdate(delta) moves a pose by
+ * exp_decoupled(T, -delta_6), v -= delta_v, b -= delta_b, and the Gauss-Newton model of the system at its
+ * linearisation state is m(delta) = E - 2 rhs^T delta + delta^T S delta.
+ *
+ * Dense prior residual on poses p_1 .. p_k, holding (x0, H, b, c): d_i(x) is the delta ApplyUpdate would need
+ * to take x0_i to x_i (d_t = t0 - t, d_w = log(q^-1 q0), d_v = v0 - v, d_b = b0 - b; zero at x0), and
+ *     E_p(x) = c - 2 b^T d + d^T H d.
+ * Linearised at x it adds J_d^T H J_d to S and J_d^T (b - H d) to rhs_p / rhs_p_sc (J_d = dd/ddelta,
+ * block-diagonal, the identity at x0); masked parameters are skipped as for every pose-pose residual; no robust
+ * weight.  E_p is folded into ba_errors.unary_error (linearize and eval_residuals) and the dogleg denominator
+ * j_rhs_sq gains (J_d g)^T H (J_d g).  Inactive poses are constants.  The priors are applied after the unary,
+ * binary and inertial residuals, in prior order, so sums stay deterministic.
+ *
+ * Marginalisation of poses M and landmarks L out of the last linearisation into a prior on their blanket B:
+ *   absorbed: every projection residual of a landmark in L; every unary residual on a pose in M; every binary
+ *             and inertial residual with a pose in M; every dense prior covering a pose in M;
+ *   dropped:  the projection residuals of landmarks NOT in L measured by a pose in M (counted);
+ *   B:        the active poses outside M that appear in an absorbed residual, sorted by pose id.
+ * With S^a, rhs^a, E^a the absorbed part of the system with L eliminated (E^a: the absorbed residuals' share of
+ * the error sums, less sum_l rhs_l^T V_l^-1 rhs_l):
+ *   H = S^a_BB - S^a_BM (S^a_MM)^-1 S^a_MB,  b = rhs^a_B - S^a_BM (S^a_MM)^-1 rhs^a_M,
+ *   c = E^a - rhs^a_M^T (S^a_MM)^-1 rhs^a_M,  x0 = the state of every blanket pose.
+ * A masked parameter of M keeps a unit pivot; one of B has zero rows and columns in H.  The system "everything
+ * not absorbed, plus the prior", linearised at the same state, is then exactly the full system with M and L
+ * eliminated.  Refused (error, the engine stays usable): M empty, duplicate, unknown or inactive; L unknown,
+ * duplicate, inactive, or non-empty with LmSize 0; an active landmark anchored in M (LmSize 1) missing from L;
+ * calibration unknowns; sharded engines and the distributed solve; no linearisation of the current state (a step,
+ * rollback, new masks or begin_solve since); |M| * PoseSize > 128; |B| * PoseSize > 4096; S^a_MM not positive
+ * definite (a pivot d_j <= tol * S_jj, tol = pivot_rel_tolerance or 1e-10 when that is 0): returns
+ * BA_HIP_FACTORIZATION_ERROR. */
+typedef struct {
+  uint32_t blanket_poses;
+  uint32_t absorbed_projection, absorbed_unary, absorbed_binary, absorbed_inertial, absorbed_priors;
+  uint32_t dropped_projection, reserved;
+  double device_ms;   /* the marginalisation kernels, assembly to the last output */
+  double host_ms;     /* the whole call: plan, uploads, kernels, read-back */
+} ba_hip_marginalization_stats;
+/* n priors, CSR ptr[n + 1] over pose_ids (caller's ids, no pose twice in a prior); per covered pose x0_16 = its
+ * 16-double state t(3) q(4) v(3) b(6); per prior H (kD x kD row-major, k = its pose count, D = PoseSize), b (kD),
+ * c (1), concatenated in prior order.  H is read as symmetric: (H + H^T) / 2 is kept.  Structural: call before ba_hip_finalize (n = 0 removes them).  Every tile
+ * of a prior's blocks joins the factor's pattern and the pose ordering's group graph.  Refused with calibration
+ * unknowns (at finalize) and on sharded engines (at linearize). */
+int ba_hip_set_dense_priors(ba_hip_engine* e, uint32_t n, const uint32_t* ptr, const uint32_t* pose_ids,
+                            const double* x0_16, const double* H, const double* b, const double* c);
+/* E_p of every prior at the last ba_hip_linearize or ba_hip_eval_residuals; n = the prior count. */
+int ba_hip_get_prior_errors(ba_hip_engine* e, uint32_t n, double* out);
+/* Computes the prior of marginalising m_ids / l_ids into an engine-owned store.  A successful call replaces
+ * the stored result; a refused call leaves it, a failed computation (BA_HIP_FACTORIZATION_ERROR) clears it.
+ * stats may be NULL. */
+int ba_hip_marginalize(ba_hip_engine* e, uint32_t nm, const uint32_t* m_ids, uint32_t nl, const uint32_t* l_ids,
+                       ba_hip_marginalization_stats* stats);
+/* The stored result: blanket_ids (|B|), x0_16 (|B| x 16), H (|B|D x |B|D, bitwise symmetric), b (|B|D), c (1);
+ * any pointer may be NULL. */
+int ba_hip_get_marginalization(ba_hip_engine* e, uint32_t* blanket_ids, double* x0_16, double* H, double* b, double* c);
+/* Frees the store (also freed with the engine). */
+int ba_hip_release_marginalization(ba_hip_engine* e);
 
 /* ---- stand-alone kernels exposed for tests and benchmarks ------------------------- */
 /* Dense Cholesky solve of an SPD system given by its LOWER triangle (row-major n x n,
