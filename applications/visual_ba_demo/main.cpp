@@ -18,6 +18,9 @@
 //                                           (SetCommunicator; rank 0 writes the 128-byte id to F, the others wait for
 //                                           it) and the reduced solve is distributed over the GPUs — no torch, no hooks
 //   visual_ba_demo --ordering auto          Options::pose_ordering = Auto: prints the ordering statistics
+//   visual_ba_demo --pcg [tol]              Options::reduced_solver = Pcg (relative tolerance tol, default 1e-6): the reduced
+//                                           system is solved by preconditioned conjugate gradients; prints the
+//                                           iterations and the true residual of every Gauss-Newton step
 //   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
 //                                           GetLandmarkCovariance: selected inverse of the reduced system)
@@ -33,7 +36,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, pcg = false; double pcg_tol = 1e-6; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -63,6 +66,13 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   options.error_change_threshold = 1e-5;
   options.device = shard.device;
   if (shard.order_auto) options.pose_ordering = ba::PoseOrdering::Auto;
+  if (shard.pcg) { options.reduced_solver = ba::ReducedSolver::Pcg; options.pcg_tolerance = shard.pcg_tol; }
+  auto print_pcg = [&](int step) {
+    ba_hip_pcg_stats ps;
+    if (!adjuster.GetPcgStats(&ps)) return;
+    std::printf("step %d: pcg iterations %u converged %u true residual %.3e (%.3f ms, %.1f us per product)\n", step, ps.iterations,
+                ps.converged, ps.rel_residual_true, ps.solve_ms, 1e3 * ps.spmv_ms);
+  };
   if (!shard.id_file.empty()) {
     unsigned char id[128];
     if (!exchange_id(shard, id)) { std::printf("communicator id exchange failed\n"); return 3; }
@@ -178,6 +188,7 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   }
   std::printf("poses %u landmarks %u residuals %d\n", adjuster.GetNumPoses(), adjuster.GetNumLandmarks(), n_res);
   adjuster.Solve(1);
+  if (shard.pcg) print_pcg(1);
   if (shard.order_auto) {
     ba_hip_ordering_stats os;
     if (ba_hip_get_pose_ordering(adjuster.engine(), nullptr, &os) != 0) { std::printf("no pose ordering\n"); return 2; }
@@ -191,7 +202,15 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   double e0, eu, eb, ei;
   adjuster.GetErrors(e0, eu, eb, ei);
   if (!adjuster.GetSolutionSummary().IsResultGood()) { std::printf("Solve failed\n"); return 2; }
-  adjuster.Solve(8);
+  if (shard.pcg) {  // one Gauss-Newton step per call, to print the solver's statistics of each
+    for (int it = 0; it < 8; ++it) {
+      adjuster.Solve(1);
+      print_pcg(it + 2);
+      if (adjuster.GetSolutionSummary().result != ba::Success) break;
+    }
+  } else {
+    adjuster.Solve(8);
+  }
   double e1;
   adjuster.GetErrors(e1, eu, eb, ei);
   double worst = 0;
@@ -246,6 +265,12 @@ int main(int argc, char** argv) {
   Shard shard;
   for (int i = 1; i < argc; i += 2) {
     if (std::strcmp(argv[i], "--covariances") == 0) { shard.covariances = true; --i; continue; }
+    if (std::strcmp(argv[i], "--pcg") == 0) {
+      shard.pcg = true;
+      if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.pcg_tol = std::atof(argv[i + 1]);
+      else --i;
+      continue;
+    }
     if (i + 1 >= argc) break;
     if (std::strcmp(argv[i], "--ranks") == 0) shard.ranks = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--rank") == 0) shard.rank = std::atoi(argv[i + 1]);

@@ -39,7 +39,8 @@ class BaOptions(C.Structure):
                 ("use_robust_norm_for_inertial_residuals", C.c_int32),
                 ("write_reduced_camera_matrix", C.c_int32),
                 ("device", C.c_int32), ("factorization_pivot_tolerance", C.c_double),
-                ("calculate_calibration_marginals", C.c_int32), ("pose_ordering", C.c_int32)]
+                ("calculate_calibration_marginals", C.c_int32), ("pose_ordering", C.c_int32),
+                ("reduced_solver", C.c_int32), ("pcg_max_iterations", C.c_uint32), ("pcg_tolerance", C.c_double)]
 
 
 class BaSummary(C.Structure):
@@ -70,6 +71,7 @@ SYMBOLS = [
     "ba_adjuster_add_camera_fov", "ba_adjuster_get_camera_fov",
     "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
+    "ba_adjuster_get_pcg_stats",
 ]
 
 _lib = None
@@ -471,6 +473,14 @@ class BundleAdjuster:
             self.L.ba_adjuster_set_communicator(self.h, None, 0, 1, 0)
             return
         self.L.ba_adjuster_set_communicator(self.h, C.c_char_p(unique_id), int(rank), int(nranks), 1 if distributed_solve else 0)
+
+    def GetPcgStats(self):
+        """ba::BundleAdjuster::GetPcgStats: the statistics of the last reduced solve as a dict when it ran the PCG
+        solver (Options reduced_solver = 1), None otherwise."""
+        st = hipapi.PcgStats()
+        if not self.L.ba_adjuster_get_pcg_stats(self.h, C.byref(st)):
+            return None
+        return {k: getattr(st, k) for k, _ in hipapi.PcgStats._fields_}
 
     def solve_is_distributed(self):
         return bool(self.L.ba_adjuster_solve_is_distributed(self.h))

@@ -44,6 +44,7 @@ struct Iface {
   virtual void set_communicator(const void* id128, int rank, int nranks, int distributed) = 0;
   virtual void set_collectives(ba_hip_collective_fn fn, void* ctx) = 0;
   virtual int solve_is_distributed() = 0;
+  virtual int pcg_stats(ba_hip_pcg_stats* out) const = 0;
   virtual void camera_pose(uint32_t cam, double* t7) const = 0;
   virtual void camera_params(uint32_t cam, double* p4) const = 0;
   virtual void last_calib_step(double* d6) const = 0;
@@ -81,6 +82,9 @@ struct Impl : Iface {
     opt.factorization_pivot_tolerance = o->factorization_pivot_tolerance;
     opt.calculate_calibration_marginals = o->calculate_calibration_marginals != 0;
     opt.pose_ordering = o->pose_ordering == 1 ? ba::PoseOrdering::Auto : ba::PoseOrdering::Natural;
+    opt.reduced_solver = o->reduced_solver == 1 ? ba::ReducedSolver::Pcg : ba::ReducedSolver::Direct;
+    opt.pcg_tolerance = o->pcg_tolerance;
+    opt.pcg_max_iterations = o->pcg_max_iterations;
     ba.Init(opt);
   }
   void set_gravity(const double* g) override { ba.SetGravity(ba::Vector3t({g[0], g[1], g[2]})); }
@@ -194,6 +198,7 @@ struct Impl : Iface {
     else ba.ClearCommunicator();
   }
   int solve_is_distributed() override { return ba.SolveIsDistributed() ? 1 : 0; }
+  int pcg_stats(ba_hip_pcg_stats* out) const override { return ba.GetPcgStats(out) ? 1 : 0; }
   void set_collectives(ba_hip_collective_fn fn, void* ctx) override { ba.SetCollectives(fn, ctx); }
   void set_allreduce(ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) override {
     ba.SetAllReduce(fn, ctx, rank, nranks);
@@ -302,6 +307,9 @@ void ba_default_options(ba_options* o) {
   o->factorization_pivot_tolerance = d.factorization_pivot_tolerance;
   o->calculate_calibration_marginals = d.calculate_calibration_marginals;
   o->pose_ordering = d.pose_ordering == ba::PoseOrdering::Auto ? 1 : 0;
+  o->reduced_solver = d.reduced_solver == ba::ReducedSolver::Pcg ? 1 : 0;
+  o->pcg_tolerance = d.pcg_tolerance;
+  o->pcg_max_iterations = d.pcg_max_iterations;
 }
 ba_adjuster* ba_adjuster_create(int lm_dim, int pose_dim) { return ba_adjuster_create_calib(lm_dim, pose_dim, 0, 0); }
 ba_adjuster* ba_adjuster_create_calib(int lm_dim, int pose_dim, int calib_size, int do_tvs) {
@@ -399,6 +407,7 @@ uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t*
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) { a->p->set_allreduce(fn, ctx, rank, nranks); }
 void ba_adjuster_set_communicator(ba_adjuster* a, const void* id128, int rank, int nranks, int distributed_solve) { a->p->set_communicator(id128, rank, nranks, distributed_solve); }
 int ba_adjuster_solve_is_distributed(ba_adjuster* a) { return a->p->solve_is_distributed(); }
+int ba_adjuster_get_pcg_stats(const ba_adjuster* a, ba_hip_pcg_stats* out) { return a->p->pcg_stats(out); }
 void ba_adjuster_set_collectives(ba_adjuster* a, ba_hip_collective_fn fn, void* ctx) { a->p->set_collectives(fn, ctx); }
 
 }  // extern "C"

@@ -193,6 +193,8 @@ int ba_hip_comm_init(ba_hip_engine* h, const void* id128, int rank, int nranks) 
   if (!id128 || nranks < 1 || rank < 0 || rank >= nranks) return e->fail_msg("ba_hip_comm_init: bad arguments");
   if (e->order_mode != kOrderNatural)
     return e->fail_msg("the communicator needs natural pose order (ba_hip_set_pose_ordering is set)");
+  if (e->solver_mode == BA_HIP_SOLVER_PCG)
+    return e->fail_msg("the communicator needs the direct reduced solver (ba_hip_set_reduced_solver selected PCG)");
   RcclApi* a = rccl();
   if (!a) return e->fail_msg("ba_hip_comm_init: librccl could not be loaded");
   BAE_HIP(hipSetDevice(e->device));

@@ -10,6 +10,7 @@
 #include "ordering.h"
 #include "selinv.h"
 #include "marg.h"
+#include "pcg.h"
 #include "dist_plan.h"
 
 namespace bae {
@@ -272,6 +273,32 @@ struct Engine {
   std::vector<double> marg_x0, marg_H, marg_b;
   double marg_c = 0.0;
 
+  // iterative reduced solve (ba_hip_set_reduced_solver, k_pcg.hip, pcg.h): the mode of the next ba_hip_solve_gn,
+  // its options, the statistics of the last PCG solve (pcg_last: the last ba_hip_solve_gn ran PCG, so A still holds
+  // S), the plan of nzS_host (rebuilt when the pattern's version changes) and the device work space
+  int solver_mode = BA_HIP_SOLVER_DIRECT;
+  ba_hip_pcg_options pcg_opt = {};
+  ba_hip_pcg_stats pcg_stats = {};
+  bool pcg_last = false;
+  bool pcg_solved = false;   // ... and no linearisation since: gn_p solves the S in A
+  bool pcg_refused() const { return allreduce || coll || comm; }
+  PcgPlan pcg_plan;
+  std::vector<uint32_t> pcg_blk, pcg_blocks;
+  uint64_t pcg_plan_version = ~0ull;
+  struct PcgWork {
+    DBuf<uint2> tiles, blk, blocks;
+    DBuf<uint32_t> row_ptr, col_ptr, col_slot;
+    DBuf<uint8_t> nz;
+    DBuf<double> rowslot, colslot, minv, x, r, z, p, q, parts;
+    DBuf<PcgState> state;
+    DBuf<int32_t> status;
+    void release() {
+      tiles.release(); blk.release(); blocks.release(); row_ptr.release(); col_ptr.release(); col_slot.release();
+      nz.release(); rowslot.release(); colslot.release(); minv.release(); x.release(); r.release(); z.release();
+      p.release(); q.release(); parts.release(); state.release(); status.release();
+    }
+  } pcg;
+
   // optional per-kernel timing (ba_hip_set_profiling)
   bool profiling = false;
   ba_hip_kernel_stats kstats = {};
@@ -375,6 +402,11 @@ void marginals_release(Engine* e);
 int priors_upload(Engine* e);
 int launch_priors(Engine* e, int mode, double* err_host);
 int launch_priors_jrhs(Engine* e, double* out);
+// block-Jacobi PCG on the system in dA (k_pcg.hip): uploads `plan` / the row blocks when `upload` is set, solves
+// S x = rhs for the first n unknowns of the padded system into dx (ld doubles), fills *stats; *status != 0 on a breakdown
+int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const double* d_rhs, const PcgPlan& plan,
+                     const std::vector<uint8_t>& nz, const std::vector<uint32_t>& blk, const std::vector<uint32_t>& blocks,
+                     bool upload, const ba_hip_pcg_options& opt, double* dx, ba_hip_pcg_stats* stats, int* status);
 int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& lmask, double tol, double* dev_ms);
 
 }  // namespace bae

@@ -563,6 +563,7 @@ void ba_hip_destroy(ba_hip_engine* h) {
   REL(dist_tiles); REL(dist_sq_list); REL(dist_pairs); REL(dist_sp_srect); REL(dist_sp_rrect); REL(dist_usend); REL(dist_urecv); REL(dist_ssend); REL(dist_srecv); REL(dist_back);
   for (int b = 0; b < 2; ++b) { REL(pose_state[b]); REL(lm_x[b]); REL(lm_reliable[b]); }
   REL(lm_xw); REL(tsw); REL(tws); REL(twp); REL(lm_outliers); REL(obs_e); REL(obs_w); REL(obs_e_state[0]); REL(obs_e_state[1]); REL(obs_jl);
+  e->pcg.release();
   REL(frow); REL(diag_blocks); REL(scal); REL(lm_vinv); REL(lm_bl); REL(A); REL(A_keep); REL(rhs_p); REL(rhs_sc); REL(gn_p);
   REL(gn_l); REL(step_p); REL(step_l); REL(invdiag); REL(partials); REL(scalars_out); REL(hist);
   REL(flags); REL(pivot_floor);
@@ -1051,6 +1052,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   t_l.mark();
   EventTimer t_s(e);
   e->factored = false;
+  e->pcg_solved = false;
   e->sig_valid = false;
   if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) { (void)defer_flush(e); return rc; }
   // dense priors after k_pp_scatter, in prior order; their E_p is folded into unary_error
@@ -1114,7 +1116,22 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
   const bool skip = st.K && st.Pact == 0;
   e->sig_valid = false;
   if (skip) BAE_HIP(hipMemsetAsync(e->gn_p.p, 0, e->gn_p.bytes(), e->stream));
-  if (st.n > 0 && !skip) {
+  e->pcg_last = e->pcg_solved = false;
+  if (st.n > 0 && !skip && e->solver_mode == BA_HIP_SOLVER_PCG) {
+    // S stays in A: no factor, no kept copy
+    if (e->pcg_refused()) return e->fail_msg("the PCG solver is not available on a sharded engine");
+    if (!e->nzL_valid && (rc = factor_tile_pattern(e))) return rc;
+    const bool rebuild = e->pcg_plan_version != e->nzL_version || e->pcg_plan.nt != st.ld / 64 || e->pcg_blk.size() != (size_t)2 * st.ld;
+    if (rebuild) {
+      build_pcg_plan(e->nzS_host, st.ld / 64, e->pcg_plan);
+      pcg_row_blocks(st.np, (uint32_t)e->pose_dim, st.K, st.ld, e->pcg_blk, e->pcg_blocks);
+      e->pcg_plan_version = e->nzL_version;
+    }
+    if ((rc = pcg_solve_device(e, e->A.p, st.n, st.ld, e->rhs_sc.p, e->pcg_plan, e->nzS_host, e->pcg_blk, e->pcg_blocks, rebuild,
+                               e->pcg_opt, e->gn_p.p, &e->pcg_stats, &status))) return rc;
+    e->factored = false;
+    e->pcg_last = e->pcg_solved = true;
+  } else if (st.n > 0 && !skip) {
     if (e->opt.keep_reduced_system) {
       BAE_HIP(e->A_keep.alloc((size_t)st.ld * st.ld));
       BAE_HIP(hipMemcpyAsync(e->A_keep.p, e->A.p, (size_t)st.ld * st.ld * sizeof(double),
@@ -1336,6 +1353,9 @@ int ba_hip_get_calibration_marginals(ba_hip_engine* h, double* cov) {
   ENG(h);
   NEED_FINAL();
   if (!e->st.K) return e->fail_msg("no calibration columns (ba_hip_set_calibration)");
+  if (!e->factored && e->pcg_solved)
+    return e->fail_msg("ba_hip_get_calibration_marginals: the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), "
+                       "which leaves no factor");
   if (!e->factored) return e->fail_msg("ba_hip_get_calibration_marginals needs the factor of the last ba_hip_solve_gn");
   if (dist_solve_enabled(e)) return e->fail_msg("calibration marginals: not available with the distributed solve");
   BAE_HIP(hipSetDevice(e->device));
@@ -1415,6 +1435,9 @@ static int marginals_ready(Engine* e, const char* what, bool landmarks) {
   if (dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
   if (landmarks && e->sharded())
     return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
+  if (!e->factored && e->pcg_solved)
+    return e->fail_msg((m + "the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor; "
+                            "marginals need a direct solve (ba_hip_set_reduced_solver)").c_str());
   if (!e->factored)
     return e->fail_msg((m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised "
                             "since)").c_str());
@@ -1657,11 +1680,12 @@ int ba_hip_check_solve(ba_hip_engine* h, double* residual_norm, double* rhs_norm
   ENG(h);
   NEED_FINAL();
   BAE_HIP(hipSetDevice(e->device));
-  if (!(e->factored && e->opt.keep_reduced_system && e->A_keep.p))
+  // after a PCG solve A itself still holds S
+  if (!e->pcg_solved && !(e->factored && e->opt.keep_reduced_system && e->A_keep.p))
     return e->fail_msg("ba_hip_check_solve needs keep_reduced_system and a finished ba_hip_solve_gn");
   if (e->sharded()) return e->fail_msg("ba_hip_check_solve: single shard only");
   double o[2];
-  int rc = check_solve_residual(e, e->A_keep.p, e->gn_p.p, e->rhs_sc.p, o);
+  int rc = check_solve_residual(e, e->pcg_solved ? e->A.p : e->A_keep.p, e->gn_p.p, e->rhs_sc.p, o);
   if (rc) return rc;
   if (residual_norm) *residual_norm = o[0];
   if (rhs_norm) *rhs_norm = o[1];
@@ -1810,6 +1834,30 @@ int ba_hip_set_pose_ordering(ba_hip_engine* h, int mode) {
   return 0;
 }
 
+int ba_hip_set_reduced_solver(ba_hip_engine* h, int mode, const ba_hip_pcg_options* o) {
+  ENG(h);
+  if (mode != BA_HIP_SOLVER_DIRECT && mode != BA_HIP_SOLVER_PCG) return e->fail_msg("ba_hip_set_reduced_solver: unknown mode");
+  if (mode == BA_HIP_SOLVER_PCG) {
+    if (e->pcg_refused())
+      return e->fail_msg("the PCG solver is not available on a sharded engine (all-reduce hook, collectives hook or communicator set)");
+    ba_hip_pcg_options v = {};
+    v.rel_tolerance = 1e-6;
+    if (o) v = *o;
+    if (!(v.rel_tolerance > 0.0) || !(v.rel_tolerance < 1.0))
+      return e->fail_msg("ba_hip_set_reduced_solver: rel_tolerance must lie in (0, 1)");
+    e->pcg_opt = v;
+  }
+  e->solver_mode = mode;
+  return 0;
+}
+
+int ba_hip_get_pcg_stats(ba_hip_engine* h, ba_hip_pcg_stats* out) {
+  ENG(h);
+  if (!e->pcg_last) return e->fail_msg("ba_hip_get_pcg_stats: the last ba_hip_solve_gn did not run the PCG solver");
+  if (out) *out = e->pcg_stats;
+  return 0;
+}
+
 int ba_hip_set_pose_permutation(ba_hip_engine* h, const uint32_t* opt_of_natural, uint32_t n) {
   ENG(h);
   if (n && !opt_of_natural) return e->fail_msg("ba_hip_set_pose_permutation: NULL permutation");
@@ -1841,6 +1889,8 @@ int ba_hip_set_collectives(ba_hip_engine* h, ba_hip_collective_fn fn, void* ctx)
   ENG(h);
   if (fn && e->order_mode != kOrderNatural)
     return e->fail_msg("the collectives hook needs natural pose order (ba_hip_set_pose_ordering is set)");
+  if (fn && e->solver_mode == BA_HIP_SOLVER_PCG)
+    return e->fail_msg("the collectives hook needs the direct reduced solver (ba_hip_set_reduced_solver selected PCG)");
   e->coll = fn; e->coll_ctx = ctx;
   e->dist_plan_version = ~0ull;
   return 0;
@@ -1850,6 +1900,8 @@ int ba_hip_set_allreduce(ba_hip_engine* h, ba_hip_allreduce_fn fn, void* ctx, in
   ENG(h);
   if (fn && e->order_mode != kOrderNatural)
     return e->fail_msg("the all-reduce hook needs natural pose order (ba_hip_set_pose_ordering is set)");
+  if (fn && e->solver_mode == BA_HIP_SOLVER_PCG)
+    return e->fail_msg("the all-reduce hook needs the direct reduced solver (ba_hip_set_reduced_solver selected PCG)");
   e->allreduce = fn; e->allreduce_ctx = ctx; e->rank = rank; e->nranks = nranks < 1 ? 1 : nranks;
   e->nzL_valid = false;  // the tile pattern of S is the union over the shards
   e->dist_plan_version = ~0ull;
@@ -1998,6 +2050,48 @@ int ba_hip_dense_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, cons
     hipError_t err = hipMemcpy(xx.data(), dx.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
     if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
     for (uint32_t i = 0; i < n; ++i) x[i] = xx[i];
+  }
+  dA.release(); dx.release();
+  if (rc) return rc;
+  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
+}
+
+int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, uint32_t block,
+                     const ba_hip_pcg_options* o, double* x, ba_hip_pcg_stats* stats) {
+  ENG(h);
+  if (!n || !a_lower || !b || !o || !x) return e->fail_msg("ba_hip_pcg_solve: NULL or empty argument");
+  if (block < 1 || block > kPcgMaxBlock) return e->fail_msg("ba_hip_pcg_solve: block must lie in 1 .. 16");
+  if (!(o->rel_tolerance > 0.0) || !(o->rel_tolerance < 1.0)) return e->fail_msg("ba_hip_pcg_solve: rel_tolerance must lie in (0, 1)");
+  BAE_HIP(hipSetDevice(e->device));
+  const uint32_t ld = std::max(((n + 63) / 64) * 64, 64u), nt = ld / 64;
+  std::vector<double> A((size_t)(ld + 1) * ld, 0.0);
+  std::vector<uint8_t> nz((size_t)nt * nt, 0);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c <= r; ++c) {
+      const double v = a_lower[(size_t)r * n + c];
+      A[(size_t)r * ld + c] = v;
+      if (v != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
+    }
+  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
+  for (uint32_t c = 0; c < n; ++c) A[(size_t)ld * ld + c] = b[c];
+  PcgPlan plan;
+  build_pcg_plan(nz, nt, plan);
+  std::vector<uint32_t> blk, blocks;
+  pcg_row_blocks(n, block, 0, ld, blk, blocks);
+  DBuf<double> dA, dx;
+  BAE_HIP(dA.alloc(A.size()));
+  BAE_HIP(dx.alloc(ld));
+  BAE_HIP(hipMemcpy(dA.p, A.data(), A.size() * 8, hipMemcpyHostToDevice));
+  int status = 0;
+  ba_hip_pcg_stats st;
+  e->pcg_plan_version = ~0ull;   // the work space now holds this system's plan, not the engine's
+  int rc = pcg_solve_device(e, dA.p, n, ld, dA.p + (size_t)ld * ld, plan, nz, blk, blocks, true, *o, dx.p, &st, &status);
+  if (rc == 0) {
+    std::vector<double> xx(ld);
+    hipError_t err = hipMemcpy(xx.data(), dx.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
+    if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
+    for (uint32_t i = 0; i < n; ++i) x[i] = xx[i];
+    if (stats) *stats = st;
   }
   dA.release(); dx.release();
   if (rc) return rc;

@@ -446,3 +446,49 @@ extern "C" int ba_hostcheck_marg_plan(int LM, int D, uint32_t P, const uint8_t* 
   for (uint32_t i = 0; i < pl.nB; ++i) blanket[i] = pl.local_pose[pl.nM + i];
   return 0;
 }
+
+// ---- iterative reduced solve (pcg.h) ----------------------------------------------------------------------
+#include "pcg.h"
+
+// q = S v by the tile plan on the lower storage A (row-major, 64 nt x 64 nt; tiles outside nz and the strict upper
+// triangle of diagonal tiles are not read).  Returns the number of tiles visited.
+extern "C" uint32_t ba_hostcheck_pcg_spmv(uint32_t nt, const uint8_t* nz, const double* A, const double* v, double* q) {
+  std::vector<uint8_t> z(nz, nz + (size_t)nt * nt);
+  bae::PcgPlan pl;
+  bae::build_pcg_plan(z, nt, pl);
+  std::vector<double> rs, cs;
+  bae::pcg_spmv_host(pl, A, (size_t)64 * nt, v, q, rs, cs);
+  return pl.n_tiles;
+}
+
+// pcg_host on a symmetric n x n system given by its LOWER triangle (row-major n x n): padded like the engine pads A,
+// tile pattern from the nonzeros, np rows in blocks of D then one block of K = n - np.  out_u32: iterations, converged,
+// residual replacements, breakdown, passes, tiles; out_f64: rel. residual of the recurrence, true, |b|.
+extern "C" int ba_hostcheck_pcg(uint32_t n, const double* a_lower, const double* b, uint32_t np, uint32_t D, double rel_tolerance,
+                                uint32_t max_iterations, double* x, uint32_t* out_u32, double* out_f64) {
+  if (np > n || D < 1 || D > bae::kPcgMaxBlock || n - np > bae::kPcgMaxBlock) return -1;
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  std::vector<double> A((size_t)ld * ld, 0.0), rhs(ld, 0.0), xx(ld, 0.0);
+  std::vector<uint8_t> nz((size_t)nt * nt, 0);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c <= r; ++c) {
+      const double v = a_lower[(size_t)r * n + c];
+      A[(size_t)r * ld + c] = v;
+      if (v != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
+    }
+  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
+  for (uint32_t r = 0; r < n; ++r) rhs[r] = b[r];
+  bae::PcgPlan pl;
+  bae::build_pcg_plan(nz, nt, pl);
+  std::vector<uint32_t> blk, blocks;
+  bae::pcg_row_blocks(np, D, n - np, ld, blk, blocks);
+  bae::PcgResult res;
+  const int rc = bae::pcg_host(pl, A.data(), ld, rhs.data(), n, nz, blk, blocks, rel_tolerance, max_iterations, xx.data(), &res);
+  for (uint32_t r = 0; r < n; ++r) x[r] = xx[r];
+  out_u32[0] = res.iterations; out_u32[1] = res.converged; out_u32[2] = res.replacements; out_u32[3] = res.breakdown;
+  out_u32[4] = res.passes; out_u32[5] = pl.n_tiles;
+  out_f64[0] = res.bb > 0.0 ? std::sqrt(res.rr_recur / res.bb) : 0.0;
+  out_f64[1] = res.bb > 0.0 ? std::sqrt(res.rr_true / res.bb) : 0.0;
+  out_f64[2] = std::sqrt(res.bb);
+  return rc;
+}

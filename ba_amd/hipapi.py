@@ -115,6 +115,22 @@ class MarginalizationStats(C.Structure):
                [("device_ms", C.c_double), ("host_ms", C.c_double)]
 
 
+class PcgOptions(C.Structure):
+    _fields_ = [("rel_tolerance", C.c_double), ("max_iterations", C.c_uint32), ("check_every", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class PcgStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("iterations", "converged", "residual_replacements", "breakdown")] + \
+               [(n, C.c_double) for n in ("rel_residual_recurrence", "rel_residual_true", "rhs_norm", "solve_ms", "spmv_ms",
+                                          "precond_ms")] + \
+               [("tiles_read_per_spmv", C.c_uint64), ("bytes_read_per_spmv", C.c_double)]
+
+
+def _pcg_stats_dict(st):
+    return {k: getattr(st, k) for k, _ in PcgStats._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
 
@@ -143,9 +159,11 @@ SYMBOLS = [
     "ba_hip_release_marginals",
     "ba_hip_set_dense_priors", "ba_hip_get_prior_errors", "ba_hip_marginalize", "ba_hip_get_marginalization",
     "ba_hip_release_marginalization", "ba_hip_set_unary_scales",
+    "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
+SOLVER_DIRECT, SOLVER_PCG = 0, 1                 # ba_hip_set_reduced_solver modes
 
 
 def build(force=False):
@@ -628,6 +646,31 @@ class Engine:
         out = np.zeros((nblk, nblk), dtype=np.uint8)
         self._chk(self.L.ba_hip_get_factor_tile_pattern(self.h, nblk, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    def set_reduced_solver(self, mode, rel_tolerance=1e-6, max_iterations=0, check_every=0):
+        """SOLVER_DIRECT (tile-sparse LDL^T, the default) or SOLVER_PCG (block-Jacobi preconditioned conjugate
+        gradients on S) for the following solve_gn calls; not structural, no finalize needed."""
+        if int(mode) == SOLVER_DIRECT:
+            self._chk(self.L.ba_hip_set_reduced_solver(self.h, SOLVER_DIRECT, None))
+            return
+        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every))
+        self._chk(self.L.ba_hip_set_reduced_solver(self.h, int(mode), C.byref(o)))
+
+    def pcg_stats(self):
+        """Statistics of the last solve_gn (a dict of ba_hip_pcg_stats); HipError if that solve was direct."""
+        st = PcgStats()
+        self._chk(self.L.ba_hip_get_pcg_stats(self.h, C.byref(st)))
+        return _pcg_stats_dict(st)
+
+    def pcg_solve(self, a_lower, b, block, rel_tolerance, max_iterations=0, check_every=0):
+        """Stand-alone PCG on an SPD system given by its lower triangle: (x, rc, stats dict)."""
+        a, b = _d(a_lower), _d(b)
+        x = np.zeros(b.shape[0])
+        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every))
+        st = PcgStats()
+        rc = self._chk(self.L.ba_hip_pcg_solve(self.h, b.shape[0], _p(a, dp), _p(b, dp), int(block), C.byref(o), _p(x, dp),
+                                               C.byref(st)), positive_ok=True)
+        return x, rc, _pcg_stats_dict(st)
 
     def dense_solve(self, a_lower, b):
         a, b = _d(a_lower), _d(b)

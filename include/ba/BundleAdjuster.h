@@ -65,6 +65,8 @@ struct SolutionSummary {  // reference BundleAdjuster.h:48-70
 
 // values of Options::pose_ordering (extension)
 enum class PoseOrdering { Natural = 0, Auto = 1 };
+// values of Options::reduced_solver (extension)
+enum class ReducedSolver { Direct = 0, Pcg = 1 };
 
 template <typename Scalar = double>
 struct Options {  // reference BundleAdjuster.h:72-107, same names and defaults
@@ -101,6 +103,15 @@ struct Options {  // reference BundleAdjuster.h:72-107, same names and defaults
   // tile-aligned groups of poses when that needs fewer tile products (multi-lap routes, loop closures).
   // Results are the same either way; not available with a sharded engine.
   PoseOrdering pose_ordering = PoseOrdering::Natural;
+  // extension: how the reduced camera system is solved (include/ba_hip.h: ba_hip_set_reduced_solver).  Direct =
+  // the tile-sparse LDL^T (the reference's CalculateGn); Pcg = block-Jacobi preconditioned conjugate gradients on
+  // S (inexact Gauss-Newton): the step solves S delta = rhs to pcg_tolerance relative residual, or is the iterate
+  // after pcg_max_iterations steps (0 = the number of unknowns).  May change between Solve() calls.  No factor
+  // exists after a Pcg iteration: the covariance getters and calculate_calibration_marginals report SolverError.
+  // Not available with a sharded engine.
+  ReducedSolver reduced_solver = ReducedSolver::Direct;
+  Scalar pcg_tolerance = 1e-6;
+  uint32_t pcg_max_iterations = 0;
 };
 
 // A dense Gaussian prior on poses (extension; include/ba_hip.h, ba_hip_marginalize): pose_ids (k), x0 (k x 16:
@@ -596,6 +607,9 @@ class BundleAdjuster {
     comm_set_ = false; comm_dirty_ = false; rank_ = 0; nranks_ = 1;
     mask_counts_dirty_ = true;
   }
+  // statistics of the last reduced solve when it ran Options::reduced_solver = Pcg (iterations, converged, true
+  // residual, times; include/ba_hip.h: ba_hip_pcg_stats); false when it was direct or nothing was solved yet
+  bool GetPcgStats(ba_hip_pcg_stats* out) const { return engine_ && ba_hip_get_pcg_stats(engine_, out) == 0; }
   bool SolveIsDistributed() const { return engine_ && ba_hip_solve_is_distributed(engine_) != 0; }
 
  private:
@@ -741,6 +755,16 @@ bool BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::SyncEngine() {
   o.gyro_bias_sigma = options_.gyro_bias_sigma; o.accel_bias_sigma = options_.accel_bias_sigma;
   o.pivot_rel_tolerance = options_.factorization_pivot_tolerance;
   if (!Check(ba_hip_set_options(engine_, &o), "ba_hip_set_options")) return false;
+  if (options_.reduced_solver == ReducedSolver::Pcg) {
+    if (comm_set_ || allreduce_ || collectives_) {
+      std::cerr << "ba::BundleAdjuster: Options::reduced_solver = Pcg is not available with a communicator or the "
+                   "all-reduce / collectives hooks (the sharded solve is direct)" << std::endl;
+      summary_.result = SolverError;
+      return false;
+    }
+  } else if (!Check(ba_hip_set_reduced_solver(engine_, BA_HIP_SOLVER_DIRECT, nullptr), "ba_hip_set_reduced_solver")) {
+    return false;
+  }
   if (comm_set_) {
     // native communicator: joined once per engine (a collective), the solve switch refreshed with it
     if (comm_dirty_) {
@@ -759,6 +783,13 @@ bool BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::SyncEngine() {
       ba_hip_set_collectives(engine_, collectives_, collectives_ctx_);
       collectives_dirty_ = false;
     }
+  }
+  if (options_.reduced_solver == ReducedSolver::Pcg) {  // after the hooks were cleared: the engine refuses PCG beside them
+    ba_hip_pcg_options po;
+    std::memset(&po, 0, sizeof(po));
+    po.rel_tolerance = options_.pcg_tolerance;
+    po.max_iterations = options_.pcg_max_iterations;
+    if (!Check(ba_hip_set_reduced_solver(engine_, BA_HIP_SOLVER_PCG, &po), "ba_hip_set_reduced_solver")) return false;
   }
   if (structure_dirty_) {
     EnsureHostState();  // the graph is re-marshalled from poses_ / landmarks_: they must be current

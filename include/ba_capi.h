@@ -31,6 +31,9 @@ typedef struct { /* ba::Options<double>, reference BundleAdjuster.h:72-107 */
   double factorization_pivot_tolerance; /* extension, 0 = off: ba::Options::factorization_pivot_tolerance */
   int32_t calculate_calibration_marginals; /* reference BundleAdjuster.h:95 (do_tvs adjusters) */
   int32_t pose_ordering; /* extension: 0 natural, 1 auto (ba::Options::pose_ordering, ba_hip_set_pose_ordering) */
+  int32_t reduced_solver; /* extension: 0 direct, 1 PCG (ba::Options::reduced_solver, ba_hip_set_reduced_solver) */
+  uint32_t pcg_max_iterations; /* ba::Options::pcg_max_iterations, 0 = the number of unknowns */
+  double pcg_tolerance;   /* ba::Options::pcg_tolerance */
 } ba_options;
 
 typedef struct { /* ba::SolutionSummary<double> + GetErrors, reference :48-70,593-602 */
@@ -136,6 +139,8 @@ void ba_adjuster_get_marginalization(const ba_adjuster* a, uint32_t* pose_ids, d
                                      double* c, uint32_t* dropped_projection);
 uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t* pose_ids, const double* x0_16,
                                      const double* H, const double* b, double c);
+/* ba::BundleAdjuster::GetPcgStats: 1 and *out filled when the last reduced solve ran PCG, 0 otherwise */
+int ba_adjuster_get_pcg_stats(const ba_adjuster* a, ba_hip_pcg_stats* out);
 /* GetLastStep().delta_k (zeros without do_tvs) */
 void ba_adjuster_get_last_calib_step(const ba_adjuster* a, double delta_k[6]);
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks);

@@ -275,7 +275,8 @@ uint32_t ba_hip_num_lm_params(const ba_hip_engine* e);
  * row-major (n = pose + calibration unknowns); block (i,j) kept only for i <= j when
  * use_triangular_matrices (the calibration border counts as the last block: S_pk is kept, S_kp not,
  * :513-518).  The vectors of get_rhs / get_delta_gn / get_step sized by the pose unknowns carry the
- * calibration entries behind them. */
+ * calibration entries behind them.  After a direct ba_hip_solve_gn S was factorised in place and is read from the
+ * copy of keep_reduced_system; after a PCG solve (ba_hip_set_reduced_solver) S is intact and no copy is needed. */
 int ba_hip_get_S(ba_hip_engine* e, double* s_nxn);
 int ba_hip_get_rhs(ba_hip_engine* e, double* rhs_p_sc, double* rhs_p, double* rhs_l);
 int ba_hip_get_delta_gn(ba_hip_engine* e, double* delta_p, double* delta_l);
@@ -299,7 +300,8 @@ int ba_hip_get_timers(ba_hip_engine* e, ba_hip_timers* t);
  * || S delta_gn - rhs_p_sc || and || rhs_p_sc || ON THE DEVICE from the copy of S kept before the
  * in-place factorisation (needs ba_hip_options.keep_reduced_system) and the Gauss-Newton pose
  * step of the last ba_hip_solve_gn — i.e. checks what CalculateGn promises,
- * S delta = rhs (BundleAdjuster.cpp:748-833).  Single shard only. */
+ * S delta = rhs (BundleAdjuster.cpp:748-833).  Single shard only.  After a PCG solve (ba_hip_set_reduced_solver)
+ * it runs on S itself, without keep_reduced_system. */
 int ba_hip_check_solve(ba_hip_engine* e, double* residual_norm, double* rhs_norm);
 /* Residual vectors of the inertial residuals at the current state (ImuResidualT::residual after
  * EvaluateResiduals, BundleAdjuster.cpp:225-256): 15 doubles per residual in residual-id order,
@@ -572,7 +574,62 @@ int ba_hip_get_marginalization(ba_hip_engine* e, uint32_t* blanket_ids, double* 
 /* Frees the store (also freed with the engine). */
 int ba_hip_release_marginalization(ba_hip_engine* e);
 
+/* ---- iterative reduced solve: block-Jacobi preconditioned conjugate gradients (extension) ----------
+ * The second solver behind ba_hip_solve_gn (inexact Gauss-Newton; Agarwal et al., "Bundle adjustment in the
+ * large"): S delta = rhs is solved by conjugate gradients from x0 = 0 on the tiles of S's own pattern (no fill),
+ * preconditioned by the diagonal blocks of S — one PoseSize x PoseSize block per active pose in the order the
+ * engine factorises, one K x K block for the calibration unknowns.  FP64, no atomics: two solves of the same
+ * system give the same bits.  The default stays the direct tile-sparse LDL^T.
+ *
+ * Stopping rule: when the recurrence reports ||r|| <= rel_tolerance * ||rhs|| the residual rhs - S x is recomputed
+ * and only that TRUE residual ends the solve with converged = 1; if it fails, the solve continues from the
+ * recomputed residual (residual_replacements counts these).  Reaching max_iterations is not an error: ba_hip_solve_gn
+ * returns 0 with converged = 0 (CG iterates from x0 = 0 are descent directions of the model).  A breakdown — p.Sp <= 0,
+ * a non-finite scalar, a preconditioner block that is not positive definite — returns BA_HIP_FACTORIZATION_ERROR
+ * and leaves the last iterate whose scalars were finite (zeros if none) in delta_gn.  The host reads the device's
+ * state every check_every passes only; alpha, beta and the decisions are formed on the device.
+ *
+ * The mode is not structural: it may change between two iterations without ba_hip_finalize.  After a PCG solve
+ *   - A still holds S: ba_hip_get_S works without keep_reduced_system, and ba_hip_check_solve runs on S itself
+ *     (its dense two-pass product shares no code with the solver's tile product: an independent check of
+ *     rel_residual_true);
+ *   - there is no factor: ba_hip_compute_marginals, the marginal getters and ba_hip_get_calibration_marginals
+ *     refuse with a message that names the solver.  ba_hip_marginalize reads the linearisation (factor rows,
+ *     pose-pose blocks), not the factor, and works as before;
+ *   - pose orderings, calibration unknowns, dense priors, LmSize 0 and the dogleg path work unchanged (outputs
+ *     stay in natural order; delta_gn is simply inexact).
+ * Sharded engines (all-reduce hook, collectives hook, communicator) refuse PCG, whichever call comes second. */
+#define BA_HIP_SOLVER_DIRECT 0   /* default: tile-sparse LDL^T */
+#define BA_HIP_SOLVER_PCG    1   /* block-Jacobi preconditioned conjugate gradients on S */
+typedef struct {
+  double rel_tolerance;
+  uint32_t max_iterations;   /* CG steps; 0 = the number of unknowns */
+  uint32_t check_every;      /* passes between two reads of the device state; 0 = the engine's choice */
+  uint32_t reserved[3];
+} ba_hip_pcg_options;
+typedef struct {
+  uint32_t iterations, converged, residual_replacements;
+  uint32_t breakdown;               /* 0 none, 1 p.Sp <= 0, 2 non-finite scalar, 3 preconditioner block not PD */
+  double rel_residual_recurrence;   /* ||r|| / ||rhs|| of the recurrence at the end */
+  double rel_residual_true;         /* ... of the last recomputed rhs - S x (0 if none was formed) */
+  double rhs_norm;
+  double solve_ms;                  /* the whole solve, preconditioner included */
+  double spmv_ms;                   /* mean device time of one product q = S p (sampled once per check_every) */
+  double precond_ms;                /* gathering and inverting the blocks */
+  uint64_t tiles_read_per_spmv;     /* lower tiles of S's pattern */
+  double bytes_read_per_spmv;       /* tiles + partial-sum slots + vectors */
+} ba_hip_pcg_stats;
+/* mode: BA_HIP_SOLVER_*; o: NULL with DIRECT (and with PCG: rel_tolerance 1e-6, the defaults above). */
+int ba_hip_set_reduced_solver(ba_hip_engine* e, int mode, const ba_hip_pcg_options* o);
+/* Statistics of the last ba_hip_solve_gn; an error if that solve was direct (or skipped). */
+int ba_hip_get_pcg_stats(ba_hip_engine* e, ba_hip_pcg_stats* out);
+
 /* ---- stand-alone kernels exposed for tests and benchmarks ------------------------- */
+/* The PCG solver on an SPD system given by its LOWER triangle (row-major n x n, host memory); `block`: size of the
+ * preconditioner's diagonal blocks (1 .. 16; the last block is shorter when it does not divide n).  The tile
+ * pattern is that of the nonzeros of a_lower.  Returns 0 or BA_HIP_FACTORIZATION_ERROR as described above. */
+int ba_hip_pcg_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const double* b, uint32_t block,
+                     const ba_hip_pcg_options* o, double* x, ba_hip_pcg_stats* stats);
 /* Dense Cholesky solve of an SPD system given by its LOWER triangle (row-major n x n,
  * host memory): x = A^-1 b.  Runs the same kernels ba_hip_solve_gn uses. */
 int ba_hip_dense_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const double* b, double* x);
