@@ -23,7 +23,9 @@
 //                                           iterations and the true residual of every Gauss-Newton step
 //   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
-//                                           GetLandmarkCovariance: selected inverse of the reduced system)
+//                                           GetLandmarkCovariance: selected inverse of the reduced system), then
+//                                           the norm of the cross covariance between the first active and the last
+//                                           pose and the time of the joint call (GetJointPoseCovariance)
 #include <ba/BundleAdjuster.h>
 
 #include <algorithm>
@@ -253,6 +255,20 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
     std::printf("pose %d sigma translation %.3e %.3e %.3e  rotation %.3e %.3e %.3e\n", kPoses - 1, std::sqrt(c(0, 0)),
                 std::sqrt(c(1, 1)), std::sqrt(c(2, 2)), std::sqrt(c(3, 3)), std::sqrt(c(4, 4)), std::sqrt(c(5, 5)));
     std::printf("median landmark sigma (inverse depth) %.3e over %zu landmarks\n", sl[sl.size() / 2], sl.size());
+    // poses 0 and 1 are fixed: pose 2 is the first with columns in S
+    ba::MatX joint;
+    const auto j0 = std::chrono::steady_clock::now();
+    const bool jok = adjuster.GetJointPoseCovariance({2u, (uint32_t)(kPoses - 1)}, joint);
+    const double joint_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - j0).count();
+    if (!jok || joint.rows() != 12) { std::printf("joint covariance unavailable\n"); return 2; }
+    double cross = 0.0, diag = 0.0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = 0; j < 6; ++j) {
+        cross += joint(i, 6 + j) * joint(i, 6 + j);
+        diag += joint(6 + i, 6 + j) * joint(6 + i, 6 + j);
+      }
+    std::printf("cross covariance of poses 2 and %d: norm %.3e (%.3e of pose %d's own block), joint call %.3f ms\n", kPoses - 1,
+                std::sqrt(cross), std::sqrt(cross / diag), kPoses - 1, joint_ms);
     ok = ok && std::isfinite(c(0, 0)) && c(0, 0) > 0 && sl[sl.size() / 2] > 0;
   }
   return ok ? 0 : 1;

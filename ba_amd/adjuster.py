@@ -70,6 +70,7 @@ SYMBOLS = [
     "ba_adjuster_get_last_calib_step", "ba_adjuster_get_calibration_marginals", "ba_adjuster_get_camera_params",
     "ba_adjuster_add_camera_fov", "ba_adjuster_get_camera_fov",
     "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
+    "ba_adjuster_get_joint_pose_covariance",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
     "ba_adjuster_get_pcg_stats",
 ]
@@ -421,6 +422,21 @@ class BundleAdjuster:
         if k != D:
             raise RuntimeError("pose covariance of pose %d unavailable (see stderr)" % pose_id)
         return c.reshape(D, D)
+
+    def GetJointPoseCovariance(self, ids, include_calibration=False):
+        """GetJointPoseCovariance: the (M, M) joint covariance of the poses `ids` in the given order, M =
+        len(ids) * PoseSize (+ the calibration rows last); raises when unavailable."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32).ravel()
+        k = self.L.ba_hip_num_calib_params(self.engine().h) if include_calibration else 0
+        m = len(ids) * self.pose_dim + k
+        c = np.zeros((m, m))
+        self.L.ba_adjuster_get_joint_pose_covariance.restype = C.c_uint32
+        got = self.L.ba_adjuster_get_joint_pose_covariance(self.h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                           int(bool(include_calibration)),
+                                                           c.ctypes.data_as(C.POINTER(C.c_double)))
+        if got != m or m == 0:
+            raise RuntimeError("joint pose covariance unavailable (see stderr)")
+        return c
 
     def landmark_covariance(self, landmark_id):
         """GetLandmarkCovariance: LmSize x LmSize; raises when unavailable."""

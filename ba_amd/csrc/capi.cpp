@@ -50,6 +50,7 @@ struct Iface {
   virtual void last_calib_step(double* d6) const = 0;
   virtual uint32_t marginals(double* cov) const = 0;
   virtual uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) = 0;
+  virtual uint32_t joint_covariance(uint32_t n, const uint32_t* ids, int include_calibration, double* out) = 0;
   virtual int marginalize(uint32_t nm, const uint32_t* m, uint32_t nl, const uint32_t* l, uint32_t* nb) = 0;
   virtual void marginalization(uint32_t* ids, double* x0, double* H, double* b, double* c, uint32_t* dropped) const = 0;
   virtual uint32_t add_dense_prior(uint32_t k, const uint32_t* ids, const double* x0, const double* H, const double* b,
@@ -251,6 +252,12 @@ struct Impl : Iface {
     for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
     return (uint32_t)m.rows();
   }
+  uint32_t joint_covariance(uint32_t n, const uint32_t* ids, int include_calibration, double* out) override {
+    ba::MatX m;
+    if (!ba.GetJointPoseCovariance(std::vector<uint32_t>(ids, ids + n), m, include_calibration != 0)) return 0;
+    for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
+    return (uint32_t)m.rows();
+  }
   void last_calib_step(double* d6) const override {
     const auto& d = ba.GetLastStep().delta_k;
     for (size_t i = 0; i < 6; ++i) d6[i] = i < d.size() ? d[i] : 0.0;
@@ -389,6 +396,11 @@ uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, 
 }
 uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov) {
   return a->p->covariance(2, landmark_id, 0, cov);
+}
+uint32_t ba_adjuster_get_joint_pose_covariance(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids,
+                                               int include_calibration, double* cov) {
+  if ((n && !pose_ids) || !cov) return 0;
+  return a->p->joint_covariance(n, pose_ids, include_calibration, cov);
 }
 int ba_adjuster_marginalize(ba_adjuster* a, uint32_t nm, const uint32_t* pose_ids, uint32_t nl,
                             const uint32_t* landmark_ids, uint32_t* blanket_poses) {

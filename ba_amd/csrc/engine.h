@@ -251,6 +251,12 @@ struct Engine {
   uint64_t sig_plan_version = ~0ull;
   bool sig_valid = false;
   ba_hip_marginal_stats mstats = {};
+  // joint covariances of arbitrary pose sets (ba_hip_get_joint_marginals, k_jointcov.hip): the workspace of the
+  // forward substitution Y = L^-1 E and the Gram product, allocated by the first request, reused, freed by
+  // ba_hip_release_marginals and with the engine.  jc_idx: the plan of the last request (jointcov.h)
+  DBuf<uint32_t> jc_idx;
+  DBuf<double> jc_Y, jc_slots, jc_part, jc_out;
+  ba_hip_joint_marginal_stats jstats = {};
   // dense pose priors (ba_hip_set_dense_priors, k_marg.hip): the caller's priors, their device copies (uploaded
   // by ba_hip_finalize), the lower D x D blocks of every prior (dp_blk, prior q from dp_blk_first[q]) and the
   // per-linearisation values: d, J_d, G = J_d^T H J_d, g = J_d^T (b - H d), w = b - H d, E_p
@@ -397,6 +403,10 @@ int marginals_gather(Engine* e, uint32_t n, const std::vector<uint32_t>& ra, con
                      int Db, double* out);
 int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out);
 void marginals_release(Engine* e);
+// joint covariance of the rows `sel` of S (engine numbering) from the factor in A (k_jointcov.hip): out is
+// sel x sel on the host; reads A and invdiag only
+int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out);
+void jointcov_release(Engine* e);
 // dense priors and marginalisation (k_marg.hip): upload at finalize; linearise (mode 1: into A, rhs_p, rhs_p_sc) or
 // evaluate (mode 0) every prior at the current state, E_p summed into *err_host; the dogleg term; one marginalisation
 int priors_upload(Engine* e);

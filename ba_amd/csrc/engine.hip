@@ -568,6 +568,7 @@ void ba_hip_destroy(ba_hip_engine* h) {
   REL(gn_l); REL(step_p); REL(step_l); REL(invdiag); REL(partials); REL(scalars_out); REL(hist);
   REL(flags); REL(pivot_floor);
   marginals_release(e);
+  jointcov_release(e);
   REL(pose_active); REL(un_pose); REL(un_t); REL(un_cov_inv); REL(un_scale); REL(un_rot);
   REL(bin_p1); REL(bin_p2); REL(bin_t); REL(bin_cov_inv); REL(bin_cov_inv_sqrt); REL(bin_w); REL(bin_rot);
   REL(imu_p1); REL(imu_p2); REL(imu_ptr); REL(imu_meas); REL(imu_consts); REL(imu_cov_inv);
@@ -1501,6 +1502,53 @@ int ba_hip_get_landmark_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* 
       }
   return marginals_landmarks(e, n, lm_ids, out);
 }
+// ---- joint covariance of a pose set (k_jointcov.hip): Y = L^-1 E over the reach, Sigma = Y^T D Y ----
+int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,
+                               double* out) {
+  ENG(h);
+  static const char* what = "ba_hip_get_joint_marginals";
+  const std::string m = std::string(what) + ": ";
+  if (!e->finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
+  if (dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
+  if (!e->factored && e->pcg_solved)
+    return e->fail_msg((m + "the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor; "
+                            "joint marginals need a direct solve (ba_hip_set_reduced_solver)").c_str());
+  if (!e->factored)
+    return e->fail_msg((m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised "
+                            "since)").c_str());
+  if ((n && !pose_ids) || !out) return e->fail_msg((m + "NULL argument").c_str());
+  const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K;
+  if (include_calibration && !K)
+    return e->fail_msg((m + "include_calibration without calibration unknowns (ba_hip_set_calibration)").c_str());
+  const uint64_t M = (uint64_t)n * D + (include_calibration ? K : 0);
+  if (M == 0) return e->fail_msg((m + "no pose and no calibration rows requested").c_str());
+  if (M > BA_HIP_JOINT_MAX_COLUMNS)
+    return e->fail_msg((m + std::to_string(M) + " columns requested, the limit is BA_HIP_JOINT_MAX_COLUMNS (" +
+                        std::to_string(BA_HIP_JOINT_MAX_COLUMNS) + ")").c_str());
+  std::vector<uint32_t> sel;
+  sel.reserve(M);
+  std::vector<uint32_t> seen(pose_ids, pose_ids + n);
+  std::sort(seen.begin(), seen.end());
+  for (uint32_t i = 0; i + 1 < n; ++i)
+    if (seen[i] == seen[i + 1])
+      return e->fail_msg((m + "pose " + std::to_string(seen[i]) + " is repeated (the joint block would be singular)").c_str());
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t r;
+    int rc;
+    if ((rc = pose_row(e, pose_ids[i], &r, what))) return rc;
+    for (uint32_t x = 0; x < D; ++x) sel.push_back(r + x);
+  }
+  if (include_calibration)
+    for (uint32_t x = 0; x < K; ++x) sel.push_back(e->st.np + x);
+  BAE_HIP(hipSetDevice(e->device));
+  return jointcov_run(e, sel, out);
+}
+int ba_hip_get_joint_marginal_stats(ba_hip_engine* h, ba_hip_joint_marginal_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_joint_marginal_stats: NULL argument");
+  *out = e->jstats;
+  return 0;
+}
 int ba_hip_get_marginal_stats(ba_hip_engine* h, ba_hip_marginal_stats* out) {
   ENG(h);
   if (!out) return e->fail_msg("ba_hip_get_marginal_stats: NULL argument");
@@ -1512,6 +1560,7 @@ int ba_hip_release_marginals(ba_hip_engine* h) {
   (void)hipSetDevice(e->device);
   (void)hipStreamSynchronize(e->stream);
   marginals_release(e);
+  jointcov_release(e);
   return 0;
 }
 

@@ -331,22 +331,19 @@ extern "C" uint64_t ba_hostcheck_group_order_products(uint32_t Pact, int D, uint
 #include <cmath>
 #include "selinv.h"
 
-// The selected inverse on a dense symmetric n x n matrix S (row-major; n need not be a multiple of 64:
-// the last tile is padded with an identity, as the engine pads A).  The tile pattern is that of S
-// (diagonal tiles always), closed by tile_symbolic_factor.  S is factorised like the engine does —
-// un-pivoted L D L^T, L carrying sqrt|pivot|, D = diag(+-1) — and selinv_host runs on the factor.
-// Out: sigma (n x n, both halves, NaN outside the factor's pattern), nzL (nt x nt lower pattern), the
-// tile products of the plan and its number of levels.  Returns -1 on a zero pivot.
-extern "C" int ba_hostcheck_selinv(uint32_t n, const double* S, double* sigma, uint8_t* nzL_out, uint64_t* products,
-                                   uint32_t* levels) {
+// Pattern and factor of a dense symmetric S for the two harnesses below: the closed tile pattern, L (lower
+// storage, ld = 64 nt), the pivot signs and linvT; -1 on a zero pivot
+static int host_tile_factor(uint32_t n, const double* S, std::vector<uint8_t>& nz, std::vector<double>& L,
+                            std::vector<double>& d, std::vector<double>& linvT) {
   const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
-  std::vector<uint8_t> nz((size_t)nt * nt, 0);
+  nz.assign((size_t)nt * nt, 0);
   for (uint32_t r = 0; r < n; ++r)
     for (uint32_t c = 0; c < n; ++c)
       if (S[(size_t)r * n + c] != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
   for (uint32_t t = 0; t < nt; ++t) nz[(size_t)t * nt + t] = 1;
   bae::tile_symbolic_factor(nz, nt);
-  std::vector<double> L((size_t)ld * ld, 0.0), d(ld, 1.0);
+  L.assign((size_t)ld * ld, 0.0);
+  d.assign(ld, 1.0);
   for (uint32_t r = 0; r < ld; ++r)
     for (uint32_t c = 0; c <= r; ++c) L[(size_t)r * ld + c] = (r < n && c < n) ? S[(size_t)r * n + c] : (r == c ? 1.0 : 0.0);
   for (uint32_t j = 0; j < ld; ++j) {
@@ -363,7 +360,7 @@ extern "C" int ba_hostcheck_selinv(uint32_t n, const double* S, double* sigma, u
     }
   }
   // linvT[J] = L_JJ^-T: forward substitution on the identity, stored transposed
-  std::vector<double> linvT((size_t)nt * 4096, 0.0);
+  linvT.assign((size_t)nt * 4096, 0.0);
   for (uint32_t J = 0; J < nt; ++J) {
     const double* Ljj = &L[(size_t)J * 64 * ld + (size_t)J * 64];
     double* G = &linvT[(size_t)J * 4096];
@@ -374,6 +371,21 @@ extern "C" int ba_hostcheck_selinv(uint32_t n, const double* S, double* sigma, u
         G[(size_t)c * 64 + r] = s / Ljj[(size_t)r * ld + r];  // (L^-1)[r][c] at G[c][r]
       }
   }
+  return 0;
+}
+
+// The selected inverse on a dense symmetric n x n matrix S (row-major; n need not be a multiple of 64:
+// the last tile is padded with an identity, as the engine pads A).  The tile pattern is that of S
+// (diagonal tiles always), closed by tile_symbolic_factor.  S is factorised like the engine does —
+// un-pivoted L D L^T, L carrying sqrt|pivot|, D = diag(+-1) — and selinv_host runs on the factor.
+// Out: sigma (n x n, both halves, NaN outside the factor's pattern), nzL (nt x nt lower pattern), the
+// tile products of the plan and its number of levels.  Returns -1 on a zero pivot.
+extern "C" int ba_hostcheck_selinv(uint32_t n, const double* S, double* sigma, uint8_t* nzL_out, uint64_t* products,
+                                   uint32_t* levels) {
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  std::vector<uint8_t> nz;
+  std::vector<double> L, d, linvT;
+  if (host_tile_factor(n, S, nz, L, d, linvT)) return -1;
   bae::SelinvPlan plan;
   bae::build_selinv_plan(nz, nt, plan);
   std::vector<double> store((size_t)plan.n_slots * 4096, 0.0);
@@ -390,6 +402,43 @@ extern "C" int ba_hostcheck_selinv(uint32_t n, const double* S, double* sigma, u
 extern "C" uint64_t ba_hostcheck_selinv_products(uint32_t nt, const uint8_t* nzL) {
   std::vector<uint8_t> v(nzL, nzL + (size_t)nt * nt);
   return bae::selinv_tile_products(v, nt);
+}
+
+// ---- joint covariance of a row set (jointcov.h) ---------------------------------------------------------
+#include "jointcov.h"
+
+// Sigma[sel, sel] of a dense symmetric S (as ba_hostcheck_selinv: same pattern, same factorisation) by
+// build_joint_plan + jointcov_host.  Out: cov (m x m), Y (64 nt x m: the panels scattered to their tile rows,
+// zero outside the reach), reach (nt flags), level_of (nt, 0xffffffff outside the reach), nzL (nt x nt), the
+// tile products and the number of levels.  Returns -1 on a zero pivot, -2 on a row out of range.
+extern "C" int ba_hostcheck_joint_marginals(uint32_t n, const double* S, uint32_t m, const uint32_t* sel, double* cov,
+                                            double* Y_out, uint8_t* reach_out, uint32_t* level_of, uint8_t* nzL_out,
+                                            uint64_t* products, uint32_t* levels) {
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  for (uint32_t c = 0; c < m; ++c)
+    if (sel[c] >= n) return -2;
+  std::vector<uint8_t> nz;
+  std::vector<double> L, d, linvT;
+  if (host_tile_factor(n, S, nz, L, d, linvT)) return -1;
+  std::vector<uint32_t> tiles(m);
+  for (uint32_t c = 0; c < m; ++c) tiles[c] = sel[c] / 64;
+  bae::JointPlan p;
+  bae::build_joint_plan(nz, nt, tiles, m, p);
+  std::vector<double> Y(p.y_count());
+  bae::jointcov_host(p, L.data(), ld, linvT.data(), d.data(), sel, Y.data(), cov);
+  std::fill(Y_out, Y_out + (size_t)ld * m, 0.0);
+  for (uint32_t t = 0; t < nt; ++t) {
+    reach_out[t] = p.pos[t] != bae::kJointNone;
+    level_of[t] = reach_out[t] ? p.level_of[p.pos[t]] : bae::kJointNone;
+    if (reach_out[t])
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < m; ++c)
+          Y_out[((size_t)t * 64 + r) * m + c] = Y[((size_t)p.pos[t] * 64 + r) * p.m_pad + c];
+  }
+  std::copy(nz.begin(), nz.end(), nzL_out);
+  *products = p.products;
+  *levels = p.levels();
+  return 0;
 }
 
 // ---- marginalisation plan and the dense prior's error state (marg.h) ----------------------------------

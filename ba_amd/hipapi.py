@@ -109,6 +109,15 @@ class MarginalStats(C.Structure):
                 ("levels", C.c_uint32)]
 
 
+class JointMarginalStats(C.Structure):
+    _fields_ = [("solve_ms", C.c_double), ("gram_ms", C.c_double), ("workspace_bytes", C.c_double),
+                ("tile_products", C.c_uint64), ("columns", C.c_uint32), ("reach_tiles", C.c_uint32),
+                ("levels", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+JOINT_MAX_COLUMNS = 512  # BA_HIP_JOINT_MAX_COLUMNS
+
+
 class MarginalizationStats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("blanket_poses", "absorbed_projection", "absorbed_unary", "absorbed_binary",
                                           "absorbed_inertial", "absorbed_priors", "dropped_projection", "reserved")] + \
@@ -156,7 +165,7 @@ SYMBOLS = [
     "ba_hip_set_pose_ordering", "ba_hip_set_pose_permutation", "ba_hip_get_pose_ordering", "ba_hip_get_pose_group_graph",
     "ba_hip_compute_marginals", "ba_hip_get_pose_marginals", "ba_hip_get_pose_pair_marginals",
     "ba_hip_get_calibration_block_marginals", "ba_hip_get_landmark_marginals", "ba_hip_get_marginal_stats",
-    "ba_hip_release_marginals",
+    "ba_hip_release_marginals", "ba_hip_get_joint_marginals", "ba_hip_get_joint_marginal_stats",
     "ba_hip_set_dense_priors", "ba_hip_get_prior_errors", "ba_hip_marginalize", "ba_hip_get_marginalization",
     "ba_hip_release_marginalization", "ba_hip_set_unary_scales",
     "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve",
@@ -433,6 +442,22 @@ class Engine:
 
     def release_marginals(self):
         self._chk(self.L.ba_hip_release_marginals(self.h))
+
+    # ---- joint covariance of a pose set (forward substitution + Gram product, no selected inverse) ----
+    def joint_marginals(self, ids, include_calibration=False):
+        """(M, M) joint covariance of the poses `ids` in the caller's order, the calibration rows last when asked
+        for; M = len(ids) * D (+ K).  Any active poses, coupled by the factor's pattern or not."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32).ravel()
+        m = len(ids) * self.pose_dim + (self.num_calib_params() if include_calibration else 0)
+        out = np.empty((m, m))
+        self._chk(self.L.ba_hip_get_joint_marginals(self.h, len(ids), _p(ids, u32p), int(bool(include_calibration)),
+                                                    _p(out, dp)))
+        return out
+
+    def joint_marginal_stats(self):
+        st = JointMarginalStats()
+        self._chk(self.L.ba_hip_get_joint_marginal_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in JointMarginalStats._fields_ if k != "reserved"}
 
     # ---- dense pose priors and marginalisation (ba_hip.h) ----
     def set_dense_priors(self, priors):

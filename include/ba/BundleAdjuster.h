@@ -500,6 +500,23 @@ class BundleAdjuster {
       return MatX();
     return m;
   }
+  // Joint covariance of the poses `ids` in the given order (extension; include/ba_hip.h
+  // ba_hip_get_joint_marginals): an M x M matrix, M = ids.size() * kPoseDim
+  // (+ kCalibDim rows last with include_calibration), block (i, j) = Cov(ids[i], ids[j]).  Unlike
+  // GetPoseCrossCovariance it serves any active poses, coupled by the factor's pattern or not, and needs no
+  // selected inverse.  false, reported through Check(), and a 0 x 0 cov when unavailable (no solve yet, an
+  // inactive or repeated pose, more than BA_HIP_JOINT_MAX_COLUMNS columns, the PCG or the distributed solve).
+  bool GetJointPoseCovariance(const std::vector<uint32_t>& ids, MatrixXt& cov, bool include_calibration = false) {
+    const int M = (int)(ids.size() * kPoseDim + (include_calibration ? kCalibDim : 0));
+    cov = MatX(M, M);
+    if (!engine_ || !Check(ba_hip_get_joint_marginals(engine_, (uint32_t)ids.size(), ids.data(), include_calibration ? 1 : 0,
+                                                      cov.data()),
+                           "ba_hip_get_joint_marginals")) {
+      cov = MatX();
+      return false;
+    }
+    return true;
+  }
   // Sliding-window marginalisation (extension; include/ba_hip.h).  Called after Solve():
   // relinearises at the state Solve() left (masks as Solve() computes them) and eliminates pose_ids and
   // landmark_ids into a dense prior on their blanket.  The unary Huber scales the extra linearisation compounds

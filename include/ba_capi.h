@@ -127,6 +127,11 @@ uint32_t ba_adjuster_get_calibration_marginals(const ba_adjuster* a, double cov[
 uint32_t ba_adjuster_get_pose_covariance(ba_adjuster* a, uint32_t pose_id, double* cov);
 uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, uint32_t pose_b, double* cov);
 uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov);
+/* GetJointPoseCovariance (extension): the M x M joint covariance of the n poses pose_ids in the caller's order,
+ * M = n PoseSize (+ the calibration rows last with include_calibration), row-major into cov (room for M^2
+ * values); returns M, 0 when unavailable (the summary's result then reads SolverError) */
+uint32_t ba_adjuster_get_joint_pose_covariance(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids,
+                                               int include_calibration, double* cov);
 /* Marginalize / AddDensePrior (extension; include/ba_hip.h).  ba_adjuster_marginalize:
  * after a solve, eliminates the poses and landmarks into a dense prior kept by the adjuster; returns 0 and the
  * blanket size, or 1 when refused.  ba_adjuster_get_marginalization reads it: |B| pose ids, |B| x 16 states,

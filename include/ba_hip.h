@@ -513,8 +513,40 @@ int ba_hip_get_calibration_block_marginals(ba_hip_engine* e, double* out);
  * LmSize 3).  lm_ids NULL: every active landmark, by optimisation index (n = active landmark count). */
 int ba_hip_get_landmark_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* lm_ids, double* out);
 int ba_hip_get_marginal_stats(ba_hip_engine* e, ba_hip_marginal_stats* out);
-/* Frees the Sigma store (also freed with the engine). */
+/* Frees the Sigma store and the workspace of ba_hip_get_joint_marginals (also freed with the engine). */
 int ba_hip_release_marginals(ba_hip_engine* e);
+
+/* ---- joint covariance of an arbitrary pose set (no selected inverse) ------------------
+ * The M x M block of Sigma = S^-1 over the rows of the poses pose_ids (and, with include_calibration, the K
+ * calibration rows after them), M = n D + (include_calibration ? K : 0): block (i, j) of out (row-major) is
+ * Cov(pose_ids[i], pose_ids[j]) in the caller's order, in the coordinates and with the Sigma of the getters
+ * above (masked parameters read ~1e-6, pose orderings are invisible).  Any set of active poses is served,
+ * whether or not the factor's tile pattern couples them: with S = L D L^T the block is Y^T D Y, Y = L^-1 E for
+ * the unit columns E of the requested rows, a forward substitution over the tile rows on the elimination-tree
+ * paths from the requested tiles to the root (the reach) and a Gram product.  The selected inverse is neither
+ * computed nor allocated, ba_hip_get_marginal_stats is untouched; the call reads the factor only.  out is
+ * bitwise symmetric and two calls give the same bits.
+ *   - Preconditions of the pose getters: finalized, the factor of the last direct ba_hip_solve_gn, not
+ *     re-linearised since, not the distributed solve (replicated sharded engines are served).
+ *   - Errors: an inactive pose, a repeated id, include_calibration without calibration unknowns, no column at
+ *     all, M > BA_HIP_JOINT_MAX_COLUMNS, NULL arguments.
+ *   - The workspace (the Y panels and the partial tiles) is allocated by the first request, reused, and freed
+ *     by ba_hip_release_marginals and with the engine. */
+#define BA_HIP_JOINT_MAX_COLUMNS 512
+typedef struct {
+  double solve_ms;          /* device time of the forward substitution (events) */
+  double gram_ms;           /* device time of the Gram product and its combine */
+  double workspace_bytes;   /* device bytes the joint path holds */
+  uint64_t tile_products;   /* 64x64x64 products: (sum_{I in reach} |row(I) n reach| + |reach|) per 64 columns */
+  uint32_t columns;         /* M */
+  uint32_t reach_tiles;     /* tile rows visited */
+  uint32_t levels;          /* launch pairs of the substitution */
+  uint32_t reserved;
+} ba_hip_joint_marginal_stats;
+int ba_hip_get_joint_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* pose_ids, int include_calibration,
+                               double* out);
+/* The figures of the last successful ba_hip_get_joint_marginals (zeros before the first). */
+int ba_hip_get_joint_marginal_stats(ba_hip_engine* e, ba_hip_joint_marginal_stats* out);
 
 /* ---- sliding-window marginalisation and dense pose priors (extension) ----------------
  * Conventions are the engine's: S delta = rhs (rhs_p_sc), ApplyUpdate(delta) moves a pose by
