@@ -1775,7 +1775,11 @@ int ba_hip_get_structure_stats(ba_hip_engine* h, ba_hip_structure_stats* out) {
 int ba_hip_debug_set(ba_hip_engine* h, int key, int value) {
   ENG(h);
   switch (key) {
-    case 1: e->dbg_assemble_variant = value; break;
+    case 1:
+      if (value != 0 && value != 1 && value != 2 && value != 5 && value != 6)
+        return e->fail_msg("ba_hip_debug_set: key 1 takes the assembly variants 0, 1, 2, 5 and 6");
+      e->dbg_assemble_variant = value;
+      break;
     case 2: e->dbg_tile_order = value; e->tile_order_version = ~0ull; break;
     case 4: e->dbg_linearize_variant = value; break;
     case 5: e->dbg_host_structure = value; e->finalized = false; break;

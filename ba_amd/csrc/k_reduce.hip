@@ -29,6 +29,10 @@ namespace bae {
 // VAR 2: six threads per block, terms four at a time — the four (rowA, rowB) index pairs are loaded
 //        first, then the eight row pieces, so that a block's dependent-load chain is
 //        2 x ceil(terms / 4) memory latencies instead of 2 x terms
+// VAR 5: one thread per block, terms two at a time (both index pairs first, then the four rows).  This is the
+//        variant that runs; every other variant ba_hip_debug_set accepts gives bitwise its S
+//        (tests/test_track_lengths_gpu.py).  VAR 3 and 4, the write-only and gather-only timing floors of
+//        DESIGN.md §4b, left S wrong on purpose and are gone.
 // VAR 6 (round-3 experiment, ba_hip_debug_set key 1; VAR 5 is what runs): a test of the hypothesis that the kernel
 //        is bound by the LATENCY of its dependent loads (a tile lives ~20 us in a workgroup, at most 4.7 tiles fit
 //        a CU's LDS): half the threads (a tile has at most ~145 blocks), the launch entry carries the tile's list
@@ -68,9 +72,7 @@ k_assemble_tiles(uint32_t nt, const uint32_t* __restrict__ tile_order, const uin
   if (q1 > q0) {
     for (int i = tid; i < 64 * TS / 2; i += NT) reinterpret_cast<double2*>(T)[i] = make_double2(0.0, 0.0);
     __syncthreads();
-    if constexpr (VAR == 3) {
-      // experiment: no gather at all (floor of the write phase)
-    } else if constexpr (VAR == 6) {
+    if constexpr (VAR == 6) {
       for (uint32_t q = q0 + tid; q < q1; q += NT) {
         const uint2 ref = tile_ref[q];
         const uint32_t cnt = ref.y >> 14;
@@ -118,7 +120,7 @@ k_assemble_tiles(uint32_t nt, const uint32_t* __restrict__ tile_order, const uin
           }
         }
       }
-    } else if constexpr (VAR == 0 || VAR == 4 || VAR == 5) {
+    } else if constexpr (VAR == 0 || VAR == 5) {
       for (uint32_t q = q0 + tid; q < q1; q += 256) {
         const uint2 ref = tile_ref[q];
         const uint32_t cnt = ref.y >> 14;
@@ -259,7 +261,6 @@ k_assemble_tiles(uint32_t nt, const uint32_t* __restrict__ tile_order, const uin
 #pragma unroll
   for (int r = tid >> 5; r < 64; r += NT / 32) {
     const double2 v = q1 > q0 ? *reinterpret_cast<const double2*>(T + r * TS + 2 * c2) : make_double2(0.0, 0.0);
-    if (VAR == 4 && r >= 8) break;  // experiment: gather only (the tile is NOT written in full: wrong results)
     // 14 GB of tiles nobody re-reads before the factorisation reaches them: streaming stores (-2 %)
     typedef double d2_t __attribute__((ext_vector_type(2)));
     d2_t v2; v2.x = v.x; v2.y = v.y;
@@ -579,7 +580,7 @@ int launch_gather_S(Engine* e) {
                      e->tile_ptr.p, e->tile_ref.p, e->pair_ent.p, e->frow.p, ld, e->A.p, (const uint4*)e->tile_desc.p)
   switch (e->dbg_assemble_variant) {
     case 0: BAE_ASM(0); break; case 1: BAE_ASM(1); break; case 2: BAE_ASM(2); break;
-    case 3: BAE_ASM(3); break; case 4: BAE_ASM(4); break; case 5: BAE_ASM(5); break; default: BAE_ASM(6); break;
+    case 6: BAE_ASM(6); break; default: BAE_ASM(5); break;
   }
 #undef BAE_ASM
   e->prof_end(e->ev_gather);

@@ -379,7 +379,11 @@ __device__ void lm_sigma(const LmArgs& g, uint32_t l, double* __restrict__ out) 
       U[a][b] = u;
     }
   if (lane == 0) {
-    const double* Vi = g.lm_vinv + (size_t)l * LM * LM;
+    // a landmark without observations is in no linearisation range: k_linearize never wrote its V^-1 (the buffer
+    // holds zeros there).  Its V is zero and the guard of invert_v (BundleAdjuster.cpp:431-439) makes it 1e-6 I.
+    double Vi[LM * LM];
+#pragma unroll
+    for (int a = 0; a < LM * LM; ++a) Vi[a] = nobs ? g.lm_vinv[(size_t)l * LM * LM + a] : (a % (LM + 1) == 0 ? 1e6 : 0.0);
     double T[LM][LM];
 #pragma unroll
     for (int a = 0; a < LM; ++a)

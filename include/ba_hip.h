@@ -346,8 +346,8 @@ typedef struct {
 } ba_hip_structure_stats;
 int ba_hip_get_structure_stats(ba_hip_engine* e, ba_hip_structure_stats* out);
 /* Experiment knobs for scratch/ micro-benchmarks (kernel variants with identical results): key 1 =
- * variant of the tile assembly kernel (0, 1, 2), key 2 = launch order of its tiles (0 row-major,
- * 1 XCD-aware columns), key 3 = 1: write every lower tile instead of the factor's pattern only,
+ * variant of the tile assembly kernel (0, 1, 2, 6; 5 is what runs; any other value is refused),
+ * key 2 = launch order of its tiles (0 row-major, 1 XCD-aware columns), key 3 = 1: write every lower tile instead of the factor's pattern only,
  * key 4 = linearisation variant (0 LDS-staged rows, 1 direct stores), key 5 = 1: build the static
  * lists on the host (structure.h) instead of on the device at the next ba_hip_finalize, key 6 = variant
  * of the inertial linearisation (-1 chosen by residual count, 0 one lane per sample / per residual, 1 a
@@ -510,7 +510,9 @@ int ba_hip_get_pose_pair_marginals(ba_hip_engine* e, uint32_t n, const uint32_t*
 int ba_hip_get_calibration_block_marginals(ba_hip_engine* e, double* out);
 /* out: n x LmSize x LmSize, Sigma_ll = V^-1 + V^-1 W^T Sigma_pp W V^-1 (the (l, l) block of the inverse of
  * the full poses + landmarks system) in the coordinates of delta_l (inverse depth for LmSize 1, x_w for
- * LmSize 3).  lm_ids NULL: every active landmark, by optimisation index (n = active landmark count). */
+ * LmSize 3).  lm_ids NULL: every active landmark, by optimisation index (n = active landmark count).
+ * An active landmark without observations has V = 0, which the guard of BundleAdjuster.cpp:431-439 turns
+ * into 1e-6 I, and no W: its block is 1e6 I. */
 int ba_hip_get_landmark_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* lm_ids, double* out);
 int ba_hip_get_marginal_stats(ba_hip_engine* e, ba_hip_marginal_stats* out);
 /* Frees the Sigma store and the workspace of ba_hip_get_joint_marginals (also freed with the engine). */

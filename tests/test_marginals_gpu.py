@@ -50,7 +50,8 @@ class Setup:
 
 
 def _engine(sc, lm_dim, pa, mode=hipapi.ORDER_NATURAL, tvs=False, pose_pose=False, keep=True, extra_obs=None,
-            calib=0, lm_active=None):
+            calib=0, lm_active=None, obs=None):
+    """obs = (z, pose, lm): the accepted residuals as given (scenes whose observation table is not make_scene's)."""
     eng = hipapi.Engine(lm_dim, 6)
     o = hipapi.Options()
     o.projection_outlier_threshold = 1.0
@@ -59,13 +60,13 @@ def _engine(sc, lm_dim, pa, mode=hipapi.ORDER_NATURAL, tvs=False, pose_pose=Fals
     eng.set_options(o)
     if tvs or calib:
         eng.set_calibration(calib, tvs)
-    nsel = sc.obs_per_landmark + (1 if lm_dim == 1 else 0)
+    nsel = (sc.obs_per_landmark or 0) + (1 if lm_dim == 1 else 0)
     sel = np.ones(len(sc.obs_pose), dtype=bool)
-    if lm_dim == 1 and not hasattr(sc, "revisited"):
+    if lm_dim == 1 and not hasattr(sc, "revisited") and obs is None:
         sel[::nsel] = False
     if hasattr(sc, "revisited") and lm_dim == 1:
         sel &= ~np.r_[True, np.diff(sc.obs_lm) != 0]
-    z, pose, lm = sc.obs_z[sel], sc.obs_pose[sel], sc.obs_lm[sel]
+    z, pose, lm = (sc.obs_z[sel], sc.obs_pose[sel], sc.obs_lm[sel]) if obs is None else obs
     if extra_obs is not None:
         z, pose, lm = (np.concatenate([a, b]) for a, b in zip((z, pose, lm), extra_obs))
     eng.set_cameras(sc.cam_params, [0.01, -0.02, 0.03, 0, 0, 0, 1] if tvs else [0, 0, 0, 0, 0, 0, 1])

@@ -10,27 +10,18 @@ dense brute-force restatement of the reference's algebra from the same per-resid
 Covers: inactive poses and landmarks, unlisted observations (measured from the reference pose),
 duplicate observations of a landmark from one pose, landmarks with more than 64 observations,
 landmarks without observations, PoseSize 6 / 9 / 15 (blocks straddling 64-tile boundaries).
+Track lengths here are drawn from 0..kmax (kmax <= 12) plus one fixed 150; the edges of the range packing (exactly
+64, sums of 64, 65 / 128 / 129, empty landmarks next to long tracks) and the range COUNT are the subject of
+tests/test_track_lengths.py, on the graphs of tests/track_cases.py and with the helpers shared through helpers.py.
 """
-import ctypes
-import os
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "ba_amd", "lib", "libba_hostcheck.so")
-
-
-def _p(a, t):
-    return a.ctypes.data_as(ctypes.POINTER(t))
-
+from helpers import brute_force_schur, hostcheck_lib, schur_lists
 
 @pytest.fixture(scope="module")
 def hc():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    return ctypes.CDLL(LIB)
+    return hostcheck_lib()
 
 
 def _random_graph(rng, P, L, LM, kmax, big=False):
@@ -55,41 +46,6 @@ def _random_graph(rng, P, L, LM, kmax, big=False):
     return pose_active, lm_active, lm_ref, np.array(pp, dtype=np.uint32)[perm], np.array(pl, dtype=np.uint32)[perm]
 
 
-def _brute_force(LM, D, pose_active, lm_active, lm_ref, pp, pl, jm, jr, jl, r, w):
-    P, L, O = len(pose_active), len(lm_active), len(pp)
-    popt = -np.ones(P, dtype=int)
-    popt[pose_active > 0] = np.arange(int(pose_active.sum()))
-    lopt = -np.ones(L, dtype=int)
-    lopt[lm_active > 0] = np.arange(int(lm_active.sum()))
-    n, nl = int(pose_active.sum()) * D, int(lm_active.sum()) * LM
-    Jp, Jl, rr = np.zeros((2 * O, n)), np.zeros((2 * O, max(nl, 1))), np.zeros(2 * O)
-    for a in range(O):
-        sw = np.sqrt(w[a])
-        l, m, ref = pl[a], pp[a], lm_ref[pl[a]]
-        listed = LM != 1 or m != ref
-        rr[2 * a:2 * a + 2] = sw * r[a]
-        if listed and popt[m] >= 0:
-            Jp[2 * a:2 * a + 2, popt[m] * D:popt[m] * D + 6] += sw * jm[a].reshape(2, 6)
-        if LM == 1 and listed and popt[ref] >= 0:
-            Jp[2 * a:2 * a + 2, popt[ref] * D:popt[ref] * D + 6] += sw * jr[a].reshape(2, 6)
-        if lopt[l] >= 0:
-            Jl[2 * a:2 * a + 2, lopt[l] * LM:lopt[l] * LM + LM] = sw * jl[a].reshape(2, LM)
-    U, W = Jp.T @ Jp, Jp.T @ Jl
-    V = Jl.T @ Jl
-    Vi = np.zeros_like(V)
-    for k in range(int(lm_active.sum())):
-        blk = V[k * LM:(k + 1) * LM, k * LM:(k + 1) * LM].copy()
-        if LM == 1:
-            if abs(blk[0, 0]) < 1e-6:
-                blk[0, 0] += 1e-6            # BundleAdjuster.cpp:431-434
-        elif np.linalg.norm(blk) < 1e-6:
-            blk += 1e-6 * np.eye(3)          # :435-439
-        Vi[k * LM:(k + 1) * LM, k * LM:(k + 1) * LM] = np.linalg.inv(blk)
-    rhs_p = Jp.T @ rr
-    rhs_l = Jl.T @ rr
-    return U - W @ Vi @ W.T, rhs_p, rhs_p - W @ Vi @ rhs_l
-
-
 @pytest.mark.parametrize("LM,D,P,L,kmax,big", [(1, 6, 40, 60, 8, False), (3, 6, 40, 60, 8, False),
                                                 (1, 15, 30, 50, 6, True), (3, 9, 25, 40, 6, True),
                                                 (1, 6, 5, 8, 3, False), (1, 6, 120, 300, 12, True)])
@@ -101,25 +57,8 @@ def test_lists_reproduce_the_dense_schur_complement(hc, LM, D, P, L, kmax, big):
     jl, r = rng.normal(size=(O, 2 * LM)), rng.normal(size=(O, 2))
     w = rng.uniform(0.3, 2.0, O)
     n = int(pose_active.sum()) * D
-    ld = max(64, (n + 63) // 64 * 64)
-    S_lower, rhs_p, rhs_sc = np.zeros((ld, ld)), np.zeros(ld), np.zeros(ld)
-    vinv, bl = np.zeros((L, LM * LM)), np.zeros((L, LM))
-    out_ld = ctypes.c_uint32()
-    counts = np.zeros(8, dtype=np.uint32)
-    dbl, u32, u8 = ctypes.c_double, ctypes.c_uint32, ctypes.c_uint8
-    rc = hc.ba_hostcheck_schur_lists(
-        LM, D, P, _p(pose_active, u8), L, _p(lm_active, u8), _p(lm_ref, u32), O, _p(pp, u32), _p(pl, u32),
-        _p(jm, dbl), _p(jr, dbl), _p(jl, dbl), _p(r, dbl), _p(w, dbl), _p(S_lower, dbl), _p(rhs_p, dbl),
-        _p(rhs_sc, dbl), _p(vinv, dbl), _p(bl, dbl), ctypes.byref(out_ld), _p(counts, u32))
-    assert rc == 0, rc
-    assert out_ld.value == ld
-    S_ref, rhs_p_ref, rhs_sc_ref = _brute_force(LM, D, pose_active, lm_active, lm_ref, pp, pl, jm, jr, jl, r, w)
-    # lower storage -> symmetric: blocks (i < j) are stored transposed below the diagonal, the
-    # diagonal 6x6 blocks with both triangles
-    S = np.tril(S_lower[:n, :n], -1)
-    S = S + S.T
-    for p in range(n // D):
-        S[p * D:p * D + D, p * D:p * D + D] = S_lower[p * D:p * D + D, p * D:p * D + D]
+    S, S_lower, rhs_p, rhs_sc, counts = schur_lists(hc, LM, D, pose_active, lm_active, lm_ref, pp, pl, jm, jr, jl, r, w)
+    S_ref, rhs_p_ref, rhs_sc_ref = brute_force_schur(LM, D, pose_active, lm_active, lm_ref, pp, pl, jm, jr, jl, r, w)
     scale = np.abs(S_ref).max()
     assert np.abs(S - S_ref).max() < 1e-11 * scale
     assert np.abs(rhs_p[:n] - rhs_p_ref).max() < 1e-11 * max(np.abs(rhs_p_ref).max(), 1.0)
