@@ -77,6 +77,7 @@ struct Engine {
   int cur = 0;  // current state buffer (0/1)
   bool has_snapshot = false;
   bool factored = false;  // A currently holds the Cholesky factor, not S
+  bool factor_foreign = false;  // invdiag holds the factor of a stand-alone solve, not of A (cleared by ba_hip_solve_gn)
   ba_hip_timers timers;
   ba_hip_allreduce_fn allreduce = nullptr;
   void* allreduce_ctx = nullptr;

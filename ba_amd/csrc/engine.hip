@@ -1143,6 +1143,7 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
       if ((rc = cholesky_solve_dist(e, e->A.p, st.ld, e->gn_p.p, &status, e->nzL.p))) return rc;
     } else if ((rc = cholesky_solve(e, e->A.p, st.n, st.ld, e->gn_p.p, &status, e->nzL.p))) return rc;
     e->factored = true;
+    e->factor_foreign = false;
   }
   e->timers.solve = t.stop_ms();
   EventTimer tb(e);
@@ -1358,6 +1359,9 @@ int ba_hip_get_calibration_marginals(ba_hip_engine* h, double* cov) {
     return e->fail_msg("ba_hip_get_calibration_marginals: the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), "
                        "which leaves no factor");
   if (!e->factored) return e->fail_msg("ba_hip_get_calibration_marginals needs the factor of the last ba_hip_solve_gn");
+  if (e->factor_foreign)
+    return e->fail_msg("ba_hip_get_calibration_marginals: a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has "
+                       "replaced the kept factor since the last ba_hip_solve_gn");
   if (dist_solve_enabled(e)) return e->fail_msg("calibration marginals: not available with the distributed solve");
   BAE_HIP(hipSetDevice(e->device));
   return trailing_marginals(e, e->A.p, e->st.ld, e->st.np, e->st.K, cov);
@@ -1442,6 +1446,9 @@ static int marginals_ready(Engine* e, const char* what, bool landmarks) {
   if (!e->factored)
     return e->fail_msg((m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised "
                             "since)").c_str());
+  if (e->factor_foreign && !e->sig_valid)  // (a selected inverse computed before the stand-alone solve stays good)
+    return e->fail_msg((m + "a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has replaced the kept factor "
+                            "since the last ba_hip_solve_gn").c_str());
   BAE_HIP(hipSetDevice(e->device));
   return marginals_compute(e);
 }
@@ -1516,6 +1523,9 @@ int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pos
   if (!e->factored)
     return e->fail_msg((m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised "
                             "since)").c_str());
+  if (e->factor_foreign)
+    return e->fail_msg((m + "a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has replaced the kept factor "
+                            "since the last ba_hip_solve_gn").c_str());
   if ((n && !pose_ids) || !out) return e->fail_msg((m + "NULL argument").c_str());
   const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K;
   if (include_calibration && !K)
@@ -2097,6 +2107,7 @@ int ba_hip_dense_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, cons
   BAE_HIP(e->flags.alloc(16));
   BAE_HIP(hipMemcpy(dA.p, A.data(), A.size() * 8, hipMemcpyHostToDevice));
   int status = 0;
+  e->factor_foreign = true;  // invdiag is about to hold this system's factor, not the scene's
   int rc = cholesky_solve(e, dA.p, n, ld, dx.p, &status, nullptr);  // arbitrary matrix: dense
   if (rc == 0) {
     std::vector<double> xx(ld);
@@ -2147,6 +2158,66 @@ int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const 
     if (stats) *stats = st;
   }
   dA.release(); dx.release();
+  if (rc) return rc;
+  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
+}
+
+// The direct tile-sparse factorisation on a host system with a caller-supplied tile pattern (test entry: the
+// kept factor comes back as the engine holds it).  Uses buffers of its own for the matrix and the pattern; the
+// engine's invdiag work space is shared with ba_hip_solve_gn, so the scene's kept factor is marked gone.
+int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, const uint8_t* tile_map,
+                      double* x, uint8_t* nz_factor, double* factor, double* linvT, double* dsgn) {
+  ENG(h);
+  if (!n || !a_lower || !b || !x) return e->fail_msg("ba_hip_tile_solve: NULL or empty argument");
+  BAE_HIP(hipSetDevice(e->device));
+  const uint32_t ld = std::max(((n + 63) / 64) * 64, 64u), nt = ld / 64;
+  std::vector<double> A((size_t)(ld + 1) * ld, 0.0);
+  std::vector<uint8_t> nz((size_t)nt * nt, 0);
+  if (tile_map)
+    for (uint32_t i = 0; i < nt; ++i)
+      for (uint32_t k = 0; k <= i; ++k) nz[(size_t)i * nt + k] = tile_map[(size_t)i * nt + k] ? 1 : 0;
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c <= r; ++c) {
+      const double v = a_lower[(size_t)r * n + c];
+      A[(size_t)r * ld + c] = v;
+      if (v != 0.0) {
+        uint8_t& t = nz[(size_t)(r / 64) * nt + c / 64];
+        if (!t && tile_map && r / 64 != c / 64) {
+          e->err = "ba_hip_tile_solve: entry (" + std::to_string(r) + ", " + std::to_string(c) + ") is nonzero but tile (" +
+                   std::to_string(r / 64) + ", " + std::to_string(c / 64) + ") is not in the tile map";
+          return -1;
+        }
+        t = 1;
+      }
+    }
+  for (uint32_t i = 0; i < nt; ++i) nz[(size_t)i * nt + i] = 1;  // diagonal tiles always
+  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
+  for (uint32_t c = 0; c < n; ++c) A[(size_t)ld * ld + c] = b[c];
+  tile_symbolic_factor(nz, nt);
+  if (nz_factor) std::copy(nz.begin(), nz.end(), nz_factor);
+  DBuf<double> dA, dx;
+  DBuf<uint8_t> dnz;
+  BAE_HIP(dA.alloc(A.size()));
+  BAE_HIP(dx.alloc(ld));
+  BAE_HIP(dnz.alloc(nz.size()));
+  BAE_HIP(e->flags.alloc(16));
+  BAE_HIP(hipMemcpy(dA.p, A.data(), A.size() * 8, hipMemcpyHostToDevice));
+  BAE_HIP(hipMemcpy(dnz.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
+  int status = 0;
+  e->factor_foreign = true;  // invdiag is about to hold this system's factor, not the scene's
+  int rc = cholesky_solve(e, dA.p, n, ld, dx.p, &status, dnz.p);
+  if (rc == 0) {
+    std::vector<double> xx(ld);
+    hipError_t err = hipDeviceSynchronize();  // both streams of the factorisation
+    if (err == hipSuccess) err = hipMemcpy(xx.data(), dx.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
+    if (err == hipSuccess && factor) err = hipMemcpy(factor, dA.p, (size_t)ld * ld * 8, hipMemcpyDeviceToHost);
+    if (err == hipSuccess && dsgn) err = hipMemcpy(dsgn, e->invdiag.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
+    if (err == hipSuccess && linvT)
+      err = hipMemcpy(linvT, e->invdiag.p + ld, (size_t)nt * 64 * 64 * 8, hipMemcpyDeviceToHost);
+    if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
+    for (uint32_t i = 0; i < n; ++i) x[i] = xx[i];
+  }
+  dA.release(); dx.release(); dnz.release();
   if (rc) return rc;
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
 }

@@ -19,6 +19,8 @@
 //     k_update128<false> / k_update2   (b) everything right of the next panel, K = 64 KOUT
 //                      concurrently with the next panel's serial chain               [stream s1]
 //   k_linvT, k_backward2  L^T x = y, two tile rows per launch
+// BA_HIP_LEFT_MIN_TILES (default 512, read on every call) moves the tile count from which the sub-panels are
+// the left-looking ones of 8, so that small test systems reach that chain.
 //
 // All products run on the FP64 matrix cores (v_mfma_f64_16x16x4_f64 — the one true dense
 // contraction of the path).  L carries sqrt|pivot| and D the pivot signs: for SPD systems it
@@ -1635,7 +1637,8 @@ static void launch_panel_chain(hipStream_t s, double* dA, uint32_t ld, uint32_t 
   // full duration): sub-panels of 8, left-looking inside — every column is read and written once
   // per sub-panel instead of once per earlier column.  Small systems are latency-bound on the
   // diagonal tile: right-looking keeps its update shallow (K = 64).
-  const bool left = nblk >= 512;
+  const char* le = getenv("BA_HIP_LEFT_MIN_TILES");  // (read on every call, like BA_HIP_KOUT: tests lower it)
+  const bool left = nblk >= (le ? (uint32_t)std::max(1, atoi(le)) : 512u);
   const uint32_t KINv = left ? 2 * KIN : KIN;
   // rows from tile `from` on: the whole range, or the tail of the list
   auto rows_from = [&](uint32_t from, const uint32_t** lp, uint32_t* cnt) {

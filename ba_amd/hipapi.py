@@ -168,7 +168,7 @@ SYMBOLS = [
     "ba_hip_release_marginals", "ba_hip_get_joint_marginals", "ba_hip_get_joint_marginal_stats",
     "ba_hip_set_dense_priors", "ba_hip_get_prior_errors", "ba_hip_marginalize", "ba_hip_get_marginalization",
     "ba_hip_release_marginalization", "ba_hip_set_unary_scales",
-    "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve",
+    "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve", "ba_hip_tile_solve",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -703,6 +703,27 @@ class Engine:
         rc = self._chk(self.L.ba_hip_dense_solve(self.h, b.shape[0], _p(a, dp), _p(b, dp), _p(x, dp)),
                        positive_ok=True)
         return x, rc
+
+    def tile_solve(self, a_lower, b, tile_map=None, keep_factor=False):
+        """The direct tile-sparse L D L^T solve on a symmetric system given by its lower triangle, with the lower
+        64x64-tile pattern `tile_map` (nt x nt; None: the pattern of the nonzeros): (x, rc, nzL), and with
+        keep_factor (x, rc, nzL, storage (64 nt)^2, linvT (nt, 64, 64), dsgn (64 nt)) — the kept factor."""
+        a, b = _d(a_lower), _d(b)
+        n = b.shape[0]
+        nt = max((n + 63) // 64, 1)
+        tm = None
+        if tile_map is not None:
+            tm = np.ascontiguousarray(tile_map, dtype=np.uint8)
+            if tm.shape != (nt, nt):
+                raise ValueError("tile_map must be %d x %d" % (nt, nt))
+        x = np.zeros(n)
+        nzl = np.zeros((nt, nt), dtype=np.uint8)
+        st = np.zeros((64 * nt, 64 * nt)) if keep_factor else None
+        li = np.zeros((nt, 64, 64)) if keep_factor else None
+        sg = np.zeros(64 * nt) if keep_factor else None
+        rc = self._chk(self.L.ba_hip_tile_solve(self.h, n, _p(a, dp), _p(b, dp), _p(tm, u8p), _p(x, dp), _p(nzl, u8p),
+                                                _p(st, dp), _p(li, dp), _p(sg, dp)), positive_ok=True)
+        return (x, rc, nzl, st, li, sg) if keep_factor else (x, rc, nzl)
 
     def select_kth(self, values, k):
         v = _d(values)

@@ -667,6 +667,20 @@ int ba_hip_pcg_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const 
 /* Dense Cholesky solve of an SPD system given by its LOWER triangle (row-major n x n,
  * host memory): x = A^-1 b.  Runs the same kernels ba_hip_solve_gn uses. */
 int ba_hip_dense_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const double* b, double* x);
+/* The direct tile-sparse L D L^T solve (the kernels of ba_hip_solve_gn) of a symmetric system given by its LOWER
+ * triangle (row-major n x n, host memory), with a caller-supplied pattern of 64x64 tiles.  nt = max(1, ceil(n / 64)).
+ *   tile_map   nt x nt bytes, row-major; byte (i, k), k <= i, nonzero = tile (i, k) of the matrix may hold nonzeros
+ *              (a superset of the true pattern is fine; the diagonal tiles always count).  A nonzero entry in a
+ *              tile the map leaves out is refused.  NULL: the pattern of the nonzeros of a_lower.
+ *   x          n doubles, the solution.
+ *   nz_factor  (may be NULL) nt x nt bytes: the lower tile pattern of L after symbolic elimination.
+ *   factor, linvT, dsgn  (each may be NULL) the kept factor as the engine holds it: the (64 nt) x (64 nt) row-major
+ *              storage after the factorisation (L's tiles below the diagonal tiles; rows >= n are identity padding),
+ *              nt row-major 64x64 tiles L_JJ^-T, and the 64 nt pivot signs.
+ * Returns 0 or BA_HIP_FACTORIZATION_ERROR.  The engine's scene is left alone, but the factor kept by the last
+ * ba_hip_solve_gn is gone afterwards: the marginal covariances are refused until the next ba_hip_solve_gn. */
+int ba_hip_tile_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const double* b, const uint8_t* tile_map,
+                      double* x, uint8_t* nz_factor, double* factor, double* linvT, double* dsgn);
 /* exact k-th smallest (0-based) of n non-negative doubles — the device selection behind
  * the Huber sigma (std::nth_element at floor(N/2), BundleAdjuster.cpp:1356-1358) */
 int ba_hip_select_kth(ba_hip_engine* e, uint32_t n, const double* values, uint32_t k, double* out);

@@ -1240,7 +1240,8 @@ def test_blocked_128_trailing_update_on_small_systems():
     """k_update128 (the 128x128 trailing-update kernel, its row-mode companion launch, its
     indefinite fallback and the ownership filter of the distributed solve) normally only runs on
     trailing matrices of >= 128 tiles.  BA_HIP_BULK_FULL_M is read once per process, so the solver
-    tests are re-run in a child process with the threshold lowered to 16 tiles."""
+    tests are re-run in a child process with the threshold lowered to 16 tiles.  (The grid of explicit tile
+    patterns under this and the other per-process switches lives in test_tile_factor_gpu.py.)"""
     import subprocess
     import sys
     if os.environ.get("BA_TEST_NESTED"):
@@ -1260,7 +1261,8 @@ def test_one_workgroup_square_factorisation(width):
     """BA_HIP_SQUARE=1 (k_square + k_rowpanel: the diagonal square of a sub-panel factorised by one workgroup;
     measured slower than the per-column chain and therefore opt-in) — the solver tests re-run in a
     child process with it switched on, at square widths 4 and 3 (ragged squares, structurally zero tiles,
-    indefinite systems, the rhs row; width 2 was run by hand: scratch/gpu_r03_square3.sh)."""
+    indefinite systems, the rhs row).  Widths 1 to 4 on explicit tile patterns, checked on the factor itself:
+    test_tile_factor_gpu.py."""
     import subprocess
     import sys
     if os.environ.get("BA_TEST_NESTED"):
