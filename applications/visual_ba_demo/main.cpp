@@ -21,6 +21,8 @@
 //   visual_ba_demo --pcg [tol]              Options::reduced_solver = Pcg (relative tolerance tol, default 1e-6): the reduced
 //                                           system is solved by preconditioned conjugate gradients; prints the
 //                                           iterations and the true residual of every Gauss-Newton step
+//   visual_ba_demo --pcg [tol] --pcg-coarse G   ... with the two-level preconditioner over aggregates of G poses
+//                                           (Options::pcg_coarse_aggregate); prints the coarse space of every step
 //   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
 //                                           GetLandmarkCovariance: selected inverse of the reduced system), then
@@ -38,7 +40,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, pcg = false; double pcg_tol = 1e-6; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -68,12 +70,16 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   options.error_change_threshold = 1e-5;
   options.device = shard.device;
   if (shard.order_auto) options.pose_ordering = ba::PoseOrdering::Auto;
-  if (shard.pcg) { options.reduced_solver = ba::ReducedSolver::Pcg; options.pcg_tolerance = shard.pcg_tol; }
+  if (shard.pcg) { options.reduced_solver = ba::ReducedSolver::Pcg; options.pcg_tolerance = shard.pcg_tol; options.pcg_coarse_aggregate = shard.pcg_coarse; }
   auto print_pcg = [&](int step) {
     ba_hip_pcg_stats ps;
     if (!adjuster.GetPcgStats(&ps)) return;
     std::printf("step %d: pcg iterations %u converged %u true residual %.3e (%.3f ms, %.1f us per product)\n", step, ps.iterations,
                 ps.converged, ps.rel_residual_true, ps.solve_ms, 1e3 * ps.spmv_ms);
+    ba_hip_pcg_coarse_stats cs;
+    if (adjuster.GetPcgCoarseStats(&cs))
+      std::printf("step %d: pcg coarse space %u unknowns, %u aggregates of %u (setup %.3f ms, %.1f us per pass)\n", step,
+                  cs.coarse_unknowns, cs.aggregates, cs.aggregate_used, cs.setup_ms, 1e3 * cs.apply_ms);
   };
   if (!shard.id_file.empty()) {
     unsigned char id[128];
@@ -288,7 +294,8 @@ int main(int argc, char** argv) {
       continue;
     }
     if (i + 1 >= argc) break;
-    if (std::strcmp(argv[i], "--ranks") == 0) shard.ranks = std::atoi(argv[i + 1]);
+    if (std::strcmp(argv[i], "--pcg-coarse") == 0) shard.pcg_coarse = (unsigned)std::atoi(argv[i + 1]);
+    else if (std::strcmp(argv[i], "--ranks") == 0) shard.ranks = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--rank") == 0) shard.rank = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--device") == 0) shard.device = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--comm-id-file") == 0) shard.id_file = argv[i + 1];

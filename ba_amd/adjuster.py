@@ -40,7 +40,8 @@ class BaOptions(C.Structure):
                 ("write_reduced_camera_matrix", C.c_int32),
                 ("device", C.c_int32), ("factorization_pivot_tolerance", C.c_double),
                 ("calculate_calibration_marginals", C.c_int32), ("pose_ordering", C.c_int32),
-                ("reduced_solver", C.c_int32), ("pcg_max_iterations", C.c_uint32), ("pcg_tolerance", C.c_double)]
+                ("reduced_solver", C.c_int32), ("pcg_max_iterations", C.c_uint32), ("pcg_tolerance", C.c_double),
+                ("pcg_coarse_aggregate", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
 class BaSummary(C.Structure):
@@ -72,7 +73,7 @@ SYMBOLS = [
     "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
     "ba_adjuster_get_joint_pose_covariance",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
-    "ba_adjuster_get_pcg_stats",
+    "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
 ]
 
 _lib = None
@@ -489,6 +490,14 @@ class BundleAdjuster:
             self.L.ba_adjuster_set_communicator(self.h, None, 0, 1, 0)
             return
         self.L.ba_adjuster_set_communicator(self.h, C.c_char_p(unique_id), int(rank), int(nranks), 1 if distributed_solve else 0)
+
+    def GetPcgCoarseStats(self):
+        """ba::BundleAdjuster::GetPcgCoarseStats: the coarse space of the last reduced solve as a dict when
+        Options::pcg_coarse_aggregate was in force, None otherwise."""
+        st = hipapi.PcgCoarseStats()
+        if not self.L.ba_adjuster_get_pcg_coarse_stats(self.h, C.byref(st)):
+            return None
+        return hipapi._pcg_stats_dict(st)
 
     def GetPcgStats(self):
         """ba::BundleAdjuster::GetPcgStats: the statistics of the last reduced solve as a dict when it ran the PCG

@@ -45,6 +45,7 @@ struct Iface {
   virtual void set_collectives(ba_hip_collective_fn fn, void* ctx) = 0;
   virtual int solve_is_distributed() = 0;
   virtual int pcg_stats(ba_hip_pcg_stats* out) const = 0;
+  virtual int pcg_coarse_stats(ba_hip_pcg_coarse_stats* out) const = 0;
   virtual void camera_pose(uint32_t cam, double* t7) const = 0;
   virtual void camera_params(uint32_t cam, double* p4) const = 0;
   virtual void last_calib_step(double* d6) const = 0;
@@ -86,6 +87,7 @@ struct Impl : Iface {
     opt.reduced_solver = o->reduced_solver == 1 ? ba::ReducedSolver::Pcg : ba::ReducedSolver::Direct;
     opt.pcg_tolerance = o->pcg_tolerance;
     opt.pcg_max_iterations = o->pcg_max_iterations;
+    opt.pcg_coarse_aggregate = o->pcg_coarse_aggregate;
     ba.Init(opt);
   }
   void set_gravity(const double* g) override { ba.SetGravity(ba::Vector3t({g[0], g[1], g[2]})); }
@@ -200,6 +202,7 @@ struct Impl : Iface {
   }
   int solve_is_distributed() override { return ba.SolveIsDistributed() ? 1 : 0; }
   int pcg_stats(ba_hip_pcg_stats* out) const override { return ba.GetPcgStats(out) ? 1 : 0; }
+  int pcg_coarse_stats(ba_hip_pcg_coarse_stats* out) const override { return ba.GetPcgCoarseStats(out) ? 1 : 0; }
   void set_collectives(ba_hip_collective_fn fn, void* ctx) override { ba.SetCollectives(fn, ctx); }
   void set_allreduce(ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) override {
     ba.SetAllReduce(fn, ctx, rank, nranks);
@@ -317,6 +320,8 @@ void ba_default_options(ba_options* o) {
   o->reduced_solver = d.reduced_solver == ba::ReducedSolver::Pcg ? 1 : 0;
   o->pcg_tolerance = d.pcg_tolerance;
   o->pcg_max_iterations = d.pcg_max_iterations;
+  o->pcg_coarse_aggregate = d.pcg_coarse_aggregate;
+  o->reserved0 = 0;
 }
 ba_adjuster* ba_adjuster_create(int lm_dim, int pose_dim) { return ba_adjuster_create_calib(lm_dim, pose_dim, 0, 0); }
 ba_adjuster* ba_adjuster_create_calib(int lm_dim, int pose_dim, int calib_size, int do_tvs) {
@@ -420,6 +425,7 @@ void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx
 void ba_adjuster_set_communicator(ba_adjuster* a, const void* id128, int rank, int nranks, int distributed_solve) { a->p->set_communicator(id128, rank, nranks, distributed_solve); }
 int ba_adjuster_solve_is_distributed(ba_adjuster* a) { return a->p->solve_is_distributed(); }
 int ba_adjuster_get_pcg_stats(const ba_adjuster* a, ba_hip_pcg_stats* out) { return a->p->pcg_stats(out); }
+int ba_adjuster_get_pcg_coarse_stats(const ba_adjuster* a, ba_hip_pcg_coarse_stats* out) { return a->p->pcg_coarse_stats(out); }
 void ba_adjuster_set_collectives(ba_adjuster* a, ba_hip_collective_fn fn, void* ctx) { a->p->set_collectives(fn, ctx); }
 
 }  // extern "C"

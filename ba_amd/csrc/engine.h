@@ -286,6 +286,9 @@ struct Engine {
   int solver_mode = BA_HIP_SOLVER_DIRECT;
   ba_hip_pcg_options pcg_opt = {};
   ba_hip_pcg_stats pcg_stats = {};
+  ba_hip_pcg_coarse_stats pcg_coarse_stats = {};
+  bool pcg_coarse_last = false;   // the last solve (ba_hip_solve_gn or ba_hip_pcg_solve) used the coarse space
+  uint32_t pcg_coarse_built = 0;  // coarse_aggregate the tables of pcg_plan were built for
   bool pcg_last = false;
   bool pcg_solved = false;   // ... and no linearisation since: gn_p solves the S in A
   bool pcg_refused() const { return allreduce || coll || comm; }
@@ -298,8 +301,18 @@ struct Engine {
     DBuf<uint8_t> nz;
     DBuf<double> rowslot, colslot, minv, x, r, z, p, q, parts;
     DBuf<PcgState> state;
-    DBuf<int32_t> status;
+    DBuf<int32_t> status;   // [0] k_pcg_blocks, [1] the coarse factorisation
+    // two-level preconditioner (k_pcg_coarse.hip): tables of the plan, C, its factor L, W = L^-1, C^-1, r_c, y_c
+    DBuf<uint32_t> cmap, crow_ptr, crow_rows;
+    DBuf<double> C, Lc, Wc, Cinv, rc, yc, ryc_part;
+    uint32_t coarse_key = 0, coarse_nc = 0, coarse_ncp = 0;   // aggregate the tables were uploaded for; size of the last C
+    void release_coarse() {
+      cmap.release(); crow_ptr.release(); crow_rows.release(); C.release(); Lc.release(); Wc.release(); Cinv.release();
+      rc.release(); yc.release(); ryc_part.release();
+      coarse_key = coarse_nc = coarse_ncp = 0;
+    }
     void release() {
+      release_coarse();
       tiles.release(); blk.release(); blocks.release(); row_ptr.release(); col_ptr.release(); col_slot.release();
       nz.release(); rowslot.release(); colslot.release(); minv.release(); x.release(); r.release(); z.release();
       p.release(); q.release(); parts.release(); state.release(); status.release();
@@ -418,6 +431,10 @@ int launch_priors_jrhs(Engine* e, double* out);
 int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const double* d_rhs, const PcgPlan& plan,
                      const std::vector<uint8_t>& nz, const std::vector<uint32_t>& blk, const std::vector<uint32_t>& blocks,
                      bool upload, const ba_hip_pcg_options& opt, double* dx, ba_hip_pcg_stats* stats, int* status);
+// two-level preconditioner (k_pcg_coarse.hip): C and C^-1 of the plan's coarse space once per solve; the two coarse
+// launches of a pass on the residual r
+int pcg_coarse_setup_device(Engine* e, const double* dA, uint32_t ld, const PcgPlan& plan);
+void pcg_coarse_apply_device(Engine* e, const PcgPlan& plan, const PcgState* st, const double* r);
 int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& lmask, double tol, double* dev_ms);
 
 }  // namespace bae

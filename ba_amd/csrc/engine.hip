@@ -1117,7 +1117,7 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
   const bool skip = st.K && st.Pact == 0;
   e->sig_valid = false;
   if (skip) BAE_HIP(hipMemsetAsync(e->gn_p.p, 0, e->gn_p.bytes(), e->stream));
-  e->pcg_last = e->pcg_solved = false;
+  e->pcg_last = e->pcg_solved = e->pcg_coarse_last = false;
   if (st.n > 0 && !skip && e->solver_mode == BA_HIP_SOLVER_PCG) {
     // S stays in A: no factor, no kept copy
     if (e->pcg_refused()) return e->fail_msg("the PCG solver is not available on a sharded engine");
@@ -1127,6 +1127,21 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
       build_pcg_plan(e->nzS_host, st.ld / 64, e->pcg_plan);
       pcg_row_blocks(st.np, (uint32_t)e->pose_dim, st.K, st.ld, e->pcg_blk, e->pcg_blocks);
       e->pcg_plan_version = e->nzL_version;
+      e->pcg_coarse_built = 0;
+    }
+    if (e->pcg_opt.coarse_aggregate && e->pcg_coarse_built != e->pcg_opt.coarse_aggregate) {
+      // aggregates of consecutive active poses in pose-id order; pose_opt says where a pose ordering put their rows
+      const uint32_t D = (uint32_t)e->pose_dim;
+      std::vector<uint32_t> nat(st.ld, kPcgNone);
+      uint32_t a = 0;
+      for (uint32_t p = 0; p < st.P; ++p)
+        if (st.pose_opt[p] >= 0) {
+          for (uint32_t d = 0; d < D; ++d) nat[(size_t)st.pose_opt[p] * D + d] = a * D + d;
+          ++a;
+        }
+      for (uint32_t k = 0; k < st.K; ++k) nat[st.np + k] = st.Pact * D + k;
+      build_pcg_coarse(e->pcg_plan, nat, st.Pact, D, st.K, e->pcg_opt.coarse_aggregate);
+      e->pcg_coarse_built = e->pcg_opt.coarse_aggregate;
     }
     if ((rc = pcg_solve_device(e, e->A.p, st.n, st.ld, e->rhs_sc.p, e->pcg_plan, e->nzS_host, e->pcg_blk, e->pcg_blocks, rebuild,
                                e->pcg_opt, e->gn_p.p, &e->pcg_stats, &status))) return rc;
@@ -1921,6 +1936,29 @@ int ba_hip_get_pcg_stats(ba_hip_engine* h, ba_hip_pcg_stats* out) {
   return 0;
 }
 
+int ba_hip_get_pcg_coarse_stats(ba_hip_engine* h, ba_hip_pcg_coarse_stats* out) {
+  ENG(h);
+  if (!e->pcg_coarse_last) return e->fail_msg("ba_hip_get_pcg_coarse_stats: the last solve did not use the coarse space");
+  if (out) *out = e->pcg_coarse_stats;
+  return 0;
+}
+
+int ba_hip_get_pcg_coarse(ba_hip_engine* h, uint32_t nc, double* C, double* Cinv) {
+  ENG(h);
+  Engine::PcgWork& w = e->pcg;
+  if (!e->pcg_coarse_last || !w.coarse_nc || !w.C.p || !w.Cinv.p)
+    return e->fail_msg("ba_hip_get_pcg_coarse: the last solve did not use the coarse space");
+  if (nc != w.coarse_nc) return e->fail_msg("ba_hip_get_pcg_coarse: nc differs from the coarse unknowns of the last solve");
+  BAE_HIP(hipSetDevice(e->device));
+  const double* src[2] = {w.C.p, w.Cinv.p};
+  double* dst[2] = {C, Cinv};
+  for (int i = 0; i < 2; ++i)
+    if (dst[i])
+      BAE_HIP(hipMemcpy2D(dst[i], (size_t)nc * sizeof(double), src[i], (size_t)w.coarse_ncp * sizeof(double),
+                          (size_t)nc * sizeof(double), nc, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int ba_hip_set_pose_permutation(ba_hip_engine* h, const uint32_t* opt_of_natural, uint32_t n) {
   ENG(h);
   if (n && !opt_of_natural) return e->fail_msg("ba_hip_set_pose_permutation: NULL permutation");
@@ -2142,6 +2180,12 @@ int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const 
   build_pcg_plan(nz, nt, plan);
   std::vector<uint32_t> blk, blocks;
   pcg_row_blocks(n, block, 0, ld, blk, blocks);
+  if (o->coarse_aggregate) {
+    std::vector<uint32_t> nat;
+    uint32_t nblk = 0;
+    pcg_natural_rows(n, block, 0, ld, nat, nblk);
+    build_pcg_coarse(plan, nat, nblk, block, 0, o->coarse_aggregate);
+  }
   DBuf<double> dA, dx;
   BAE_HIP(dA.alloc(A.size()));
   BAE_HIP(dx.alloc(ld));

@@ -541,3 +541,77 @@ extern "C" int ba_hostcheck_pcg(uint32_t n, const double* a_lower, const double*
   out_f64[2] = std::sqrt(res.bb);
   return rc;
 }
+
+// ba_hostcheck_pcg with the two-level preconditioner (coarse_aggregate = 0: the very call of ba_hostcheck_pcg).
+// out_coarse (4 uint32): aggregate used, coarse unknowns, aggregates, padded coarse dimension; C / Cinv (optional):
+// coarse unknowns x coarse unknowns, row-major.
+extern "C" int ba_hostcheck_pcg2(uint32_t n, const double* a_lower, const double* b, uint32_t np, uint32_t D, double rel_tolerance,
+                                 uint32_t max_iterations, uint32_t coarse_aggregate, double* x, uint32_t* out_u32, double* out_f64,
+                                 uint32_t* out_coarse, double* C_out, double* Cinv_out) {
+  if (out_coarse) out_coarse[0] = out_coarse[1] = out_coarse[2] = out_coarse[3] = 0;
+  if (!coarse_aggregate) return ba_hostcheck_pcg(n, a_lower, b, np, D, rel_tolerance, max_iterations, x, out_u32, out_f64);
+  if (np > n || D < 1 || D > bae::kPcgMaxBlock || n - np > bae::kPcgMaxBlock) return -1;
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  std::vector<double> A((size_t)ld * ld, 0.0), rhs(ld, 0.0), xx(ld, 0.0);
+  std::vector<uint8_t> nz((size_t)nt * nt, 0);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c <= r; ++c) {
+      const double v = a_lower[(size_t)r * n + c];
+      A[(size_t)r * ld + c] = v;
+      if (v != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
+    }
+  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
+  for (uint32_t r = 0; r < n; ++r) rhs[r] = b[r];
+  bae::PcgPlan pl;
+  bae::build_pcg_plan(nz, nt, pl);
+  std::vector<uint32_t> blk, blocks, nat;
+  bae::pcg_row_blocks(np, D, n - np, ld, blk, blocks);
+  uint32_t nblk = 0;
+  bae::pcg_natural_rows(np, D, n - np, ld, nat, nblk);
+  bae::build_pcg_coarse(pl, nat, nblk, D, n - np, coarse_aggregate);
+  bae::PcgResult res;
+  std::vector<double> C, Cinv;
+  const int rc = bae::pcg_host(pl, A.data(), ld, rhs.data(), n, nz, blk, blocks, rel_tolerance, max_iterations, xx.data(), &res,
+                               true, &C, &Cinv);
+  for (uint32_t r = 0; r < n; ++r) x[r] = xx[r];
+  out_u32[0] = res.iterations; out_u32[1] = res.converged; out_u32[2] = res.replacements; out_u32[3] = res.breakdown;
+  out_u32[4] = res.passes; out_u32[5] = pl.n_tiles;
+  out_f64[0] = res.bb > 0.0 ? std::sqrt(res.rr_recur / res.bb) : 0.0;
+  out_f64[1] = res.bb > 0.0 ? std::sqrt(res.rr_true / res.bb) : 0.0;
+  out_f64[2] = std::sqrt(res.bb);
+  if (out_coarse) { out_coarse[0] = pl.coarse_g; out_coarse[1] = pl.nc; out_coarse[2] = pl.naggr; out_coarse[3] = pl.ncp; }
+  for (uint32_t r = 0; r < pl.nc; ++r)
+    for (uint32_t c = 0; c < pl.nc; ++c) {
+      if (C_out) C_out[(size_t)r * pl.nc + c] = C[(size_t)r * pl.ncp + c];
+      if (Cinv_out) Cinv_out[(size_t)r * pl.nc + c] = Cinv[(size_t)r * pl.ncp + c];
+    }
+  return rc;
+}
+
+// C = Z^T S Z from a padded tile store (A: 64 nt x 64 nt, row-major; only the lower tiles of nz and the lower
+// triangle of the diagonal tiles are read): the first n rows are np rows in blocks of D and a border of n - np.
+// C_out: coarse unknowns x coarse unknowns (the caller sizes it by D ceil(ceil(np / D) / g) + n - np; the aggregate is
+// not raised here: -1 if that exceeds the limit).  opt_of_natural (optional, np / D entries, np a multiple of D): the
+// store holds the system under a pose ordering, block a of the natural order at block position opt_of_natural[a];
+// the aggregates stay those of the natural order.  Returns the number of coarse unknowns.
+extern "C" int ba_hostcheck_pcg_coarse(uint32_t nt, const uint8_t* nz, const double* A, uint32_t n, uint32_t np, uint32_t D,
+                                       uint32_t coarse_aggregate, double* C_out, const uint32_t* opt_of_natural) {
+  if (np > n || n > 64 * nt || D < 1 || D > bae::kPcgMaxBlock || !coarse_aggregate) return -1;
+  if (opt_of_natural && np % D) return -1;
+  std::vector<uint8_t> z(nz, nz + (size_t)nt * nt);
+  bae::PcgPlan pl;
+  bae::build_pcg_plan(z, nt, pl);
+  std::vector<uint32_t> nat;
+  uint32_t nblk = 0;
+  bae::pcg_natural_rows(np, D, n - np, 64 * nt, nat, nblk);
+  if (opt_of_natural)
+    for (uint32_t a = 0; a < nblk; ++a)
+      for (uint32_t d = 0; d < D; ++d) nat[(size_t)opt_of_natural[a] * D + d] = a * D + d;
+  bae::build_pcg_coarse(pl, nat, nblk, D, n - np, coarse_aggregate);
+  if (pl.coarse_g != coarse_aggregate) return -1;
+  std::vector<double> C;
+  bae::pcg_coarse_assemble_host(pl, A, (size_t)64 * nt, z, C);
+  for (uint32_t r = 0; r < pl.nc; ++r)
+    for (uint32_t c = 0; c < pl.nc; ++c) C_out[(size_t)r * pl.nc + c] = C[(size_t)r * pl.ncp + c];
+  return (int)pl.nc;
+}

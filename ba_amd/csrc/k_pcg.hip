@@ -1,6 +1,7 @@
 // Block-Jacobi preconditioned conjugate gradients on the reduced camera system (pcg.h has the algorithm, the
 // plan and the host restatement).  One pass is four launches: k_pcg_spmv_tiles, k_pcg_spmv_gather, k_pcg_update1,
-// k_pcg_update2; every kernel starts by reading the device state and returns at once when `done` is set, so the
+// k_pcg_update2 (six with the two-level preconditioner: the two coarse launches of k_pcg_coarse.hip run between
+// update1 and update2<true>, which adds the prolongated coarse correction to z); every kernel starts by reading the device state and returns at once when `done` is set, so the
 // host enqueues check_every passes blind and reads the state back once per batch.  FP64 VALU only (a mat-vec has no
 // use for MFMA), no atomics, every sum in a fixed order.
 #include <algorithm>
@@ -195,12 +196,16 @@ __global__ __launch_bounds__(256) void k_pcg_update1(uint32_t n, uint32_t ld, ui
 }
 
 // Sums the partials (every block forms the same three scalars), decides (pcg_decide), moves x and p; block 0
-// writes the next state into the other copy.
+// writes the next state into the other copy.  COARSE: z = z_bj + y_c[cmap[row]] and r.z = r.z_bj + r_c.y_c (the sum
+// of the nc partials of k_pcg_coarse_apply); the coarse factorisation's status word is bit 1 of the block status.
+template <bool COARSE>
 __global__ __launch_bounds__(256) void k_pcg_update2(uint32_t ld, uint32_t nt, uint32_t nb, const PcgState* __restrict__ st,
                                                      PcgState* __restrict__ st_out, const int32_t* __restrict__ status,
                                                      const double* __restrict__ pq_part, const double* __restrict__ rz_part,
                                                      const double* __restrict__ rr_part, const double* __restrict__ z,
-                                                     double* __restrict__ x, double* __restrict__ p) {
+                                                     double* __restrict__ x, double* __restrict__ p, uint32_t nc,
+                                                     const uint32_t* __restrict__ cmap, const double* __restrict__ yc,
+                                                     const double* __restrict__ ryc_part) {
   __shared__ double red[256];
   const PcgState s = *st;
   if (s.done) {
@@ -208,17 +213,27 @@ __global__ __launch_bounds__(256) void k_pcg_update2(uint32_t ld, uint32_t nt, u
     return;
   }
   const double pq = s.mode == kPcgIter ? block_sum256(pq_part, nt, red) : 0.0;
-  const double rz = block_sum256(rz_part, nb, red);
+  double rz = block_sum256(rz_part, nb, red);
   const double rr = block_sum256(rr_part, nb, red);
+  int block_status = status[0];
+  if (COARSE) {
+    rz += block_sum256(ryc_part, nc, red);
+    block_status = (status[0] ? 1 : 0) | (status[1] ? 2 : 0);
+  }
   PcgState o;
   double alpha, beta;
-  const uint32_t act = pcg_decide(s, pq, rz, rr, *status, o, alpha, beta);
+  const uint32_t act = pcg_decide(s, pq, rz, rr, block_status, o, alpha, beta);
   const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (row < ld) {
     const double pv = p[row];
+    double zr = z[row];
+    if (COARSE) {
+      const uint32_t c = cmap[row];
+      if (c != kPcgNone) zr += yc[c];
+    }
     if (act & kPcgStep) x[row] += alpha * pv;
-    if (act & kPcgDir) p[row] = z[row] + beta * pv;
-    else if (act & kPcgRestart) p[row] = z[row];
+    if (act & kPcgDir) p[row] = zr + beta * pv;
+    else if (act & kPcgRestart) p[row] = zr;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) *st_out = o;
 }
@@ -243,7 +258,11 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
   *status = 0;
   if (ld != 64 * nt || blk.size() != (size_t)2 * ld || nz.size() != (size_t)nt * nt)
     return e->fail_msg("pcg_solve_device: plan does not match the system");
-  hipEvent_t ev[6];
+  e->pcg_coarse_last = false;
+  const bool coarse = opt.coarse_aggregate != 0;
+  if (coarse && (plan.cmap.size() != (size_t)ld || plan.coarse_req != opt.coarse_aggregate || plan.ncp % 64 || plan.nc > plan.ncp))
+    return e->fail_msg("pcg_solve_device: the plan's coarse space does not match the options");
+  hipEvent_t ev[10];
   for (auto& v : ev) BAE_HIP(hipEventCreate(&v));
   auto drop = [&]() { for (auto& v : ev) (void)hipEventDestroy(v); };
 #define PCG_TRY(call) do { hipError_t _e = (call); if (_e != hipSuccess) { drop(); return e->fail(_e, #call); } } while (0)
@@ -258,8 +277,21 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
     PCG_TRY(w.x.alloc(ld)); PCG_TRY(w.r.alloc((size_t)2 * ld)); PCG_TRY(w.z.alloc(ld)); PCG_TRY(w.p.alloc(ld)); PCG_TRY(w.q.alloc(ld));
     PCG_TRY(w.parts.alloc((size_t)nt + 2 * nb));
     PCG_TRY(w.state.alloc(2));
-    PCG_TRY(w.status.alloc(1));
+    PCG_TRY(w.status.alloc(2));
   }
+  const uint32_t nc = plan.nc, ncp = plan.ncp;
+  if (upload) w.coarse_key = 0;   // the work space changes hands: coarse tables uploaded earlier belong to another system
+  if (coarse) {
+    if (upload || w.coarse_key != plan.coarse_req || !w.cmap.p) {
+      if ((rc = upload_vec(e, w.cmap, plan.cmap)) || (rc = upload_vec(e, w.crow_ptr, plan.crow_ptr)) ||
+          (rc = upload_vec(e, w.crow_rows, plan.crow_rows))) { drop(); return rc; }
+      w.coarse_key = plan.coarse_req;
+    }
+    PCG_TRY(w.C.alloc((size_t)ncp * ncp)); PCG_TRY(w.Lc.alloc((size_t)ncp * ncp)); PCG_TRY(w.Wc.alloc((size_t)ncp * ncp));
+    PCG_TRY(w.Cinv.alloc((size_t)ncp * ncp));
+    PCG_TRY(w.rc.alloc(ncp)); PCG_TRY(w.yc.alloc(ncp)); PCG_TRY(w.ryc_part.alloc(ncp));
+  }
+  w.coarse_nc = w.coarse_ncp = 0;
   double* pq_part = w.parts.p;
   double* rz_part = w.parts.p + nt;
   double* rr_part = rz_part + nb;
@@ -270,7 +302,7 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
   h0.mode = kPcgInit;
   const uint32_t check_every = opt.check_every ? opt.check_every : 10;
   PCG_TRY(hipMemcpyAsync(w.state.p, &h0, sizeof(h0), hipMemcpyHostToDevice, s));
-  PCG_TRY(hipMemsetAsync(w.status.p, 0, sizeof(int32_t), s));
+  PCG_TRY(hipMemsetAsync(w.status.p, 0, 2 * sizeof(int32_t), s));
   PCG_TRY(hipMemsetAsync(w.x.p, 0, (size_t)ld * sizeof(double), s));
   PCG_TRY(hipMemsetAsync(w.p.p, 0, (size_t)ld * sizeof(double), s));
   PCG_TRY(hipMemsetAsync(w.minv.p, 0, (size_t)ld * 16 * sizeof(double), s));
@@ -279,14 +311,19 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
     hipLaunchKernelGGL(k_pcg_blocks, dim3((nblocks + 3) / 4), dim3(64), 0, s, dA, ld, (const uint8_t*)w.nz.p, nt,
                        (const uint2*)w.blocks.p, nblocks, w.minv.p, w.status.p);
   PCG_TRY(hipEventRecord(ev[2], s));
+  if (coarse) {
+    PCG_TRY(hipEventRecord(ev[6], s));
+    if ((rc = pcg_coarse_setup_device(e, dA, ld, plan))) { drop(); return rc; }
+    PCG_TRY(hipEventRecord(ev[7], s));
+  }
   PcgState hs = h0;
-  double spmv_ms = 0.0;
-  uint32_t spmv_samples = 0;
+  double spmv_ms = 0.0, apply_ms = 0.0;
+  uint32_t spmv_samples = 0, apply_samples = 0;
   const uint32_t max_passes = pcg_max_passes(h0.max_it);
   uint32_t k = 0;
   while (k < max_passes) {
     const uint32_t batch_end = std::min(max_passes, k + check_every);
-    bool sampled = false;
+    bool sampled = false, sampled_c = false;
     for (; k < batch_end; ++k) {
       const PcgState* sin = w.state.p + (k & 1);
       PcgState* sout = w.state.p + ((k + 1) & 1);
@@ -304,8 +341,19 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
       }
       hipLaunchKernelGGL(k_pcg_update1, dim3(nb), dim3(256), 0, s, n, ld, nt, sin, (const double*)pq_part, d_rhs,
                          (const double*)w.q.p, rin, (const uint2*)w.blk.p, (const double*)w.minv.p, rout, w.z.p, rz_part, rr_part);
-      hipLaunchKernelGGL(k_pcg_update2, dim3(nb), dim3(256), 0, s, ld, nt, nb, sin, sout, (const int32_t*)w.status.p,
-                         (const double*)pq_part, (const double*)rz_part, (const double*)rr_part, (const double*)w.z.p, w.x.p, w.p.p);
+      if (coarse) {
+        const bool sample = !sampled_c;
+        if (sample) PCG_TRY(hipEventRecord(ev[8], s));
+        pcg_coarse_apply_device(e, plan, sin, rout);
+        if (sample) { PCG_TRY(hipEventRecord(ev[9], s)); sampled_c = true; }
+        hipLaunchKernelGGL(k_pcg_update2<true>, dim3(nb), dim3(256), 0, s, ld, nt, nb, sin, sout, (const int32_t*)w.status.p,
+                           (const double*)pq_part, (const double*)rz_part, (const double*)rr_part, (const double*)w.z.p, w.x.p,
+                           w.p.p, nc, (const uint32_t*)w.cmap.p, (const double*)w.yc.p, (const double*)w.ryc_part.p);
+      } else {
+        hipLaunchKernelGGL(k_pcg_update2<false>, dim3(nb), dim3(256), 0, s, ld, nt, nb, sin, sout, (const int32_t*)w.status.p,
+                           (const double*)pq_part, (const double*)rz_part, (const double*)rr_part, (const double*)w.z.p, w.x.p,
+                           w.p.p, 0u, (const uint32_t*)nullptr, (const double*)nullptr, (const double*)nullptr);
+      }
     }
     PCG_TRY(hipGetLastError());
     PCG_TRY(hipMemcpyAsync(&hs, w.state.p + (k & 1), sizeof(hs), hipMemcpyDeviceToHost, s));
@@ -313,6 +361,10 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
     if (sampled) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, ev[3], ev[4]) == hipSuccess) { spmv_ms += ms; spmv_samples++; }
+    }
+    if (sampled_c) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ev[8], ev[9]) == hipSuccess) { apply_ms += ms; apply_samples++; }
     }
     if (hs.done) break;
   }
@@ -322,6 +374,19 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
   float ms_all = 0.f, ms_pre = 0.f;
   (void)hipEventElapsedTime(&ms_all, ev[0], ev[5]);
   (void)hipEventElapsedTime(&ms_pre, ev[1], ev[2]);
+  e->pcg_coarse_last = coarse;
+  if (coarse) {
+    float ms_setup = 0.f;
+    (void)hipEventElapsedTime(&ms_setup, ev[6], ev[7]);
+    ba_hip_pcg_coarse_stats& c = e->pcg_coarse_stats;
+    memset(&c, 0, sizeof(c));
+    c.aggregate_used = plan.coarse_g; c.coarse_unknowns = nc; c.aggregates = plan.naggr;
+    c.setup_ms = ms_setup;
+    c.apply_ms = apply_samples ? apply_ms / apply_samples : 0.0;
+    c.coarse_bytes = 8.0 * (4.0 * ncp * ncp + 3.0 * ncp) + 4.0 * (plan.cmap.size() + plan.crow_ptr.size() + plan.crow_rows.size());
+    w.coarse_nc = nc;
+    w.coarse_ncp = ncp;
+  }
 #undef PCG_TRY
   drop();
   stats->iterations = hs.iterations; stats->converged = hs.converged; stats->residual_replacements = hs.replacements;

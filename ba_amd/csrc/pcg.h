@@ -16,6 +16,14 @@
 // The state lives on the device in two copies: pass k reads copy k & 1 and writes the other, so that no block
 // reads a word another block of the same launch writes.  r is double buffered in the same way (z = M^-1 r reads
 // the neighbours' rows of r).  Once `done` is set every further launch is a no-op.
+//
+// Two-level preconditioner (ba_hip_pcg_options.coarse_aggregate = g > 0, k_pcg_coarse.hip): M^-1 = M_bj^-1 +
+// Z (Z^T S Z)^-1 Z^T, Z summing parameter d of the g consecutive poses of an aggregate (natural order) into one
+// coarse unknown; the K calibration unknowns are coarse unknowns of their own.  C = Z^T S Z is assembled entry by
+// entry, every entry as ONE sum over the fine rows and columns of its two coarse unknowns in natural order: the
+// bits of C do not depend on where a pose ordering puts the rows (per-tile partial sums would).  C^-1 is formed
+// explicitly (blocked Cholesky on 64-tiles, triangular inverse, L^-T L^-1, symmetrised); a pass then runs
+// update1 -> restriction r_c = Z^T r -> y_c = C^-1 r_c -> update2 with z = z_bj + Z y_c and r.z = r.z_bj + r_c.y_c.
 #pragma once
 #include <stdint.h>
 
@@ -32,6 +40,8 @@
 namespace bae {
 
 static const uint32_t kPcgMaxBlock = 16;   // largest preconditioner block (PoseSize 15)
+static const uint32_t kPcgCoarseMax = 1024;   // BA_HIP_PCG_COARSE_MAX: coarse unknowns
+static const uint32_t kPcgNone = 0xffffffffu;
 enum : uint32_t { kPcgInit = 0, kPcgIter = 1, kPcgVerify = 2 };
 enum : uint32_t { kPcgStep = 1 /* x += alpha p */, kPcgDir = 2 /* p = z + beta p */, kPcgRestart = 4 /* p = z */ };
 
@@ -47,6 +57,12 @@ struct PcgPlan {
   std::vector<uint32_t> col_ptr;   // nt + 1: the slots of tile column J are col_slot[col_ptr[J] .. col_ptr[J + 1]),
   std::vector<uint32_t> col_slot;  //         ascending row, the diagonal tile first
   double bytes_per_spmv = 0.0;     // tiles read + slots written and read back + the vectors
+  // two-level preconditioner (build_pcg_coarse; coarse_req = 0: none)
+  uint32_t coarse_req = 0, coarse_g = 0;   // aggregate size asked for / used (raised until nc <= kPcgCoarseMax)
+  uint32_t nc = 0, ncp = 0, naggr = 0;     // coarse unknowns, padded to 64, aggregates
+  std::vector<uint32_t> cmap;       // ld: coarse unknown of matrix row r, kPcgNone for padding rows
+  std::vector<uint32_t> crow_ptr;   // nc + 1: the fine rows of coarse unknown c are crow_rows[crow_ptr[c] .. crow_ptr[c + 1]),
+  std::vector<uint32_t> crow_rows;  //         in ascending natural order (ascending rows without a pose ordering)
 };
 
 // nz: nt x nt bytes, lower part read; diagonal tiles always belong to the operator.
@@ -78,6 +94,43 @@ inline void pcg_row_blocks(uint32_t np, uint32_t D, uint32_t K, uint32_t ld, std
   if (K) { blocks.push_back(np); blocks.push_back(K); }
   for (size_t b = 0; b < blocks.size(); b += 2)
     for (uint32_t r = 0; r < blocks[b + 1]; ++r) { blk[2 * (size_t)(blocks[b] + r)] = blocks[b]; blk[2 * (size_t)(blocks[b] + r) + 1] = blocks[b + 1]; }
+}
+
+// nat_of_row: ld entries, the natural index of the unknown in matrix row r (nblk blocks of D unknowns, block-major,
+// then K border unknowns; a short last block simply lacks its trailing unknowns) or kPcgNone for padding rows.
+// Coarse unknown of natural index i < nblk D: (i / D / g) D + i % D; border unknown k: naggr D + k.  A coarse
+// unknown without fine rows (only a short last block in its aggregate) is kept, with C = 1 on its diagonal.
+inline void build_pcg_coarse(PcgPlan& p, const std::vector<uint32_t>& nat_of_row, uint32_t nblk, uint32_t D, uint32_t K,
+                             uint32_t g_req) {
+  uint32_t g = std::min(std::max(g_req, 1u), std::max(nblk, 1u));   // one aggregate for everything is the largest
+  while ((uint64_t)D * ((nblk + g - 1) / g) + K > kPcgCoarseMax && g < nblk) ++g;
+  p.coarse_req = g_req;
+  p.coarse_g = g;
+  p.naggr = (nblk + g - 1) / g;
+  p.nc = D * p.naggr + K;
+  p.ncp = std::max(((p.nc + 63) / 64) * 64, 64u);
+  const uint32_t ld = (uint32_t)nat_of_row.size(), nn = nblk * D + K;
+  std::vector<uint32_t> row_of_nat(nn, kPcgNone);
+  for (uint32_t r = 0; r < ld; ++r)
+    if (nat_of_row[r] != kPcgNone) row_of_nat[nat_of_row[r]] = r;
+  auto coarse = [&](uint32_t i) { return i < nblk * D ? (i / D / g) * D + i % D : p.naggr * D + (i - nblk * D); };
+  p.cmap.assign(ld, kPcgNone);
+  p.crow_ptr.assign((size_t)p.nc + 1, 0);
+  for (uint32_t i = 0; i < nn; ++i)
+    if (row_of_nat[i] != kPcgNone) { p.cmap[row_of_nat[i]] = coarse(i); p.crow_ptr[coarse(i) + 1]++; }
+  for (uint32_t c = 0; c < p.nc; ++c) p.crow_ptr[c + 1] += p.crow_ptr[c];
+  p.crow_rows.assign(p.crow_ptr[p.nc], 0);
+  std::vector<uint32_t> cur(p.crow_ptr.begin(), p.crow_ptr.end() - 1);
+  for (uint32_t i = 0; i < nn; ++i)
+    if (row_of_nat[i] != kPcgNone) p.crow_rows[cur[coarse(i)]++] = row_of_nat[i];
+}
+
+// nat_of_row of a system whose rows are in natural order: np rows in blocks of D, then K border rows
+inline void pcg_natural_rows(uint32_t np, uint32_t D, uint32_t K, uint32_t ld, std::vector<uint32_t>& nat_of_row, uint32_t& nblk) {
+  nblk = (np + D - 1) / D;
+  nat_of_row.assign(ld, kPcgNone);
+  for (uint32_t r = 0; r < np; ++r) nat_of_row[r] = r;
+  for (uint32_t k = 0; k < K; ++k) nat_of_row[np + k] = nblk * D + k;
 }
 
 // In-place Gauss-Jordan inversion of a symmetric D x D block (a: 16 x 16 row-major), without pivoting: the
@@ -121,11 +174,150 @@ inline double pcg_block_sum(const double* parts, uint32_t n) {
 
 PCG_HD inline bool pcg_finite(double v) { return v - v == 0.0; }
 
+// C = Z^T S Z as k_pcg_coarse_assemble forms it: C (ncp x ncp, row-major, both triangles; the padding is the
+// identity).  Entry (a, b), a >= b, is the sum of S(i, j) over the fine rows i of a, then the fine rows j of b, in
+// list order; S(i, j) is read from the lower storage at (max, min), of the pattern's tiles only (others count 0).
+inline void pcg_coarse_assemble_host(const PcgPlan& pl, const double* A, size_t ld, const std::vector<uint8_t>& nz,
+                                     std::vector<double>& C) {
+  const uint32_t ncp = pl.ncp, nt = pl.nt;
+  C.assign((size_t)ncp * ncp, 0.0);
+  for (uint32_t a = 0; a < ncp; ++a)
+    for (uint32_t b = 0; b <= a; ++b) {
+      double sum = 0.0;
+      bool empty = true;
+      if (a < pl.nc) {
+        empty = pl.crow_ptr[a] == pl.crow_ptr[a + 1];
+        for (uint32_t x = pl.crow_ptr[a]; x < pl.crow_ptr[a + 1]; ++x)
+          for (uint32_t y = pl.crow_ptr[b]; y < pl.crow_ptr[b + 1]; ++y) {
+            const uint32_t i = pl.crow_rows[x], j = pl.crow_rows[y];
+            const uint32_t r = std::max(i, j), c = std::min(i, j);
+            if (r / 64 == c / 64 || nz[(size_t)(r / 64) * nt + c / 64]) sum += A[(size_t)r * ld + c];
+          }
+      }
+      if (empty && a == b) sum = 1.0;
+      C[(size_t)a * ncp + b] = sum;
+      C[(size_t)b * ncp + a] = sum;
+    }
+}
+
+// Cholesky factor of a 64 x 64 tile held in d[64][65] (lower triangle) and, in the strict upper triangle, the
+// transpose of its inverse W = L^-1 (W[r][c] at d[c][r]); dinv[c] = 1 / L[c][c] = W[c][c].  A pivot that is not
+// positive and finite gives a zero column and returns false (k_pcg_coarse_column runs the same steps in LDS).
+inline bool pcg_coarse_tile_factor(double (*d)[65], double* dinv) {
+  bool ok = true;
+  for (uint32_t j = 0; j < 64; ++j) {
+    const double p = d[j][j];
+    const bool good = p > 0.0 && std::isfinite(p);
+    if (!good) ok = false;
+    const double l = good ? std::sqrt(p) : 0.0, il = good ? 1.0 / l : 0.0;
+    d[j][j] = l;
+    dinv[j] = il;
+    for (uint32_t r = j + 1; r < 64; ++r) d[r][j] *= il;
+    for (uint32_t r = j + 1; r < 64; ++r)
+      for (uint32_t c = j + 1; c <= r; ++c) d[r][c] -= d[r][j] * d[c][j];
+  }
+  for (uint32_t c = 0; c < 64; ++c)
+    for (uint32_t r = c + 1; r < 64; ++r) {
+      double s = d[r][c] * dinv[c];
+      for (uint32_t m = c + 1; m < r; ++m) s += d[r][m] * d[c][m];
+      d[c][r] = -s * dinv[r];
+    }
+  return ok;
+}
+
+// Explicit symmetric C^-1 (ncp x ncp) by the steps of k_pcg_coarse.hip: left-looking blocked Cholesky on 64-tiles
+// (L_ik = (C_ik - sum_m L_im L_km^T) W_kk^T with W_kk = L_kk^-1), W = L^-1 tile column by tile column, then
+// C^-1 = W^T W with the diagonal tiles symmetrised and the upper tiles mirrored.  Returns false on a bad pivot.
+inline bool pcg_coarse_invert_host(const std::vector<double>& C, uint32_t ncp, std::vector<double>& Cinv) {
+  const uint32_t nct = ncp / 64;
+  const size_t N = ncp;
+  std::vector<double> L((size_t)ncp * ncp, 0.0), W((size_t)ncp * ncp, 0.0), T(64 * 64);
+  Cinv.assign((size_t)ncp * ncp, 0.0);
+  bool ok = true;
+  for (uint32_t k = 0; k < nct; ++k) {
+    static thread_local double d[64][65];
+    double dinv[64];
+    for (uint32_t r = 0; r < 64; ++r)
+      for (uint32_t c = 0; c < 64; ++c) {
+        double s = 0.0;
+        for (uint32_t m = 0; m < 64 * k; ++m) s += L[(64 * k + r) * N + m] * L[(64 * k + c) * N + m];
+        d[r][c] = C[(64 * k + r) * N + 64 * k + c] - s;
+      }
+    if (!pcg_coarse_tile_factor(d, dinv)) ok = false;
+    for (uint32_t r = 0; r < 64; ++r)
+      for (uint32_t c = 0; c < 64; ++c) {
+        L[(64 * k + r) * N + 64 * k + c] = c <= r ? d[r][c] : 0.0;
+        W[(64 * k + r) * N + 64 * k + c] = c < r ? d[c][r] : c == r ? dinv[c] : 0.0;
+      }
+    for (uint32_t i = k + 1; i < nct; ++i) {
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < 64; ++c) {
+          double s = 0.0;
+          for (uint32_t m = 0; m < 64 * k; ++m) s += L[(64 * i + r) * N + m] * L[(64 * k + c) * N + m];
+          T[r * 64 + c] = C[(64 * i + r) * N + 64 * k + c] - s;
+        }
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < 64; ++c) {
+          double s = 0.0;
+          for (uint32_t m = 0; m <= c; ++m) s += T[r * 64 + m] * W[(64 * k + c) * N + 64 * k + m];
+          L[(64 * i + r) * N + 64 * k + c] = s;
+        }
+    }
+  }
+  for (uint32_t k = 0; k < nct; ++k)
+    for (uint32_t i = k + 1; i < nct; ++i) {
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < 64; ++c) {
+          double s = 0.0;
+          for (uint32_t m = 64 * k; m < 64 * i; ++m) s += L[(64 * i + r) * N + m] * W[m * N + 64 * k + c];
+          T[r * 64 + c] = s;
+        }
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < 64; ++c) {
+          double s = 0.0;
+          for (uint32_t m = 0; m < 64; ++m) s += W[(64 * i + r) * N + 64 * i + m] * T[m * 64 + c];
+          W[(64 * i + r) * N + 64 * k + c] = -s;
+        }
+    }
+  for (uint32_t i = 0; i < nct; ++i)
+    for (uint32_t j = 0; j <= i; ++j) {
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < 64; ++c) {
+          double s = 0.0;
+          for (uint32_t m = 64 * i; m < ncp; ++m) s += W[m * N + 64 * i + r] * W[m * N + 64 * j + c];
+          T[r * 64 + c] = s;
+        }
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < 64; ++c) {
+          if (i == j) Cinv[(64 * i + r) * N + 64 * j + c] = 0.5 * (T[r * 64 + c] + T[c * 64 + r]);
+          else Cinv[(64 * i + r) * N + 64 * j + c] = Cinv[(64 * j + c) * N + 64 * i + r] = T[r * 64 + c];
+        }
+    }
+  return ok;
+}
+
+// y_c = C^-1 r_c and the per-row partials of r_c . y_c as k_pcg_coarse_apply forms them: 64 lanes per row, lane t
+// sums the columns t, t + 64, ..; then the tree.
+inline void pcg_coarse_apply_host(const std::vector<double>& Cinv, uint32_t nc, uint32_t ncp, const double* rc, double* yc,
+                                  double* part) {
+  for (uint32_t row = 0; row < nc; ++row) {
+    double v[64];
+    for (uint32_t t = 0; t < 64; ++t) {
+      double s = 0.0;
+      for (uint32_t m = t; m < ncp; m += 64) s += Cinv[(size_t)row * ncp + m] * rc[m];
+      v[t] = s;
+    }
+    yc[row] = pcg_tree(v, 64);
+    part[row] = rc[row] * yc[row];
+  }
+}
+
 // The decision of one pass from its three sums (pq = p.Sp, rz = r.z, rr = r.r of the NEW residual).  `out` is the
 // next state; the return value says what update2 does to x and p.  Stopping rule: when the recurrence passes
 // ||r|| <= tol ||b|| the next pass recomputes r = b - S x (kPcgVerify) and only that residual ends the solve; if it
 // fails, the solve continues from the recomputed residual with p = z (residual replacement).  Breakdown: 1 = p.Sp
-// <= 0, 2 = a non-finite scalar, 3 = a preconditioner block that is not positive definite; x is not moved by the
+// <= 0, 2 = a non-finite scalar, 3 = a preconditioner block that is not positive definite (bit 0 of block_status),
+// 4 = a coarse matrix that is not positive definite (bit 1; 3 wins when both are set); x is not moved by the
 // pass that detects it.  max_it counts CG steps; reaching it ends the solve with converged = 0.
 PCG_HD inline uint32_t pcg_decide(const PcgState& s, double pq, double rz, double rr, int block_status, PcgState& out,
                                   double& alpha, double& beta) {
@@ -133,7 +325,7 @@ PCG_HD inline uint32_t pcg_decide(const PcgState& s, double pq, double rz, doubl
   alpha = beta = 0.0;
   if (s.done) return 0;
   if (s.mode != kPcgIter) {
-    if (s.mode == kPcgInit && block_status) { out.done = 1; out.breakdown = 3; return 0; }
+    if (s.mode == kPcgInit && block_status) { out.done = 1; out.breakdown = (block_status & 1) ? 3 : 4; return 0; }
     if (!pcg_finite(rr) || !pcg_finite(rz)) { out.done = 1; out.breakdown = 2; return 0; }
     if (s.mode == kPcgInit) {
       out.bb = rr;
@@ -243,11 +435,22 @@ inline uint32_t pcg_max_passes(uint32_t max_it) { return 2 * max_it + 3; }
 // zero rhs); x: ld doubles.  Returns 0, or 4 (BA_HIP_FACTORIZATION_ERROR) on a breakdown.
 inline int pcg_host(const PcgPlan& pl, const double* A, size_t ld, const double* rhs, uint32_t n,
                     const std::vector<uint8_t>& nz, const std::vector<uint32_t>& blk, const std::vector<uint32_t>& blocks,
-                    double rel_tolerance, uint32_t max_it, double* x, PcgResult* res) {
+                    double rel_tolerance, uint32_t max_it, double* x, PcgResult* res, bool coarse = false,
+                    std::vector<double>* C_out = nullptr, std::vector<double>* Cinv_out = nullptr) {
   std::vector<double> minv, rowslot, colslot, r[2], z(ld, 0.0), p(ld, 0.0), q(ld, 0.0);
   r[0].assign(ld, 0.0);
   r[1].assign(ld, 0.0);
-  const int block_status = pcg_blocks_host(A, ld, nz, pl.nt, blocks, minv);
+  int block_status = pcg_blocks_host(A, ld, nz, pl.nt, blocks, minv);
+  std::vector<double> C, Cinv, rc, yc, ryc_part;
+  if (coarse) {   // the plan carries build_pcg_coarse's tables
+    pcg_coarse_assemble_host(pl, A, ld, nz, C);
+    if (!pcg_coarse_invert_host(C, pl.ncp, Cinv)) block_status |= 2;
+    rc.assign(pl.ncp, 0.0);
+    yc.assign(pl.ncp, 0.0);
+    ryc_part.assign(pl.nc, 0.0);
+    if (C_out) *C_out = C;
+    if (Cinv_out) *Cinv_out = Cinv;
+  }
   std::fill(x, x + ld, 0.0);
   PcgState st[2] = {};
   st[0].tol2 = rel_tolerance * rel_tolerance;
@@ -298,14 +501,25 @@ inline int pcg_host(const PcgPlan& pl, const double* A, size_t ld, const double*
         rz_part[b] = pcg_tree(vz, 256);
         rr_part[b] = pcg_tree(vr, 256);
       }
+    if (run1 && coarse) {
+      for (uint32_t c = 0; c < pl.nc; ++c) {
+        double sum = 0.0;
+        for (uint32_t e = pl.crow_ptr[c]; e < pl.crow_ptr[c + 1]; ++e) sum += rout[pl.crow_rows[e]];
+        rc[c] = sum;
+      }
+      pcg_coarse_apply_host(Cinv, pl.nc, pl.ncp, rc.data(), yc.data(), ryc_part.data());
+    }
     const double pq = s.mode == kPcgIter ? pcg_block_sum(pq_part.data(), pl.nt) : 0.0;
-    const double rz = pcg_block_sum(rz_part.data(), nb), rr = pcg_block_sum(rr_part.data(), nb);
+    double rz = pcg_block_sum(rz_part.data(), nb);
+    const double rr = pcg_block_sum(rr_part.data(), nb);
+    if (coarse) rz += pcg_block_sum(ryc_part.data(), pl.nc);
     double alpha, beta;
     const uint32_t act = pcg_decide(s, pq, rz, rr, block_status, st[(k + 1) & 1], alpha, beta);
     for (size_t row = 0; row < ld; ++row) {
+      const double zr = coarse && pl.cmap[row] != kPcgNone ? z[row] + yc[pl.cmap[row]] : z[row];
       if (act & kPcgStep) x[row] += alpha * p[row];
-      if (act & kPcgDir) p[row] = z[row] + beta * p[row];
-      else if (act & kPcgRestart) p[row] = z[row];
+      if (act & kPcgDir) p[row] = zr + beta * p[row];
+      else if (act & kPcgRestart) p[row] = zr;
     }
   }
   const PcgState& f = st[k & 1];

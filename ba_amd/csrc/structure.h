@@ -268,7 +268,7 @@ inline bool build_lists(const Problem& pb, int LM, int D, Lists& st, std::string
   // Incidences of landmark l (only if the landmark is active): one per observation whose measuring
   // pose carries a block, plus the reference pose's (LM == 1, reference pose active, any listed
   // observation).  inc = (pose opt id, first W row).
-  struct Inc { uint32_t pose, wrow; };
+  struct Inc { uint32_t pose, wrow, id; };   // id: the pose id (natural order, whatever the pose ordering)
   auto incidences = [&](uint32_t l, Inc* out) -> uint32_t {  // out must hold k + 1 items
     if (st.lm_opt[l] < 0) return 0;
     uint32_t m = 0;
@@ -277,11 +277,11 @@ inline bool build_lists(const Problem& pb, int LM, int D, Lists& st, std::string
       if (!listed(s)) continue;
       any_listed = true;
       const int32_t po = st.pose_opt[st.obs_pose[s]];
-      if (po >= 0) out[m++] = {(uint32_t)po, s * R + WO};
+      if (po >= 0) out[m++] = {(uint32_t)po, s * R + WO, st.obs_pose[s]};
     }
     if (LM == 1 && any_listed) {
       const int32_t ro = st.pose_opt[pb.lm_ref_pose[l]];
-      if (ro >= 0) out[m++] = {(uint32_t)ro, st.lrow_base + 2 * l};
+      if (ro >= 0) out[m++] = {(uint32_t)ro, st.lrow_base + 2 * l, pb.lm_ref_pose[l]};
     }
     return m;
   };
@@ -336,8 +336,12 @@ inline bool build_lists(const Problem& pb, int LM, int D, Lists& st, std::string
             const Inc& lo_i = tmp[x].pose < tmp[y].pose ? tmp[x] : tmp[y];  // block row side i (smaller opt id)
             const Inc& hi_i = tmp[x].pose < tmp[y].pose ? tmp[y] : tmp[x];
             const uint64_t key = home_key(lo_i.pose, hi_i.pose);
+            // (-W V^-1)_i W_j^T or W_i (-W V^-1)_j^T: the V^-1-weighted rows are those of the pose with the smaller
+            // pose id, so that every rank-1 term multiplies the same two numbers under any pose ordering and the
+            // bits of S do not depend on it (the natural order takes the first form, as ever)
+            const bool lo_weighted = lo_i.id < hi_i.id;
             for (int k = 0; k < LM; ++k)
-              recs[w++] = {key, lo_i.wrow + LM + k, hi_i.wrow + k};  // (-W V^-1)_i W_j^T
+              recs[w++] = {key, lo_i.wrow + (lo_weighted ? LM : 0) + k, hi_i.wrow + (lo_weighted ? 0 : LM) + k};
           }
       }
     };

@@ -176,9 +176,14 @@ __global__ void k_lm_records(DevGraph g, const uint32_t* __restrict__ linc_ptr, 
       if (px == py) continue;
       const uint32_t lo = px < py ? x : y, hi = px < py ? y : x;  // block row side i = the smaller opt id
       const unsigned long long key = d_home_key(inc_pose[lo], inc_pose[hi], g.D);
+      // the V^-1-weighted rows are those of the pose with the smaller pose id (structure.h); the pose id of an
+      // incidence follows from its W row: an observation's, or the reference pose's landmark row
+      const uint32_t id_lo = inc_wrow[lo] >= g.lrow_base ? g.lm_ref_pose[l] : g.obs_pose[(inc_wrow[lo] - g.WO) / g.R];
+      const uint32_t id_hi = inc_wrow[hi] >= g.lrow_base ? g.lm_ref_pose[l] : g.obs_pose[(inc_wrow[hi] - g.WO) / g.R];
+      const uint32_t wl = id_lo < id_hi ? (uint32_t)g.LM : 0u, wh = id_lo < id_hi ? 0u : (uint32_t)g.LM;
       for (int k = 0; k < g.LM; ++k) {
         keys[w] = key;
-        vals[w] = (unsigned long long)(inc_wrow[lo] + g.LM + k) | ((unsigned long long)(inc_wrow[hi] + k) << 32);
+        vals[w] = (unsigned long long)(inc_wrow[lo] + wl + k) | ((unsigned long long)(inc_wrow[hi] + wh + k) << 32);
         ++w;
       }
     }

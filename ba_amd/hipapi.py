@@ -126,7 +126,7 @@ class MarginalizationStats(C.Structure):
 
 class PcgOptions(C.Structure):
     _fields_ = [("rel_tolerance", C.c_double), ("max_iterations", C.c_uint32), ("check_every", C.c_uint32),
-                ("reserved", C.c_uint32 * 3)]
+                ("coarse_aggregate", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class PcgStats(C.Structure):
@@ -136,8 +136,13 @@ class PcgStats(C.Structure):
                [("tiles_read_per_spmv", C.c_uint64), ("bytes_read_per_spmv", C.c_double)]
 
 
+class PcgCoarseStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("aggregate_used", "coarse_unknowns", "aggregates", "reserved")] + \
+               [(n, C.c_double) for n in ("setup_ms", "apply_ms", "coarse_bytes")]
+
+
 def _pcg_stats_dict(st):
-    return {k: getattr(st, k) for k, _ in PcgStats._fields_}
+    return {k: getattr(st, k) for k, _ in type(st)._fields_ if k != "reserved"}
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
@@ -169,6 +174,7 @@ SYMBOLS = [
     "ba_hip_set_dense_priors", "ba_hip_get_prior_errors", "ba_hip_marginalize", "ba_hip_get_marginalization",
     "ba_hip_release_marginalization", "ba_hip_set_unary_scales",
     "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve", "ba_hip_tile_solve",
+    "ba_hip_get_pcg_coarse_stats", "ba_hip_get_pcg_coarse",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -672,13 +678,14 @@ class Engine:
         self._chk(self.L.ba_hip_get_factor_tile_pattern(self.h, nblk, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
-    def set_reduced_solver(self, mode, rel_tolerance=1e-6, max_iterations=0, check_every=0):
+    def set_reduced_solver(self, mode, rel_tolerance=1e-6, max_iterations=0, check_every=0, coarse_aggregate=0):
         """SOLVER_DIRECT (tile-sparse LDL^T, the default) or SOLVER_PCG (block-Jacobi preconditioned conjugate
-        gradients on S) for the following solve_gn calls; not structural, no finalize needed."""
+        gradients on S; coarse_aggregate = g >= 1 adds the coarse-space correction over aggregates of g poses) for the
+        following solve_gn calls; not structural, no finalize needed."""
         if int(mode) == SOLVER_DIRECT:
             self._chk(self.L.ba_hip_set_reduced_solver(self.h, SOLVER_DIRECT, None))
             return
-        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every))
+        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every), int(coarse_aggregate))
         self._chk(self.L.ba_hip_set_reduced_solver(self.h, int(mode), C.byref(o)))
 
     def pcg_stats(self):
@@ -687,11 +694,24 @@ class Engine:
         self._chk(self.L.ba_hip_get_pcg_stats(self.h, C.byref(st)))
         return _pcg_stats_dict(st)
 
-    def pcg_solve(self, a_lower, b, block, rel_tolerance, max_iterations=0, check_every=0):
+    def pcg_coarse_stats(self):
+        """ba_hip_pcg_coarse_stats of the last solve_gn / pcg_solve as a dict; HipError if it did not use the coarse space."""
+        st = PcgCoarseStats()
+        self._chk(self.L.ba_hip_get_pcg_coarse_stats(self.h, C.byref(st)))
+        return _pcg_stats_dict(st)
+
+    def pcg_coarse(self):
+        """(C, C^-1) of the last two-level solve, nc x nc each."""
+        nc = self.pcg_coarse_stats()["coarse_unknowns"]
+        c, ci = np.empty((nc, nc)), np.empty((nc, nc))
+        self._chk(self.L.ba_hip_get_pcg_coarse(self.h, nc, _p(c, dp), _p(ci, dp)))
+        return c, ci
+
+    def pcg_solve(self, a_lower, b, block, rel_tolerance, max_iterations=0, check_every=0, coarse_aggregate=0):
         """Stand-alone PCG on an SPD system given by its lower triangle: (x, rc, stats dict)."""
         a, b = _d(a_lower), _d(b)
         x = np.zeros(b.shape[0])
-        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every))
+        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every), int(coarse_aggregate))
         st = PcgStats()
         rc = self._chk(self.L.ba_hip_pcg_solve(self.h, b.shape[0], _p(a, dp), _p(b, dp), int(block), C.byref(o), _p(x, dp),
                                                C.byref(st)), positive_ok=True)

@@ -112,6 +112,9 @@ struct Options {  // reference BundleAdjuster.h:72-107, same names and defaults
   ReducedSolver reduced_solver = ReducedSolver::Direct;
   Scalar pcg_tolerance = 1e-6;
   uint32_t pcg_max_iterations = 0;
+  // Pcg only: g >= 1 adds the coarse-space correction over aggregates of g consecutive active poses to the
+  // block-Jacobi preconditioner (ba_hip_pcg_options.coarse_aggregate); 0 = block-Jacobi alone.
+  uint32_t pcg_coarse_aggregate = 0;
 };
 
 // A dense Gaussian prior on poses (extension; include/ba_hip.h, ba_hip_marginalize): pose_ids (k), x0 (k x 16:
@@ -627,6 +630,8 @@ class BundleAdjuster {
   // statistics of the last reduced solve when it ran Options::reduced_solver = Pcg (iterations, converged, true
   // residual, times; include/ba_hip.h: ba_hip_pcg_stats); false when it was direct or nothing was solved yet
   bool GetPcgStats(ba_hip_pcg_stats* out) const { return engine_ && ba_hip_get_pcg_stats(engine_, out) == 0; }
+  // ... and of its coarse space when Options::pcg_coarse_aggregate was set (aggregate used, coarse unknowns, times)
+  bool GetPcgCoarseStats(ba_hip_pcg_coarse_stats* out) const { return engine_ && ba_hip_get_pcg_coarse_stats(engine_, out) == 0; }
   bool SolveIsDistributed() const { return engine_ && ba_hip_solve_is_distributed(engine_) != 0; }
 
  private:
@@ -806,6 +811,7 @@ bool BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::SyncEngine() {
     std::memset(&po, 0, sizeof(po));
     po.rel_tolerance = options_.pcg_tolerance;
     po.max_iterations = options_.pcg_max_iterations;
+    po.coarse_aggregate = options_.pcg_coarse_aggregate;
     if (!Check(ba_hip_set_reduced_solver(engine_, BA_HIP_SOLVER_PCG, &po), "ba_hip_set_reduced_solver")) return false;
   }
   if (structure_dirty_) {

@@ -34,6 +34,8 @@ typedef struct { /* ba::Options<double>, reference BundleAdjuster.h:72-107 */
   int32_t reduced_solver; /* extension: 0 direct, 1 PCG (ba::Options::reduced_solver, ba_hip_set_reduced_solver) */
   uint32_t pcg_max_iterations; /* ba::Options::pcg_max_iterations, 0 = the number of unknowns */
   double pcg_tolerance;   /* ba::Options::pcg_tolerance */
+  uint32_t pcg_coarse_aggregate; /* ba::Options::pcg_coarse_aggregate, 0 = block-Jacobi alone */
+  uint32_t reserved0;
 } ba_options;
 
 typedef struct { /* ba::SolutionSummary<double> + GetErrors, reference :48-70,593-602 */
@@ -146,6 +148,8 @@ uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t*
                                      const double* H, const double* b, double c);
 /* ba::BundleAdjuster::GetPcgStats: 1 and *out filled when the last reduced solve ran PCG, 0 otherwise */
 int ba_adjuster_get_pcg_stats(const ba_adjuster* a, ba_hip_pcg_stats* out);
+/* ba::BundleAdjuster::GetPcgCoarseStats: 1 and *out filled when the last reduced solve used the coarse space */
+int ba_adjuster_get_pcg_coarse_stats(const ba_adjuster* a, ba_hip_pcg_coarse_stats* out);
 /* GetLastStep().delta_k (zeros without do_tvs) */
 void ba_adjuster_get_last_calib_step(const ba_adjuster* a, double delta_k[6]);
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks);

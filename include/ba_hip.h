@@ -634,16 +634,18 @@ int ba_hip_release_marginalization(ba_hip_engine* e);
  *     stay in natural order; delta_gn is simply inexact).
  * Sharded engines (all-reduce hook, collectives hook, communicator) refuse PCG, whichever call comes second. */
 #define BA_HIP_SOLVER_DIRECT 0   /* default: tile-sparse LDL^T */
-#define BA_HIP_SOLVER_PCG    1   /* block-Jacobi preconditioned conjugate gradients on S */
+#define BA_HIP_SOLVER_PCG    1   /* preconditioned conjugate gradients on S (block-Jacobi; optionally two-level) */
 typedef struct {
   double rel_tolerance;
   uint32_t max_iterations;   /* CG steps; 0 = the number of unknowns */
   uint32_t check_every;      /* passes between two reads of the device state; 0 = the engine's choice */
-  uint32_t reserved[3];
+  uint32_t coarse_aggregate; /* 0 = block-Jacobi alone; g >= 1 = two-level preconditioner, aggregates of g poses (below) */
+  uint32_t reserved[2];
 } ba_hip_pcg_options;
 typedef struct {
   uint32_t iterations, converged, residual_replacements;
-  uint32_t breakdown;               /* 0 none, 1 p.Sp <= 0, 2 non-finite scalar, 3 preconditioner block not PD */
+  uint32_t breakdown;               /* 0 none, 1 p.Sp <= 0, 2 non-finite scalar, 3 preconditioner block not PD,
+                                     * 4 coarse matrix not PD (two-level preconditioner) */
   double rel_residual_recurrence;   /* ||r|| / ||rhs|| of the recurrence at the end */
   double rel_residual_true;         /* ... of the last recomputed rhs - S x (0 if none was formed) */
   double rhs_norm;
@@ -657,6 +659,26 @@ typedef struct {
 int ba_hip_set_reduced_solver(ba_hip_engine* e, int mode, const ba_hip_pcg_options* o);
 /* Statistics of the last ba_hip_solve_gn; an error if that solve was direct (or skipped). */
 int ba_hip_get_pcg_stats(ba_hip_engine* e, ba_hip_pcg_stats* out);
+/* Two-level preconditioner (ba_hip_pcg_options.coarse_aggregate = g >= 1; 0 keeps the block-Jacobi solver bit for
+ * bit): M^-1 = M_bj^-1 + Z (Z^T S Z)^-1 Z^T.  Z sums parameter d of the g consecutive active poses of an aggregate
+ * (pose-id order, whatever the pose ordering; the last aggregate may be short) into coarse unknown (aggregate, d);
+ * the K calibration unknowns are K coarse unknowns of their own.  In ba_hip_pcg_solve an aggregate is g consecutive
+ * preconditioner blocks; a short last block feeds the leading coarse parameters of its aggregate.  When
+ * D ceil(Pact / g) + K would exceed BA_HIP_PCG_COARSE_MAX the engine raises g to the smallest value that fits
+ * (aggregate_used): a request never fails for size.  The coarse matrix and its explicit inverse are formed once per
+ * solve; a pivot <= 0 in its factorisation is breakdown 4 (BA_HIP_FACTORIZATION_ERROR, delta_gn zero). */
+#define BA_HIP_PCG_COARSE_MAX 1024
+typedef struct {
+  uint32_t aggregate_used, coarse_unknowns, aggregates, reserved;
+  double setup_ms;                  /* assembling and inverting the coarse matrix */
+  double apply_ms;                  /* the two coarse launches of one pass, mean over the sampled passes */
+  double coarse_bytes;              /* device memory of the coarse matrices and vectors */
+} ba_hip_pcg_coarse_stats;
+/* Of the last ba_hip_solve_gn or ba_hip_pcg_solve; an error if that solve did not use the coarse space. */
+int ba_hip_get_pcg_coarse_stats(ba_hip_engine* e, ba_hip_pcg_coarse_stats* out);
+/* Test tap: the coarse matrix and its inverse of the last two-level solve, row-major nc x nc (nc = coarse_unknowns);
+ * either pointer may be NULL. */
+int ba_hip_get_pcg_coarse(ba_hip_engine* e, uint32_t nc, double* C, double* Cinv);
 
 /* ---- stand-alone kernels exposed for tests and benchmarks ------------------------- */
 /* The PCG solver on an SPD system given by its LOWER triangle (row-major n x n, host memory); `block`: size of the
