@@ -35,6 +35,14 @@ struct DBuf {
   }
   size_t bytes() const { return n * sizeof(T); }
 };
+// a temporary of one call: released on every exit path (early error returns included)
+template <typename T>
+struct TBuf : DBuf<T> {
+  TBuf() = default;
+  TBuf(const TBuf&) = delete;
+  TBuf& operator=(const TBuf&) = delete;
+  ~TBuf() { this->release(); }
+};
 
 // Rigid transform in matrix form as stored on the device: R row-major (9) then t (3).
 static const int kRt = 12;
@@ -351,6 +359,57 @@ inline int shard_allreduce(Engine* e, void* dev_ptr, size_t count, int dtype) {
     hipError_t _e = (call);                                              \
     if (_e != hipSuccess) return e->fail(_e, #call);                     \
   } while (0)
+
+// N timing events of one call, destroyed on every exit path.  (Engine::prof_begin keeps its own pairs: those
+// are collected later.)
+template <int N>
+struct Events {
+  hipEvent_t ev[N] = {};
+  Events() = default;
+  Events(const Events&) = delete;
+  Events& operator=(const Events&) = delete;
+  ~Events() {
+    for (hipEvent_t v : ev)
+      if (v) (void)hipEventDestroy(v);
+  }
+  hipError_t create() {
+    for (hipEvent_t& v : ev) {
+      const hipError_t err = hipEventCreate(&v);
+      if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+  }
+  hipEvent_t operator[](int i) const { return ev[i]; }
+  hipError_t record(int i, hipStream_t s) { return hipEventRecord(ev[i], s); }
+  // milliseconds from event a to event b, 0 when the query fails
+  double ms(int a, int b) const {
+    float t = 0.f;
+    return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0;
+  }
+};
+
+// `count` host elements into `d` (at least one element is allocated), copied asynchronously on e->stream: the
+// source must outlive the stream's next synchronisation.
+template <typename T, typename U>
+int upload_async(Engine* e, DBuf<T>& d, const U* src, size_t count) {
+  static_assert(sizeof(T) % sizeof(U) == 0, "element sizes");
+  const size_t n = count * sizeof(U) / sizeof(T);
+  BAE_HIP(d.alloc(n ? n : 1));
+  if (n) BAE_HIP(hipMemcpyAsync(d.p, src, n * sizeof(T), hipMemcpyHostToDevice, e->stream));
+  return 0;
+}
+
+// The factor that the last ba_hip_solve_gn left behind, for the kernels that read it: its tile count, the pivot
+// signs D and the L_JJ^-T of the diagonal tiles (both in invdiag).  `who` starts the message when there is none.
+inline int kept_factor(Engine* e, const char* who, uint32_t* nt, const double** dsgn, const double** linvT) {
+  const uint32_t n = e->st.ld / 64;
+  if (!e->invdiag.p || !e->nzL_valid || e->nzL_host.size() != (size_t)n * n)
+    return e->fail_msg((std::string(who) + ": no factor of the last ba_hip_solve_gn").c_str());
+  *nt = n;
+  *dsgn = e->invdiag.p;
+  *linvT = *dsgn + (size_t)n * 64;
+  return 0;
+}
 
 // ---- kernel launchers (defined in k_*.hip); all enqueue on e->stream -------------
 int launch_pose_prep(Engine* e);                       // T_sw, T_ws, T_wp of the current state

@@ -16,112 +16,19 @@
 // pivot signs D from invdiag.  FP64, no atomics: every partial tile has one writer and the sums run in the
 // plan's order, so two calls give the same bits.
 //
-// The tile products run on v_mfma_f64_16x16x4_f64 with the staging of k_selinv.hip: four waves, each owning a
+// The tile products run on v_mfma_f64_16x16x4_f64 with the staging of tile_mma.h: four waves, each owning a
 // 32x32 quarter of the output tile; operands go through LDS 32 k-rows at a time, k-major, and the next chunk
 // is fetched into registers while the matrix cores work on this one.
 #include "engine.h"
 #include "jointcov.h"
+#include "tile_mma.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace bae {
 
-namespace {
-
-const int TB = 64;         // tile size
-const int KCH = 32;        // k-rows per LDS chunk
-const int LDS_LD = TB + 4; // LDS row stride (doubles)
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-struct JointLds {
-  double X[KCH][LDS_LD];
-  double Y[KCH][LDS_LD];
-};
-
-// Thread t moves 4 double2 of a 32 x 64 chunk: element pair e = 2 t + 512 s (s < 4).
-//  k-major source (rows = k, stride `ld`, 64 contiguous indices):   k = e / 64, index = e % 64
-//  index-major source (rows = index, 64 contiguous k):              index = e / 32, k = e % 32
-struct Chunk {
-  double2 v[4];
-};
-__device__ __forceinline__ void load_kmajor(Chunk& c, const double* src, size_t ld, int k0) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    c.v[s] = *reinterpret_cast<const double2*>(src + (size_t)(k0 + e / TB) * ld + (e % TB));
-  }
-}
-__device__ __forceinline__ void load_imajor(Chunk& c, const double* src, size_t ld, int k0) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    c.v[s] = *reinterpret_cast<const double2*>(src + (size_t)(e / KCH) * ld + k0 + (e % KCH));
-  }
-}
-__device__ __forceinline__ void store_kmajor(const Chunk& c, double (*Z)[LDS_LD]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    Z[e / TB][e % TB] = c.v[s].x;
-    Z[e / TB][e % TB + 1] = c.v[s].y;
-  }
-}
-__device__ __forceinline__ void store_imajor(const Chunk& c, double (*Z)[LDS_LD]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    Z[e % KCH][e / KCH] = c.v[s].x;
-    Z[e % KCH + 1][e / KCH] = c.v[s].y;
-  }
-}
-
-__device__ __forceinline__ void zero_acc(double4_t (&acc)[2][2]) {
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = (double4_t){0.0, 0.0, 0.0, 0.0};
-}
-
-// acc[i][j] += sum_k X[k][i] Y[k][j], 32 k
-__device__ __forceinline__ void mma_chunk(double4_t (&acc)[2][2], const JointLds& s) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 15, lk = lane >> 4;
-  const int rb = 32 * (wave >> 1), cb = 32 * (wave & 1);
-#pragma unroll
-  for (int ks = 0; ks < KCH / 4; ++ks) {
-    const double a0 = s.X[4 * ks + lk][rb + li];
-    const double a1 = s.X[4 * ks + lk][rb + 16 + li];
-    const double b0 = s.Y[4 * ks + lk][cb + li];
-    const double b1 = s.Y[4 * ks + lk][cb + 16 + li];
-    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-  }
-}
-
-// 64 x 64 tile out of the accumulators, row stride ld
-__device__ __forceinline__ void store_tile(double* __restrict__ dst, size_t ld, const double4_t (&v)[2][2]) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 15, lk = lane >> 4;
-  const int rb = 32 * (wave >> 1), cb = 32 * (wave & 1);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int r = rb + 16 * ti + lk + 4 * reg, c = cb + 16 * tj + li;
-        dst[(size_t)r * ld + c] = v[ti][tj][reg];
-      }
-}
-
-}  // namespace
+using namespace tile64;
 
 // col_key[c]: 64 position + row inside the tile of the unit entry of column c (kJointNone for padding columns)
 __global__ void __launch_bounds__(256)
@@ -137,7 +44,7 @@ __global__ void __launch_bounds__(256)
 k_joint_fsolve(const uint4* __restrict__ chunks, const uint32_t* __restrict__ src, const uint32_t* __restrict__ pos,
                const double* __restrict__ A, uint32_t ld, const double* __restrict__ Y, uint32_t mp,
                double* __restrict__ slots) {
-  __shared__ JointLds s;
+  __shared__ Lds s;
   const uint4 c = chunks[blockIdx.x];
   const uint32_t I = c.x, s0 = c.z, b = blockIdx.y;
   const uint32_t nch = 2 * (c.w - s0);
@@ -167,7 +74,7 @@ k_joint_fsolve(const uint4* __restrict__ chunks, const uint32_t* __restrict__ sr
 __global__ void __launch_bounds__(256)
 k_joint_epilogue(const uint4* __restrict__ rows, const uint32_t* __restrict__ pos, const double* __restrict__ linvT,
                  double* __restrict__ Y, uint32_t mp, const double* __restrict__ slots) {
-  __shared__ JointLds s;
+  __shared__ Lds s;
   const uint4 r = rows[blockIdx.x];
   const uint32_t I = r.x, b = blockIdx.y, ncb = gridDim.y;
   double* YI = Y + (size_t)pos[I] * TB * mp + (size_t)b * TB;
@@ -206,7 +113,7 @@ k_joint_epilogue(const uint4* __restrict__ rows, const uint32_t* __restrict__ po
 __global__ void __launch_bounds__(256)
 k_joint_gram(const double* __restrict__ Y, uint32_t mp, const uint32_t* __restrict__ reach, uint32_t nr,
              const double* __restrict__ dsgn, double* __restrict__ part) {
-  __shared__ JointLds s;
+  __shared__ Lds s;
   const uint32_t g = blockIdx.x, t = blockIdx.y;
   uint32_t bi = 0;
   while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
@@ -259,17 +166,13 @@ k_joint_combine(const double* __restrict__ part, uint32_t groups, uint32_t ntl, 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-static double joint_elapsed_ms(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
-}
-
 // sel: the requested rows of S in the engine's (factorised) numbering, out: M x M on the host
 int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
   const Structure& st = e->st;
-  const uint32_t nt = st.ld / TB, M = (uint32_t)sel.size();
-  if (!e->invdiag.p || !e->nzL_valid || e->nzL_host.size() != (size_t)nt * nt)
-    return e->fail_msg("joint marginals: no factor of the last ba_hip_solve_gn");
+  const uint32_t M = (uint32_t)sel.size();
+  uint32_t nt;
+  const double *dsgn, *linvT;
+  if (int rc = kept_factor(e, "joint marginals", &nt, &dsgn, &linvT)) return rc;
   std::vector<uint32_t> tiles(M);
   for (uint32_t c = 0; c < M; ++c) tiles[c] = sel[c] / TB;
   JointPlan p;
@@ -303,13 +206,9 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
   const uint32_t* d_idx = e->jc_idx.p;
   const uint4* d_chunks = reinterpret_cast<const uint4*>(d_idx + o_chunks);
   const uint4* d_rows = reinterpret_cast<const uint4*>(d_idx + o_rows);
-  const double* dsgn = e->invdiag.p;
-  const double* linvT = dsgn + (size_t)nt * TB;
-  hipEvent_t t0, t1, t2;
-  BAE_HIP(hipEventCreate(&t0));
-  BAE_HIP(hipEventCreate(&t1));
-  BAE_HIP(hipEventCreate(&t2));
-  (void)hipEventRecord(t0, e->stream);
+  Events<3> ev;
+  BAE_HIP(ev.create());
+  (void)ev.record(0, e->stream);
   hipLaunchKernelGGL(k_joint_init, dim3((unsigned)((n_y + 255) / 256)), dim3(256), 0, e->stream, e->jc_Y.p, (uint64_t)n_y,
                      mp, d_idx + o_key);
   for (uint32_t v = 0; v < p.levels(); ++v) {
@@ -321,20 +220,17 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
     hipLaunchKernelGGL(k_joint_epilogue, dim3(r1 - r0, ncb), dim3(256), 0, e->stream, d_rows + r0, d_idx + o_pos, linvT,
                        e->jc_Y.p, mp, (const double*)e->jc_slots.p);
   }
-  (void)hipEventRecord(t1, e->stream);
+  (void)ev.record(1, e->stream);
   hipLaunchKernelGGL(k_joint_gram, dim3(p.gram_groups, ntl), dim3(256), 0, e->stream, (const double*)e->jc_Y.p, mp,
                      d_idx + o_reach, nr, dsgn, e->jc_part.p);
   hipLaunchKernelGGL(k_joint_combine, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, e->stream,
                      (const double*)e->jc_part.p, p.gram_groups, ntl, M, e->jc_out.p);
-  (void)hipEventRecord(t2, e->stream);
+  (void)ev.record(2, e->stream);
   const hipError_t lerr = hipGetLastError();
-  const hipError_t serr = hipEventSynchronize(t2);
+  const hipError_t serr = hipEventSynchronize(ev[2]);
   ba_hip_joint_marginal_stats js = {};
-  js.solve_ms = joint_elapsed_ms(t0, t1);
-  js.gram_ms = joint_elapsed_ms(t1, t2);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  (void)hipEventDestroy(t2);
+  js.solve_ms = ev.ms(0, 1);
+  js.gram_ms = ev.ms(1, 2);
   if (lerr != hipSuccess) return e->fail(lerr, "k_joint launch");
   if (serr != hipSuccess) return e->fail(serr, "k_joint");
   BAE_HIP(hipMemcpy(out, e->jc_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost));

@@ -323,13 +323,6 @@ __global__ void k_marg_vec(uint32_t m, uint32_t N, const double* __restrict__ S,
   else *c = s;
 }
 
-template <typename T>
-int up(Engine* e, DBuf<T>& buf, const T* p, size_t n) {
-  BAE_HIP(buf.alloc(std::max<size_t>(n, 1)));
-  if (n) BAE_HIP(hipMemcpyAsync(buf.p, p, n * sizeof(T), hipMemcpyHostToDevice, e->stream));
-  return 0;
-}
-
 // a fixed-order sum of n device doubles into *host (deferred while the engine defers its sums)
 int small_sum(Engine* e, int n, const double* d_v, double* host) {
   *host = 0.0;
@@ -376,10 +369,14 @@ int priors_upload(Engine* e) {
   }
   const size_t ktot = pr.pose.size();
   int rc;
-  if ((rc = up(e, e->dp_ptr, pr.ptr.data(), pr.ptr.size())) || (rc = up(e, e->dp_pose, pr.pose.data(), ktot)) ||
-      (rc = up(e, e->dp_x0, pr.x0.data(), pr.x0.size())) || (rc = up(e, e->dp_H, pr.H.data(), pr.H.size())) ||
-      (rc = up(e, e->dp_b, pr.b.data(), pr.b.size())) || (rc = up(e, e->dp_c, pr.c.data(), pr.c.size())) ||
-      (rc = up(e, e->dp_hoff, hoff.data(), hoff.size())) || (rc = up(e, e->dp_blk, blk.data(), blk.size())))
+  if ((rc = upload_async(e, e->dp_ptr, pr.ptr.data(), pr.ptr.size())) ||
+      (rc = upload_async(e, e->dp_pose, pr.pose.data(), ktot)) ||
+      (rc = upload_async(e, e->dp_x0, pr.x0.data(), pr.x0.size())) ||
+      (rc = upload_async(e, e->dp_H, pr.H.data(), pr.H.size())) ||
+      (rc = upload_async(e, e->dp_b, pr.b.data(), pr.b.size())) ||
+      (rc = upload_async(e, e->dp_c, pr.c.data(), pr.c.size())) ||
+      (rc = upload_async(e, e->dp_hoff, hoff.data(), hoff.size())) ||
+      (rc = upload_async(e, e->dp_blk, blk.data(), blk.size())))
     return rc;
   BAE_HIP(e->dp_d.alloc(ktot * D)); BAE_HIP(e->dp_J.alloc(ktot * D * D));
   BAE_HIP(e->dp_G.alloc(std::max<size_t>(pr.h_off[nq], 1))); BAE_HIP(e->dp_g.alloc(ktot * D));
@@ -439,78 +436,65 @@ int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& 
   const int D = e->pose_dim;
   const uint32_t n = pl.nM + pl.nB, N = n * D, m = pl.nM * D, nb = pl.nB * D;
   static_assert(sizeof(MargTerm) == sizeof(uint4), "term records are plain words");
-  DBuf<uint32_t> blk_ij, blk_ptr, rhs_ptr;
-  DBuf<uint4> terms, rterms, eterms;
-  DBuf<uint16_t> dmask;
-  DBuf<double> S, rhs, Ea, Hd, bd;
-  DBuf<int32_t> status;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  auto cleanup = [&]() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    blk_ij.release(); blk_ptr.release(); rhs_ptr.release(); terms.release(); rterms.release(); eterms.release();
-    dmask.release(); S.release(); rhs.release(); Ea.release(); Hd.release(); bd.release(); status.release();
-  };
-  int rc = 0;
-  auto run = [&]() -> int {
-    if ((rc = up(e, blk_ij, pl.blk_ij.data(), pl.blk_ij.size())) || (rc = up(e, blk_ptr, pl.blk_ptr.data(), pl.blk_ptr.size())) ||
-        (rc = up(e, terms, (const uint4*)pl.blk_terms.data(), pl.blk_terms.size())) ||
-        (rc = up(e, rhs_ptr, pl.rhs_ptr.data(), pl.rhs_ptr.size())) ||
-        (rc = up(e, rterms, (const uint4*)pl.rhs_terms.data(), pl.rhs_terms.size())) ||
-        (rc = up(e, eterms, (const uint4*)pl.err_terms.data(), pl.err_terms.size())) ||
-        (rc = up(e, dmask, lmask.data(), lmask.size())))
-      return rc;
-    BAE_HIP(S.alloc((size_t)N * N)); BAE_HIP(rhs.alloc(N)); BAE_HIP(Ea.alloc(1));
-    BAE_HIP(Hd.alloc(std::max<size_t>((size_t)nb * nb, 1))); BAE_HIP(bd.alloc(nb + 1)); BAE_HIP(status.alloc(1));
-    BAE_HIP(hipMemsetAsync(S.p, 0, S.bytes(), e->stream));
-    BAE_HIP(hipEventCreate(&ev0));
-    BAE_HIP(hipEventCreate(&ev1));
-    BAE_HIP(hipEventRecord(ev0, e->stream));
-    MargIn in;
-    in.frow = e->frow.p; in.scal = e->scal.p; in.pp_h = e->pp_h.p; in.pp_g = e->pp_g.p; in.pp_err = e->pp_err_lin.p;
-    in.G = e->dp_G.p; in.g = e->dp_g.p; in.E = e->dp_E.p; in.lm_vinv = e->lm_vinv.p;
-    in.dp_ptr = e->dp_ptr.p; in.hoff = e->dp_hoff.p;
-    hipLaunchKernelGGL(k_marg_assemble, dim3((uint32_t)pl.blk_ij.size()), dim3(256), 0, e->stream, D, N, pl.nM,
-                       blk_ij.p, blk_ptr.p, terms.p, rhs_ptr.p, rterms.p, dmask.p, in, S.p, rhs.p);
+  TBuf<uint32_t> blk_ij, blk_ptr, rhs_ptr;
+  TBuf<uint4> terms, rterms, eterms;
+  TBuf<uint16_t> dmask;
+  TBuf<double> S, rhs, Ea, Hd, bd;
+  TBuf<int32_t> status;
+  Events<2> ev;
+  int rc;
+  if ((rc = upload_async(e, blk_ij, pl.blk_ij.data(), pl.blk_ij.size())) ||
+      (rc = upload_async(e, blk_ptr, pl.blk_ptr.data(), pl.blk_ptr.size())) ||
+      (rc = upload_async(e, terms, pl.blk_terms.data(), pl.blk_terms.size())) ||
+      (rc = upload_async(e, rhs_ptr, pl.rhs_ptr.data(), pl.rhs_ptr.size())) ||
+      (rc = upload_async(e, rterms, pl.rhs_terms.data(), pl.rhs_terms.size())) ||
+      (rc = upload_async(e, eterms, pl.err_terms.data(), pl.err_terms.size())) ||
+      (rc = upload_async(e, dmask, lmask.data(), lmask.size())))
+    return rc;
+  BAE_HIP(S.alloc((size_t)N * N)); BAE_HIP(rhs.alloc(N)); BAE_HIP(Ea.alloc(1));
+  BAE_HIP(Hd.alloc(std::max<size_t>((size_t)nb * nb, 1))); BAE_HIP(bd.alloc(nb + 1)); BAE_HIP(status.alloc(1));
+  BAE_HIP(hipMemsetAsync(S.p, 0, S.bytes(), e->stream));
+  BAE_HIP(ev.create());
+  BAE_HIP(ev.record(0, e->stream));
+  MargIn in;
+  in.frow = e->frow.p; in.scal = e->scal.p; in.pp_h = e->pp_h.p; in.pp_g = e->pp_g.p; in.pp_err = e->pp_err_lin.p;
+  in.G = e->dp_G.p; in.g = e->dp_g.p; in.E = e->dp_E.p; in.lm_vinv = e->lm_vinv.p;
+  in.dp_ptr = e->dp_ptr.p; in.hoff = e->dp_hoff.p;
+  hipLaunchKernelGGL(k_marg_assemble, dim3((uint32_t)pl.blk_ij.size()), dim3(256), 0, e->stream, D, N, pl.nM,
+                     blk_ij.p, blk_ptr.p, terms.p, rhs_ptr.p, rterms.p, dmask.p, in, S.p, rhs.p);
+  BAE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_marg_error, dim3(1), dim3(1), 0, e->stream, (uint32_t)pl.err_terms.size(), eterms.p, e->st.O,
+                     e->lm_dim, in, Ea.p);
+  BAE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_marg_ldl, dim3(1), dim3(256), 0, e->stream, m, N, tol, S.p, status.p);
+  BAE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_marg_trsm, dim3((nb + 1 + 63) / 64), dim3(64), 0, e->stream, m, N, S.p, rhs.p);
+  BAE_HIP(hipGetLastError());
+  const uint32_t nt = (nb + 63) / 64;
+  if (nt) {
+    hipLaunchKernelGGL(k_marg_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, e->stream, m, N, S.p, Hd.p);
     BAE_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_marg_error, dim3(1), dim3(1), 0, e->stream, (uint32_t)pl.err_terms.size(), eterms.p, e->st.O,
-                       e->lm_dim, in, Ea.p);
-    BAE_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_marg_ldl, dim3(1), dim3(256), 0, e->stream, m, N, tol, S.p, status.p);
-    BAE_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_marg_trsm, dim3((nb + 1 + 63) / 64), dim3(64), 0, e->stream, m, N, S.p, rhs.p);
-    BAE_HIP(hipGetLastError());
-    const uint32_t nt = (nb + 63) / 64;
-    if (nt) {
-      hipLaunchKernelGGL(k_marg_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, e->stream, m, N, S.p, Hd.p);
-      BAE_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_marg_vec, dim3((nb + 1 + 63) / 64), dim3(64), 0, e->stream, m, N, S.p, rhs.p, Ea.p, bd.p,
-                       bd.p + nb);
-    BAE_HIP(hipGetLastError());
-    int32_t st_h = 0;
-    e->marg_H.assign((size_t)nb * nb, 0.0);
-    e->marg_b.assign(nb + 1, 0.0);
-    BAE_HIP(hipMemcpyAsync(&st_h, status.p, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    if (nb) BAE_HIP(hipMemcpyAsync(e->marg_H.data(), Hd.p, (size_t)nb * nb * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    BAE_HIP(hipMemcpyAsync(e->marg_b.data(), bd.p, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    BAE_HIP(hipEventRecord(ev1, e->stream));
-    BAE_HIP(hipStreamSynchronize(e->stream));
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, ev0, ev1);
-    *dev_ms = ms;
-    e->marg_c = e->marg_b[nb];
-    e->marg_b.resize(nb);
-    if (st_h) {
-      e->err = "marginalize: S^a_MM is not positive definite (pivot " + std::to_string(st_h - 1) +
-               "): the absorbed residuals do not determine M";
-      return BA_HIP_FACTORIZATION_ERROR;
-    }
-    return 0;
-  };
-  rc = run();
-  cleanup();
-  return rc;
+  }
+  hipLaunchKernelGGL(k_marg_vec, dim3((nb + 1 + 63) / 64), dim3(64), 0, e->stream, m, N, S.p, rhs.p, Ea.p, bd.p,
+                     bd.p + nb);
+  BAE_HIP(hipGetLastError());
+  int32_t st_h = 0;
+  e->marg_H.assign((size_t)nb * nb, 0.0);
+  e->marg_b.assign(nb + 1, 0.0);
+  BAE_HIP(hipMemcpyAsync(&st_h, status.p, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  if (nb) BAE_HIP(hipMemcpyAsync(e->marg_H.data(), Hd.p, (size_t)nb * nb * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  BAE_HIP(hipMemcpyAsync(e->marg_b.data(), bd.p, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  BAE_HIP(ev.record(1, e->stream));
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  *dev_ms = ev.ms(0, 1);
+  e->marg_c = e->marg_b[nb];
+  e->marg_b.resize(nb);
+  if (st_h) {
+    e->err = "marginalize: S^a_MM is not positive definite (pivot " + std::to_string(st_h - 1) +
+             "): the absorbed residuals do not determine M";
+    return BA_HIP_FACTORIZATION_ERROR;
+  }
+  return 0;
 }
 
 }  // namespace bae

@@ -238,15 +238,6 @@ __global__ __launch_bounds__(256) void k_pcg_update2(uint32_t ld, uint32_t nt, u
   if (blockIdx.x == 0 && threadIdx.x == 0) *st_out = o;
 }
 
-template <typename T, typename U>
-static int upload_vec(Engine* e, DBuf<T>& d, const std::vector<U>& v) {
-  static_assert(sizeof(T) % sizeof(U) == 0, "element sizes");
-  const size_t count = v.size() * sizeof(U) / sizeof(T);
-  BAE_HIP(d.alloc(std::max<size_t>(count, 1)));
-  if (count) BAE_HIP(hipMemcpyAsync(d.p, v.data(), count * sizeof(T), hipMemcpyHostToDevice, e->stream));
-  return 0;
-}
-
 int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const double* d_rhs, const PcgPlan& plan,
                      const std::vector<uint8_t>& nz, const std::vector<uint32_t>& blk, const std::vector<uint32_t>& blocks,
                      bool upload, const ba_hip_pcg_options& opt, double* dx, ba_hip_pcg_stats* stats, int* status) {
@@ -262,34 +253,41 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
   const bool coarse = opt.coarse_aggregate != 0;
   if (coarse && (plan.cmap.size() != (size_t)ld || plan.coarse_req != opt.coarse_aggregate || plan.ncp % 64 || plan.nc > plan.ncp))
     return e->fail_msg("pcg_solve_device: the plan's coarse space does not match the options");
-  hipEvent_t ev[10];
-  for (auto& v : ev) BAE_HIP(hipEventCreate(&v));
-  auto drop = [&]() { for (auto& v : ev) (void)hipEventDestroy(v); };
-#define PCG_TRY(call) do { hipError_t _e = (call); if (_e != hipSuccess) { drop(); return e->fail(_e, #call); } } while (0)
-  PCG_TRY(hipEventRecord(ev[0], s));
+  // event pairs: 0 / 5 the solve, 1 / 2 the block inverses, 3 / 4 one mat-vec of a batch, 6 / 7 the coarse setup,
+  // 8 / 9 one coarse apply of a batch
+  Events<10> ev;
+  BAE_HIP(ev.create());
+  BAE_HIP(ev.record(0, s));
   if (upload || !w.tiles.p) {
-    if ((rc = upload_vec(e, w.tiles, plan.tiles)) || (rc = upload_vec(e, w.blk, blk)) || (rc = upload_vec(e, w.blocks, blocks)) ||
-        (rc = upload_vec(e, w.row_ptr, plan.row_ptr)) || (rc = upload_vec(e, w.col_ptr, plan.col_ptr)) ||
-        (rc = upload_vec(e, w.col_slot, plan.col_slot)) || (rc = upload_vec(e, w.nz, nz))) { drop(); return rc; }
-    PCG_TRY(w.rowslot.alloc((size_t)plan.n_tiles * 64));
-    PCG_TRY(w.colslot.alloc((size_t)plan.n_tiles * 64));
-    PCG_TRY(w.minv.alloc((size_t)ld * 16));
-    PCG_TRY(w.x.alloc(ld)); PCG_TRY(w.r.alloc((size_t)2 * ld)); PCG_TRY(w.z.alloc(ld)); PCG_TRY(w.p.alloc(ld)); PCG_TRY(w.q.alloc(ld));
-    PCG_TRY(w.parts.alloc((size_t)nt + 2 * nb));
-    PCG_TRY(w.state.alloc(2));
-    PCG_TRY(w.status.alloc(2));
+    if ((rc = upload_async(e, w.tiles, plan.tiles.data(), plan.tiles.size())) ||
+        (rc = upload_async(e, w.blk, blk.data(), blk.size())) ||
+        (rc = upload_async(e, w.blocks, blocks.data(), blocks.size())) ||
+        (rc = upload_async(e, w.row_ptr, plan.row_ptr.data(), plan.row_ptr.size())) ||
+        (rc = upload_async(e, w.col_ptr, plan.col_ptr.data(), plan.col_ptr.size())) ||
+        (rc = upload_async(e, w.col_slot, plan.col_slot.data(), plan.col_slot.size())) ||
+        (rc = upload_async(e, w.nz, nz.data(), nz.size())))
+      return rc;
+    BAE_HIP(w.rowslot.alloc((size_t)plan.n_tiles * 64));
+    BAE_HIP(w.colslot.alloc((size_t)plan.n_tiles * 64));
+    BAE_HIP(w.minv.alloc((size_t)ld * 16));
+    BAE_HIP(w.x.alloc(ld)); BAE_HIP(w.r.alloc((size_t)2 * ld)); BAE_HIP(w.z.alloc(ld)); BAE_HIP(w.p.alloc(ld)); BAE_HIP(w.q.alloc(ld));
+    BAE_HIP(w.parts.alloc((size_t)nt + 2 * nb));
+    BAE_HIP(w.state.alloc(2));
+    BAE_HIP(w.status.alloc(2));
   }
   const uint32_t nc = plan.nc, ncp = plan.ncp;
   if (upload) w.coarse_key = 0;   // the work space changes hands: coarse tables uploaded earlier belong to another system
   if (coarse) {
     if (upload || w.coarse_key != plan.coarse_req || !w.cmap.p) {
-      if ((rc = upload_vec(e, w.cmap, plan.cmap)) || (rc = upload_vec(e, w.crow_ptr, plan.crow_ptr)) ||
-          (rc = upload_vec(e, w.crow_rows, plan.crow_rows))) { drop(); return rc; }
+      if ((rc = upload_async(e, w.cmap, plan.cmap.data(), plan.cmap.size())) ||
+          (rc = upload_async(e, w.crow_ptr, plan.crow_ptr.data(), plan.crow_ptr.size())) ||
+          (rc = upload_async(e, w.crow_rows, plan.crow_rows.data(), plan.crow_rows.size())))
+        return rc;
       w.coarse_key = plan.coarse_req;
     }
-    PCG_TRY(w.C.alloc((size_t)ncp * ncp)); PCG_TRY(w.Lc.alloc((size_t)ncp * ncp)); PCG_TRY(w.Wc.alloc((size_t)ncp * ncp));
-    PCG_TRY(w.Cinv.alloc((size_t)ncp * ncp));
-    PCG_TRY(w.rc.alloc(ncp)); PCG_TRY(w.yc.alloc(ncp)); PCG_TRY(w.ryc_part.alloc(ncp));
+    BAE_HIP(w.C.alloc((size_t)ncp * ncp)); BAE_HIP(w.Lc.alloc((size_t)ncp * ncp)); BAE_HIP(w.Wc.alloc((size_t)ncp * ncp));
+    BAE_HIP(w.Cinv.alloc((size_t)ncp * ncp));
+    BAE_HIP(w.rc.alloc(ncp)); BAE_HIP(w.yc.alloc(ncp)); BAE_HIP(w.ryc_part.alloc(ncp));
   }
   w.coarse_nc = w.coarse_ncp = 0;
   double* pq_part = w.parts.p;
@@ -301,20 +299,20 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
   h0.max_it = opt.max_iterations ? opt.max_iterations : n;
   h0.mode = kPcgInit;
   const uint32_t check_every = opt.check_every ? opt.check_every : 10;
-  PCG_TRY(hipMemcpyAsync(w.state.p, &h0, sizeof(h0), hipMemcpyHostToDevice, s));
-  PCG_TRY(hipMemsetAsync(w.status.p, 0, 2 * sizeof(int32_t), s));
-  PCG_TRY(hipMemsetAsync(w.x.p, 0, (size_t)ld * sizeof(double), s));
-  PCG_TRY(hipMemsetAsync(w.p.p, 0, (size_t)ld * sizeof(double), s));
-  PCG_TRY(hipMemsetAsync(w.minv.p, 0, (size_t)ld * 16 * sizeof(double), s));
-  PCG_TRY(hipEventRecord(ev[1], s));
+  BAE_HIP(hipMemcpyAsync(w.state.p, &h0, sizeof(h0), hipMemcpyHostToDevice, s));
+  BAE_HIP(hipMemsetAsync(w.status.p, 0, 2 * sizeof(int32_t), s));
+  BAE_HIP(hipMemsetAsync(w.x.p, 0, (size_t)ld * sizeof(double), s));
+  BAE_HIP(hipMemsetAsync(w.p.p, 0, (size_t)ld * sizeof(double), s));
+  BAE_HIP(hipMemsetAsync(w.minv.p, 0, (size_t)ld * 16 * sizeof(double), s));
+  BAE_HIP(ev.record(1, s));
   if (nblocks)
     hipLaunchKernelGGL(k_pcg_blocks, dim3((nblocks + 3) / 4), dim3(64), 0, s, dA, ld, (const uint8_t*)w.nz.p, nt,
                        (const uint2*)w.blocks.p, nblocks, w.minv.p, w.status.p);
-  PCG_TRY(hipEventRecord(ev[2], s));
+  BAE_HIP(ev.record(2, s));
   if (coarse) {
-    PCG_TRY(hipEventRecord(ev[6], s));
-    if ((rc = pcg_coarse_setup_device(e, dA, ld, plan))) { drop(); return rc; }
-    PCG_TRY(hipEventRecord(ev[7], s));
+    BAE_HIP(ev.record(6, s));
+    if ((rc = pcg_coarse_setup_device(e, dA, ld, plan))) return rc;
+    BAE_HIP(ev.record(7, s));
   }
   PcgState hs = h0;
   double spmv_ms = 0.0, apply_ms = 0.0;
@@ -331,21 +329,21 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
       double* rout = w.r.p + (size_t)((k + 1) & 1) * ld;
       if (k > 0) {
         const bool sample = !sampled;
-        if (sample) PCG_TRY(hipEventRecord(ev[3], s));
+        if (sample) BAE_HIP(ev.record(3, s));
         hipLaunchKernelGGL(k_pcg_spmv_tiles, dim3(plan.n_tiles), dim3(256), 0, s, dA, ld, (const uint2*)w.tiles.p,
                            (const double*)w.p.p, (const double*)w.x.p, sin, w.rowslot.p, w.colslot.p);
         hipLaunchKernelGGL(k_pcg_spmv_gather, dim3(nt), dim3(64), 0, s, (const uint32_t*)w.row_ptr.p, (const uint32_t*)w.col_ptr.p,
                            (const uint32_t*)w.col_slot.p, (const double*)w.rowslot.p, (const double*)w.colslot.p,
                            (const double*)w.p.p, sin, w.q.p, pq_part);
-        if (sample) { PCG_TRY(hipEventRecord(ev[4], s)); sampled = true; }
+        if (sample) { BAE_HIP(ev.record(4, s)); sampled = true; }
       }
       hipLaunchKernelGGL(k_pcg_update1, dim3(nb), dim3(256), 0, s, n, ld, nt, sin, (const double*)pq_part, d_rhs,
                          (const double*)w.q.p, rin, (const uint2*)w.blk.p, (const double*)w.minv.p, rout, w.z.p, rz_part, rr_part);
       if (coarse) {
         const bool sample = !sampled_c;
-        if (sample) PCG_TRY(hipEventRecord(ev[8], s));
+        if (sample) BAE_HIP(ev.record(8, s));
         pcg_coarse_apply_device(e, plan, sin, rout);
-        if (sample) { PCG_TRY(hipEventRecord(ev[9], s)); sampled_c = true; }
+        if (sample) { BAE_HIP(ev.record(9, s)); sampled_c = true; }
         hipLaunchKernelGGL(k_pcg_update2<true>, dim3(nb), dim3(256), 0, s, ld, nt, nb, sin, sout, (const int32_t*)w.status.p,
                            (const double*)pq_part, (const double*)rz_part, (const double*)rr_part, (const double*)w.z.p, w.x.p,
                            w.p.p, nc, (const uint32_t*)w.cmap.p, (const double*)w.yc.p, (const double*)w.ryc_part.p);
@@ -355,9 +353,9 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
                            w.p.p, 0u, (const uint32_t*)nullptr, (const double*)nullptr, (const double*)nullptr);
       }
     }
-    PCG_TRY(hipGetLastError());
-    PCG_TRY(hipMemcpyAsync(&hs, w.state.p + (k & 1), sizeof(hs), hipMemcpyDeviceToHost, s));
-    PCG_TRY(hipStreamSynchronize(s));
+    BAE_HIP(hipGetLastError());
+    BAE_HIP(hipMemcpyAsync(&hs, w.state.p + (k & 1), sizeof(hs), hipMemcpyDeviceToHost, s));
+    BAE_HIP(hipStreamSynchronize(s));
     if (sampled) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, ev[3], ev[4]) == hipSuccess) { spmv_ms += ms; spmv_samples++; }
@@ -368,33 +366,26 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
     }
     if (hs.done) break;
   }
-  PCG_TRY(hipMemcpyAsync(dx, w.x.p, (size_t)ld * sizeof(double), hipMemcpyDeviceToDevice, s));
-  PCG_TRY(hipEventRecord(ev[5], s));
-  PCG_TRY(hipStreamSynchronize(s));
-  float ms_all = 0.f, ms_pre = 0.f;
-  (void)hipEventElapsedTime(&ms_all, ev[0], ev[5]);
-  (void)hipEventElapsedTime(&ms_pre, ev[1], ev[2]);
+  BAE_HIP(hipMemcpyAsync(dx, w.x.p, (size_t)ld * sizeof(double), hipMemcpyDeviceToDevice, s));
+  BAE_HIP(ev.record(5, s));
+  BAE_HIP(hipStreamSynchronize(s));
   e->pcg_coarse_last = coarse;
   if (coarse) {
-    float ms_setup = 0.f;
-    (void)hipEventElapsedTime(&ms_setup, ev[6], ev[7]);
     ba_hip_pcg_coarse_stats& c = e->pcg_coarse_stats;
     memset(&c, 0, sizeof(c));
     c.aggregate_used = plan.coarse_g; c.coarse_unknowns = nc; c.aggregates = plan.naggr;
-    c.setup_ms = ms_setup;
+    c.setup_ms = ev.ms(6, 7);
     c.apply_ms = apply_samples ? apply_ms / apply_samples : 0.0;
     c.coarse_bytes = 8.0 * (4.0 * ncp * ncp + 3.0 * ncp) + 4.0 * (plan.cmap.size() + plan.crow_ptr.size() + plan.crow_rows.size());
     w.coarse_nc = nc;
     w.coarse_ncp = ncp;
   }
-#undef PCG_TRY
-  drop();
   stats->iterations = hs.iterations; stats->converged = hs.converged; stats->residual_replacements = hs.replacements;
   stats->breakdown = hs.breakdown;
   stats->rhs_norm = sqrt(hs.bb);
   stats->rel_residual_recurrence = hs.bb > 0.0 ? sqrt(hs.rr_recur / hs.bb) : 0.0;
   stats->rel_residual_true = hs.bb > 0.0 ? sqrt(hs.rr_true / hs.bb) : 0.0;
-  stats->solve_ms = ms_all; stats->precond_ms = ms_pre;
+  stats->solve_ms = ev.ms(0, 5); stats->precond_ms = ev.ms(1, 2);
   stats->spmv_ms = spmv_samples ? spmv_ms / spmv_samples : 0.0;
   stats->tiles_read_per_spmv = plan.n_tiles;
   stats->bytes_read_per_spmv = plan.bytes_per_spmv;

@@ -8,10 +8,13 @@
 // FP64, no atomics, every sum in a fixed order.  These buffers are the solver's own: nothing of the direct solver's
 // factor, selected inverse or joint-covariance work space is touched.
 #include "engine.h"
+#include "tile_mma.h"
 
 namespace bae {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
+using tile64::double4_t;
+using tile64::each;
+using tile64::zero_acc;
 
 // One thread per entry (a, b), b <= a, of the padded C: the sum of S(i, j) over the fine rows of a and of b in list
 // order (ascending natural order), S read at (max, min) of the lower storage and only inside the pattern's tiles.
@@ -41,9 +44,9 @@ __global__ __launch_bounds__(256) void k_pcg_coarse_assemble(const double* __res
   C[(size_t)b * ncp + a] = sum;
 }
 
-// acc[r][c] += sum_{m < 64} X(r, m) Y(c, m) on v_mfma_f64_16x16x4_f64: four waves, each a 32 x 32 quarter of the
-// 64 x 64 output (row = rb + 16 ti + (lane >> 4) + 4 reg, column = cb + 16 tj + (lane & 15)); the operands go
-// through LDS 16 contraction indices at a time.  XT / YT: the source is contiguous in its first index (r or c)
+// acc[r][c] += sum_{m < 64} X(r, m) Y(c, m) on v_mfma_f64_16x16x4_f64 into the accumulator layout of tile_mma.h
+// (zero_acc, each); unlike the staging there, the operands come from the callers' lambdas and go through LDS 16
+// contraction indices at a time, index-major with stride 17.  XT / YT: the source is contiguous in its first index (r or c)
 // rather than in m; it only picks which threads fetch which element.
 template <bool XT, bool YT, class FX, class FY>
 static __device__ __forceinline__ void cc_mma64(double4_t (&acc)[2][2], double (*Xs)[17], double (*Ys)[17], FX fx, FY fy) {
@@ -71,27 +74,6 @@ static __device__ __forceinline__ void cc_mma64(double4_t (&acc)[2][2], double (
   }
 }
 
-static __device__ __forceinline__ void cc_zero(double4_t (&acc)[2][2]) {
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = (double4_t){0.0, 0.0, 0.0, 0.0};
-}
-
-// f(r, c, value) for every element of the accumulators this thread holds
-template <class F>
-static __device__ __forceinline__ void cc_each(const double4_t (&acc)[2][2], F f) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 15, lk = lane >> 4;
-  const int rb = 32 * (wave >> 1), cb = 32 * (wave & 1);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) f(rb + 16 * ti + lk + 4 * reg, cb + 16 * tj + li, acc[ti][tj][reg]);
-}
-
 // Tile column k of the factor, block i - k for tile row i >= k.  Every block forms D = C_kk - sum_{m<k} L_km L_km^T
 // and factors it in LDS (pcg_coarse_tile_factor: L_kk in the lower triangle, W_kk^T = L_kk^-T in the strict upper
 // one, dinv = the diagonal of W_kk); block 0 stores L_kk and W_kk, block i - k stores
@@ -109,8 +91,8 @@ __global__ __launch_bounds__(256) void k_pcg_coarse_column(const double* __restr
   double* Li = L + (size_t)64 * i * N;
   if (tid == 0) bad = 0;
   double4_t accD[2][2], accT[2][2];
-  cc_zero(accD);
-  cc_zero(accT);
+  zero_acc(accD);
+  zero_acc(accT);
   for (uint32_t m = 0; m < k; ++m) {
     auto fk = [&](int r, int t) { return Lk[(size_t)r * N + 64 * m + t]; };
     cc_mma64<false, false>(accD, Xs, Ys, fk, fk);
@@ -119,7 +101,7 @@ __global__ __launch_bounds__(256) void k_pcg_coarse_column(const double* __restr
       cc_mma64<false, false>(accT, Xs, Ys, fi, fk);
     }
   }
-  cc_each(accD, [&](int r, int c, double v) { d[r][c] = C[(size_t)(64 * k + r) * N + 64 * k + c] - v; });
+  each(accD, [&](int r, int c, double v) { d[r][c] = C[(size_t)(64 * k + r) * N + 64 * k + c] - v; });
   // right-looking Cholesky of the lower triangle: thread (r, cq) owns the columns c = cq (mod 4) of row r
   const uint32_t r = tid & 63u, cq = tid >> 6;
   for (uint32_t j = 0; j < 64; ++j) {
@@ -156,14 +138,14 @@ __global__ __launch_bounds__(256) void k_pcg_coarse_column(const double* __restr
     return;
   }
   // T = C_ik - accT goes through the tile's own place in L
-  cc_each(accT, [&](int rr, int c, double v) { Li[(size_t)rr * N + 64 * k + c] = C[(size_t)(64 * i + rr) * N + 64 * k + c] - v; });
+  each(accT, [&](int rr, int c, double v) { Li[(size_t)rr * N + 64 * k + c] = C[(size_t)(64 * i + rr) * N + 64 * k + c] - v; });
   __threadfence_block();
   double4_t acc[2][2];
-  cc_zero(acc);
+  zero_acc(acc);
   auto fT = [&](int rr, int t) { return Li[(size_t)rr * N + 64 * k + t]; };
   auto fW = [&](int c, int t) { return t < c ? d[t][c] : t == c ? dinv[c] : 0.0; };
   cc_mma64<false, false>(acc, Xs, Ys, fT, fW);
-  cc_each(acc, [&](int rr, int c, double v) { Li[(size_t)rr * N + 64 * k + c] = v; });
+  each(acc, [&](int rr, int c, double v) { Li[(size_t)rr * N + 64 * k + c] = v; });
 }
 
 // W = L^-1 below the diagonal tiles, block k for tile column k: for i = k + 1 ..: W_ik = - W_ii sum_{k<=m<i} L_im W_mk
@@ -174,20 +156,20 @@ __global__ __launch_bounds__(256) void k_pcg_coarse_trinv(const double* __restri
   const size_t N = ncp;
   for (uint32_t i = k + 1; i < nct; ++i) {
     double4_t acc[2][2];
-    cc_zero(acc);
+    zero_acc(acc);
     for (uint32_t m = k; m < i; ++m) {
       auto fL = [&](int r, int t) { return L[(size_t)(64 * i + r) * N + 64 * m + t]; };
       auto fW = [&](int c, int t) { return W[(size_t)(64 * m + t) * N + 64 * k + c]; };
       cc_mma64<false, true>(acc, Xs, Ys, fL, fW);
     }
     double* Wik = W + (size_t)64 * i * N + 64 * k;
-    cc_each(acc, [&](int r, int c, double v) { Wik[(size_t)r * N + c] = v; });
+    each(acc, [&](int r, int c, double v) { Wik[(size_t)r * N + c] = v; });
     __threadfence_block();
-    cc_zero(acc);
+    zero_acc(acc);
     auto fD = [&](int r, int t) { return W[(size_t)(64 * i + r) * N + 64 * i + t]; };
     auto fT = [&](int c, int t) { return Wik[(size_t)t * N + c]; };
     cc_mma64<false, true>(acc, Xs, Ys, fD, fT);
-    cc_each(acc, [&](int r, int c, double v) { Wik[(size_t)r * N + c] = -v; });
+    each(acc, [&](int r, int c, double v) { Wik[(size_t)r * N + c] = -v; });
     __threadfence_block();
   }
 }
@@ -204,13 +186,13 @@ __global__ __launch_bounds__(256) void k_pcg_coarse_ltl(const double* __restrict
   const uint32_t j = rest;
   const size_t N = ncp;
   double4_t acc[2][2];
-  cc_zero(acc);
+  zero_acc(acc);
   for (uint32_t m = i; m < nct; ++m) {
     auto fI = [&](int r, int t) { return W[(size_t)(64 * m + t) * N + 64 * i + r]; };
     auto fJ = [&](int c, int t) { return W[(size_t)(64 * m + t) * N + 64 * j + c]; };
     cc_mma64<true, true>(acc, Xs, Ys, fI, fJ);
   }
-  cc_each(acc, [&](int r, int c, double v) { o[r][c] = v; });
+  each(acc, [&](int r, int c, double v) { o[r][c] = v; });
   __syncthreads();
   for (uint32_t e = threadIdx.x; e < 4096; e += 256) {
     const uint32_t r = e >> 6, c = e & 63u;

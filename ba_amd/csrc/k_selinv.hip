@@ -11,11 +11,10 @@
 // written: L_KJ from A, L_JJ^-T (linvT) and the pivot signs D from invdiag.  k_selinv_diag reads the
 // Sigma_KJ its column's k_selinv_col launch wrote, so it is a second launch.
 //
-// The tile products run on v_mfma_f64_16x16x4_f64 with the 4-wave 2x2 layout of update_tile: each wave
-// owns a 32x32 quarter of the output tile.  The operands are staged through LDS 32 k-rows at a time,
-// k-major ([k][index]); the next chunk is fetched into registers while the matrix cores work on this one.
+// The tile products run on v_mfma_f64_16x16x4_f64 with the staging and the 4-wave 2x2 layout of tile_mma.h.
 #include "engine.h"
 #include "selinv.h"
+#include "tile_mma.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,95 +22,20 @@
 
 namespace bae {
 
+using namespace tile64;
+
 namespace {
-
-const int TB = 64;         // tile size
-const int KCH = 32;        // k-rows per LDS chunk
-const int LDS_LD = TB + 4; // LDS row stride (doubles)
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-// one chunk of 32 k-rows of both operands, k-major
-struct SelLds {
-  double X[KCH][LDS_LD];
-  double Y[KCH][LDS_LD];
-};
 
 __device__ __forceinline__ const double* slot_tile(const double* store, const uint32_t* slot, uint32_t nt, uint32_t i,
                                                    uint32_t k) {
   return store + (size_t)slot[(size_t)i * nt + k] * (TB * TB);
 }
 
-// Thread t moves 4 double2 of a 32 x 64 chunk: element pair e = 2 t + 512 s (s < 4).
-//  k-major source (rows = k, stride `ld`, 64 contiguous indices):   k = e / 64, index = e % 64
-//  index-major source (rows = index, 64 contiguous k):              index = e / 32, k = e % 32
-struct Chunk {
-  double2 v[4];
-};
-__device__ __forceinline__ void load_kmajor(Chunk& c, const double* src, size_t ld, int k0) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    c.v[s] = *reinterpret_cast<const double2*>(src + (size_t)(k0 + e / TB) * ld + (e % TB));
-  }
-}
-__device__ __forceinline__ void load_imajor(Chunk& c, const double* src, size_t ld, int k0) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    c.v[s] = *reinterpret_cast<const double2*>(src + (size_t)(e / KCH) * ld + k0 + (e % KCH));
-  }
-}
-__device__ __forceinline__ void store_kmajor(const Chunk& c, double (*Z)[LDS_LD]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    Z[e / TB][e % TB] = c.v[s].x;
-    Z[e / TB][e % TB + 1] = c.v[s].y;
-  }
-}
-__device__ __forceinline__ void store_imajor(const Chunk& c, double (*Z)[LDS_LD]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int e = 2 * tid + 512 * s;
-    Z[e % KCH][e / KCH] = c.v[s].x;
-    Z[e % KCH + 1][e / KCH] = c.v[s].y;
-  }
-}
-
-__device__ __forceinline__ void zero_acc(double4_t (&acc)[2][2]) {
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = (double4_t){0.0, 0.0, 0.0, 0.0};
-}
-
-// acc += X^T-chunk (k-major A operand) x Y-chunk (k-major B operand), 32 k
-__device__ __forceinline__ void mma_chunk(double4_t (&acc)[2][2], const SelLds& s) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 15, lk = lane >> 4;
-  const int rb = 32 * (wave >> 1), cb = 32 * (wave & 1);
-#pragma unroll
-  for (int ks = 0; ks < KCH / 4; ++ks) {
-    const double a0 = s.X[4 * ks + lk][rb + li];
-    const double a1 = s.X[4 * ks + lk][rb + 16 + li];
-    const double b0 = s.Y[4 * ks + lk][cb + li];
-    const double b1 = s.Y[4 * ks + lk][cb + 16 + li];
-    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-  }
-}
-
 // The K loop of both kernels: acc = sum over the tiles K of R_J (2 chunks each) of  A_K x L_KJ, where the
 // A operand is Sigma_IK (COL, I >= K: index-major slot (I, K); I < K: k-major slot (K, I)) or Sigma_KJ^T
 // (DIAG: k-major slot (K, J)).  B = L_KJ from A (k-major).
 template <bool DIAG>
-__device__ __forceinline__ void k_loop(double4_t (&acc)[2][2], SelLds& s, uint32_t I, uint32_t J, const uint32_t* R,
+__device__ __forceinline__ void k_loop(double4_t (&acc)[2][2], Lds& s, uint32_t I, uint32_t J, const uint32_t* R,
                                        uint32_t m, const double* __restrict__ A, size_t ld,
                                        const uint32_t* __restrict__ slot, uint32_t nt,
                                        const double* __restrict__ store) {
@@ -148,7 +72,7 @@ __device__ __forceinline__ void k_loop(double4_t (&acc)[2][2], SelLds& s, uint32
 // Epilogue product: out = M x L_JJ^-1 with M[r][x] = sgn * T[r][x] (+ L_JJ^-T[r][x] d_x when DIAG), T in acc.
 // B[x][c] = (L_JJ^-1)[x][c] = linvT[c][x]: an index-major source.
 template <bool DIAG>
-__device__ __forceinline__ void epilogue(double4_t (&out)[2][2], const double4_t (&acc)[2][2], SelLds& s,
+__device__ __forceinline__ void epilogue(double4_t (&out)[2][2], const double4_t (&acc)[2][2], Lds& s,
                                          const double* __restrict__ G, const double* __restrict__ dsgn) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, lk = lane >> 4;
@@ -186,21 +110,6 @@ __device__ __forceinline__ void epilogue(double4_t (&out)[2][2], const double4_t
   }
 }
 
-__device__ __forceinline__ void store_tile(double* __restrict__ dst, const double4_t (&v)[2][2]) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 15, lk = lane >> 4;
-  const int rb = 32 * (wave >> 1), cb = 32 * (wave & 1);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int r = rb + 16 * ti + lk + 4 * reg, c = cb + 16 * tj + li;
-        dst[(size_t)r * TB + c] = v[ti][tj][reg];
-      }
-}
-
 }  // namespace
 
 // items: (J, I) pairs of one level; Sigma_IJ = -(sum_K Sigma_IK L_KJ) L_JJ^-1
@@ -209,7 +118,7 @@ k_selinv_col(const uint2* __restrict__ items, const uint32_t* __restrict__ col_p
              const uint32_t* __restrict__ col_rows, const double* __restrict__ A, uint32_t ld,
              const double* __restrict__ linvT, const uint32_t* __restrict__ slot, uint32_t nt,
              double* __restrict__ store) {
-  __shared__ SelLds s;
+  __shared__ Lds s;
   const uint2 it = items[blockIdx.x];
   const uint32_t J = it.x, I = it.y;
   const uint32_t* R = col_rows + col_ptr[J];
@@ -218,7 +127,7 @@ k_selinv_col(const uint2* __restrict__ items, const uint32_t* __restrict__ col_p
   zero_acc(acc);
   k_loop<false>(acc, s, I, J, R, m, A, ld, slot, nt, store);
   epilogue<false>(out, acc, s, linvT + (size_t)J * TB * TB, nullptr);
-  store_tile(store + (size_t)slot[(size_t)I * nt + J] * TB * TB, out);
+  store_tile(store + (size_t)slot[(size_t)I * nt + J] * TB * TB, TB, out);
 }
 
 // cols: the columns J of one level; Sigma_JJ = (L_JJ^-T D_J - sum_K Sigma_KJ^T L_KJ) L_JJ^-1
@@ -227,7 +136,7 @@ k_selinv_diag(const uint32_t* __restrict__ cols, const uint32_t* __restrict__ co
               const uint32_t* __restrict__ col_rows, const double* __restrict__ A, uint32_t ld,
               const double* __restrict__ linvT, const double* __restrict__ dsgn,
               const uint32_t* __restrict__ slot, uint32_t nt, double* __restrict__ store) {
-  __shared__ SelLds s;
+  __shared__ Lds s;
   const uint32_t J = cols[blockIdx.x];
   const uint32_t* R = col_rows + col_ptr[J];
   const uint32_t m = col_ptr[J + 1] - col_ptr[J];
@@ -235,7 +144,7 @@ k_selinv_diag(const uint32_t* __restrict__ cols, const uint32_t* __restrict__ co
   zero_acc(acc);
   k_loop<true>(acc, s, J, J, R, m, A, ld, slot, nt, store);
   epilogue<true>(out, acc, s, linvT + (size_t)J * TB * TB, dsgn + (size_t)J * TB);
-  store_tile(store + (size_t)slot[(size_t)J * nt + J] * TB * TB, out);
+  store_tile(store + (size_t)slot[(size_t)J * nt + J] * TB * TB, TB, out);
 }
 
 // Sigma element (r, c), either half; NaN outside the pattern
@@ -440,28 +349,22 @@ __global__ void __launch_bounds__(256) k_selinv_lm_bare(LmArgs g, uint32_t L, do
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-static double elapsed_ms(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
-}
-
 int marginals_compute(Engine* e) {
   const Structure& st = e->st;
   if (e->sig_valid) return 0;
-  const uint32_t nt = st.ld / TB;
-  if (!e->invdiag.p || !e->nzL_valid || e->nzL_host.size() != (size_t)nt * nt)
-    return e->fail_msg("marginals: no factor of the last ba_hip_solve_gn");
+  uint32_t nt;
+  const double *dsgn, *linvT;
+  int rc;
+  if ((rc = kept_factor(e, "marginals", &nt, &dsgn, &linvT))) return rc;
   if (e->sig_plan_version != e->nzL_version) {
     build_selinv_plan(e->nzL_host, nt, e->sig_plan);
     const SelinvPlan& p = e->sig_plan;
-    auto up = [&](DBuf<uint32_t>& b, const std::vector<uint32_t>& v) -> int {
-      BAE_HIP(b.alloc(std::max<size_t>(v.size(), 1)));
-      if (!v.empty()) BAE_HIP(hipMemcpy(b.p, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      return 0;
-    };
-    int rc;
-    if ((rc = up(e->sig_slot, p.slot)) || (rc = up(e->sig_col_ptr, p.col_ptr)) || (rc = up(e->sig_col_rows, p.col_rows)) ||
-        (rc = up(e->sig_level_cols, p.level_cols)) || (rc = up(e->sig_items, p.items)))
+    // the tables are members of e->sig_plan and the kernels that read them run on the same stream
+    if ((rc = upload_async(e, e->sig_slot, p.slot.data(), p.slot.size())) ||
+        (rc = upload_async(e, e->sig_col_ptr, p.col_ptr.data(), p.col_ptr.size())) ||
+        (rc = upload_async(e, e->sig_col_rows, p.col_rows.data(), p.col_rows.size())) ||
+        (rc = upload_async(e, e->sig_level_cols, p.level_cols.data(), p.level_cols.size())) ||
+        (rc = upload_async(e, e->sig_items, p.items.data(), p.items.size())))
       return rc;
     e->sig_plan_version = e->nzL_version;
   }
@@ -478,12 +381,9 @@ int marginals_compute(Engine* e) {
       return e->fail_msg(msg);
     }
   }
-  const double* dsgn = e->invdiag.p;
-  const double* linvT = dsgn + (size_t)nt * TB;
-  hipEvent_t t0, t1;
-  BAE_HIP(hipEventCreate(&t0));
-  BAE_HIP(hipEventCreate(&t1));
-  (void)hipEventRecord(t0, e->stream);
+  Events<2> ev;
+  BAE_HIP(ev.create());
+  (void)ev.record(0, e->stream);
   const uint32_t levels = (uint32_t)p.level_ptr.size() - 1;
   for (uint32_t v = 0; v < levels; ++v) {
     const uint32_t i0 = p.item_ptr[v], i1 = p.item_ptr[v + 1];
@@ -497,12 +397,10 @@ int marginals_compute(Engine* e) {
                        (const uint32_t*)e->sig_col_ptr.p, (const uint32_t*)e->sig_col_rows.p, (const double*)e->A.p,
                        st.ld, linvT, dsgn, (const uint32_t*)e->sig_slot.p, nt, e->sig.p);
   }
-  (void)hipEventRecord(t1, e->stream);
+  (void)ev.record(1, e->stream);
   const hipError_t lerr = hipGetLastError();
-  const hipError_t serr = hipEventSynchronize(t1);
-  e->mstats.selinv_ms = elapsed_ms(t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
+  const hipError_t serr = hipEventSynchronize(ev[1]);
+  e->mstats.selinv_ms = ev.ms(0, 1);
   if (lerr != hipSuccess) return e->fail(lerr, "k_selinv launch");
   if (serr != hipSuccess) return e->fail(serr, "k_selinv");
   e->mstats.tile_products = p.products;
@@ -527,12 +425,11 @@ int marginals_gather(Engine* e, uint32_t n, const std::vector<uint32_t>& ra, con
           return e->fail_msg("marginals: the requested block lies outside the factor's tile pattern (the two poses share "
                              "no landmark and no pose-pose residual, and no fill couples them)");
       }
-  DBuf<uint32_t> d;
-  DBuf<double> o;
+  TBuf<uint32_t> d;
+  TBuf<double> o;
   BAE_HIP(d.alloc(2 * (size_t)n));
   const size_t cnt = (size_t)n * Da * Db;
-  if (o.alloc(cnt) != hipSuccess) { d.release(); return e->fail_msg("marginals: output allocation failed"); }
-  int rc = 0;
+  if (o.alloc(cnt) != hipSuccess) return e->fail_msg("marginals: output allocation failed");
   hipError_t err = hipMemcpy(d.p, ra.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(d.p + n, rb.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (err == hipSuccess) {
@@ -543,10 +440,7 @@ int marginals_gather(Engine* e, uint32_t n, const std::vector<uint32_t>& ra, con
   }
   if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
   if (err == hipSuccess) err = hipMemcpy(out, o.p, cnt * sizeof(double), hipMemcpyDeviceToHost);
-  if (err != hipSuccess) rc = e->fail(err, "k_selinv_gather");
-  d.release();
-  o.release();
-  return rc;
+  return err == hipSuccess ? 0 : e->fail(err, "k_selinv_gather");
 }
 
 int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out) {
@@ -560,24 +454,23 @@ int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out)
   g.nt = st.ld / TB; g.lrow_base = st.lrow_base; g.np = st.np; g.D = e->pose_dim; g.K = (int)st.K;
   const size_t cnt = (size_t)n * LM * LM;
   if (cnt == 0) return 0;
-  DBuf<uint32_t> d;
-  DBuf<double> o;
+  TBuf<uint32_t> d;
+  TBuf<double> o;
   if (o.alloc(cnt) != hipSuccess) return e->fail_msg("marginals: output allocation failed");
   hipError_t err = hipSuccess;
-  hipEvent_t t0, t1;
-  (void)hipEventCreate(&t0);
-  (void)hipEventCreate(&t1);
+  Events<2> ev;
+  (void)ev.create();
   if (ids) {
     err = d.alloc(n);
     if (err == hipSuccess) err = hipMemcpy(d.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice);
-    (void)hipEventRecord(t0, e->stream);
+    (void)ev.record(0, e->stream);
     if (err == hipSuccess) {
       if (LM == 1) hipLaunchKernelGGL(k_selinv_lm_ids<1>, dim3((n + 3) / 4), dim3(256), 0, e->stream, g, n, (const uint32_t*)d.p, o.p);
       else hipLaunchKernelGGL(k_selinv_lm_ids<3>, dim3((n + 3) / 4), dim3(256), 0, e->stream, g, n, (const uint32_t*)d.p, o.p);
       err = hipGetLastError();
     }
   } else {
-    (void)hipEventRecord(t0, e->stream);
+    (void)ev.record(0, e->stream);
     if (st.n_chunks) {
       if (LM == 1) hipLaunchKernelGGL(k_selinv_lm_ranges<1>, dim3((st.n_chunks + 3) / 4), dim3(256), 0, e->stream, g, st.n_chunks, (const uint2*)e->wave_rng.p, o.p);
       else hipLaunchKernelGGL(k_selinv_lm_ranges<3>, dim3((st.n_chunks + 3) / 4), dim3(256), 0, e->stream, g, st.n_chunks, (const uint2*)e->wave_rng.p, o.p);
@@ -586,16 +479,12 @@ int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out)
     else hipLaunchKernelGGL(k_selinv_lm_bare<3>, dim3((st.L + 3) / 4), dim3(256), 0, e->stream, g, st.L, o.p);
     err = hipGetLastError();
   }
-  (void)hipEventRecord(t1, e->stream);
-  if (err == hipSuccess) err = hipEventSynchronize(t1);
+  (void)ev.record(1, e->stream);
+  if (err == hipSuccess) err = hipEventSynchronize(ev[1]);
   if (err == hipSuccess) {
-    e->mstats.landmark_ms = elapsed_ms(t0, t1);
+    e->mstats.landmark_ms = ev.ms(0, 1);
     err = hipMemcpy(out, o.p, cnt * sizeof(double), hipMemcpyDeviceToHost);
   }
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  d.release();
-  o.release();
   return err == hipSuccess ? 0 : e->fail(err, "k_selinv_lm");
 }
 

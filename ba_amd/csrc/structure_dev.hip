@@ -325,14 +325,6 @@ int bits_for(unsigned long long maxval) {
   while ((1ull << b) <= maxval) ++b;
   return b;
 }
-// temporary of build_lists_device: released on every exit path (early error returns included)
-template <typename T>
-struct TBuf : DBuf<T> {
-  TBuf() = default;
-  TBuf(const TBuf&) = delete;
-  TBuf& operator=(const TBuf&) = delete;
-  ~TBuf() { this->release(); }
-};
 
 // 64-bit sum of 32-bit counts (block partials, one 64-bit atomic per block)
 __global__ void __launch_bounds__(256) k_sum_counts64(const uint32_t* __restrict__ cnt, size_t n,

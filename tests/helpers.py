@@ -6,6 +6,38 @@ import numpy as np
 
 from ba_amd import scene
 
+u32p = ctypes.POINTER(ctypes.c_uint32)
+dp = ctypes.POINTER(ctypes.c_double)
+u8p = ctypes.POINTER(ctypes.c_uint8)
+
+
+def _p(a, t):
+    return a.ctypes.data_as(t)
+
+
+def _add_pose_pose(eng, sc, P, seed=3):
+    """unary priors on every 7th pose and binary odometry between neighbours (every 3rd pair)"""
+    rng = np.random.default_rng(seed)
+    un = np.arange(0, P, 7, dtype=np.uint32)
+    cov = np.ascontiguousarray(np.tile(np.diag([1e2] * 3 + [1e3] * 3).reshape(1, 36), (len(un), 1)))
+    prior = np.ascontiguousarray(sc.gt_poses[un])
+    rot = np.ones(len(un), dtype=np.uint8)
+    eng._chk(eng.L.ba_hip_set_unary_residuals(eng.h, len(un), _p(un, u32p), _p(prior, dp), _p(cov, dp), _p(rot, u8p)))
+    p1 = np.arange(0, P - 1, 3, dtype=np.uint32)
+    p2 = p1 + 1
+    nb = len(p1)
+    t12 = np.zeros((nb, 7))
+    for k, (a, b) in enumerate(zip(p1, p2)):
+        Ra = scene.quat_to_rot(sc.gt_poses[a, 3:7])
+        t12[k, :3] = Ra.T @ (sc.gt_poses[b, :3] - sc.gt_poses[a, :3]) + 0.01 * rng.normal(size=3)
+        t12[k, 3:7] = scene.quat_mul(sc.gt_poses[a, 3:7] * np.array([-1, -1, -1, 1]), sc.gt_poses[b, 3:7])
+    ci = np.ascontiguousarray(np.tile(np.diag([50.0] * 6).reshape(1, 36), (nb, 1)))
+    cs = np.ascontiguousarray(np.tile(np.diag([np.sqrt(50.0)] * 6).reshape(1, 36), (nb, 1)))
+    w = np.ones(nb)
+    rot = np.ones(nb, dtype=np.uint8)
+    eng._chk(eng.L.ba_hip_set_binary_residuals(eng.h, nb, _p(p1, u32p), _p(p2, u32p), _p(t12, dp), _p(ci, dp),
+                                               _p(cs, dp), _p(w, dp), _p(rot, u8p)))
+
 
 def hostcheck_lib():
     """libba_hostcheck.so (ba_amd/csrc/hostcheck.cpp: host restatements of the device code), built on first use"""

@@ -3,23 +3,15 @@ on the MI355X, checked by the identity that makes the two halves exact: the syst
 the prior", linearised at the same state, is the full system with M and L eliminated.  Engine F holds the full
 problem; engine R the same state with the absorbed residuals removed, M and L inactive and the prior added.
 Tolerance: max(1e-9, 4.5 eps cond(S)) relative."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ba_amd import hipapi, scene
+from helpers import _p, dp, u32p, u8p
 
 pytestmark = pytest.mark.gpu
 
-u32p = C.POINTER(C.c_uint32)
-dp = C.POINTER(C.c_double)
-u8p = C.POINTER(C.c_uint8)
 EPS = np.finfo(np.float64).eps
-
-
-def _p(a, t):
-    return a.ctypes.data_as(t)
 
 
 class Prob:

@@ -2,47 +2,15 @@
 pose-pair, calibration and landmark blocks against dense inverses of the reduced system S (read with
 keep_reduced_system) and of the full poses + landmarks system H, assembled from the engine's Jacobians.
 Tolerance per block: max(1e-9, 4.5 eps cond(S)) relative."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from ba_amd import hipapi, scene
+from helpers import _add_pose_pose
 
 pytestmark = pytest.mark.gpu
 
-u32p = C.POINTER(C.c_uint32)
-dp = C.POINTER(C.c_double)
-u8p = C.POINTER(C.c_uint8)
 EPS = np.finfo(np.float64).eps
-
-
-def _p(a, t):
-    return a.ctypes.data_as(t)
-
-
-def _add_pose_pose(eng, sc, P, seed=3):
-    """unary priors on every 7th pose and binary odometry between neighbours (every 3rd pair)"""
-    rng = np.random.default_rng(seed)
-    un = np.arange(0, P, 7, dtype=np.uint32)
-    cov = np.ascontiguousarray(np.tile(np.diag([1e2] * 3 + [1e3] * 3).reshape(1, 36), (len(un), 1)))
-    prior = np.ascontiguousarray(sc.gt_poses[un])
-    rot = np.ones(len(un), dtype=np.uint8)
-    eng._chk(eng.L.ba_hip_set_unary_residuals(eng.h, len(un), _p(un, u32p), _p(prior, dp), _p(cov, dp), _p(rot, u8p)))
-    p1 = np.arange(0, P - 1, 3, dtype=np.uint32)
-    p2 = p1 + 1
-    nb = len(p1)
-    t12 = np.zeros((nb, 7))
-    for k, (a, b) in enumerate(zip(p1, p2)):
-        Ra = scene.quat_to_rot(sc.gt_poses[a, 3:7])
-        t12[k, :3] = Ra.T @ (sc.gt_poses[b, :3] - sc.gt_poses[a, :3]) + 0.01 * rng.normal(size=3)
-        t12[k, 3:7] = scene.quat_mul(sc.gt_poses[a, 3:7] * np.array([-1, -1, -1, 1]), sc.gt_poses[b, 3:7])
-    ci = np.ascontiguousarray(np.tile(np.diag([50.0] * 6).reshape(1, 36), (nb, 1)))
-    cs = np.ascontiguousarray(np.tile(np.diag([np.sqrt(50.0)] * 6).reshape(1, 36), (nb, 1)))
-    w = np.ones(nb)
-    rot = np.ones(nb, dtype=np.uint8)
-    eng._chk(eng.L.ba_hip_set_binary_residuals(eng.h, nb, _p(p1, u32p), _p(p2, u32p), _p(t12, dp), _p(ci, dp),
-                                               _p(cs, dp), _p(w, dp), _p(rot, u8p)))
 
 
 class Setup:
