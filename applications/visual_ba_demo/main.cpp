@@ -28,6 +28,10 @@
 //                                           GetLandmarkCovariance: selected inverse of the reduced system), then
 //                                           the norm of the cross covariance between the first active and the last
 //                                           pose and the time of the joint call (GetJointPoseCovariance)
+//   visual_ba_demo --leverages              after the solve: the median and the smallest redundancy number
+//                                           2 - tr H_aa of the projection residuals (GetProjectionLeverages: hat
+//                                           blocks from the selected inverse) and the five residuals with the
+//                                           largest studentised value r^T (I - H_aa)^-1 r, r the whitened residual
 #include <ba/BundleAdjuster.h>
 
 #include <algorithm>
@@ -36,11 +40,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <random>
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -277,6 +282,33 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
                 std::sqrt(cross), std::sqrt(cross / diag), kPoses - 1, joint_ms);
     ok = ok && std::isfinite(c(0, 0)) && c(0, 0) > 0 && sl[sl.size() / 2] > 0;
   }
+  if (shard.leverages) {
+    const uint32_t nres = adjuster.GetNumProjResiduals();
+    std::vector<double> h, red(nres);
+    if (!adjuster.GetProjectionLeverages({}, h) || h.size() != 4 * (size_t)nres) { std::printf("leverages unavailable\n"); return 2; }
+    for (uint32_t a = 0; a < nres; ++a) red[a] = 2.0 - (h[4 * (size_t)a] + h[4 * (size_t)a + 3]);
+    // studentised residuals on the host: the whitened residual against the post-fit covariance I - H_aa
+    std::vector<std::pair<double, uint32_t>> stud(nres);
+    for (uint32_t a = 0; a < nres; ++a) {
+      const auto& r = adjuster.GetProjectionResidual(a);
+      const double sw = std::sqrt(r.weight), r0 = sw * r.residual[0], r1 = sw * r.residual[1];
+      const double c00 = 1.0 - h[4 * (size_t)a], c01 = -h[4 * (size_t)a + 1], c11 = 1.0 - h[4 * (size_t)a + 3];
+      const double det = c00 * c11 - c01 * c01;
+      stud[a] = {det > 1e-12 ? (c11 * r0 * r0 - 2.0 * c01 * r0 * r1 + c00 * r1 * r1) / det : 0.0, a};
+    }
+    std::vector<double> sorted(red);
+    std::nth_element(sorted.begin(), sorted.begin() + sorted.size() / 2, sorted.end());
+    std::printf("redundancy of %u projection residuals: median %.4f, minimum %.4f\n", nres, sorted[sorted.size() / 2],
+                *std::min_element(red.begin(), red.end()));
+    const size_t top = std::min<size_t>(5, stud.size());
+    std::partial_sort(stud.begin(), stud.begin() + top, stud.end(), std::greater<std::pair<double, uint32_t>>());
+    for (size_t q = 0; q < top; ++q) {
+      const auto& r = adjuster.GetProjectionResidual(stud[q].second);
+      std::printf("residual %u (pose %u, landmark %u): studentised %.3f, redundancy %.4f\n", stud[q].second, r.x_meas_id,
+                  r.landmark_id, stud[q].first, red[stud[q].second]);
+    }
+    for (double v : red) ok = ok && v > -1e-9 && v < 2.0 + 1e-9;
+  }
   return ok ? 0 : 1;
 }
 
@@ -287,6 +319,7 @@ int main(int argc, char** argv) {
   Shard shard;
   for (int i = 1; i < argc; i += 2) {
     if (std::strcmp(argv[i], "--covariances") == 0) { shard.covariances = true; --i; continue; }
+    if (std::strcmp(argv[i], "--leverages") == 0) { shard.leverages = true; --i; continue; }
     if (std::strcmp(argv[i], "--pcg") == 0) {
       shard.pcg = true;
       if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.pcg_tol = std::atof(argv[i + 1]);

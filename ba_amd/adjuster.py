@@ -71,6 +71,7 @@ SYMBOLS = [
     "ba_adjuster_get_last_calib_step", "ba_adjuster_get_calibration_marginals", "ba_adjuster_get_camera_params",
     "ba_adjuster_add_camera_fov", "ba_adjuster_get_camera_fov",
     "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
+    "ba_adjuster_get_projection_leverage", "ba_adjuster_get_projection_redundancy",
     "ba_adjuster_get_joint_pose_covariance",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
@@ -448,6 +449,23 @@ class BundleAdjuster:
         if k != m:
             raise RuntimeError("landmark covariance of landmark %d unavailable (see stderr)" % landmark_id)
         return c.reshape(m, m)
+
+    def projection_leverage(self, residual_id):
+        """GetProjectionLeverage: the 2 x 2 hat block of an accepted projection residual; raises when unavailable."""
+        h = np.zeros(4)
+        self.L.ba_adjuster_get_projection_leverage.restype = C.c_uint32
+        k = self.L.ba_adjuster_get_projection_leverage(self.h, C.c_uint32(int(residual_id) & 0xFFFFFFFF),
+                                                       h.ctypes.data_as(C.POINTER(C.c_double)))
+        if k != 2:
+            raise RuntimeError("leverage of projection residual %d unavailable (see stderr)" % residual_id)
+        return h.reshape(2, 2)
+
+    def projection_redundancy(self, residual_id):
+        """GetProjectionRedundancy: 2 - trace of the hat block; raises when unavailable."""
+        r = C.c_double()
+        if self.L.ba_adjuster_get_projection_redundancy(self.h, C.c_uint32(int(residual_id) & 0xFFFFFFFF), C.byref(r)):
+            raise RuntimeError("redundancy of projection residual %d unavailable (see stderr)" % residual_id)
+        return r.value
 
     def camera_params(self, cam_id=0):
         """rig()->cameras_[cam_id]->GetParams()"""

@@ -251,7 +251,7 @@ struct Impl : Iface {
   }
   uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) override {
     const ba::MatX m = kind == 0 ? ba.GetPoseCovariance(a) : kind == 1 ? ba.GetPoseCrossCovariance(a, b)
-                                                                        : ba.GetLandmarkCovariance(a);
+                       : kind == 2 ? ba.GetLandmarkCovariance(a) : ba.GetProjectionLeverage(a);
     for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
     return (uint32_t)m.rows();
   }
@@ -401,6 +401,15 @@ uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, 
 }
 uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov) {
   return a->p->covariance(2, landmark_id, 0, cov);
+}
+uint32_t ba_adjuster_get_projection_leverage(ba_adjuster* a, uint32_t residual_id, double* h4) {
+  return a->p->covariance(3, residual_id, 0, h4);
+}
+int ba_adjuster_get_projection_redundancy(ba_adjuster* a, uint32_t residual_id, double* redundancy) {
+  double h[4];
+  if (!redundancy || a->p->covariance(3, residual_id, 0, h) != 2) return 1;
+  *redundancy = 2.0 - (h[0] + h[3]);
+  return 0;
 }
 uint32_t ba_adjuster_get_joint_pose_covariance(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids,
                                                int include_calibration, double* cov) {

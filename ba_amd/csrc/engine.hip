@@ -940,6 +940,7 @@ int ba_hip_finalize(ba_hip_engine* h) {
   e->group_ptr.clear(); e->group_adj.clear();
   e->order_stats = ba_hip_ordering_stats();
   e->lin_valid = false;
+  e->lev_pos.clear();
   e->mask_host.assign(pb.num_poses, 0);
   int rc = build_structure(e);
   if (rc) return rc;
@@ -1523,6 +1524,30 @@ int ba_hip_get_landmark_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* 
         return -1;
       }
   return marginals_landmarks(e, n, lm_ids, out);
+}
+// ---- leverages of projection residuals (k_lever.hip) ----
+int ba_hip_get_projection_leverages(ba_hip_engine* h, uint32_t n, const uint32_t* residual_ids, double* out) {
+  ENG(h);
+  static const char* what = "ba_hip_get_projection_leverages";
+  const std::string m = std::string(what) + ": ";
+  if (e->lm_dim == 0) return e->fail_msg((m + "LmSize 0 has no projection residuals").c_str());
+  int rc;
+  if ((rc = marginals_ready(e, what, true))) return rc;
+  if (n && !out) return e->fail_msg((m + "NULL argument").c_str());
+  if (!residual_ids && n != e->st.O)
+    return e->fail_msg((m + "with NULL ids n must be the projection residual count").c_str());
+  if (residual_ids)
+    for (uint32_t i = 0; i < n; ++i)
+      if (residual_ids[i] >= e->st.O)
+        return e->fail_msg((m + "id " + std::to_string(residual_ids[i]) + " is not a projection residual (there are " +
+                            std::to_string(e->st.O) + ")").c_str());
+  return leverages_run(e, n, residual_ids, out);
+}
+int ba_hip_get_leverage_stats(ba_hip_engine* h, ba_hip_leverage_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_leverage_stats: NULL argument");
+  *out = e->lstats;
+  return 0;
 }
 // ---- joint covariance of a pose set (k_jointcov.hip): Y = L^-1 E over the reach, Sigma = Y^T D Y ----
 int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,

@@ -615,3 +615,77 @@ extern "C" int ba_hostcheck_pcg_coarse(uint32_t nt, const uint8_t* nz, const dou
     for (uint32_t c = 0; c < pl.nc; ++c) C_out[(size_t)r * pl.nc + c] = C[(size_t)r * pl.ncp + c];
   return (int)pl.nc;
 }
+
+// ---- leverages of projection residuals (lever.h) ---------------------------------------------------------
+#include "lever.h"
+
+// leverage_host on one graph: k_linearize's rows (factor rows, obs_jl, calibration rows) emulated from the
+// caller's per-residual Jacobians (jk12: two rows of six per residual, or null with K == 0) and weights, then the
+// device formula over the caller's dense Sigma (n x n, n = active poses * D + K, poses in id order).
+// out: [O][4] by residual id.  variant: lever.h.
+extern "C" int ba_hostcheck_leverages(int LM, int D, int K, uint32_t P, const uint8_t* pose_active, uint32_t L,
+                                      const uint8_t* lm_active, const uint32_t* lm_ref_pose, uint32_t O,
+                                      const uint32_t* proj_pose, const uint32_t* proj_lm, const double* jm12,
+                                      const double* jr12, const double* jl, const double* jk12, const double* w,
+                                      const double* sigma, int variant, double* out) {
+  using namespace bae;
+  if ((LM != 1 && LM != 3) || (K > 0 && !jk12) || K > 6) return -1;
+  Problem pb;
+  pb.num_cams = 1; pb.num_poses = P; pb.num_lms = L; pb.num_proj = O;
+  pb.pose_active.assign(pose_active, pose_active + P);
+  pb.lm_active.assign(lm_active, lm_active + L);
+  pb.lm_ref_pose.assign(lm_ref_pose, lm_ref_pose + L);
+  pb.lm_ref_cam.assign(L, 0);
+  pb.proj_pose.assign(proj_pose, proj_pose + O);
+  pb.proj_lm.assign(proj_lm, proj_lm + O);
+  pb.proj_cam.assign(O, 0);
+  pb.proj_z.assign(2 * (size_t)O, 0.0);
+  pb.proj_w.assign(O, 1.0);
+  Lists st;
+  std::string err;
+  if (!build_lists(pb, LM, D, st, err, nullptr, K)) return -2;
+  const uint32_t R = st.R, WO = (uint32_t)w_row_offset(LM);
+  std::vector<double> frow((size_t)st.n_rows * 6, 0.0), obs_jl((size_t)O * 2 * LM, 0.0);
+  std::vector<double> crow(K > 0 ? (2 * (size_t)O + L) * 6 : 0, 0.0);
+  for (uint32_t l = 0; l < L; ++l) {
+    const bool act = st.lm_opt[l] >= 0;
+    for (uint32_t s = st.lm_ptr[l]; s < st.lm_ptr[l + 1]; ++s) {
+      const uint32_t a = st.obs_rid[s];
+      const bool same = LM == 1 && st.obs_pose[s] == lm_ref_pose[l];
+      const double sw = std::sqrt(w[a]);
+      const double* Jl = jl + 2 * LM * (size_t)a;
+      double* rows = &frow[(size_t)s * R * 6];
+      for (int i = 0; i < 12; ++i) {
+        const double m = same ? 0.0 : jm12[12 * (size_t)a + i];
+        rows[i] = m * sw;
+        if (LM == 1) rows[12 + i] = (same ? 0.0 : jr12[12 * (size_t)a + i]) * sw;
+      }
+      if (K > 0)
+        for (int r = 0; r < 2; ++r)
+          for (int x = 0; x < K; ++x) crow[(2 * (size_t)s + r) * 6 + x] = jk12[12 * (size_t)a + 6 * r + x] * sw;
+      if (!act) continue;
+      for (int i = 0; i < 2 * LM; ++i) obs_jl[(size_t)s * 2 * LM + i] = Jl[i] * sw;
+      for (int k = 0; k < LM; ++k)
+        for (int x = 0; x < 6; ++x)
+          rows[(WO + k) * 6 + x] = (rows[x] * Jl[k] + rows[6 + x] * Jl[LM + k]) * sw;
+      if (LM == 1) {
+        double* lr = &frow[((size_t)st.lrow_base + 2 * l) * 6];
+        for (int x = 0; x < 6; ++x) lr[x] += (rows[12 + x] * Jl[0] + rows[18 + x] * Jl[1]) * sw;
+      }
+      if (K > 0)
+        for (int x = 0; x < K; ++x)
+          crow[(2 * (size_t)O + l) * 6 + x] += (crow[2 * (size_t)s * 6 + x] * Jl[0] + crow[(2 * (size_t)s + 1) * 6 + x] * Jl[1]) * sw;
+    }
+  }
+  LeverHostIn in;
+  in.LM = LM; in.D = D; in.K = K; in.L = L; in.O = O; in.np = st.np; in.n = st.n; in.lrow_base = st.lrow_base;
+  in.lm_ptr = st.lm_ptr.data(); in.obs_pose = st.obs_pose.data(); in.lm_ref_pose = lm_ref_pose;
+  in.pose_opt = st.pose_opt.data(); in.lm_opt = st.lm_opt.data();
+  in.frow = frow.data(); in.obs_jl = obs_jl.data(); in.crow = K > 0 ? crow.data() : nullptr;
+  in.sigma = sigma;
+  std::vector<double> sorted((size_t)O * 4, 0.0);
+  leverage_host(in, variant, sorted.data());
+  for (uint32_t s = 0; s < O; ++s)
+    for (int i = 0; i < 4; ++i) out[4 * (size_t)st.obs_perm[s] + i] = sorted[4 * (size_t)s + i];
+  return 0;
+}

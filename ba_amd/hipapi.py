@@ -115,6 +115,11 @@ class JointMarginalStats(C.Structure):
                 ("levels", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LeverageStats(C.Structure):
+    _fields_ = [("device_ms", C.c_double), ("block_reads", C.c_uint64), ("residuals", C.c_uint32),
+                ("landmarks", C.c_uint32)]
+
+
 JOINT_MAX_COLUMNS = 512  # BA_HIP_JOINT_MAX_COLUMNS
 
 
@@ -175,6 +180,7 @@ SYMBOLS = [
     "ba_hip_release_marginalization", "ba_hip_set_unary_scales",
     "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve", "ba_hip_tile_solve",
     "ba_hip_get_pcg_coarse_stats", "ba_hip_get_pcg_coarse",
+    "ba_hip_get_projection_leverages", "ba_hip_get_leverage_stats",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -448,6 +454,25 @@ class Engine:
 
     def release_marginals(self):
         self._chk(self.L.ba_hip_release_marginals(self.h))
+
+    # ---- leverages of projection residuals (hat blocks; ba_hip.h) ----
+    def projection_leverages(self, ids=None, count=None):
+        """(n, 2, 2) blocks H_aa of the hat matrix per accepted projection residual id; ids=None: every residual in
+        residual-id order (count: their number, default the engine's)."""
+        if ids is None:
+            n = int(self.structure_stats()["observations"]) if count is None else int(count)
+            out = np.empty((n, 2, 2))
+            self._chk(self.L.ba_hip_get_projection_leverages(self.h, n, None, _p(out, dp)))
+            return out
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32).ravel()
+        out = np.empty((len(ids), 2, 2))
+        self._chk(self.L.ba_hip_get_projection_leverages(self.h, len(ids), _p(ids, u32p), _p(out, dp)))
+        return out
+
+    def leverage_stats(self):
+        st = LeverageStats()
+        self._chk(self.L.ba_hip_get_leverage_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in LeverageStats._fields_}
 
     # ---- joint covariance of a pose set (forward substitution + Gram product, no selected inverse) ----
     def joint_marginals(self, ids, include_calibration=False):

@@ -25,6 +25,7 @@
 #include <cmath>
 #include <cstdio>
 #include <iostream>
+#include <limits>
 #include <memory>
 #include <vector>
 
@@ -591,6 +592,52 @@ class BundleAdjuster {
                            "ba_hip_get_landmark_marginals"))
       return MatX();
     return m;
+  }
+  // Leverage of an accepted projection residual (extension; include/ba_hip.h ba_hip_get_projection_leverages,
+  // DESIGN.md section 15): the 2 x 2 diagonal block H_aa of the hat matrix of the system the last Solve()
+  // factorised, for the id AddProjectionResidual returned.  Post-fit residual covariance I - H_aa, studentised
+  // residual r^T (I - H_aa)^-1 r, innovation gate I + H_aa.  A 0 x 0 matrix, reported through Check() or on
+  // stderr, when unavailable: a rejected residual ((uint32_t)-1) or an id that was never returned, no solve yet,
+  // the PCG, sharded or distributed solve, LmSize 0.
+  MatX GetProjectionLeverage(uint32_t residual_id) {
+    if (residual_id >= pr_pose_.size()) {
+      std::cerr << "ba::BundleAdjuster::GetProjectionLeverage: " << residual_id
+                << " is not the id of an accepted projection residual" << std::endl;
+      return MatX();
+    }
+    MatX m(2, 2);
+    if (!engine_ || !Check(ba_hip_get_projection_leverages(engine_, 1, &residual_id, m.data()),
+                           "ba_hip_get_projection_leverages"))
+      return MatX();
+    return m;
+  }
+  // ... of many residuals in one call: out holds 4 values (row-major 2 x 2) per id, in the order of ids; an empty
+  // ids means every accepted residual in id order.  One launch for all of them, and a landmark's sums are formed
+  // once however many of its residuals are asked for: the form to use for more than a handful.  false (out
+  // empty) when unavailable.
+  bool GetProjectionLeverages(const std::vector<uint32_t>& ids, std::vector<double>& out) {
+    const uint32_t n = ids.empty() ? (uint32_t)pr_pose_.size() : (uint32_t)ids.size();
+    out.assign(4 * (size_t)n, 0.0);
+    for (uint32_t id : ids)
+      if (id >= pr_pose_.size()) {
+        std::cerr << "ba::BundleAdjuster::GetProjectionLeverages: " << id
+                  << " is not the id of an accepted projection residual" << std::endl;
+        out.clear();
+        return false;
+      }
+    if (!engine_ || !Check(ba_hip_get_projection_leverages(engine_, n, ids.empty() ? nullptr : ids.data(), out.data()),
+                           "ba_hip_get_projection_leverages")) {
+      out.clear();
+      return false;
+    }
+    return true;
+  }
+  // Redundancy number 2 - tr H_aa of the residual: how much of it the fit cannot absorb (0: none, the residual
+  // is always fitted exactly; 2: all).  NaN when GetProjectionLeverage is unavailable.
+  Scalar GetProjectionRedundancy(uint32_t residual_id) {
+    const MatX h = GetProjectionLeverage(residual_id);
+    if (h.rows() != 2) return std::numeric_limits<Scalar>::quiet_NaN();
+    return 2.0 - (h.data()[0] + h.data()[3]);
   }
   Scalar trust_region_size() const { return trust_region_size_; }
   const ba_hip_timers& GetLastTimers() const { return last_timers_; }

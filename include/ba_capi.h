@@ -129,6 +129,12 @@ uint32_t ba_adjuster_get_calibration_marginals(const ba_adjuster* a, double cov[
 uint32_t ba_adjuster_get_pose_covariance(ba_adjuster* a, uint32_t pose_id, double* cov);
 uint32_t ba_adjuster_get_pose_cross_covariance(ba_adjuster* a, uint32_t pose_a, uint32_t pose_b, double* cov);
 uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_id, double* cov);
+/* GetProjectionLeverage / GetProjectionRedundancy (extension): the 2 x 2 hat block of the accepted projection
+ * residual residual_id (the id ba_adjuster_add_projection_residuals returned), row-major into h4; returns 2, or 0
+ * when unavailable (a rejected residual's id (uint32_t)-1 included).  The redundancy is 2 - trace; returns 0, or 1
+ * when unavailable. */
+uint32_t ba_adjuster_get_projection_leverage(ba_adjuster* a, uint32_t residual_id, double* h4);
+int ba_adjuster_get_projection_redundancy(ba_adjuster* a, uint32_t residual_id, double* redundancy);
 /* GetJointPoseCovariance (extension): the M x M joint covariance of the n poses pose_ids in the caller's order,
  * M = n PoseSize (+ the calibration rows last with include_calibration), row-major into cov (room for M^2
  * values); returns M, 0 when unavailable (the summary's result then reads SolverError) */

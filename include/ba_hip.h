@@ -518,6 +518,45 @@ int ba_hip_get_marginal_stats(ba_hip_engine* e, ba_hip_marginal_stats* out);
 /* Frees the Sigma store and the workspace of ba_hip_get_joint_marginals (also freed with the engine). */
 int ba_hip_release_marginals(ba_hip_engine* e);
 
+/* ---- leverages of projection residuals (hat blocks) -----------------------------------
+ * For projection residual a with whitened Jacobian row block J_a = [A_a | B_a] (A_a: sqrt(w) dz_dx_meas at the
+ * measuring pose, sqrt(w) dz_dx_ref at the reference pose (LmSize 1), sqrt(w) dz_dk at the calibration columns;
+ * B_a = sqrt(w) dz_dlm; w = observation weight x Huber weight of the last linearisation; masked columns zero)
+ * the 2 x 2 diagonal block of the hat matrix J (J^T J)^-1 J^T over all unknowns (poses, calibration, landmarks):
+ *   H_aa = A Sigma A^T - sym2((sum_f A_f t_f) V^-1 B^T) + B Sigma_ll B^T,  t_f = sum_e Sigma_{p_f p_e} W_e,
+ * with Sigma = S^-1 from the selected inverse (computed on demand) and Sigma_ll the landmark marginal.  From it:
+ * redundancy 2 - tr H_aa, post-fit residual covariance I - H_aa, studentised residual r^T (I - H_aa)^-1 r,
+ * innovation gate I + H_aa.  0 <= H_aa <= I; with projection residuals only and nothing masked the traces sum
+ * to the number of unknowns.
+ *   - Preconditions of ba_hip_get_landmark_marginals: finalized, the factor of the last direct ba_hip_solve_gn
+ *     (not PCG), not re-linearised since, not sharded or distributed.  Pose orderings are invisible.
+ *   - Errors: an id that is no projection residual, NULL with n > 0, n != residual count with NULL ids, LmSize 0.
+ *   - An inactive landmark drops B and the Schur part: H_aa = A Sigma A^T.  An inactive pose contributes no
+ *     block.  An observation with no active incidence and an inactive landmark reads zero; w = 0 reads exactly
+ *     zero.  An LmSize 1 observation taken from the landmark's reference pose itself carries no pose block (the
+ *     listing rule of the reduced system): H_aa = B Sigma_ll B^T plus its calibration terms.
+ *   - A repeated id returns the same bits twice, and an id's bits are those of the all-residuals call.
+ *   - V^-1 does not enter as the explicit inverse the solve uses (its unstructured error of eps cond(V) |V^-1| is
+ *     amplified by cond(V) again in B V^-1 B^T): the pass re-forms V = sum_a B_a^T B_a from the whitened dz_dlm
+ *     with the same 1e-6 guard, factors it V = L L^T and works with L^-1.  A pivot that is not positive (a
+ *     numerically singular V, which the solve's inverse does not survive either) is replaced by 1e-6.
+ *   - Cost: a landmark with k incidences costs k^2 blocks of Sigma (2 k^2 beyond 64 observations) once per call,
+ *     however many of its residuals the call asks for, plus O(1) blocks per residual.  Asking for the residuals of
+ *     one landmark in separate calls pays the k^2 each time (k^3 for a whole track): ask for them together.
+ *   - Nothing is allocated on the device before the first request and nothing is kept there between requests
+ *     (the host keeps the sorted position of every residual id until the next ba_hip_finalize). */
+/* out: n x 4 (row-major 2 x 2, bitwise symmetric) per ACCEPTED projection residual id; residual_ids NULL:
+ * every residual in residual-id order (n = their count). */
+int ba_hip_get_projection_leverages(ba_hip_engine* e, uint32_t n, const uint32_t* residual_ids, double* out);
+typedef struct {
+  double device_ms;      /* device time of the last leverage pass (events) */
+  uint64_t block_reads;  /* blocks of Sigma it read: v^2 per landmark with v incidences (twice beyond 64
+                            observations), c^2 per residual with c blocks in A */
+  uint32_t residuals, landmarks;  /* residuals served, landmarks they belong to */
+} ba_hip_leverage_stats;
+/* The figures of the last successful ba_hip_get_projection_leverages (zeros before the first). */
+int ba_hip_get_leverage_stats(ba_hip_engine* e, ba_hip_leverage_stats* out);
+
 /* ---- joint covariance of an arbitrary pose set (no selected inverse) ------------------
  * The M x M block of Sigma = S^-1 over the rows of the poses pose_ids (and, with include_calibration, the K
  * calibration rows after them), M = n D + (include_calibration ? K : 0): block (i, j) of out (row-major) is
