@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ba_hip.h"
@@ -15,33 +17,36 @@
 
 namespace bae {
 
-// ---- small RAII-less device buffer (engine owns and frees explicitly) -------------
+// ---- owning device buffer: freed by its destructor (DESIGN.md "ownership") ---------
+// bytes held by every DBuf of the process (ba_hip_device_bytes_live)
+inline std::atomic<int64_t> g_device_bytes_live{0};
 template <typename T>
 struct DBuf {
   T* p = nullptr;
   size_t n = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  DBuf(DBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DBuf& operator=(DBuf&& o) noexcept {
+    if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+    return *this;
+  }
+  ~DBuf() { release(); }
   hipError_t alloc(size_t count) {
     if (count <= n && p) return hipSuccess;
     release();
     if (count == 0) { n = 0; return hipSuccess; }
     hipError_t err = hipMalloc((void**)&p, count * sizeof(T));
-    if (err == hipSuccess) n = count;
+    if (err == hipSuccess) { n = count; g_device_bytes_live += (int64_t)bytes(); }
     return err;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) { (void)hipFree(p); g_device_bytes_live -= (int64_t)bytes(); }
     p = nullptr;
     n = 0;
   }
   size_t bytes() const { return n * sizeof(T); }
-};
-// a temporary of one call: released on every exit path (early error returns included)
-template <typename T>
-struct TBuf : DBuf<T> {
-  TBuf() = default;
-  TBuf(const TBuf&) = delete;
-  TBuf& operator=(const TBuf&) = delete;
-  ~TBuf() { this->release(); }
 };
 
 // Rigid transform in matrix form as stored on the device: R row-major (9) then t (3).
@@ -262,7 +267,7 @@ struct Engine {
   ba_hip_marginal_stats mstats = {};
   // joint covariances of arbitrary pose sets (ba_hip_get_joint_marginals, k_jointcov.hip): the workspace of the
   // forward substitution Y = L^-1 E and the Gram product, allocated by the first request, reused, freed by
-  // ba_hip_release_marginals and with the engine.  jc_idx: the plan of the last request (jointcov.h)
+  // ba_hip_release_marginals.  jc_idx: the plan of the last request (jointcov.h)
   DBuf<uint32_t> jc_idx;
   DBuf<double> jc_Y, jc_slots, jc_part, jc_out;
   ba_hip_joint_marginal_stats jstats = {};
@@ -318,17 +323,6 @@ struct Engine {
     DBuf<uint32_t> cmap, crow_ptr, crow_rows;
     DBuf<double> C, Lc, Wc, Cinv, rc, yc, ryc_part;
     uint32_t coarse_key = 0, coarse_nc = 0, coarse_ncp = 0;   // aggregate the tables were uploaded for; size of the last C
-    void release_coarse() {
-      cmap.release(); crow_ptr.release(); crow_rows.release(); C.release(); Lc.release(); Wc.release(); Cinv.release();
-      rc.release(); yc.release(); ryc_part.release();
-      coarse_key = coarse_nc = coarse_ncp = 0;
-    }
-    void release() {
-      release_coarse();
-      tiles.release(); blk.release(); blocks.release(); row_ptr.release(); col_ptr.release(); col_slot.release();
-      nz.release(); rowslot.release(); colslot.release(); minv.release(); x.release(); r.release(); z.release();
-      p.release(); q.release(); parts.release(); state.release(); status.release();
-    }
   } pcg;
 
   // optional per-kernel timing (ba_hip_set_profiling)
@@ -347,6 +341,9 @@ struct Engine {
     (void)hipEventRecord(v.back().second, s ? s : stream);
   }
   void prof_collect();
+
+  // synchronises the streams, destroys the events and the streams the engine created; the members free the rest
+  ~Engine();
 
   int fail(hipError_t e, const char* what);
   int fail_msg(const char* what);

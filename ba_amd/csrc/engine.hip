@@ -43,6 +43,19 @@ int Engine::fail_msg(const char* what) {
   err = what;
   return -1;
 }
+Engine::~Engine() {
+  for (hipStream_t s : {stream, stream2, stream3, stream4})
+    if (s) (void)hipStreamSynchronize(s);
+  for (auto* v : {&ev_panel, &ev_bulk, &ev_dist, &timer_events})
+    for (hipEvent_t ev : *v) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {ev_imu_start, ev_imu_done, ev_fork, ev_join})
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto* v : {&ev_syrk, &ev_gather, &ev_landmarks, &ev_imu, &ev_pose})   // profiling pairs nobody collected
+    for (auto& pr : *v) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+  for (hipStream_t s : {stream2, stream3, stream4})
+    if (s) (void)hipStreamDestroy(s);
+  if (own_stream && stream) (void)hipStreamDestroy(stream);   // a caller's stream is only synchronised
+}
 
 template <typename T>
 static int upload(Engine* e, DBuf<T>& buf, const std::vector<T>& v, size_t min_count = 0) {
@@ -497,6 +510,54 @@ static int set_masks_device(Engine* e, const std::vector<uint16_t>& by_id) {
   return 0;
 }
 
+// Is the factor that the last ba_hip_solve_gn left in A there to be read?  The one statement of it, for everything
+// that reads the factor: `who` starts the message, `noun` names what was asked for.  foreign_ok: a stand-alone solve
+// since then does not matter to the caller.  ba_hip_get_calibration_marginals (noun == nullptr) is older than the
+// rest and keeps its shorter wording, and its later place for the distributed solve.
+static int kept_factor_ready(Engine* e, const char* who, const char* noun, bool foreign_ok) {
+  const std::string w = who, m = w + ": ";
+  if (noun && dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
+  if (!e->factored && e->pcg_solved)
+    return e->fail_msg((m + "the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor" +
+                        (noun ? std::string("; ") + noun + " need a direct solve (ba_hip_set_reduced_solver)" : "")).c_str());
+  if (!e->factored)
+    return e->fail_msg((noun ? m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised since)"
+                             : w + " needs the factor of the last ba_hip_solve_gn").c_str());
+  if (e->factor_foreign && !foreign_ok)
+    return e->fail_msg((m + "a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has replaced the kept factor "
+                            "since the last ba_hip_solve_gn").c_str());
+  if (!noun && dist_solve_enabled(e)) return e->fail_msg("calibration marginals: not available with the distributed solve");
+  return 0;
+}
+
+// The host work that ba_hip_dense_solve, ba_hip_pcg_solve and ba_hip_tile_solve share.  pad_system: the caller's
+// n x n lower triangle in (ld + 1) x ld storage, ones on the padded diagonal, the right-hand side as row ld; with
+// want_nz also the nt x nt map of the tiles that hold a nonzero entry.
+struct PaddedSystem {
+  uint32_t ld = 0, nt = 0;
+  std::vector<double> A;
+  std::vector<uint8_t> nz;
+};
+static PaddedSystem pad_system(uint32_t n, const double* a_lower, const double* b, bool want_nz) {
+  PaddedSystem s;
+  const uint32_t ld = s.ld = std::max(((n + 63) / 64) * 64, 64u), nt = s.nt = ld / 64;
+  s.A.assign((size_t)(ld + 1) * ld, 0.0);
+  if (want_nz) s.nz.assign((size_t)nt * nt, 0);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c <= r; ++c) {
+      const double v = a_lower[(size_t)r * n + c];
+      s.A[(size_t)r * ld + c] = v;
+      if (want_nz && v != 0.0) s.nz[(size_t)(r / 64) * nt + c / 64] = 1;
+    }
+  for (uint32_t r = n; r < ld; ++r) s.A[(size_t)r * ld + r] = 1.0;
+  for (uint32_t c = 0; c < n; ++c) s.A[(size_t)ld * ld + c] = b[c];
+  return s;
+}
+// ... and the first n entries of the solution back
+static hipError_t download_x(const DBuf<double>& dx, uint32_t n, double* x) {
+  return hipMemcpy(x, dx.p, (size_t)n * 8, hipMemcpyDeviceToHost);
+}
+
 }  // namespace bae
 
 using namespace bae;
@@ -553,44 +614,12 @@ void ba_hip_destroy(ba_hip_engine* h) {
   if (!h) return;
   ENG(h);
   (void)hipSetDevice(e->device);
-  (void)hipStreamSynchronize(e->stream);
-#define REL(b) e->b.release()
-  REL(cam); REL(cam_eval); REL(lm_zref); REL(crow); REL(border_blocks); REL(calib_partials); REL(pose_opt); REL(lm_opt); REL(pose_mask); REL(lm_ref_pose); REL(lm_ref_cam);
-  REL(lm_ptr); REL(obs_z); REL(obs_pose); REL(obs_cam); REL(obs_lm); REL(obs_rid); REL(obs_w0); REL(obs_cond);
-  REL(wave_rng); REL(tile_order); REL(tile_desc); REL(tile_ptr); REL(tile_ref); REL(pair_ent); REL(pose_ptr); REL(pose_mid); REL(pose_ent);
-  REL(imu_frozen); REL(imu_steps); REL(imu_cov_done); REL(pose_cam);
-  REL(packed); REL(nzL); REL(dist_msg); REL(dist_rows); REL(dist_srows);
-  REL(dist_tiles); REL(dist_sq_list); REL(dist_pairs); REL(dist_sp_srect); REL(dist_sp_rrect); REL(dist_usend); REL(dist_urecv); REL(dist_ssend); REL(dist_srecv); REL(dist_back);
-  for (int b = 0; b < 2; ++b) { REL(pose_state[b]); REL(lm_x[b]); REL(lm_reliable[b]); }
-  REL(lm_xw); REL(tsw); REL(tws); REL(twp); REL(lm_outliers); REL(obs_e); REL(obs_w); REL(obs_e_state[0]); REL(obs_e_state[1]); REL(obs_jl);
-  e->pcg.release();
-  REL(frow); REL(diag_blocks); REL(scal); REL(lm_vinv); REL(lm_bl); REL(A); REL(A_keep); REL(rhs_p); REL(rhs_sc); REL(gn_p);
-  REL(gn_l); REL(step_p); REL(step_l); REL(invdiag); REL(partials); REL(scalars_out); REL(hist);
-  REL(flags); REL(pivot_floor);
-  marginals_release(e);
-  jointcov_release(e);
-  REL(pose_active); REL(un_pose); REL(un_t); REL(un_cov_inv); REL(un_scale); REL(un_rot);
-  REL(bin_p1); REL(bin_p2); REL(bin_t); REL(bin_cov_inv); REL(bin_cov_inv_sqrt); REL(bin_w); REL(bin_rot);
-  REL(imu_p1); REL(imu_p2); REL(imu_ptr); REL(imu_meas); REL(imu_consts); REL(imu_cov_inv);
-  REL(pp_h); REL(pp_g); REL(pp_dz); REL(pp_info); REL(pp_err); REL(pp_ptr); REL(pp_res_p1);
-  REL(pp_res_p2); REL(pp_ent); REL(pp_err_lin);
-  REL(dp_ptr); REL(dp_pose); REL(dp_x0); REL(dp_H); REL(dp_b); REL(dp_c); REL(dp_hoff); REL(dp_blk);
-  REL(dp_d); REL(dp_J); REL(dp_G); REL(dp_g); REL(dp_w); REL(dp_E); REL(dp_E_eval); REL(dp_jr);
-#undef REL
+  (void)hipStreamSynchronize(e->stream);   // nothing of the engine's in flight when the communicator goes
   comm_release(e);
-  if (e->ev_imu_done) { (void)hipEventDestroy(e->ev_imu_done); (void)hipEventDestroy(e->ev_imu_start); }
-  if (e->ev_fork) { (void)hipEventDestroy(e->ev_fork); (void)hipEventDestroy(e->ev_join); }
-  for (hipEvent_t ev : e->timer_events) (void)hipEventDestroy(ev);
-  e->timer_events.clear();
-  for (hipEvent_t ev : e->ev_panel) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : e->ev_bulk) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : e->ev_dist) (void)hipEventDestroy(ev);
-  if (e->stream3) (void)hipStreamDestroy(e->stream3);
-  if (e->stream4) (void)hipStreamDestroy(e->stream4);
-  if (e->stream2) (void)hipStreamDestroy(e->stream2);
-  if (e->own_stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
+
+uint64_t ba_hip_device_bytes_live(void) { return (uint64_t)g_device_bytes_live.load(); }
 
 const char* ba_hip_last_error(const ba_hip_engine* h) {
   return h ? reinterpret_cast<const Engine*>(h)->err.c_str() : "null engine";
@@ -1371,14 +1400,8 @@ int ba_hip_get_calibration_marginals(ba_hip_engine* h, double* cov) {
   ENG(h);
   NEED_FINAL();
   if (!e->st.K) return e->fail_msg("no calibration columns (ba_hip_set_calibration)");
-  if (!e->factored && e->pcg_solved)
-    return e->fail_msg("ba_hip_get_calibration_marginals: the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), "
-                       "which leaves no factor");
-  if (!e->factored) return e->fail_msg("ba_hip_get_calibration_marginals needs the factor of the last ba_hip_solve_gn");
-  if (e->factor_foreign)
-    return e->fail_msg("ba_hip_get_calibration_marginals: a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has "
-                       "replaced the kept factor since the last ba_hip_solve_gn");
-  if (dist_solve_enabled(e)) return e->fail_msg("calibration marginals: not available with the distributed solve");
+  int rc;
+  if ((rc = kept_factor_ready(e, "ba_hip_get_calibration_marginals", nullptr, false))) return rc;
   BAE_HIP(hipSetDevice(e->device));
   return trailing_marginals(e, e->A.p, e->st.ld, e->st.np, e->st.K, cov);
 }
@@ -1453,18 +1476,10 @@ int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
 static int marginals_ready(Engine* e, const char* what, bool landmarks) {
   std::string m = std::string(what) + ": ";
   if (!e->finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
-  if (dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
-  if (landmarks && e->sharded())
+  if (landmarks && e->sharded() && !dist_solve_enabled(e))   // (the distributed solve refuses first, for every block)
     return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
-  if (!e->factored && e->pcg_solved)
-    return e->fail_msg((m + "the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor; "
-                            "marginals need a direct solve (ba_hip_set_reduced_solver)").c_str());
-  if (!e->factored)
-    return e->fail_msg((m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised "
-                            "since)").c_str());
-  if (e->factor_foreign && !e->sig_valid)  // (a selected inverse computed before the stand-alone solve stays good)
-    return e->fail_msg((m + "a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has replaced the kept factor "
-                            "since the last ba_hip_solve_gn").c_str());
+  int rc;   // (a selected inverse computed before a stand-alone solve stays good)
+  if ((rc = kept_factor_ready(e, what, "marginals", e->sig_valid))) return rc;
   BAE_HIP(hipSetDevice(e->device));
   return marginals_compute(e);
 }
@@ -1556,16 +1571,8 @@ int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pos
   static const char* what = "ba_hip_get_joint_marginals";
   const std::string m = std::string(what) + ": ";
   if (!e->finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
-  if (dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
-  if (!e->factored && e->pcg_solved)
-    return e->fail_msg((m + "the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor; "
-                            "joint marginals need a direct solve (ba_hip_set_reduced_solver)").c_str());
-  if (!e->factored)
-    return e->fail_msg((m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised "
-                            "since)").c_str());
-  if (e->factor_foreign)
-    return e->fail_msg((m + "a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has replaced the kept factor "
-                            "since the last ba_hip_solve_gn").c_str());
+  int rc;
+  if ((rc = kept_factor_ready(e, what, "joint marginals", false))) return rc;
   if ((n && !pose_ids) || !out) return e->fail_msg((m + "NULL argument").c_str());
   const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K;
   if (include_calibration && !K)
@@ -1676,11 +1683,10 @@ int ba_hip_get_proj_residuals(ba_hip_engine* h, double* residual2) {
   DBuf<double> d;
   BAE_HIP(d.alloc((size_t)2 * st.O));
   int rc = launch_residual_vectors(e, d.p);
-  if (rc) { d.release(); return rc; }
+  if (rc) return rc;
   std::vector<double> r((size_t)2 * st.O);
   BAE_HIP(hipStreamSynchronize(e->stream));
   BAE_HIP(hipMemcpy(r.data(), d.p, r.size() * sizeof(double), hipMemcpyDeviceToHost));
-  d.release();
   for (uint32_t s = 0; s < st.O; ++s) {
     residual2[2 * (size_t)st.obs_perm[s]] = r[2 * (size_t)s];
     residual2[2 * (size_t)st.obs_perm[s] + 1] = r[2 * (size_t)s + 1];
@@ -1736,10 +1742,9 @@ int ba_hip_get_imu_residuals(ba_hip_engine* h, double* residual15) {
   DBuf<double> d;
   BAE_HIP(d.alloc((size_t)15 * ni));
   int rc = launch_imu_residual_vectors(e, d.p);
-  if (rc) { d.release(); return rc; }
+  if (rc) return rc;
   BAE_HIP(hipStreamSynchronize(e->stream));
   BAE_HIP(hipMemcpy(residual15, d.p, (size_t)15 * ni * sizeof(double), hipMemcpyDeviceToHost));
-  d.release();
   return 0;
 }
 
@@ -1874,7 +1879,6 @@ int ba_hip_allreduce_host(ba_hip_engine* h, void* host, size_t count, int dtype)
   if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
   if (!rc && shard_allreduce(e, d.p, count, dtype) != 0) rc = e->fail_msg("allreduce hook failed");
   if (!rc && (err = hipMemcpy(host, d.p, count * 8, hipMemcpyDeviceToHost)) != hipSuccess) rc = e->fail(err, "hipMemcpy");
-  d.release();
   return rc;
 }
 
@@ -2158,28 +2162,17 @@ int ba_hip_release_marginalization(ba_hip_engine* h) {
 int ba_hip_dense_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, double* x) {
   ENG(h);
   BAE_HIP(hipSetDevice(e->device));
-  const uint32_t ld = std::max(((n + 63) / 64) * 64, 64u);
-  std::vector<double> A((size_t)(ld + 1) * ld, 0.0);
-  for (uint32_t r = 0; r < n; ++r)
-    for (uint32_t c = 0; c <= r; ++c) A[(size_t)r * ld + c] = a_lower[(size_t)r * n + c];
-  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
-  for (uint32_t c = 0; c < n; ++c) A[(size_t)ld * ld + c] = b[c];
+  const PaddedSystem sys = pad_system(n, a_lower, b, false);
   DBuf<double> dA, dx;
-  BAE_HIP(dA.alloc(A.size()));
-  BAE_HIP(dx.alloc(ld));
+  BAE_HIP(dA.alloc(sys.A.size()));
+  BAE_HIP(dx.alloc(sys.ld));
   BAE_HIP(e->flags.alloc(16));
-  BAE_HIP(hipMemcpy(dA.p, A.data(), A.size() * 8, hipMemcpyHostToDevice));
+  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
   int status = 0;
   e->factor_foreign = true;  // invdiag is about to hold this system's factor, not the scene's
-  int rc = cholesky_solve(e, dA.p, n, ld, dx.p, &status, nullptr);  // arbitrary matrix: dense
-  if (rc == 0) {
-    std::vector<double> xx(ld);
-    hipError_t err = hipMemcpy(xx.data(), dx.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
-    if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
-    for (uint32_t i = 0; i < n; ++i) x[i] = xx[i];
-  }
-  dA.release(); dx.release();
+  int rc = cholesky_solve(e, dA.p, n, sys.ld, dx.p, &status, nullptr);  // arbitrary matrix: dense
   if (rc) return rc;
+  BAE_HIP(download_x(dx, n, x));
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
 }
 
@@ -2190,19 +2183,10 @@ int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const 
   if (block < 1 || block > kPcgMaxBlock) return e->fail_msg("ba_hip_pcg_solve: block must lie in 1 .. 16");
   if (!(o->rel_tolerance > 0.0) || !(o->rel_tolerance < 1.0)) return e->fail_msg("ba_hip_pcg_solve: rel_tolerance must lie in (0, 1)");
   BAE_HIP(hipSetDevice(e->device));
-  const uint32_t ld = std::max(((n + 63) / 64) * 64, 64u), nt = ld / 64;
-  std::vector<double> A((size_t)(ld + 1) * ld, 0.0);
-  std::vector<uint8_t> nz((size_t)nt * nt, 0);
-  for (uint32_t r = 0; r < n; ++r)
-    for (uint32_t c = 0; c <= r; ++c) {
-      const double v = a_lower[(size_t)r * n + c];
-      A[(size_t)r * ld + c] = v;
-      if (v != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
-    }
-  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
-  for (uint32_t c = 0; c < n; ++c) A[(size_t)ld * ld + c] = b[c];
+  const PaddedSystem sys = pad_system(n, a_lower, b, true);
+  const uint32_t ld = sys.ld;
   PcgPlan plan;
-  build_pcg_plan(nz, nt, plan);
+  build_pcg_plan(sys.nz, sys.nt, plan);
   std::vector<uint32_t> blk, blocks;
   pcg_row_blocks(n, block, 0, ld, blk, blocks);
   if (o->coarse_aggregate) {
@@ -2212,22 +2196,16 @@ int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const 
     build_pcg_coarse(plan, nat, nblk, block, 0, o->coarse_aggregate);
   }
   DBuf<double> dA, dx;
-  BAE_HIP(dA.alloc(A.size()));
+  BAE_HIP(dA.alloc(sys.A.size()));
   BAE_HIP(dx.alloc(ld));
-  BAE_HIP(hipMemcpy(dA.p, A.data(), A.size() * 8, hipMemcpyHostToDevice));
+  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
   int status = 0;
   ba_hip_pcg_stats st;
   e->pcg_plan_version = ~0ull;   // the work space now holds this system's plan, not the engine's
-  int rc = pcg_solve_device(e, dA.p, n, ld, dA.p + (size_t)ld * ld, plan, nz, blk, blocks, true, *o, dx.p, &st, &status);
-  if (rc == 0) {
-    std::vector<double> xx(ld);
-    hipError_t err = hipMemcpy(xx.data(), dx.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
-    if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
-    for (uint32_t i = 0; i < n; ++i) x[i] = xx[i];
-    if (stats) *stats = st;
-  }
-  dA.release(); dx.release();
+  int rc = pcg_solve_device(e, dA.p, n, ld, dA.p + (size_t)ld * ld, plan, sys.nz, blk, blocks, true, *o, dx.p, &st, &status);
   if (rc) return rc;
+  BAE_HIP(download_x(dx, n, x));
+  if (stats) *stats = st;
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
 }
 
@@ -2239,55 +2217,42 @@ int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const
   ENG(h);
   if (!n || !a_lower || !b || !x) return e->fail_msg("ba_hip_tile_solve: NULL or empty argument");
   BAE_HIP(hipSetDevice(e->device));
-  const uint32_t ld = std::max(((n + 63) / 64) * 64, 64u), nt = ld / 64;
-  std::vector<double> A((size_t)(ld + 1) * ld, 0.0);
-  std::vector<uint8_t> nz((size_t)nt * nt, 0);
-  if (tile_map)
-    for (uint32_t i = 0; i < nt; ++i)
-      for (uint32_t k = 0; k <= i; ++k) nz[(size_t)i * nt + k] = tile_map[(size_t)i * nt + k] ? 1 : 0;
-  for (uint32_t r = 0; r < n; ++r)
-    for (uint32_t c = 0; c <= r; ++c) {
-      const double v = a_lower[(size_t)r * n + c];
-      A[(size_t)r * ld + c] = v;
-      if (v != 0.0) {
-        uint8_t& t = nz[(size_t)(r / 64) * nt + c / 64];
-        if (!t && tile_map && r / 64 != c / 64) {
+  PaddedSystem sys = pad_system(n, a_lower, b, true);
+  const uint32_t ld = sys.ld, nt = sys.nt;
+  std::vector<uint8_t>& nz = sys.nz;
+  if (tile_map) {
+    for (uint32_t r = 0; r < n; ++r)
+      for (uint32_t c = 0; c <= r; ++c)
+        if (a_lower[(size_t)r * n + c] != 0.0 && r / 64 != c / 64 && !tile_map[(size_t)(r / 64) * nt + c / 64]) {
           e->err = "ba_hip_tile_solve: entry (" + std::to_string(r) + ", " + std::to_string(c) + ") is nonzero but tile (" +
                    std::to_string(r / 64) + ", " + std::to_string(c / 64) + ") is not in the tile map";
           return -1;
         }
-        t = 1;
-      }
-    }
+    for (uint32_t i = 0; i < nt; ++i)
+      for (uint32_t k = 0; k <= i; ++k) nz[(size_t)i * nt + k] |= tile_map[(size_t)i * nt + k] ? 1 : 0;
+  }
   for (uint32_t i = 0; i < nt; ++i) nz[(size_t)i * nt + i] = 1;  // diagonal tiles always
-  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
-  for (uint32_t c = 0; c < n; ++c) A[(size_t)ld * ld + c] = b[c];
   tile_symbolic_factor(nz, nt);
   if (nz_factor) std::copy(nz.begin(), nz.end(), nz_factor);
   DBuf<double> dA, dx;
   DBuf<uint8_t> dnz;
-  BAE_HIP(dA.alloc(A.size()));
+  BAE_HIP(dA.alloc(sys.A.size()));
   BAE_HIP(dx.alloc(ld));
   BAE_HIP(dnz.alloc(nz.size()));
   BAE_HIP(e->flags.alloc(16));
-  BAE_HIP(hipMemcpy(dA.p, A.data(), A.size() * 8, hipMemcpyHostToDevice));
+  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
   BAE_HIP(hipMemcpy(dnz.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
   int status = 0;
   e->factor_foreign = true;  // invdiag is about to hold this system's factor, not the scene's
   int rc = cholesky_solve(e, dA.p, n, ld, dx.p, &status, dnz.p);
-  if (rc == 0) {
-    std::vector<double> xx(ld);
-    hipError_t err = hipDeviceSynchronize();  // both streams of the factorisation
-    if (err == hipSuccess) err = hipMemcpy(xx.data(), dx.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && factor) err = hipMemcpy(factor, dA.p, (size_t)ld * ld * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && dsgn) err = hipMemcpy(dsgn, e->invdiag.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && linvT)
-      err = hipMemcpy(linvT, e->invdiag.p + ld, (size_t)nt * 64 * 64 * 8, hipMemcpyDeviceToHost);
-    if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
-    for (uint32_t i = 0; i < n; ++i) x[i] = xx[i];
-  }
-  dA.release(); dx.release(); dnz.release();
   if (rc) return rc;
+  hipError_t err = hipDeviceSynchronize();  // both streams of the factorisation
+  if (err == hipSuccess) err = download_x(dx, n, x);
+  if (err == hipSuccess && factor) err = hipMemcpy(factor, dA.p, (size_t)ld * ld * 8, hipMemcpyDeviceToHost);
+  if (err == hipSuccess && dsgn) err = hipMemcpy(dsgn, e->invdiag.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
+  if (err == hipSuccess && linvT)
+    err = hipMemcpy(linvT, e->invdiag.p + ld, (size_t)nt * 64 * 64 * 8, hipMemcpyDeviceToHost);
+  if (err != hipSuccess) return e->fail(err, "hipMemcpy");
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
 }
 
@@ -2299,7 +2264,6 @@ int ba_hip_select_kth(ba_hip_engine* h, uint32_t n, const double* values, uint32
   BAE_HIP(e->hist.alloc(2048 + 8));
   if (n) BAE_HIP(hipMemcpy(dv.p, values, (size_t)n * 8, hipMemcpyHostToDevice));
   int rc = select_kth(e, dv.p, n, k, out);
-  dv.release();
   return rc;
 }
 

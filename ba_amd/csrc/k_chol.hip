@@ -1554,9 +1554,8 @@ int factor_tile_pattern(Engine* e) {
     DBuf<double> d;
     BAE_HIP(d.alloc(cnt.size()));
     BAE_HIP(hipMemcpy(d.p, cnt.data(), cnt.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (shard_allreduce(e, d.p, cnt.size(), 0) != 0) { d.release(); return e->fail_msg("allreduce hook failed"); }
+    if (shard_allreduce(e, d.p, cnt.size(), 0) != 0) return e->fail_msg("allreduce hook failed");
     BAE_HIP(hipMemcpy(cnt.data(), d.p, cnt.size() * sizeof(double), hipMemcpyDeviceToHost));
-    d.release();
     for (size_t i = 0; i < nz.size(); ++i) nz[i] = cnt[i] > 0.5 ? 1 : 0;
   }
   e->nzS_host = nz;
@@ -1941,7 +1940,6 @@ int dist_scatter_S_sparse(Engine* e) {
       if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
       if (!rc && shard_allreduce(e, d.p, all.size(), 1) != 0) rc = e->fail_msg("allreduce hook failed");
       if (!rc && (err = hipMemcpy(all.data(), d.p, all.size() * 8, hipMemcpyDeviceToHost)) != hipSuccess) rc = e->fail(err, "hipMemcpy");
-      d.release();
       if (rc) return rc;
     }
     auto has = [&](uint32_t s_, uint32_t i, uint32_t c0, uint32_t c1) {

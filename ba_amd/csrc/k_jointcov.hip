@@ -244,12 +244,8 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
   return 0;
 }
 
-void jointcov_release(Engine* e) {
-  e->jc_idx.release();
-  e->jc_Y.release();
-  e->jc_slots.release();
-  e->jc_part.release();
-  e->jc_out.release();
+void jointcov_release(Engine* e) {   // (ba_hip_release_marginals promises the memory back while the engine lives)
+  e->jc_idx.release(); e->jc_Y.release(); e->jc_slots.release(); e->jc_part.release(); e->jc_out.release();
 }
 
 }  // namespace bae

@@ -405,8 +405,8 @@ int leverages_run(Engine* e, uint32_t n, const uint32_t* ids, double* out) {
       i = j;
     }
   }
-  TBuf<uint32_t> d;
-  TBuf<double> o;
+  DBuf<uint32_t> d;
+  DBuf<double> o;
   if (o.alloc(4 * (size_t)n) != hipSuccess) return e->fail_msg("leverages: output allocation failed");
   hipError_t err = hipSuccess;
   Events<2> ev;

@@ -436,11 +436,11 @@ int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& 
   const int D = e->pose_dim;
   const uint32_t n = pl.nM + pl.nB, N = n * D, m = pl.nM * D, nb = pl.nB * D;
   static_assert(sizeof(MargTerm) == sizeof(uint4), "term records are plain words");
-  TBuf<uint32_t> blk_ij, blk_ptr, rhs_ptr;
-  TBuf<uint4> terms, rterms, eterms;
-  TBuf<uint16_t> dmask;
-  TBuf<double> S, rhs, Ea, Hd, bd;
-  TBuf<int32_t> status;
+  DBuf<uint32_t> blk_ij, blk_ptr, rhs_ptr;
+  DBuf<uint4> terms, rterms, eterms;
+  DBuf<uint16_t> dmask;
+  DBuf<double> S, rhs, Ea, Hd, bd;
+  DBuf<int32_t> status;
   Events<2> ev;
   int rc;
   if ((rc = upload_async(e, blk_ij, pl.blk_ij.data(), pl.blk_ij.size())) ||

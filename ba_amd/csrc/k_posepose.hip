@@ -395,8 +395,7 @@ int launch_imu_early(Engine* e, double c_huber_proj) {
         BAE_HIP(hipMemcpyAsync(dn.p, e->imu_cov_done.p, e->imu_cov_count, hipMemcpyDeviceToDevice, s2));
       }
       BAE_HIP(hipStreamSynchronize(s2));
-      e->imu_frozen.release(); e->imu_cov_done.release();
-      e->imu_frozen = fz; e->imu_cov_done = dn;
+      e->imu_frozen = std::move(fz); e->imu_cov_done = std::move(dn);   // (the old ones are freed by the assignment)
     } else if (e->imu_cov_count == 0) {
       BAE_HIP(hipMemsetAsync(e->imu_cov_done.p, 0, e->imu_cov_done.n, s2));
     }

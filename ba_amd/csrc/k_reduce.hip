@@ -697,7 +697,6 @@ int check_solve_residual(Engine* e, const double* dS, const double* dx, const do
   hipLaunchKernelGGL(k_resid_norms, dim3(nb), dim3(256), 0, e->stream, n, (const double*)y.p, db, e->partials.p, nb);
   hipError_t err = hipGetLastError();
   int rc = err == hipSuccess ? sum_partials(e, nb, 2, out2, false) : e->fail(err, "check_solve kernels");
-  y.release();
   if (rc) return rc;
   out2[0] = sqrt(out2[0]); out2[1] = sqrt(out2[1]);
   return 0;

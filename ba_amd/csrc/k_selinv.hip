@@ -310,7 +310,7 @@ int marginals_compute(Engine* e) {
   const SelinvPlan& p = e->sig_plan;
   const size_t count = (size_t)p.n_slots * TB * TB;
   if (e->sig.n < count) {
-    e->sig.release();
+    e->sig.release();   // (before the larger store is allocated: lowers the peak)
     const hipError_t err = e->sig.alloc(count);
     if (err != hipSuccess) {
       (void)hipGetLastError();
@@ -364,8 +364,8 @@ int marginals_gather(Engine* e, uint32_t n, const std::vector<uint32_t>& ra, con
           return e->fail_msg("marginals: the requested block lies outside the factor's tile pattern (the two poses share "
                              "no landmark and no pose-pose residual, and no fill couples them)");
       }
-  TBuf<uint32_t> d;
-  TBuf<double> o;
+  DBuf<uint32_t> d;
+  DBuf<double> o;
   BAE_HIP(d.alloc(2 * (size_t)n));
   const size_t cnt = (size_t)n * Da * Db;
   if (o.alloc(cnt) != hipSuccess) return e->fail_msg("marginals: output allocation failed");
@@ -388,8 +388,8 @@ int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out)
   const LmArgs g = lm_args(e);
   const size_t cnt = (size_t)n * LM * LM;
   if (cnt == 0) return 0;
-  TBuf<uint32_t> d;
-  TBuf<double> o;
+  DBuf<uint32_t> d;
+  DBuf<double> o;
   if (o.alloc(cnt) != hipSuccess) return e->fail_msg("marginals: output allocation failed");
   hipError_t err = hipSuccess;
   Events<2> ev;
@@ -422,13 +422,9 @@ int marginals_landmarks(Engine* e, uint32_t n, const uint32_t* ids, double* out)
   return err == hipSuccess ? 0 : e->fail(err, "k_selinv_lm");
 }
 
-void marginals_release(Engine* e) {
-  e->sig.release();
-  e->sig_slot.release();
-  e->sig_col_ptr.release();
-  e->sig_col_rows.release();
-  e->sig_level_cols.release();
-  e->sig_items.release();
+void marginals_release(Engine* e) {   // (ba_hip_release_marginals promises the memory back while the engine lives)
+  e->sig.release(); e->sig_slot.release(); e->sig_col_ptr.release();
+  e->sig_col_rows.release(); e->sig_level_cols.release(); e->sig_items.release();
   e->sig_plan = SelinvPlan();
   e->sig_plan_version = ~0ull;
   e->sig_valid = false;

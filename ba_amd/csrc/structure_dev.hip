@@ -357,7 +357,6 @@ int total_of(Engine* e, const uint32_t* off, const uint32_t* cnt, size_t n, uint
   }
   if (err == hipSuccess) err = hipMemcpyAsync(&tot, acc.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream);
   if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  acc.release();
   if (err != hipSuccess) return e->fail(err, "total_of");
   if (tot >= 0xFFFFFFFFull) {
     e->err = std::string(what) + " exceeds 2^32 entries";
@@ -408,10 +407,10 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   const size_t O1 = std::max<size_t>(O, 1), L1 = std::max<size_t>(L, 1);
 
   // ---- raw arrays to the device -----------------------------------------------------------------------
-  TBuf<double> r_z, r_w;
-  TBuf<uint32_t> r_pose, r_lm, r_cam, perm_in, key_tmp;
-  TBuf<uint8_t> r_cond;
-  TBuf<char> tmp;
+  DBuf<double> r_z, r_w;
+  DBuf<uint32_t> r_pose, r_lm, r_cam, perm_in, key_tmp;
+  DBuf<uint8_t> r_cond;
+  DBuf<char> tmp;
   int rc = 0;
 #define UPV(buf, vec) { BAE_HIP(buf.alloc(std::max<size_t>((vec).size(), 1))); \
     if (!(vec).empty()) BAE_HIP(hipMemcpyAsync(buf.p, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, e->stream)); }
@@ -431,7 +430,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   BAE_HIP(e->obs_z.alloc(2 * O1)); BAE_HIP(e->obs_w0.alloc(O1)); BAE_HIP(e->obs_w.alloc(O1));
   BAE_HIP(e->obs_pose.alloc(O1)); BAE_HIP(e->obs_cam.alloc(O1)); BAE_HIP(e->obs_lm.alloc(O1));
   BAE_HIP(e->obs_cond.alloc(O1));
-  TBuf<uint32_t> lm_cnt;
+  DBuf<uint32_t> lm_cnt;
   BAE_HIP(lm_cnt.alloc((size_t)L + 1));
   BAE_HIP(hipMemsetAsync(lm_cnt.p, 0, ((size_t)L + 1) * 4, e->stream));
   if (O) {
@@ -451,6 +450,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   BAE_HIP(hipMemcpyAsync(st.lm_ptr.data(), e->lm_ptr.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, e->stream));
   if (O) BAE_HIP(hipMemcpyAsync(st.obs_perm.data(), e->obs_rid.p, (size_t)O * 4, hipMemcpyDeviceToHost, e->stream));
   BAE_HIP(hipStreamSynchronize(e->stream));
+  // (freed here, not at return: the lists below are built in the room these leave)
   r_z.release(); r_w.release(); r_pose.release(); r_lm.release(); r_cam.release(); r_cond.release();
   perm_in.release(); key_tmp.release(); lm_cnt.release();
   if (stage) stage("obs sort by landmark");
@@ -482,7 +482,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   DevGraph g = {LM, D, O, L, R, WO, st.lrow_base, e->obs_pose.p, e->obs_lm.p, e->lm_ptr.p,
                 e->lm_ref_pose.p, e->pose_opt.p, e->lm_opt.p};
   // ---- incidences -----------------------------------------------------------------------------------------
-  TBuf<uint32_t> linc_cnt, linc_ptr, inc_pose, inc_wrow;
+  DBuf<uint32_t> linc_cnt, linc_ptr, inc_pose, inc_wrow;
   BAE_HIP(linc_cnt.alloc((size_t)L + 1)); BAE_HIP(linc_ptr.alloc((size_t)L + 1));
   BAE_HIP(hipMemsetAsync(linc_cnt.p, 0, ((size_t)L + 1) * 4, e->stream));
   if (L) hipLaunchKernelGGL(k_inc_count, GRID(L), g, linc_cnt.p);
@@ -499,7 +499,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
     if (ordering_wants_graph(e) && L) {
       const auto t0 = std::chrono::steady_clock::now();
       const uint32_t G = pose_group_size(D), ng = (st.Pact + G - 1) / G;
-      TBuf<uint32_t> gp_cnt, gp_off, n_unique;
+      DBuf<uint32_t> gp_cnt, gp_off, n_unique;
       BAE_HIP(gp_cnt.alloc(L1)); BAE_HIP(gp_off.alloc(L1)); BAE_HIP(n_unique.alloc(1));
       hipLaunchKernelGGL(k_group_pair_count, GRID(L), L, G, (const uint32_t*)linc_ptr.p, (const uint32_t*)inc_pose.p,
                          gp_cnt.p);
@@ -508,7 +508,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
       uint32_t n_gp = 0;
       if ((rc = total_of(e, gp_off.p, gp_cnt.p, L, &n_gp, "group pair list"))) return rc;
       if (n_gp) {
-        TBuf<unsigned long long> gk0, gk1;
+        DBuf<unsigned long long> gk0, gk1;
         BAE_HIP(gk0.alloc(n_gp)); BAE_HIP(gk1.alloc(n_gp));
         hipLaunchKernelGGL(k_group_pairs, GRID(L), L, G, (const uint32_t*)linc_ptr.p, (const uint32_t*)inc_pose.p,
                            (const uint32_t*)gp_off.p, gk0.p);
@@ -548,7 +548,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   }
 
   // ---- rank-1 terms of the off-diagonal blocks -----------------------------------------------------------
-  TBuf<uint32_t> lrec_cnt, lrec_off, orec_cnt, orec_off, schur_cnt, schur_off, jt_cnt, jt_off;
+  DBuf<uint32_t> lrec_cnt, lrec_off, orec_cnt, orec_off, schur_cnt, schur_off, jt_cnt, jt_off;
   BAE_HIP(lrec_cnt.alloc(L1)); BAE_HIP(lrec_off.alloc(L1)); BAE_HIP(schur_cnt.alloc(L1)); BAE_HIP(schur_off.alloc(L1));
   BAE_HIP(orec_cnt.alloc(O1)); BAE_HIP(orec_off.alloc(O1)); BAE_HIP(jt_cnt.alloc(O1)); BAE_HIP(jt_off.alloc(O1));
   uint32_t n_lm_recs = 0, n_obs_recs = 0, n_schur = 0, n_jterms = 0;
@@ -576,7 +576,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   BAE_HIP(hipMemsetAsync(e->tile_ptr.p, 0, (tiles_lower + 1) * 4, e->stream));
   st.tile_nz.assign((size_t)nt * nt, 0);
   if (n_recs) {
-    TBuf<unsigned long long> k0, k1, v0;
+    DBuf<unsigned long long> k0, k1, v0;
     BAE_HIP(k0.alloc(n_recs)); BAE_HIP(k1.alloc(n_recs)); BAE_HIP(v0.alloc(n_recs));
     if (L) hipLaunchKernelGGL(k_lm_records, GRID(L), g, (const uint32_t*)linc_ptr.p, (const uint32_t*)inc_pose.p,
                               (const uint32_t*)inc_wrow.p, (const uint32_t*)lrec_off.p, k0.p, v0.p);
@@ -587,11 +587,11 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
     if ((rc = sort_pairs(e, tmp, (const unsigned long long*)k0.p, k1.p, (const unsigned long long*)v0.p,
                          reinterpret_cast<unsigned long long*>(e->pair_ent.p), n_recs,
                          bits_for((tiles_lower << 12) | 4095ull)))) return rc;
-    k0.release(); v0.release();
+    k0.release(); v0.release();   // (before the block lists are allocated: lowers the peak)
     if (stage) { BAE_HIP(hipStreamSynchronize(e->stream)); stage("pair terms sorted"); }
     // blocks, tile references
-    TBuf<uint32_t> flag, fidx, starts, cursor;
-    TBuf<int> ovf;
+    DBuf<uint32_t> flag, fidx, starts, cursor;
+    DBuf<int> ovf;
     BAE_HIP(flag.alloc(n_recs)); BAE_HIP(fidx.alloc(n_recs)); BAE_HIP(ovf.alloc(1));
     BAE_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), e->stream));
     hipLaunchKernelGGL(k_block_flags, GRID(n_recs), n_recs, (const unsigned long long*)k1.p, flag.p);
@@ -616,14 +616,13 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
     BAE_HIP(hipMemcpyAsync(cursor.p, e->tile_ptr.p, (tiles_lower + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
     hipLaunchKernelGGL(k_tile_refs<1>, GRID(st.n_pairs), st.n_pairs, nt, (const uint32_t*)starts.p,
                        (const unsigned long long*)k1.p, cursor.p, e->tile_ref.p, ovf.p);
-    TBuf<uint8_t> nz;
+    DBuf<uint8_t> nz;
     BAE_HIP(nz.alloc((size_t)nt * nt));
     BAE_HIP(hipMemsetAsync(nz.p, 0, (size_t)nt * nt, e->stream));
     hipLaunchKernelGGL(k_tile_pattern, GRID(tiles_lower), nt, (const uint32_t*)e->tile_ptr.p, nz.p);
     BAE_HIP(hipGetLastError());
     BAE_HIP(hipMemcpyAsync(st.tile_nz.data(), nz.p, (size_t)nt * nt, hipMemcpyDeviceToHost, e->stream));
     BAE_HIP(hipStreamSynchronize(e->stream));
-    flag.release(); fidx.release(); starts.release(); cursor.release(); ovf.release(); nz.release(); k1.release();
   } else {
     BAE_HIP(e->tile_ref.alloc(1));
   }
@@ -638,8 +637,8 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
   BAE_HIP(e->pose_ent.alloc(std::max<size_t>(3 * (size_t)n_pe, 1)));
   static_assert(sizeof(PoseEnt) == sizeof(U3), "per-pose term = three words");
   {
-    TBuf<uint32_t> pk0, pk1;
-    TBuf<PoseEnt> pe0;
+    DBuf<uint32_t> pk0, pk1;
+    DBuf<PoseEnt> pe0;
     BAE_HIP(pk0.alloc(std::max<size_t>(n_pe, 1))); BAE_HIP(pk1.alloc(std::max<size_t>(n_pe, 1)));
     BAE_HIP(pe0.alloc(std::max<size_t>(n_pe, 1)));
     if (O) hipLaunchKernelGGL(k_pose_jterms, GRID(O), g, (const uint32_t*)jt_off.p, pk0.p, pe0.p);
@@ -654,12 +653,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
                        e->pose_mid.p);
     BAE_HIP(hipGetLastError());
     BAE_HIP(hipStreamSynchronize(e->stream));
-    pk0.release(); pk1.release(); pe0.release();
   }
-  linc_cnt.release(); linc_ptr.release(); inc_pose.release(); inc_wrow.release();
-  lrec_cnt.release(); lrec_off.release(); orec_cnt.release(); orec_off.release();
-  schur_cnt.release(); schur_off.release(); jt_cnt.release(); jt_off.release();
-  tmp.release();
   // the diagonal D x D blocks (and the padding identity) are always present in the tile pattern
   for (uint32_t p = 0; p < st.Pact; ++p) {
     const uint32_t r0 = p * D / 64, r1 = (p * D + D - 1) / 64;

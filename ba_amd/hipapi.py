@@ -180,7 +180,7 @@ SYMBOLS = [
     "ba_hip_release_marginalization", "ba_hip_set_unary_scales",
     "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve", "ba_hip_tile_solve",
     "ba_hip_get_pcg_coarse_stats", "ba_hip_get_pcg_coarse",
-    "ba_hip_get_projection_leverages", "ba_hip_get_leverage_stats",
+    "ba_hip_get_projection_leverages", "ba_hip_get_leverage_stats", "ba_hip_device_bytes_live",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -222,11 +222,17 @@ def lib():
         _lib.ba_hip_num_pose_params.restype = C.c_uint32
         _lib.ba_hip_num_lm_params.restype = C.c_uint32
         _lib.ba_hip_num_calib_params.restype = C.c_uint32
+        _lib.ba_hip_device_bytes_live.restype = C.c_uint64
     return _lib
 
 
 class HipError(RuntimeError):
     pass
+
+
+def device_bytes_live():
+    """Device bytes held by the buffers of every live engine of this process (ba_hip_device_bytes_live)."""
+    return int(lib().ba_hip_device_bytes_live())
 
 
 def _d(a):

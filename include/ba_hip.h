@@ -99,6 +99,9 @@ typedef struct {
 int ba_hip_create(int lm_dim, int pose_dim, int device, void* stream, ba_hip_engine** out);
 void ba_hip_destroy(ba_hip_engine* e);
 const char* ba_hip_last_error(const ba_hip_engine* e);
+/* Bytes of device memory currently held by the engines' own buffers, summed over all engines of the process
+ * (work space of calls in flight included); back at its earlier value once an engine is destroyed. */
+uint64_t ba_hip_device_bytes_live(void);
 int ba_hip_set_options(ba_hip_engine* e, const ba_hip_options* o);
 /* The reference's CalibSize / DoTvs template parameters (BundleAdjuster.h:110-134).  do_tvs != 0:
  * the extrinsics T_vs of camera 0 become six more unknowns BEHIND the pose unknowns of the reduced
