@@ -14,15 +14,19 @@
 // The reference's recording (`log.dat`) is elided from its tree; `make_log.py` next to this file
 // writes a synthetic one in the same format (committed as log.dat).
 //
-//   unary_binary_imu_test <log.dat> [--dump-graph <file>]
+//   unary_binary_imu_test <log.dat> [--dump-graph <file>] [--leverages]
 //
 // prints one line per node (id, time, position) after the solve; --dump-graph writes the graph the
 // program handed to the adjuster (poses, unary constraints, IMU residuals) so that the test can
-// feed the identical graph to the oracle.  Exit code 0 iff the solver reports a good result.
+// feed the identical graph to the oracle.  --leverages: after the solve, the median and the largest
+// leverage tr(C Lambda) of the position fixes and of the inertial residuals (GetPosePoseLeverages: how
+// much of each the fit absorbs; a fix with a leverage near its rank is checked by nothing else).
+// Exit code 0 iff the solver reports a good result.
 #include <ba/BundleAdjuster.h>
 #include <ba/InterpolationBuffer.h>
 #include <ba/Types.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -183,11 +187,25 @@ bool parse_file(const char* filename) {
   return ok;
 }
 
+// median and maximum of the leverages of one residual kind; false when they are unavailable
+bool print_leverages(const char* label, int kind) {
+  std::vector<double> lev;
+  if (!slam.GetPosePoseLeverages(kind, {}, nullptr, nullptr, &lev)) return false;
+  if (lev.empty()) { std::printf("LEVERAGES %s count 0\n", label); return true; }
+  std::sort(lev.begin(), lev.end());
+  std::printf("LEVERAGES %s count %zu median %.17g max %.17g\n", label, lev.size(), lev[lev.size() / 2], lev.back());
+  return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc < 2) { std::fprintf(stderr, "usage: %s <log.dat> [--dump-graph <file>]\n", argv[0]); return 2; }
-  if (argc >= 4 && std::strcmp(argv[2], "--dump-graph") == 0) graph_dump = std::fopen(argv[3], "w");
+  if (argc < 2) { std::fprintf(stderr, "usage: %s <log.dat> [--dump-graph <file>] [--leverages]\n", argv[0]); return 2; }
+  bool leverages = false;
+  for (int i = 2; i < argc; ++i) {
+    if (std::strcmp(argv[i], "--dump-graph") == 0 && i + 1 < argc) graph_dump = std::fopen(argv[++i], "w");
+    else if (std::strcmp(argv[i], "--leverages") == 0) leverages = true;
+  }
   setup();
   if (!parse_file(argv[1])) return 2;
   if (graph_dump) std::fclose(graph_dump);
@@ -204,5 +222,10 @@ int main(int argc, char** argv) {
   slam.GetErrors(e_proj, e_unary, e_binary, e_inertial);
   std::printf("SUMMARY result %d unary_error %.17g inertial_error %.17g delta_norm %.17g\n", (int)s.result, e_unary,
               e_inertial, (double)s.delta_norm);
-  return s.IsResultGood() ? 0 : 1;
+  const bool good = s.IsResultGood();   // (a refused leverage request below marks the summary)
+  if (leverages && !(print_leverages("unary", BA_HIP_RES_UNARY) && print_leverages("inertial", BA_HIP_RES_IMU))) {
+    std::printf("leverages unavailable\n");
+    return 2;
+  }
+  return good ? 0 : 1;
 }

@@ -73,6 +73,7 @@ SYMBOLS = [
     "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
     "ba_adjuster_get_projection_leverage", "ba_adjuster_get_projection_redundancy",
     "ba_adjuster_get_joint_pose_covariance",
+    "ba_adjuster_get_pose_pose_leverages", "ba_adjuster_get_pose_pose_leverage",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
 ]
@@ -466,6 +467,42 @@ class BundleAdjuster:
         if self.L.ba_adjuster_get_projection_redundancy(self.h, C.c_uint32(int(residual_id) & 0xFFFFFFFF), C.byref(r)):
             raise RuntimeError("redundancy of projection residual %d unavailable (see stderr)" % residual_id)
         return r.value
+
+    def pose_pose_leverages(self, kind, ids=None, count=None):
+        """GetPosePoseLeverages: (cov, info, leverage) = ((n, 15, 15), (n, 15, 15), (n,)) of the unary / binary /
+        inertial residuals `ids` (kind: hipapi.RES_UNARY / RES_BINARY / RES_IMU; ids=None: every residual of the
+        kind in id order, `count` of them); raises when unavailable."""
+        dp, n = C.POINTER(C.c_double), count
+        if ids is not None:
+            ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32).ravel()
+            n = len(ids)
+        elif n is None:
+            raise ValueError("pose_pose_leverages: ids=None needs the residual count of the kind")
+        cov, info, lev = np.zeros((n, 15, 15)), np.zeros((n, 15, 15)), np.zeros(n)
+        if self.L.ba_adjuster_get_pose_pose_leverages(
+                self.h, int(kind), int(n), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                cov.ctypes.data_as(dp), info.ctypes.data_as(dp), lev.ctypes.data_as(dp)):
+            raise RuntimeError("pose-pose leverages of kind %d unavailable (see stderr)" % kind)
+        return cov, info, lev
+
+    def _pose_pose_leverage(self, kind, residual_id):
+        r = C.c_double()
+        if self.L.ba_adjuster_get_pose_pose_leverage(self.h, int(kind), C.c_uint32(int(residual_id) & 0xFFFFFFFF),
+                                                     C.byref(r)):
+            raise RuntimeError("leverage of residual %d of kind %d unavailable (see stderr)" % (residual_id, kind))
+        return r.value
+
+    def GetUnaryLeverage(self, residual_id):
+        """GetUnaryLeverage: tr(C Lambda) of a unary residual; raises when unavailable."""
+        return self._pose_pose_leverage(hipapi.RES_UNARY, residual_id)
+
+    def GetBinaryLeverage(self, residual_id):
+        """GetBinaryLeverage: tr(C Lambda) of a binary residual; raises when unavailable."""
+        return self._pose_pose_leverage(hipapi.RES_BINARY, residual_id)
+
+    def GetImuLeverage(self, residual_id):
+        """GetImuLeverage: tr(C Lambda) of an inertial residual; raises when unavailable."""
+        return self._pose_pose_leverage(hipapi.RES_IMU, residual_id)
 
     def camera_params(self, cam_id=0):
         """rig()->cameras_[cam_id]->GetParams()"""

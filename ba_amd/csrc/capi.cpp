@@ -52,6 +52,8 @@ struct Iface {
   virtual uint32_t marginals(double* cov) const = 0;
   virtual uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) = 0;
   virtual uint32_t joint_covariance(uint32_t n, const uint32_t* ids, int include_calibration, double* out) = 0;
+  virtual int pose_pose_leverages(int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev) = 0;
+  virtual double pose_pose_leverage(int kind, uint32_t id) = 0;
   virtual int marginalize(uint32_t nm, const uint32_t* m, uint32_t nl, const uint32_t* l, uint32_t* nb) = 0;
   virtual void marginalization(uint32_t* ids, double* x0, double* H, double* b, double* c, uint32_t* dropped) const = 0;
   virtual uint32_t add_dense_prior(uint32_t k, const uint32_t* ids, const double* x0, const double* H, const double* b,
@@ -261,6 +263,21 @@ struct Impl : Iface {
     for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
     return (uint32_t)m.rows();
   }
+  int pose_pose_leverages(int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev) override {
+    std::vector<double> c, i, l;
+    if (!ba.GetPosePoseLeverages(kind, ids ? std::vector<uint32_t>(ids, ids + n) : std::vector<uint32_t>(),
+                                 cov ? &c : nullptr, info ? &i : nullptr, lev ? &l : nullptr))
+      return 1;
+    if ((cov && c.size() != 225 * (size_t)n) || (info && i.size() != 225 * (size_t)n) || (lev && l.size() != n)) return 1;
+    if (cov) std::copy(c.begin(), c.end(), cov);
+    if (info) std::copy(i.begin(), i.end(), info);
+    if (lev) std::copy(l.begin(), l.end(), lev);
+    return 0;
+  }
+  double pose_pose_leverage(int kind, uint32_t id) override {
+    return kind == BA_HIP_RES_UNARY ? ba.GetUnaryLeverage(id) : kind == BA_HIP_RES_BINARY ? ba.GetBinaryLeverage(id)
+                                                                                           : ba.GetImuLeverage(id);
+  }
   void last_calib_step(double* d6) const override {
     const auto& d = ba.GetLastStep().delta_k;
     for (size_t i = 0; i < 6; ++i) d6[i] = i < d.size() ? d[i] : 0.0;
@@ -410,6 +427,16 @@ int ba_adjuster_get_projection_redundancy(ba_adjuster* a, uint32_t residual_id, 
   if (!redundancy || a->p->covariance(3, residual_id, 0, h) != 2) return 1;
   *redundancy = 2.0 - (h[0] + h[3]);
   return 0;
+}
+int ba_adjuster_get_pose_pose_leverages(ba_adjuster* a, int kind, uint32_t n, const uint32_t* ids, double* cov,
+                                        double* info, double* leverage) {
+  if (kind < BA_HIP_RES_UNARY || kind > BA_HIP_RES_IMU || (ids && !n)) return 1;
+  return a->p->pose_pose_leverages(kind, n, ids, cov, info, leverage);
+}
+int ba_adjuster_get_pose_pose_leverage(ba_adjuster* a, int kind, uint32_t id, double* leverage) {
+  if (kind < BA_HIP_RES_UNARY || kind > BA_HIP_RES_IMU || !leverage) return 1;
+  *leverage = a->p->pose_pose_leverage(kind, id);
+  return *leverage == *leverage ? 0 : 1;
 }
 uint32_t ba_adjuster_get_joint_pose_covariance(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids,
                                                int include_calibration, double* cov) {

@@ -275,6 +275,7 @@ struct Engine {
   std::vector<uint32_t> lev_pos;         // its plan (lever.h): sorted position of every residual id, and the block
   uint64_t lev_reads_all = 0;            // reads / landmarks of the all-residuals pass; rebuilt after ba_hip_finalize
   uint32_t lev_lms_all = 0;
+  ba_hip_pose_pose_leverage_stats ppl_stats = {};   // the last ba_hip_get_pose_pose_leverages (k_pplever.hip)
   // dense pose priors (ba_hip_set_dense_priors, k_marg.hip): the caller's priors, their device copies (uploaded
   // by ba_hip_finalize), the lower D x D blocks of every prior (dp_blk, prior q from dp_blk_first[q]) and the
   // per-linearisation values: d, J_d, G = J_d^T H J_d, g = J_d^T (b - H d), w = b - H d, E_p
@@ -480,6 +481,10 @@ void marginals_release(Engine* e);
 // leverages of projection residuals from the selected inverse (k_lever.hip): out[q] = the 2 x 2 block of residual
 // ids[q] (checked by the caller), or with null ids of every residual in residual-id order (n = st.O)
 int leverages_run(Engine* e, uint32_t n, const uint32_t* ids, double* out);
+// leverages of unary / binary / inertial residuals from the selected inverse (k_pplever.hip): per requested residual
+// of `kind` (ids within the kind, checked by the caller; null: all n of them in id order) the 15 x 15 blocks C and
+// Lambda and the leverage tr(C Lambda); any output may be null
+int pose_pose_leverages_run(Engine* e, int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev);
 // joint covariance of the rows `sel` of S (engine numbering) from the factor in A (k_jointcov.hip): out is
 // sel x sel on the host; reads A and invdiag only
 int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out);

@@ -1564,6 +1564,39 @@ int ba_hip_get_leverage_stats(ba_hip_engine* h, ba_hip_leverage_stats* out) {
   *out = e->lstats;
   return 0;
 }
+// ---- leverages of unary, binary and inertial residuals (k_pplever.hip) ----
+int ba_hip_get_pose_pose_leverages(ba_hip_engine* h, int kind, uint32_t n, const uint32_t* ids, double* cov, double* info,
+                                   double* leverage) {
+  ENG(h);
+  static const char* what = "ba_hip_get_pose_pose_leverages";
+  const std::string m = std::string(what) + ": ";
+  if (kind != BA_HIP_RES_UNARY && kind != BA_HIP_RES_BINARY && kind != BA_HIP_RES_IMU)
+    return e->fail_msg((m + "kind " + std::to_string(kind) + " is none of BA_HIP_RES_UNARY, _BINARY, _IMU").c_str());
+  int rc;
+  if ((rc = marginals_ready(e, what, false))) return rc;
+  static const char* names[3] = {"a unary", "a binary", "an inertial"};
+  const Problem& pb = e->prob;
+  const uint32_t count = kind == BA_HIP_RES_UNARY ? pb.num_unary : kind == BA_HIP_RES_BINARY ? pb.num_binary : pb.num_imu;
+  if (n && !cov && !info && !leverage) return e->fail_msg((m + "every output is NULL").c_str());
+  if (!ids && n != count)
+    return e->fail_msg((m + "with NULL ids n must be the residual count of the kind (" + std::to_string(count) + ")").c_str());
+  if (ids)
+    for (uint32_t i = 0; i < n; ++i)
+      if (ids[i] >= count)
+        return e->fail_msg((m + "id " + std::to_string(ids[i]) + " is not " + names[kind] + " residual (there are " +
+                            std::to_string(count) + ")").c_str());
+  return pose_pose_leverages_run(e, kind, n, ids, cov, info, leverage);
+}
+uint32_t ba_hip_num_pose_pose_residuals(const ba_hip_engine* h, int kind) {
+  const Problem& pb = reinterpret_cast<const Engine*>(h)->prob;
+  return kind == BA_HIP_RES_UNARY ? pb.num_unary : kind == BA_HIP_RES_BINARY ? pb.num_binary : kind == BA_HIP_RES_IMU ? pb.num_imu : 0;
+}
+int ba_hip_get_pose_pose_leverage_stats(ba_hip_engine* h, ba_hip_pose_pose_leverage_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_pose_pose_leverage_stats: NULL argument");
+  *out = e->ppl_stats;
+  return 0;
+}
 // ---- joint covariance of a pose set (k_jointcov.hip): Y = L^-1 E over the reach, Sigma = Y^T D Y ----
 int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,
                                double* out) {

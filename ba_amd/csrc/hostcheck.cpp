@@ -689,3 +689,30 @@ extern "C" int ba_hostcheck_leverages(int LM, int D, int K, uint32_t P, const ui
     for (int i = 0; i < 4; ++i) out[4 * (size_t)st.obs_perm[s] + i] = sorted[4 * (size_t)s + i];
   return 0;
 }
+
+// ---- leverages of unary, binary and inertial residuals (pplever.h) -----------------------------------------
+#include "pplever.h"
+
+// pose_pose_leverage_host on the caller's residuals: dz [nres][2][225] (dz1 | dz2, unmasked columns), info
+// [nres][225] WITHOUT the weight, weight [nres] or null (Lambda = weight * info), p1 / p2 pose ids (p2 = 0xffffffff
+// for a unary residual), activity and masks by pose id, dense Sigma (n x n, n = active poses * D, poses in id
+// order).  cov, lam: [nres][225], lev: [nres]; any may be null.  variant: pplever.h.
+extern "C" int ba_hostcheck_pose_pose_leverages(int D, uint32_t P, const uint8_t* pose_active, const uint16_t* pose_mask,
+                                                uint32_t nres, const uint32_t* p1, const uint32_t* p2, const double* dz,
+                                                const double* info, const double* weight, uint32_t n, const double* sigma,
+                                                int variant, double* cov, double* lam, double* lev) {
+  using namespace bae;
+  if (D < 6 || D > kPPLevDim || !pose_active || !pose_mask || !sigma || (nres && (!p1 || !p2 || !dz || !info))) return -1;
+  std::vector<int32_t> opt(P, -1);
+  uint32_t k = 0;
+  for (uint32_t p = 0; p < P; ++p)
+    if (pose_active[p]) opt[p] = (int32_t)k++;
+  if (n != k * (uint32_t)D) return -2;
+  for (uint32_t q = 0; q < nres; ++q)
+    if (p1[q] >= P || (p2[q] != kPPLevNoPose && p2[q] >= P)) return -3;
+  PPLeverHostIn in;
+  in.D = D; in.nres = nres; in.n = n; in.p1 = p1; in.p2 = p2; in.pose_opt = opt.data(); in.pose_mask = pose_mask;
+  in.dz = dz; in.info = info; in.weight = weight; in.sigma = sigma;
+  pose_pose_leverage_host(in, variant, cov, lam, lev);
+  return 0;
+}

@@ -120,6 +120,11 @@ class LeverageStats(C.Structure):
                 ("landmarks", C.c_uint32)]
 
 
+class PosePoseLeverageStats(C.Structure):
+    _fields_ = [("device_ms", C.c_double), ("sigma_blocks", C.c_uint64), ("residuals", C.c_uint32),
+                ("kind", C.c_uint32)]
+
+
 JOINT_MAX_COLUMNS = 512  # BA_HIP_JOINT_MAX_COLUMNS
 
 
@@ -181,10 +186,12 @@ SYMBOLS = [
     "ba_hip_set_reduced_solver", "ba_hip_get_pcg_stats", "ba_hip_pcg_solve", "ba_hip_tile_solve",
     "ba_hip_get_pcg_coarse_stats", "ba_hip_get_pcg_coarse",
     "ba_hip_get_projection_leverages", "ba_hip_get_leverage_stats", "ba_hip_device_bytes_live",
+    "ba_hip_get_pose_pose_leverages", "ba_hip_get_pose_pose_leverage_stats", "ba_hip_num_pose_pose_residuals",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
 SOLVER_DIRECT, SOLVER_PCG = 0, 1                 # ba_hip_set_reduced_solver modes
+RES_UNARY, RES_BINARY, RES_IMU = 0, 1, 2         # BA_HIP_RES_*: kinds of ba_hip_get_pose_pose_leverages
 
 
 def build(force=False):
@@ -223,6 +230,7 @@ def lib():
         _lib.ba_hip_num_lm_params.restype = C.c_uint32
         _lib.ba_hip_num_calib_params.restype = C.c_uint32
         _lib.ba_hip_device_bytes_live.restype = C.c_uint64
+        _lib.ba_hip_num_pose_pose_residuals.restype = C.c_uint32
     return _lib
 
 
@@ -479,6 +487,29 @@ class Engine:
         st = LeverageStats()
         self._chk(self.L.ba_hip_get_leverage_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in LeverageStats._fields_}
+
+    # ---- leverages of unary, binary and inertial residuals (hat blocks; ba_hip.h) ----
+    def pose_pose_leverages(self, kind, ids=None, count=None, want=(True, True, True)):
+        """(cov, info, leverage) = ((n, 15, 15), (n, 15, 15), (n,)) of the residuals `ids` of `kind` (RES_UNARY,
+        RES_BINARY, RES_IMU): C = J Sigma J^T in the residual's raw coordinates, the effective information Lambda,
+        tr(C Lambda).  ids=None: every residual of the kind in id order (count: their number, default the
+        engine's).  want: which of the three outputs to ask for (None in place of the others)."""
+        if ids is None:
+            n = int(self.L.ba_hip_num_pose_pose_residuals(self.h, int(kind))) if count is None else int(count)
+            idp = None
+        else:
+            ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32).ravel()
+            n, idp = len(ids), _p(ids, u32p)
+        cov = np.empty((n, 15, 15)) if want[0] else None
+        info = np.empty((n, 15, 15)) if want[1] else None
+        lev = np.empty(n) if want[2] else None
+        self._chk(self.L.ba_hip_get_pose_pose_leverages(self.h, int(kind), n, idp, _p(cov, dp), _p(info, dp), _p(lev, dp)))
+        return cov, info, lev
+
+    def pose_pose_leverage_stats(self):
+        st = PosePoseLeverageStats()
+        self._chk(self.L.ba_hip_get_pose_pose_leverage_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in PosePoseLeverageStats._fields_}
 
     # ---- joint covariance of a pose set (forward substitution + Gram product, no selected inverse) ----
     def joint_marginals(self, ids, include_calibration=False):

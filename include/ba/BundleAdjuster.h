@@ -639,6 +639,48 @@ class BundleAdjuster {
     if (h.rows() != 2) return std::numeric_limits<Scalar>::quiet_NaN();
     return 2.0 - (h.data()[0] + h.data()[3]);
   }
+  // Leverages of unary, binary and inertial residuals (extension; include/ba_hip.h ba_hip_get_pose_pose_leverages,
+  // DESIGN.md section 16), for the ids AddUnaryConstraint / AddBinaryConstraint / AddImuResidual returned, of the
+  // system the last Solve() factorised.  kind: BA_HIP_RES_UNARY / _BINARY / _IMU; an empty ids means every residual
+  // of the kind in id order.  Per residual cov and info hold 225 values (15 x 15 row-major, zero outside the
+  // residual's own block): C = J Sigma J^T in the residual's raw coordinates and the effective information Lambda
+  // (ba_hip.h says which per kind); leverage = tr(C Lambda).  With Lambda = G G^T: whitened hat block G^T C G,
+  // post-fit covariance Lambda^-1 - C, studentised statistic r^T (Lambda^-1 - C)^-1 r, gate Lambda^-1 + C.
+  // Any output may be null.  false (outputs empty) when unavailable: an id that was never returned, no solve yet,
+  // the PCG or distributed solve.
+  bool GetPosePoseLeverages(int kind, const std::vector<uint32_t>& ids, std::vector<double>* cov,
+                            std::vector<double>* info, std::vector<double>* leverage) {
+    const size_t count = kind == BA_HIP_RES_UNARY ? un_pose_.size() : kind == BA_HIP_RES_BINARY ? bin_p1_.size()
+                         : kind == BA_HIP_RES_IMU ? imu_p1_.size() : 0;
+    const uint32_t n = ids.empty() ? (uint32_t)count : (uint32_t)ids.size();
+    auto clear = [&]() {
+      if (cov) cov->clear();
+      if (info) info->clear();
+      if (leverage) leverage->clear();
+      return false;
+    };
+    for (uint32_t id : ids)
+      if (id >= count) {
+        std::cerr << "ba::BundleAdjuster::GetPosePoseLeverages: " << id << " is not the id of a residual of kind "
+                  << kind << std::endl;
+        return clear();
+      }
+    if (cov) cov->assign(225 * (size_t)n, 0.0);
+    if (info) info->assign(225 * (size_t)n, 0.0);
+    if (leverage) leverage->assign(n, 0.0);
+    if (n == 0) return engine_ != nullptr;
+    if (!engine_ || !Check(ba_hip_get_pose_pose_leverages(engine_, kind, n, ids.empty() ? nullptr : ids.data(),
+                                                          cov ? cov->data() : nullptr, info ? info->data() : nullptr,
+                                                          leverage ? leverage->data() : nullptr),
+                           "ba_hip_get_pose_pose_leverages"))
+      return clear();
+    return true;
+  }
+  // The leverage tr(C Lambda) of one residual: how much of it the fit absorbs (0: nothing; its rank: it is always
+  // fitted exactly).  NaN, reported through Check() or on stderr, when unavailable.
+  Scalar GetUnaryLeverage(uint32_t id) { return PosePoseLeverage(BA_HIP_RES_UNARY, id); }
+  Scalar GetBinaryLeverage(uint32_t id) { return PosePoseLeverage(BA_HIP_RES_BINARY, id); }
+  Scalar GetImuLeverage(uint32_t id) { return PosePoseLeverage(BA_HIP_RES_IMU, id); }
   Scalar trust_region_size() const { return trust_region_size_; }
   const ba_hip_timers& GetLastTimers() const { return last_timers_; }
   uint32_t iterations_run() const { return iterations_run_; }
@@ -705,6 +747,12 @@ class BundleAdjuster {
               << (engine_ ? ba_hip_last_error(engine_) : "no engine") << std::endl;
     summary_.result = SolverError;
     return false;
+  }
+  Scalar PosePoseLeverage(int kind, uint32_t id) {
+    std::vector<double> lev;
+    if (!GetPosePoseLeverages(kind, std::vector<uint32_t>(1, id), nullptr, nullptr, &lev) || lev.size() != 1)
+      return std::numeric_limits<Scalar>::quiet_NaN();
+    return lev[0];
   }
   bool UploadProblem();
   bool SyncEngine();

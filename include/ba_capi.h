@@ -135,6 +135,15 @@ uint32_t ba_adjuster_get_landmark_covariance(ba_adjuster* a, uint32_t landmark_i
  * when unavailable. */
 uint32_t ba_adjuster_get_projection_leverage(ba_adjuster* a, uint32_t residual_id, double* h4);
 int ba_adjuster_get_projection_redundancy(ba_adjuster* a, uint32_t residual_id, double* redundancy);
+/* GetPosePoseLeverages / GetUnaryLeverage, GetBinaryLeverage, GetImuLeverage (extension): leverages of the unary,
+ * binary or inertial residuals (kind: BA_HIP_RES_UNARY / _BINARY / _IMU of include/ba_hip.h) with the ids the add
+ * calls returned.  The batched form writes per residual 225 values (15 x 15 row-major) into cov (C = J Sigma J^T)
+ * and info (the effective information Lambda) and one value into leverage (tr(C Lambda)); any of the three may be
+ * NULL; ids NULL: every residual of the kind in id order, n = their count.  The single form writes tr(C Lambda) of
+ * one residual (NaN when unavailable).  Both return 0, or 1 when unavailable. */
+int ba_adjuster_get_pose_pose_leverages(ba_adjuster* a, int kind, uint32_t n, const uint32_t* ids, double* cov,
+                                        double* info, double* leverage);
+int ba_adjuster_get_pose_pose_leverage(ba_adjuster* a, int kind, uint32_t id, double* leverage);
 /* GetJointPoseCovariance (extension): the M x M joint covariance of the n poses pose_ids in the caller's order,
  * M = n PoseSize (+ the calibration rows last with include_calibration), row-major into cov (room for M^2
  * values); returns M, 0 when unavailable (the summary's result then reads SolverError) */

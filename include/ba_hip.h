@@ -530,7 +530,8 @@ int ba_hip_release_marginals(ba_hip_engine* e);
  * with Sigma = S^-1 from the selected inverse (computed on demand) and Sigma_ll the landmark marginal.  From it:
  * redundancy 2 - tr H_aa, post-fit residual covariance I - H_aa, studentised residual r^T (I - H_aa)^-1 r,
  * innovation gate I + H_aa.  0 <= H_aa <= I; with projection residuals only and nothing masked the traces sum
- * to the number of unknowns.
+ * to the number of unknowns.  With unary, binary or inertial residuals in the system the sum falls short by their
+ * leverages: ba_hip_get_pose_pose_leverages serves those and completes the identity.
  *   - Preconditions of ba_hip_get_landmark_marginals: finalized, the factor of the last direct ba_hip_solve_gn
  *     (not PCG), not re-linearised since, not sharded or distributed.  Pose orderings are invisible.
  *   - Errors: an id that is no projection residual, NULL with n > 0, n != residual count with NULL ids, LmSize 0.
@@ -559,6 +560,52 @@ typedef struct {
 } ba_hip_leverage_stats;
 /* The figures of the last successful ba_hip_get_projection_leverages (zeros before the first). */
 int ba_hip_get_leverage_stats(ba_hip_engine* e, ba_hip_leverage_stats* out);
+
+/* ---- leverages of unary, binary and inertial residuals (hat blocks) -----------------------
+ * Residual i of a kind couples pose p1 and (binary, inertial) p2.  With
+ *   J_i       = [dz1 | dz2], R x 2 D: the UNWHITENED Jacobians of the residual in its own raw coordinates (R = 6 for
+ *               unary and binary residuals, PoseSize for inertial ones); the column of a masked parameter and the
+ *               block of an inactive pose are zero,
+ *   Lambda_i    the EFFECTIVE information, for which J_i^T Lambda_i J_i is what the residual added to S:
+ *                 unary     cov_inv x scale (ba_hip_get_unary_scales: the compounded Huber weights),
+ *                 binary    weight x cov_inv_sqrt^T cov_inv_sqrt, with cov_inv_sqrt as the caller supplied it (the
+ *                           engine's internal copy of cov_inv is unweighted and is NOT Lambda_i),
+ *                 inertial  cov_inv x Huber factor of the last linearisation,
+ *   Sigma_ee    the block of Sigma = S^-1 over the rows of p1, p2 (selected inverse, computed on demand),
+ * the call serves C_i = J_i Sigma_ee J_i^T (the covariance of the predicted residual, bitwise symmetric), Lambda_i
+ * as used, and the leverage l_i = tr(C_i Lambda_i).  With any square root Lambda = G G^T: the whitened hat block
+ * G^T C G (0 <= . <= I), redundancy R_eff - l_i, post-fit residual covariance Lambda^-1 - C, studentised statistic
+ * r^T (Lambda^-1 - C)^-1 r, innovation gate Lambda^-1 + C.  Over all residual kinds, nothing masked and every
+ * unknown touched: sum tr H_aa (projection) + sum l_i = number of unknowns (dense priors of
+ * ba_hip_set_dense_priors are not served; the identity holds for systems without them).
+ *   - Preconditions of the pose getters: finalized, the factor of the last direct ba_hip_solve_gn (not PCG), not
+ *     re-linearised since, not the distributed solve (replicated sharded engines are served).  LmSize 0 and every
+ *     PoseSize work; pose orderings are invisible.
+ *   - Errors: an unknown kind, an id beyond the kind's count, n != the kind's count with NULL ids, all three outputs
+ *     NULL with n > 0, a pose pair whose block of Sigma is outside the factor's pattern (not possible for poses a
+ *     residual couples; reported, never returned as NaN).
+ *   - A binary residual with use_rotation = 0 has zero rows 3..5 in J: C is zero there, info is not.
+ *   - A residual whose poses are all inactive reads zero in cov and leverage.
+ *   - A repeated id returns the same bits twice, and an id's bits are those of the all-residuals call.
+ *   - Nothing is allocated on the device before the first request and nothing is kept there between requests
+ *     beyond the Sigma store (ba_hip_release_marginals). */
+#define BA_HIP_RES_UNARY 0
+#define BA_HIP_RES_BINARY 1
+#define BA_HIP_RES_IMU 2
+/* cov, info: n x 225 (15 x 15 row-major, zero outside the residual's R x R block), either may be NULL;
+ * leverage: n, may be NULL; ids NULL: every residual of the kind in id order (n = their count). */
+int ba_hip_get_pose_pose_leverages(ba_hip_engine* e, int kind, uint32_t n, const uint32_t* ids, double* cov,
+                                   double* info, double* leverage);
+typedef struct {
+  double device_ms;       /* device time of the last pass (events) */
+  uint64_t sigma_blocks;  /* D x D blocks of Sigma it read: (live poses)^2 per residual */
+  uint32_t residuals;     /* residuals served */
+  uint32_t kind;          /* their kind */
+} ba_hip_pose_pose_leverage_stats;
+/* The residuals of a kind in the engine (what n must be with NULL ids); 0 for an unknown kind. */
+uint32_t ba_hip_num_pose_pose_residuals(const ba_hip_engine* e, int kind);
+/* The figures of the last ba_hip_get_pose_pose_leverages that passed its checks (zeros before the first). */
+int ba_hip_get_pose_pose_leverage_stats(ba_hip_engine* e, ba_hip_pose_pose_leverage_stats* out);
 
 /* ---- joint covariance of an arbitrary pose set (no selected inverse) ------------------
  * The M x M block of Sigma = S^-1 over the rows of the poses pose_ids (and, with include_calibration, the K
