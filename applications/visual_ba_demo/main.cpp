@@ -27,7 +27,9 @@
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
 //                                           GetLandmarkCovariance: selected inverse of the reduced system), then
 //                                           the norm of the cross covariance between the first active and the last
-//                                           pose and the time of the joint call (GetJointPoseCovariance)
+//                                           pose and the time of the joint call (GetJointPoseCovariance), and the
+//                                           largest correlation between the last pose and the last landmark with
+//                                           the time of that call (GetJointCovariance: the cross blocks)
 //   visual_ba_demo --leverages              after the solve: the median and the smallest redundancy number
 //                                           2 - tr H_aa of the projection residuals (GetProjectionLeverages: hat
 //                                           blocks from the selected inverse) and the five residuals with the
@@ -280,7 +282,18 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
       }
     std::printf("cross covariance of poses 2 and %d: norm %.3e (%.3e of pose %d's own block), joint call %.3f ms\n", kPoses - 1,
                 std::sqrt(cross), std::sqrt(cross / diag), kPoses - 1, joint_ms);
-    ok = ok && std::isfinite(c(0, 0)) && c(0, 0) > 0 && sl[sl.size() / 2] > 0;
+    // the last pose and the last landmark jointly: the pose-landmark cross block
+    const uint32_t lm = adjuster.GetNumLandmarks() - 1;
+    ba::MatX mixed;
+    const auto m0 = std::chrono::steady_clock::now();
+    const bool mok = adjuster.GetJointCovariance({(uint32_t)(kPoses - 1)}, {lm}, mixed);
+    const double mixed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - m0).count();
+    if (!mok || mixed.rows() != 7) { std::printf("joint pose-landmark covariance unavailable\n"); return 2; }
+    double corr = 0.0;
+    for (int i = 0; i < 6; ++i) corr = std::max(corr, std::fabs(mixed(i, 6)) / std::sqrt(mixed(i, i) * mixed(6, 6)));
+    std::printf("pose %d and landmark %u: largest pose-landmark correlation %.3f, joint call %.3f ms\n", kPoses - 1, lm, corr,
+                mixed_ms);
+    ok = ok && std::isfinite(c(0, 0)) && c(0, 0) > 0 && sl[sl.size() / 2] > 0 && std::isfinite(corr) && corr <= 1.0 + 1e-9;
   }
   if (shard.leverages) {
     const uint32_t nres = adjuster.GetNumProjResiduals();

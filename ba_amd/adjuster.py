@@ -73,6 +73,7 @@ SYMBOLS = [
     "ba_adjuster_get_pose_covariance", "ba_adjuster_get_pose_cross_covariance", "ba_adjuster_get_landmark_covariance",
     "ba_adjuster_get_projection_leverage", "ba_adjuster_get_projection_redundancy",
     "ba_adjuster_get_joint_pose_covariance",
+    "ba_adjuster_get_joint_covariance", "ba_adjuster_get_pose_landmark_cross_covariance",
     "ba_adjuster_get_pose_pose_leverages", "ba_adjuster_get_pose_pose_leverage",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
@@ -439,6 +440,32 @@ class BundleAdjuster:
                                                            c.ctypes.data_as(C.POINTER(C.c_double)))
         if got != m or m == 0:
             raise RuntimeError("joint pose covariance unavailable (see stderr)")
+        return c
+
+    def GetJointCovariance(self, pose_ids, landmark_ids, include_calibration=False):
+        """GetJointCovariance: the (M, M) block of the inverse of the full system over the poses, the calibration rows
+        (when asked for) and the landmarks, columns in that order; raises when unavailable."""
+        pose_ids = np.ascontiguousarray(np.atleast_1d(pose_ids), dtype=np.uint32).ravel()
+        landmark_ids = np.ascontiguousarray(np.atleast_1d(landmark_ids), dtype=np.uint32).ravel()
+        k = self.L.ba_hip_num_calib_params(self.engine().h) if include_calibration else 0
+        m = len(pose_ids) * self.pose_dim + k + len(landmark_ids) * self.lm_dim
+        c = np.zeros((m, m))
+        u32p = C.POINTER(C.c_uint32)
+        self.L.ba_adjuster_get_joint_covariance.restype = C.c_uint32
+        got = self.L.ba_adjuster_get_joint_covariance(self.h, len(pose_ids), pose_ids.ctypes.data_as(u32p),
+                                                      int(bool(include_calibration)), len(landmark_ids),
+                                                      landmark_ids.ctypes.data_as(u32p),
+                                                      c.ctypes.data_as(C.POINTER(C.c_double)))
+        if got != m or m == 0:
+            raise RuntimeError("joint covariance unavailable (see stderr)")
+        return c
+
+    def GetPoseLandmarkCrossCovariance(self, pose_id, landmark_id):
+        """GetPoseLandmarkCrossCovariance: the (PoseSize, LmSize) block Cov(pose, landmark); raises when unavailable."""
+        c = np.zeros((self.pose_dim, self.lm_dim))
+        if self.L.ba_adjuster_get_pose_landmark_cross_covariance(self.h, int(pose_id), int(landmark_id),
+                                                                 c.ctypes.data_as(C.POINTER(C.c_double))):
+            raise RuntimeError("pose-landmark cross covariance unavailable (see stderr)")
         return c
 
     def landmark_covariance(self, landmark_id):

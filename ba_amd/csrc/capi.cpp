@@ -52,6 +52,9 @@ struct Iface {
   virtual uint32_t marginals(double* cov) const = 0;
   virtual uint32_t covariance(int kind, uint32_t a, uint32_t b, double* out) = 0;
   virtual uint32_t joint_covariance(uint32_t n, const uint32_t* ids, int include_calibration, double* out) = 0;
+  virtual uint32_t joint_state_covariance(uint32_t n, const uint32_t* ids, int include_calibration, uint32_t nl,
+                                          const uint32_t* lms, double* out) = 0;
+  virtual int pose_landmark_cross_covariance(uint32_t pose_id, uint32_t landmark_id, double* out) = 0;
   virtual int pose_pose_leverages(int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev) = 0;
   virtual double pose_pose_leverage(int kind, uint32_t id) = 0;
   virtual int marginalize(uint32_t nm, const uint32_t* m, uint32_t nl, const uint32_t* l, uint32_t* nb) = 0;
@@ -263,6 +266,21 @@ struct Impl : Iface {
     for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
     return (uint32_t)m.rows();
   }
+  uint32_t joint_state_covariance(uint32_t n, const uint32_t* ids, int include_calibration, uint32_t nl, const uint32_t* lms,
+                                  double* out) override {
+    ba::MatX m;
+    if (!ba.GetJointCovariance(std::vector<uint32_t>(ids, ids + n), std::vector<uint32_t>(lms, lms + nl), m,
+                               include_calibration != 0))
+      return 0;
+    for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
+    return (uint32_t)m.rows();
+  }
+  int pose_landmark_cross_covariance(uint32_t pose_id, uint32_t landmark_id, double* out) override {
+    ba::MatX m;
+    if (!ba.GetPoseLandmarkCrossCovariance(pose_id, landmark_id, m)) return 1;
+    for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
+    return 0;
+  }
   int pose_pose_leverages(int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev) override {
     std::vector<double> c, i, l;
     if (!ba.GetPosePoseLeverages(kind, ids ? std::vector<uint32_t>(ids, ids + n) : std::vector<uint32_t>(),
@@ -442,6 +460,15 @@ uint32_t ba_adjuster_get_joint_pose_covariance(ba_adjuster* a, uint32_t n, const
                                                int include_calibration, double* cov) {
   if ((n && !pose_ids) || !cov) return 0;
   return a->p->joint_covariance(n, pose_ids, include_calibration, cov);
+}
+uint32_t ba_adjuster_get_joint_covariance(ba_adjuster* a, uint32_t n_poses, const uint32_t* pose_ids, int include_calibration,
+                                          uint32_t n_landmarks, const uint32_t* landmark_ids, double* cov) {
+  if ((n_poses && !pose_ids) || (n_landmarks && !landmark_ids) || !cov) return 0;
+  return a->p->joint_state_covariance(n_poses, pose_ids, include_calibration, n_landmarks, landmark_ids, cov);
+}
+int ba_adjuster_get_pose_landmark_cross_covariance(ba_adjuster* a, uint32_t pose_id, uint32_t landmark_id, double* cov) {
+  if (!cov) return 1;
+  return a->p->pose_landmark_cross_covariance(pose_id, landmark_id, cov);
 }
 int ba_adjuster_marginalize(ba_adjuster* a, uint32_t nm, const uint32_t* pose_ids, uint32_t nl,
                             const uint32_t* landmark_ids, uint32_t* blanket_poses) {

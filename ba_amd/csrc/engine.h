@@ -270,7 +270,9 @@ struct Engine {
   // ba_hip_release_marginals.  jc_idx: the plan of the last request (jointcov.h)
   DBuf<uint32_t> jc_idx;
   DBuf<double> jc_Y, jc_slots, jc_part, jc_out;
+  DBuf<uint32_t> jc_lm;                  // landmark columns (ba_hip_get_joint_state_marginals): ids | tile marks | counts
   ba_hip_joint_marginal_stats jstats = {};
+  ba_hip_joint_state_stats jsstats = {};
   ba_hip_leverage_stats lstats = {};     // the last ba_hip_get_projection_leverages (k_lever.hip)
   std::vector<uint32_t> lev_pos;         // its plan (lever.h): sorted position of every residual id, and the block
   uint64_t lev_reads_all = 0;            // reads / landmarks of the all-residuals pass; rebuilt after ba_hip_finalize
@@ -485,9 +487,10 @@ int leverages_run(Engine* e, uint32_t n, const uint32_t* ids, double* out);
 // of `kind` (ids within the kind, checked by the caller; null: all n of them in id order) the 15 x 15 blocks C and
 // Lambda and the leverage tr(C Lambda); any output may be null
 int pose_pose_leverages_run(Engine* e, int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev);
-// joint covariance of the rows `sel` of S (engine numbering) from the factor in A (k_jointcov.hip): out is
-// sel x sel on the host; reads A and invdiag only
-int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out);
+// joint covariance of the rows `sel` of S (engine numbering) and the landmarks `lms` (ids, their columns after
+// those of sel) from the factor in A (k_jointcov.hip): out is M x M on the host, M = |sel| + LM |lms|; reads A,
+// invdiag and, for landmarks, the rows of the last linearisation
+int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<uint32_t>& lms, double* out);
 void jointcov_release(Engine* e);
 // dense priors and marginalisation (k_marg.hip): upload at finalize; linearise (mode 1: into A, rhs_p, rhs_p_sc) or
 // evaluate (mode 0) every prior at the current state, E_p summed into *err_host; the dogleg term; one marginalisation

@@ -1597,21 +1597,25 @@ int ba_hip_get_pose_pose_leverage_stats(ba_hip_engine* h, ba_hip_pose_pose_lever
   *out = e->ppl_stats;
   return 0;
 }
-// ---- joint covariance of a pose set (k_jointcov.hip): Y = L^-1 E over the reach, Sigma = Y^T D Y ----
-int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,
-                               double* out) {
-  ENG(h);
-  static const char* what = "ba_hip_get_joint_marginals";
+// ---- joint covariance of a pose set (k_jointcov.hip): Y = L^-1 E over the reach, Sigma = Y^T D Y; with landmarks
+// the columns [E | -W V^-1] and V^-1 on their diagonal blocks.  One path for both getters: `what` starts the messages.
+static int joint_state_run(Engine* e, const char* what, bool state, uint32_t n, const uint32_t* pose_ids,
+                           int include_calibration, uint32_t nl, const uint32_t* lm_ids, double* out) {
   const std::string m = std::string(what) + ": ";
+  if (nl && !e->lm_dim) return e->fail_msg((m + "LmSize 0 has no landmark unknowns").c_str());
   if (!e->finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
+  if (nl && e->sharded() && !dist_solve_enabled(e))   // (the distributed solve refuses first, for every block)
+    return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
   int rc;
   if ((rc = kept_factor_ready(e, what, "joint marginals", false))) return rc;
-  if ((n && !pose_ids) || !out) return e->fail_msg((m + "NULL argument").c_str());
-  const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K;
+  if ((n && !pose_ids) || (nl && !lm_ids) || !out) return e->fail_msg((m + "NULL argument").c_str());
+  const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K, LM = (uint32_t)e->lm_dim;
   if (include_calibration && !K)
     return e->fail_msg((m + "include_calibration without calibration unknowns (ba_hip_set_calibration)").c_str());
-  const uint64_t M = (uint64_t)n * D + (include_calibration ? K : 0);
-  if (M == 0) return e->fail_msg((m + "no pose and no calibration rows requested").c_str());
+  const uint64_t M = (uint64_t)n * D + (include_calibration ? K : 0) + (uint64_t)nl * LM;
+  if (M == 0)
+    return e->fail_msg((m + (state ? "no pose, no calibration rows and no landmark requested"
+                                   : "no pose and no calibration rows requested")).c_str());
   if (M > BA_HIP_JOINT_MAX_COLUMNS)
     return e->fail_msg((m + std::to_string(M) + " columns requested, the limit is BA_HIP_JOINT_MAX_COLUMNS (" +
                         std::to_string(BA_HIP_JOINT_MAX_COLUMNS) + ")").c_str());
@@ -1624,14 +1628,41 @@ int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pos
       return e->fail_msg((m + "pose " + std::to_string(seen[i]) + " is repeated (the joint block would be singular)").c_str());
   for (uint32_t i = 0; i < n; ++i) {
     uint32_t r;
-    int rc;
     if ((rc = pose_row(e, pose_ids[i], &r, what))) return rc;
     for (uint32_t x = 0; x < D; ++x) sel.push_back(r + x);
   }
   if (include_calibration)
     for (uint32_t x = 0; x < K; ++x) sel.push_back(e->st.np + x);
+  std::vector<uint32_t> lms(lm_ids, lm_ids + nl);
+  seen = lms;
+  std::sort(seen.begin(), seen.end());
+  for (uint32_t i = 0; i + 1 < nl; ++i)
+    if (seen[i] == seen[i + 1])
+      return e->fail_msg((m + "landmark " + std::to_string(seen[i]) + " is repeated (the joint block would be singular)").c_str());
+  for (uint32_t i = 0; i < nl; ++i)
+    if (lms[i] >= e->st.L || e->st.lm_opt[lms[i]] < 0)
+      return e->fail_msg((m + "landmark " + std::to_string(lms[i]) + " is not an active landmark").c_str());
   BAE_HIP(hipSetDevice(e->device));
-  return jointcov_run(e, sel, out);
+  if ((rc = jointcov_run(e, sel, lms, out))) return rc;
+  if (state && !nl) e->jsstats = ba_hip_joint_state_stats{};
+  return 0;
+}
+int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,
+                               double* out) {
+  ENG(h);
+  return joint_state_run(e, "ba_hip_get_joint_marginals", false, n, pose_ids, include_calibration, 0, nullptr, out);
+}
+int ba_hip_get_joint_state_marginals(ba_hip_engine* h, uint32_t n_poses, const uint32_t* pose_ids, int include_calibration,
+                                     uint32_t n_landmarks, const uint32_t* lm_ids, double* out) {
+  ENG(h);
+  return joint_state_run(e, "ba_hip_get_joint_state_marginals", true, n_poses, pose_ids, include_calibration, n_landmarks,
+                         lm_ids, out);
+}
+int ba_hip_get_joint_state_stats(ba_hip_engine* h, ba_hip_joint_state_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_joint_state_stats: NULL argument");
+  *out = e->jsstats;
+  return 0;
 }
 int ba_hip_get_joint_marginal_stats(ba_hip_engine* h, ba_hip_joint_marginal_stats* out) {
   ENG(h);

@@ -441,6 +441,42 @@ extern "C" int ba_hostcheck_joint_marginals(uint32_t n, const double* S, uint32_
   return 0;
 }
 
+// B^T S^-1 B for a caller's dense right-hand side B (n x m row-major), same factorisation: the plan is seeded with
+// the tile rows that hold a non-zero of B, the substitution starts from B's non-zeros.  Outputs as above.
+extern "C" int ba_hostcheck_joint_rhs(uint32_t n, const double* S, uint32_t m, const double* B, double* cov, double* Y_out,
+                                      uint8_t* reach_out, uint32_t* level_of, uint8_t* nzL_out, uint64_t* products,
+                                      uint32_t* levels) {
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  std::vector<uint8_t> nz;
+  std::vector<double> L, d, linvT;
+  if (host_tile_factor(n, S, nz, L, d, linvT)) return -1;
+  std::vector<bae::JointEntry> ent;
+  std::vector<uint32_t> tiles;
+  for (uint32_t c = 0; c < m; ++c)
+    for (uint32_t r = 0; r < n; ++r)
+      if (B[(size_t)r * m + c] != 0.0) {
+        ent.push_back({r, c, B[(size_t)r * m + c]});
+        tiles.push_back(r / 64);
+      }
+  bae::JointPlan p;
+  bae::build_joint_plan(nz, nt, tiles, m, p);
+  std::vector<double> Y(p.y_count());
+  bae::jointcov_host_rhs(p, L.data(), ld, linvT.data(), d.data(), ent.data(), ent.size(), Y.data(), cov);
+  std::fill(Y_out, Y_out + (size_t)ld * m, 0.0);
+  for (uint32_t t = 0; t < nt; ++t) {
+    reach_out[t] = p.pos[t] != bae::kJointNone;
+    level_of[t] = reach_out[t] ? p.level_of[p.pos[t]] : bae::kJointNone;
+    if (reach_out[t])
+      for (uint32_t r = 0; r < 64; ++r)
+        for (uint32_t c = 0; c < m; ++c)
+          Y_out[((size_t)t * 64 + r) * m + c] = Y[((size_t)p.pos[t] * 64 + r) * p.m_pad + c];
+  }
+  std::copy(nz.begin(), nz.end(), nzL_out);
+  *products = p.products;
+  *levels = p.levels();
+  return 0;
+}
+
 // ---- marginalisation plan and the dense prior's error state (marg.h) ----------------------------------
 #include <cstring>
 #include <string>
@@ -619,17 +655,17 @@ extern "C" int ba_hostcheck_pcg_coarse(uint32_t nt, const uint8_t* nz, const dou
 // ---- leverages of projection residuals (lever.h) ---------------------------------------------------------
 #include "lever.h"
 
-// leverage_host on one graph: k_linearize's rows (factor rows, obs_jl, calibration rows) emulated from the
-// caller's per-residual Jacobians (jk12: two rows of six per residual, or null with K == 0) and weights, then the
-// device formula over the caller's dense Sigma (n x n, n = active poses * D + K, poses in id order).
-// out: [O][4] by residual id.  variant: lever.h.
-extern "C" int ba_hostcheck_leverages(int LM, int D, int K, uint32_t P, const uint8_t* pose_active, uint32_t L,
-                                      const uint8_t* lm_active, const uint32_t* lm_ref_pose, uint32_t O,
-                                      const uint32_t* proj_pose, const uint32_t* proj_lm, const double* jm12,
-                                      const double* jr12, const double* jl, const double* jk12, const double* w,
-                                      const double* sigma, int variant, double* out) {
+// k_linearize's rows on the host, from the caller's per-residual Jacobians (unweighted) and weights: the lists of
+// structure.h, the factor rows, obs_jl (sorted order) and the calibration rows
+struct EmulatedRows {
+  bae::Lists st;
+  std::vector<double> frow, obs_jl, crow;
+};
+static int emulate_rows(int LM, int D, int K, uint32_t P, const uint8_t* pose_active, uint32_t L, const uint8_t* lm_active,
+                        const uint32_t* lm_ref_pose, uint32_t O, const uint32_t* proj_pose, const uint32_t* proj_lm,
+                        const double* jm12, const double* jr12, const double* jl, const double* jk12, const double* w,
+                        EmulatedRows& er) {
   using namespace bae;
-  if ((LM != 1 && LM != 3) || (K > 0 && !jk12) || K > 6) return -1;
   Problem pb;
   pb.num_cams = 1; pb.num_poses = P; pb.num_lms = L; pb.num_proj = O;
   pb.pose_active.assign(pose_active, pose_active + P);
@@ -641,12 +677,14 @@ extern "C" int ba_hostcheck_leverages(int LM, int D, int K, uint32_t P, const ui
   pb.proj_cam.assign(O, 0);
   pb.proj_z.assign(2 * (size_t)O, 0.0);
   pb.proj_w.assign(O, 1.0);
-  Lists st;
+  Lists& st = er.st;
   std::string err;
   if (!build_lists(pb, LM, D, st, err, nullptr, K)) return -2;
   const uint32_t R = st.R, WO = (uint32_t)w_row_offset(LM);
-  std::vector<double> frow((size_t)st.n_rows * 6, 0.0), obs_jl((size_t)O * 2 * LM, 0.0);
-  std::vector<double> crow(K > 0 ? (2 * (size_t)O + L) * 6 : 0, 0.0);
+  std::vector<double>&frow = er.frow, &obs_jl = er.obs_jl, &crow = er.crow;
+  frow.assign((size_t)st.n_rows * 6, 0.0);
+  obs_jl.assign((size_t)O * 2 * LM, 0.0);
+  crow.assign(K > 0 ? (2 * (size_t)O + L) * 6 : 0, 0.0);
   for (uint32_t l = 0; l < L; ++l) {
     const bool act = st.lm_opt[l] >= 0;
     for (uint32_t s = st.lm_ptr[l]; s < st.lm_ptr[l + 1]; ++s) {
@@ -677,6 +715,25 @@ extern "C" int ba_hostcheck_leverages(int LM, int D, int K, uint32_t P, const ui
           crow[(2 * (size_t)O + l) * 6 + x] += (crow[2 * (size_t)s * 6 + x] * Jl[0] + crow[(2 * (size_t)s + 1) * 6 + x] * Jl[1]) * sw;
     }
   }
+  return 0;
+}
+
+// leverage_host on one graph: k_linearize's rows (factor rows, obs_jl, calibration rows) emulated from the
+// caller's per-residual Jacobians (jk12: two rows of six per residual, or null with K == 0) and weights, then the
+// device formula over the caller's dense Sigma (n x n, n = active poses * D + K, poses in id order).
+// out: [O][4] by residual id.  variant: lever.h.
+extern "C" int ba_hostcheck_leverages(int LM, int D, int K, uint32_t P, const uint8_t* pose_active, uint32_t L,
+                                      const uint8_t* lm_active, const uint32_t* lm_ref_pose, uint32_t O,
+                                      const uint32_t* proj_pose, const uint32_t* proj_lm, const double* jm12,
+                                      const double* jr12, const double* jl, const double* jk12, const double* w,
+                                      const double* sigma, int variant, double* out) {
+  using namespace bae;
+  if ((LM != 1 && LM != 3) || (K > 0 && !jk12) || K > 6) return -1;
+  EmulatedRows er;
+  if (int rc = emulate_rows(LM, D, K, P, pose_active, L, lm_active, lm_ref_pose, O, proj_pose, proj_lm, jm12, jr12, jl, jk12, w, er))
+    return rc;
+  const Lists& st = er.st;
+  const std::vector<double>&frow = er.frow, &obs_jl = er.obs_jl, &crow = er.crow;
   LeverHostIn in;
   in.LM = LM; in.D = D; in.K = K; in.L = L; in.O = O; in.np = st.np; in.n = st.n; in.lrow_base = st.lrow_base;
   in.lm_ptr = st.lm_ptr.data(); in.obs_pose = st.obs_pose.data(); in.lm_ref_pose = lm_ref_pose;
@@ -687,6 +744,73 @@ extern "C" int ba_hostcheck_leverages(int LM, int D, int K, uint32_t P, const ui
   leverage_host(in, variant, sorted.data());
   for (uint32_t s = 0; s < O; ++s)
     for (int i = 0; i < 4; ++i) out[4 * (size_t)st.obs_perm[s] + i] = sorted[4 * (size_t)s + i];
+  return 0;
+}
+
+// ---- joint covariance of poses, calibration and landmarks (jointstate.h) -----------------------------------------
+#include "jointstate.h"
+
+// The mixed block on one graph: k_linearize's rows emulated as for ba_hostcheck_leverages, V^-1 by invert_v's rule
+// from the weighted dz_dlm, the landmark columns of jointstate.h, then build_joint_plan + jointcov_host_rhs on the
+// caller's dense S (n x n, n = active poses * D + K, poses in id order; factorised as for ba_hostcheck_selinv) and
+// V^-1 on the diagonal landmark blocks.  Columns: poses (D each), calibration (K, when asked), landmarks (LM each),
+// in the caller's order.  cov: M x M; reach_out: nt flags, or null.  variant: jointstate.h.
+// Returns -1 bad arguments, -2 the lists, -3 an id out of range or inactive, -4 a zero pivot.
+extern "C" int ba_hostcheck_joint_state(int LM, int D, int K, uint32_t P, const uint8_t* pose_active, uint32_t L,
+                                        const uint8_t* lm_active, const uint32_t* lm_ref_pose, uint32_t O,
+                                        const uint32_t* proj_pose, const uint32_t* proj_lm, const double* jm12,
+                                        const double* jr12, const double* jl, const double* jk12, const double* w,
+                                        uint32_t n, const double* S, uint32_t n_poses, const uint32_t* pose_ids,
+                                        int include_calibration, uint32_t n_lms, const uint32_t* lm_ids, int variant,
+                                        double* cov, uint8_t* reach_out) {
+  using namespace bae;
+  if ((LM != 1 && LM != 3) || (K > 0 && !jk12) || K > 6 || !S || !cov || (include_calibration && !K)) return -1;
+  EmulatedRows er;
+  if (int rc = emulate_rows(LM, D, K, P, pose_active, L, lm_active, lm_ref_pose, O, proj_pose, proj_lm, jm12, jr12, jl, jk12, w, er))
+    return rc;
+  const Lists& st = er.st;
+  if (n != st.n) return -1;
+  std::vector<double> vinv((size_t)L * LM * LM, 0.0);
+  for (uint32_t l = 0; l < L; ++l) {
+    if (st.lm_opt[l] < 0 || st.lm_ptr[l + 1] == st.lm_ptr[l]) continue;
+    double V[9] = {0};
+    for (uint32_t s = st.lm_ptr[l]; s < st.lm_ptr[l + 1]; ++s) {
+      const double* B = &er.obs_jl[(size_t)s * 2 * LM];
+      for (int a = 0; a < LM; ++a)
+        for (int b = 0; b < LM; ++b) V[a * LM + b] += B[a] * B[b] + B[LM + a] * B[LM + b];
+    }
+    if (LM == 1) joint_invert_v_host<1>(V, &vinv[l]);
+    else joint_invert_v_host<3>(V, &vinv[(size_t)l * 9]);
+  }
+  const uint32_t c0 = n_poses * (uint32_t)D + (include_calibration ? (uint32_t)K : 0), M = c0 + n_lms * (uint32_t)LM;
+  std::vector<JointEntry> ent;
+  std::vector<uint32_t> tiles;
+  for (uint32_t i = 0; i < n_poses; ++i) {
+    if (pose_ids[i] >= P || st.pose_opt[pose_ids[i]] < 0) return -3;
+    for (int x = 0; x < D; ++x) ent.push_back({(uint32_t)st.pose_opt[pose_ids[i]] * D + x, i * D + x, 1.0});
+  }
+  if (include_calibration)
+    for (int x = 0; x < K; ++x) ent.push_back({st.np + x, n_poses * D + x, 1.0});
+  for (uint32_t i = 0; i < n_lms; ++i)
+    if (lm_ids[i] >= L || st.lm_opt[lm_ids[i]] < 0) return -3;
+  JointStateHostIn in;
+  in.LM = LM; in.D = D; in.K = K; in.L = L; in.O = O; in.np = st.np; in.lrow_base = st.lrow_base;
+  in.lm_ptr = st.lm_ptr.data(); in.obs_pose = st.obs_pose.data(); in.lm_ref_pose = lm_ref_pose;
+  in.pose_opt = st.pose_opt.data();
+  in.frow = er.frow.data(); in.crow = K > 0 ? er.crow.data() : nullptr; in.lm_vinv = vinv.data();
+  joint_state_columns_host(in, n_lms, lm_ids, c0, variant, ent, nullptr);
+  for (const JointEntry& x : ent) tiles.push_back(x.row / 64);
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  std::vector<uint8_t> nz;
+  std::vector<double> Lf, d, linvT;
+  if (host_tile_factor(n, S, nz, Lf, d, linvT)) return -4;
+  JointPlan p;
+  build_joint_plan(nz, nt, tiles, M, p);
+  std::vector<double> Y(p.y_count());
+  jointcov_host_rhs(p, Lf.data(), ld, linvT.data(), d.data(), ent.data(), ent.size(), Y.data(), cov);
+  if (variant != 1) joint_state_add_vinv(in, n_lms, lm_ids, c0, M, cov);
+  if (reach_out)
+    for (uint32_t t = 0; t < nt; ++t) reach_out[t] = p.pos[t] != kJointNone;
   return 0;
 }
 

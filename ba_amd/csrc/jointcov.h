@@ -50,7 +50,9 @@ struct JointPlan {
   size_t y_count() const { return reach.size() * 64 * (size_t)m_pad; }
 };
 
-// nzL: nt x nt lower factor pattern (row-major bytes), tiles: the tile rows that hold a requested row.
+// nzL: nt x nt lower factor pattern (row-major bytes), tiles: the tile rows that hold a non-zero of any column of
+// the right-hand side (for unit columns: the tile rows that hold a requested row; for the landmark columns of
+// jointstate.h: the tile rows their incidences touch).  Repeats and any order are fine.
 inline void build_joint_plan(const std::vector<uint8_t>& nzL, uint32_t nt, const std::vector<uint32_t>& tiles, uint32_t m,
                              JointPlan& p) {
   p = JointPlan();
@@ -110,16 +112,23 @@ inline void build_joint_plan(const std::vector<uint8_t>& nzL, uint32_t nt, const
   p.products = (uint64_t)p.ncb * ((uint64_t)p.src.size() + nr);
 }
 
-// Host restatement of k_joint_init, k_joint_fsolve + k_joint_epilogue per level, k_joint_gram and
+// One entry of a right-hand side column: B[row][col] += v (row: a row of S, col < m).
+struct JointEntry {
+  uint32_t row, col;
+  double v;
+};
+
+// Host restatement of k_joint_init (+ k_joint_rhs), k_joint_fsolve + k_joint_epilogue per level, k_joint_gram and
 // k_joint_combine, with the device's order of summation over chunks, slots and groups.  L: the factor in the
 // engine's lower storage (row-major, leading dimension ld >= 64 nt; only tiles of the pattern are read),
-// linvT: nt tiles L_JJ^-T (row-major), dsgn: 64 nt pivot signs, sel: the m requested rows of S.
-// Y: reach x 64 x m_pad (the panels), cov: m x m row-major.
-inline void jointcov_host(const JointPlan& p, const double* L, size_t ld, const double* linvT, const double* dsgn,
-                          const uint32_t* sel, double* Y, double* cov) {
+// linvT: nt tiles L_JJ^-T (row-major), dsgn: 64 nt pivot signs.  The right-hand side B (64 nt x m) starts from
+// zero and takes the `ne` entries in their order (entries that share a place add up); every entry's tile row must
+// be one the plan was seeded with.  Y: reach x 64 x m_pad (the panels), cov = B^T S^-1 B: m x m row-major.
+inline void jointcov_host_rhs(const JointPlan& p, const double* L, size_t ld, const double* linvT, const double* dsgn,
+                              const JointEntry* ent, size_t ne, double* Y, double* cov) {
   const uint32_t m = p.m, mp = p.m_pad, nr = (uint32_t)p.reach.size();
   std::fill(Y, Y + p.y_count(), 0.0);
-  for (uint32_t c = 0; c < m; ++c) Y[((size_t)p.pos[sel[c] / 64] * 64 + sel[c] % 64) * mp + c] = 1.0;
+  for (size_t i = 0; i < ne; ++i) Y[((size_t)p.pos[ent[i].row / 64] * 64 + ent[i].row % 64) * mp + ent[i].col] += ent[i].v;
   std::vector<double> part((size_t)64 * mp), T((size_t)64 * mp);
   for (uint32_t v = 0; v < p.levels(); ++v)
     for (uint32_t e = p.level_ptr[v]; e < p.level_ptr[v + 1]; ++e) {
@@ -164,6 +173,14 @@ inline void jointcov_host(const JointPlan& p, const double* L, size_t ld, const 
   }
   for (uint32_t a = 0; a < m; ++a)
     for (uint32_t b = 0; b <= a; ++b) cov[(size_t)a * m + b] = cov[(size_t)b * m + a] = acc[(size_t)a * m + b];
+}
+
+// The unit-column case: sel, the m requested rows of S (column c is the unit vector of row sel[c]).
+inline void jointcov_host(const JointPlan& p, const double* L, size_t ld, const double* linvT, const double* dsgn,
+                          const uint32_t* sel, double* Y, double* cov) {
+  std::vector<JointEntry> ent(p.m);
+  for (uint32_t c = 0; c < p.m; ++c) ent[c] = {sel[c], c, 1.0};
+  jointcov_host_rhs(p, L, ld, linvT, dsgn, ent.data(), ent.size(), Y, cov);
 }
 
 }  // namespace bae

@@ -3,6 +3,10 @@
 // reach of the requested tiles and a Gram product.  No selected inverse, no backward pass.
 //
 //   k_joint_init      Y panels of the reach = the unit columns E
+//   k_joint_seed      (landmark columns, ba_hip_get_joint_state_marginals) the tile rows the valid incidences of
+//                     every requested landmark touch, one wavefront per landmark; the host seeds the plan with them
+//   k_joint_rhs       the landmark columns -W_l V_l^-1 added into the Y panels, one wavefront per landmark, a fixed
+//                     lane per entry, incidences in lm_entry's order
 //   k_joint_fsolve    partial tile sum_{J in chunk} L_IJ Y_J, one workgroup per (row I, chunk of <= 4 sources,
 //                     block of 64 columns); one launch per level
 //   k_joint_epilogue  Y_I = L_II^-1 (E_I - sum of the row's partial tiles in chunk order), one workgroup per
@@ -10,6 +14,7 @@
 //   k_joint_gram      partial tile sum_{I in group} Y_I^T D_I Y_I, one workgroup per (group of <= 8 reach rows,
 //                     lower 64 x 64 tile of the output)
 //   k_joint_combine   the groups summed in order, the lower half mirrored into the upper one
+//   k_joint_lmdiag    V_l^-1 added to the diagonal block of every requested landmark, both halves from the lower one
 //
 // The plan (reach, levels, chunks, slots) and the host restatement are in jointcov.h, checked on the CPU by
 // tests/test_joint_marginals_plan.py.  The factor is read, never written: L_IJ from A, L_II^-T (linvT) and the
@@ -21,6 +26,8 @@
 // is fetched into registers while the matrix cores work on this one.
 #include "engine.h"
 #include "jointcov.h"
+#include "jointstate.h"
+#include "lm_entry.h"
 #include "tile_mma.h"
 
 #include <algorithm>
@@ -165,16 +172,145 @@ k_joint_combine(const double* __restrict__ part, uint32_t groups, uint32_t ntl, 
   out[(size_t)b * M + a] = sum;
 }
 
+// ---- landmark columns (jointstate.h; LmArgs, lm_entry: lm_entry.h) -----------------------------------------
+// does landmark l (LM == 1) have an observation from a pose other than its reference pose?  All 64 lanes call.
+template <int LM>
+__device__ __forceinline__ bool joint_any_listed(const LmArgs& g, uint32_t l, uint32_t nobs, int lane) {
+  bool any_listed = false;
+  if (LM == 1) {
+    const uint32_t rp = g.lm_ref_pose[l];
+    for (uint32_t e0 = 0; e0 < nobs; e0 += 64) {
+      const uint32_t e = e0 + lane;
+      const bool lst = e < nobs && g.obs_pose[g.lm_ptr[l] + e] != rp;
+      any_listed = any_listed || __ballot(lst) != 0;
+    }
+  }
+  return any_listed;
+}
+// a landmark without observations has no incidence (its E_l is zero)
+template <int LM>
+__device__ __forceinline__ uint32_t joint_entries(const LmArgs& g, uint32_t nobs) {
+  return nobs ? nobs + (LM == 1 ? 1u : 0u) + (g.K > 0 ? 1u : 0u) : 0u;
+}
+
+// marks[t] = 1 for every tile row t (< nt) that a valid incidence of a requested landmark touches (zeroed by the
+// caller; every writer stores the same word), cnt[q] = the valid incidences of ids[q]
+template <int LM>
+__global__ void __launch_bounds__(256)
+k_joint_seed(LmArgs g, uint32_t n, const uint32_t* __restrict__ ids, uint32_t* __restrict__ marks,
+             uint32_t* __restrict__ cnt) {
+  const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= n) return;
+  const int lane = threadIdx.x & 63;
+  const uint32_t l = ids[q], nobs = g.lm_ptr[l + 1] - g.lm_ptr[l];
+  const bool any_listed = joint_any_listed<LM>(g, l, nobs, lane);
+  const uint32_t ne = joint_entries<LM>(g, nobs);
+  uint32_t c = 0;
+  for (uint32_t e = lane; e < ne; e += 64) {
+    const LmEntry<LM> x = lm_entry<LM>(g, l, e, nobs, any_listed);
+    if (!x.valid) continue;
+    ++c;
+    const uint32_t t0 = x.base / TB, t1 = (x.base + (uint32_t)x.width - 1) / TB;   // a block may straddle two tiles
+    if (t0 < g.nt) marks[t0] = 1;
+    if (t1 < g.nt) marks[t1] = 1;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+  if (lane == 0) cnt[q] = c;
+}
+
+// Column c0 + LM q + k of landmark ids[q]: lane i LM + k owns entry (i, k) of every incidence and adds
+// -(W_e V^-1)[i][k] into row base + i of the panel that holds it.  One lane, one column, incidences in order: the
+// sums do not depend on the launch or on the other columns.
+template <int LM>
+__global__ void __launch_bounds__(256)
+k_joint_rhs(LmArgs g, uint32_t n, const uint32_t* __restrict__ ids, uint32_t c0, const uint32_t* __restrict__ pos,
+            double* __restrict__ Y, uint32_t mp) {
+  const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= n) return;
+  const int lane = threadIdx.x & 63;
+  const uint32_t l = ids[q], nobs = g.lm_ptr[l + 1] - g.lm_ptr[l];
+  const bool any_listed = joint_any_listed<LM>(g, l, nobs, lane);
+  const uint32_t ne = joint_entries<LM>(g, nobs);
+  double Vi[LM * LM];
+  joint_lm_vinv<LM>(nobs, g.lm_vinv + (size_t)l * LM * LM, Vi);
+  const int i = lane / LM, k = lane % LM;
+  if (i >= 6) return;
+  for (uint32_t e = 0; e < ne; ++e) {
+    const LmEntry<LM> x = lm_entry<LM>(g, l, e, nobs, any_listed);
+    if (!x.valid || i >= x.width) continue;
+    const uint32_t row = x.base + (uint32_t)i, t = row / TB;
+    const uint32_t pq = t < g.nt ? pos[t] : kJointNone;
+    if (pq == kJointNone) continue;   // (k_joint_seed marked the tile: it is in the reach)
+    Y[((size_t)pq * TB + row % TB) * mp + c0 + (uint32_t)LM * q + (uint32_t)k] += joint_lm_value<LM>(x.w, Vi, i, k);
+  }
+}
+
+// out[c0 + LM q + a][c0 + LM q + b] += V^-1[a][b] for b <= a, mirrored (out stays bitwise symmetric)
+template <int LM>
+__global__ void __launch_bounds__(256)
+k_joint_lmdiag(const uint32_t* __restrict__ lm_ptr, const double* __restrict__ lm_vinv, uint32_t n,
+               const uint32_t* __restrict__ ids, uint32_t c0, uint32_t M, double* __restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * LM * LM) return;
+  const uint32_t q = t / (LM * LM), a = (t / LM) % LM, b = t % LM;
+  if (b > a) return;
+  const uint32_t l = ids[q];
+  double Vi[LM * LM];
+  joint_lm_vinv<LM>(lm_ptr[l + 1] - lm_ptr[l], lm_vinv + (size_t)l * LM * LM, Vi);
+  const size_t r = c0 + (size_t)LM * q + a, c = c0 + (size_t)LM * q + b;
+  const double s = out[r * M + c] + Vi[a * LM + b];
+  out[r * M + c] = s;
+  out[c * M + r] = s;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------
-// sel: the requested rows of S in the engine's (factorised) numbering, out: M x M on the host
-int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
+// sel: the requested rows of S in the engine's (factorised) numbering (unit columns), lms: the requested landmarks
+// (active, checked by the caller), whose LM columns each follow those of sel; out: M x M on the host
+int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<uint32_t>& lms, double* out) {
   const Structure& st = e->st;
-  const uint32_t M = (uint32_t)sel.size();
+  const int LM = e->lm_dim;
+  const uint32_t Ms = (uint32_t)sel.size(), nl = (uint32_t)lms.size(), M = Ms + nl * (uint32_t)LM;
   uint32_t nt;
   const double *dsgn, *linvT;
   if (int rc = kept_factor(e, "joint marginals", &nt, &dsgn, &linvT)) return rc;
-  std::vector<uint32_t> tiles(M);
-  for (uint32_t c = 0; c < M; ++c) tiles[c] = sel[c] / TB;
+  std::vector<uint32_t> tiles(Ms);
+  for (uint32_t c = 0; c < Ms; ++c) tiles[c] = sel[c] / TB;
+  // the landmark columns: ids | marks (nt) | incidence counts, the tile rows they touch from the device
+  ba_hip_joint_state_stats ss = {};
+  LmArgs g = {};
+  const uint32_t* d_ids = nullptr;
+  if (nl) {
+    g = lm_args(e);
+    if (e->jc_lm.alloc(2 * (size_t)nl + nt) != hipSuccess) {
+      (void)hipGetLastError();
+      jointcov_release(e);
+      char msg[160];
+      snprintf(msg, sizeof msg, "joint marginals: allocating the landmark tables (%zu bytes, %u landmarks) failed",
+               (2 * (size_t)nl + nt) * sizeof(uint32_t), nl);
+      return e->fail_msg(msg);
+    }
+    uint32_t* d_marks = e->jc_lm.p + nl;
+    d_ids = e->jc_lm.p;
+    BAE_HIP(hipMemcpyAsync(e->jc_lm.p, lms.data(), nl * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    BAE_HIP(hipMemsetAsync(d_marks, 0, ((size_t)nt + nl) * sizeof(uint32_t), e->stream));
+    Events<2> evs;
+    BAE_HIP(evs.create());
+    (void)evs.record(0, e->stream);
+    if (LM == 1) hipLaunchKernelGGL(k_joint_seed<1>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, d_marks, d_marks + nt);
+    else hipLaunchKernelGGL(k_joint_seed<3>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, d_marks, d_marks + nt);
+    (void)evs.record(1, e->stream);
+    const hipError_t lerr = hipGetLastError();
+    if (lerr != hipSuccess) return e->fail(lerr, "k_joint_seed launch");
+    std::vector<uint32_t> marks((size_t)nt + nl);
+    BAE_HIP(hipMemcpyAsync(marks.data(), d_marks, marks.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    BAE_HIP(hipStreamSynchronize(e->stream));
+    ss.seed_ms = evs.ms(0, 1);
+    for (uint32_t t = 0; t < nt; ++t)
+      if (marks[t]) { tiles.push_back(t); ++ss.seed_tiles; }
+    for (uint32_t q = 0; q < nl; ++q) ss.incidences += marks[nt + q];
+    ss.landmark_columns = nl * (uint32_t)LM;
+  }
   JointPlan p;
   build_joint_plan(e->nzL_host, nt, tiles, M, p);
   const uint32_t nr = (uint32_t)p.reach.size(), mp = p.m_pad, ncb = p.ncb, ntl = ncb * (ncb + 1) / 2;
@@ -188,7 +324,7 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
   idx.insert(idx.end(), p.src.begin(), p.src.end());
   idx.insert(idx.end(), p.pos.begin(), p.pos.end());
   idx.insert(idx.end(), p.reach.begin(), p.reach.end());
-  for (uint32_t c = 0; c < mp; ++c) idx.push_back(c < M ? p.pos[sel[c] / TB] * TB + sel[c] % TB : kJointNone);
+  for (uint32_t c = 0; c < mp; ++c) idx.push_back(c < Ms ? p.pos[sel[c] / TB] * TB + sel[c] % TB : kJointNone);
   const size_t n_y = p.y_count(), n_slots = (size_t)std::max(p.max_level_chunks, 1u) * ncb * TB * TB,
                n_part = (size_t)p.gram_groups * ntl * TB * TB, n_out = (size_t)M * M;
   const size_t bytes = (n_y + n_slots + n_part + n_out) * sizeof(double) + idx.size() * sizeof(uint32_t);
@@ -206,11 +342,20 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
   const uint32_t* d_idx = e->jc_idx.p;
   const uint4* d_chunks = reinterpret_cast<const uint4*>(d_idx + o_chunks);
   const uint4* d_rows = reinterpret_cast<const uint4*>(d_idx + o_rows);
-  Events<3> ev;
+  Events<5> ev;   // start, substitution done, end; around the right-hand-side pass
   BAE_HIP(ev.create());
   (void)ev.record(0, e->stream);
-  hipLaunchKernelGGL(k_joint_init, dim3((unsigned)((n_y + 255) / 256)), dim3(256), 0, e->stream, e->jc_Y.p, (uint64_t)n_y,
-                     mp, d_idx + o_key);
+  // (a request whose columns are all zero has an empty reach: nothing to initialise, solve or multiply)
+  if (n_y)
+    hipLaunchKernelGGL(k_joint_init, dim3((unsigned)((n_y + 255) / 256)), dim3(256), 0, e->stream, e->jc_Y.p, (uint64_t)n_y,
+                       mp, d_idx + o_key);
+  const bool rhs = nl && nr;
+  if (rhs) {
+    (void)ev.record(3, e->stream);
+    if (LM == 1) hipLaunchKernelGGL(k_joint_rhs<1>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, Ms, d_idx + o_pos, e->jc_Y.p, mp);
+    else hipLaunchKernelGGL(k_joint_rhs<3>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, Ms, d_idx + o_pos, e->jc_Y.p, mp);
+    (void)ev.record(4, e->stream);
+  }
   for (uint32_t v = 0; v < p.levels(); ++v) {
     const uint32_t c0 = p.chunk_level_ptr[v], c1 = p.chunk_level_ptr[v + 1];
     if (c1 > c0)
@@ -221,15 +366,22 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
                        e->jc_Y.p, mp, (const double*)e->jc_slots.p);
   }
   (void)ev.record(1, e->stream);
-  hipLaunchKernelGGL(k_joint_gram, dim3(p.gram_groups, ntl), dim3(256), 0, e->stream, (const double*)e->jc_Y.p, mp,
-                     d_idx + o_reach, nr, dsgn, e->jc_part.p);
+  if (p.gram_groups)
+    hipLaunchKernelGGL(k_joint_gram, dim3(p.gram_groups, ntl), dim3(256), 0, e->stream, (const double*)e->jc_Y.p, mp,
+                       d_idx + o_reach, nr, dsgn, e->jc_part.p);
   hipLaunchKernelGGL(k_joint_combine, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, e->stream,
                      (const double*)e->jc_part.p, p.gram_groups, ntl, M, e->jc_out.p);
+  if (nl) {
+    const unsigned nb = (nl * (uint32_t)(LM * LM) + 255) / 256;
+    if (LM == 1) hipLaunchKernelGGL(k_joint_lmdiag<1>, dim3(nb), dim3(256), 0, e->stream, g.lm_ptr, g.lm_vinv, nl, d_ids, Ms, M, e->jc_out.p);
+    else hipLaunchKernelGGL(k_joint_lmdiag<3>, dim3(nb), dim3(256), 0, e->stream, g.lm_ptr, g.lm_vinv, nl, d_ids, Ms, M, e->jc_out.p);
+  }
   (void)ev.record(2, e->stream);
   const hipError_t lerr = hipGetLastError();
   const hipError_t serr = hipEventSynchronize(ev[2]);
   ba_hip_joint_marginal_stats js = {};
-  js.solve_ms = ev.ms(0, 1);
+  if (rhs) ss.rhs_ms = ev.ms(3, 4);
+  js.solve_ms = ev.ms(0, 1) - ss.rhs_ms;
   js.gram_ms = ev.ms(1, 2);
   if (lerr != hipSuccess) return e->fail(lerr, "k_joint launch");
   if (serr != hipSuccess) return e->fail(serr, "k_joint");
@@ -239,13 +391,14 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, double* out) {
   js.levels = p.levels();
   js.tile_products = p.products;
   js.workspace_bytes = (double)(e->jc_idx.bytes() + e->jc_Y.bytes() + e->jc_slots.bytes() + e->jc_part.bytes() +
-                                e->jc_out.bytes());
+                                e->jc_out.bytes() + e->jc_lm.bytes());
   e->jstats = js;
+  if (nl) e->jsstats = ss;
   return 0;
 }
 
 void jointcov_release(Engine* e) {   // (ba_hip_release_marginals promises the memory back while the engine lives)
-  e->jc_idx.release(); e->jc_Y.release(); e->jc_slots.release(); e->jc_part.release(); e->jc_out.release();
+  e->jc_idx.release(); e->jc_Y.release(); e->jc_slots.release(); e->jc_part.release(); e->jc_out.release(); e->jc_lm.release();
 }
 
 }  // namespace bae

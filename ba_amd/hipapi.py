@@ -115,6 +115,11 @@ class JointMarginalStats(C.Structure):
                 ("levels", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class JointStateStats(C.Structure):
+    _fields_ = [("rhs_ms", C.c_double), ("seed_ms", C.c_double), ("incidences", C.c_uint64),
+                ("landmark_columns", C.c_uint32), ("seed_tiles", C.c_uint32)]
+
+
 class LeverageStats(C.Structure):
     _fields_ = [("device_ms", C.c_double), ("block_reads", C.c_uint64), ("residuals", C.c_uint32),
                 ("landmarks", C.c_uint32)]
@@ -187,6 +192,7 @@ SYMBOLS = [
     "ba_hip_get_pcg_coarse_stats", "ba_hip_get_pcg_coarse",
     "ba_hip_get_projection_leverages", "ba_hip_get_leverage_stats", "ba_hip_device_bytes_live",
     "ba_hip_get_pose_pose_leverages", "ba_hip_get_pose_pose_leverage_stats", "ba_hip_num_pose_pose_residuals",
+    "ba_hip_get_joint_state_marginals", "ba_hip_get_joint_state_stats",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -526,6 +532,25 @@ class Engine:
         st = JointMarginalStats()
         self._chk(self.L.ba_hip_get_joint_marginal_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in JointMarginalStats._fields_ if k != "reserved"}
+
+    # ---- joint covariance of poses, calibration and landmarks (the cross blocks included) ----
+    def joint_state_marginals(self, pose_ids, lm_ids, include_calibration=False):
+        """(M, M) block of the inverse of the full system over the poses `pose_ids`, the calibration rows when asked
+        for, and the landmarks `lm_ids`, columns in that order; M = len(pose_ids) * D (+ K) + len(lm_ids) * LmSize."""
+        pose_ids = np.ascontiguousarray(np.atleast_1d(pose_ids), dtype=np.uint32).ravel()
+        lm_ids = np.ascontiguousarray(np.atleast_1d(lm_ids), dtype=np.uint32).ravel()
+        m = len(pose_ids) * self.pose_dim + (self.num_calib_params() if include_calibration else 0) + \
+            len(lm_ids) * self.lm_dim
+        out = np.empty((m, m))
+        self._chk(self.L.ba_hip_get_joint_state_marginals(self.h, len(pose_ids), _p(pose_ids, u32p),
+                                                          int(bool(include_calibration)), len(lm_ids), _p(lm_ids, u32p),
+                                                          _p(out, dp)))
+        return out
+
+    def joint_state_stats(self):
+        st = JointStateStats()
+        self._chk(self.L.ba_hip_get_joint_state_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in JointStateStats._fields_}
 
     # ---- dense pose priors and marginalisation (ba_hip.h) ----
     def set_dense_priors(self, priors):

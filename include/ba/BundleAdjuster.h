@@ -521,6 +521,37 @@ class BundleAdjuster {
     }
     return true;
   }
+  // Joint covariance of the poses `pose_ids`, the calibration rows (with include_calibration) and the landmarks
+  // `landmark_ids`, columns in that order (extension; include/ba_hip.h ba_hip_get_joint_state_marginals, DESIGN.md
+  // section 17): the block of the inverse of the full system, pose-landmark and landmark-landmark cross blocks
+  // included, M = pose_ids.size() * kPoseDim (+ kCalibDim) + landmark_ids.size() * kLmDim.  false, reported
+  // through Check(), and a 0 x 0 cov when unavailable (the refusals of GetJointPoseCovariance, an inactive or
+  // repeated landmark, a sharded engine).
+  bool GetJointCovariance(const std::vector<uint32_t>& pose_ids, const std::vector<uint32_t>& landmark_ids, MatrixXt& cov,
+                          bool include_calibration = false) {
+    const int M = (int)(pose_ids.size() * kPoseDim + (include_calibration ? kCalibDim : 0) + landmark_ids.size() * kLmDim);
+    cov = MatX(M, M);
+    if (!engine_ || !Check(ba_hip_get_joint_state_marginals(engine_, (uint32_t)pose_ids.size(), pose_ids.data(),
+                                                            include_calibration ? 1 : 0, (uint32_t)landmark_ids.size(),
+                                                            landmark_ids.data(), cov.data()),
+                           "ba_hip_get_joint_state_marginals")) {
+      cov = MatX();
+      return false;
+    }
+    return true;
+  }
+  // Cov(pose, landmark): the kPoseDim x kLmDim cross block of GetJointCovariance({pose_id}, {landmark_id}).
+  bool GetPoseLandmarkCrossCovariance(uint32_t pose_id, uint32_t landmark_id, MatrixXt& cov) {
+    MatX joint;
+    if (!GetJointCovariance({pose_id}, {landmark_id}, joint)) {
+      cov = MatX();
+      return false;
+    }
+    cov = MatX((int)kPoseDim, (int)kLmDim);
+    for (int r = 0; r < (int)kPoseDim; ++r)
+      for (int c = 0; c < (int)kLmDim; ++c) cov(r, c) = joint(r, (int)kPoseDim + c);
+    return true;
+  }
   // Sliding-window marginalisation (extension; include/ba_hip.h).  Called after Solve():
   // relinearises at the state Solve() left (masks as Solve() computes them) and eliminates pose_ids and
   // landmark_ids into a dense prior on their blanket.  The unary Huber scales the extra linearisation compounds

@@ -149,6 +149,13 @@ int ba_adjuster_get_pose_pose_leverage(ba_adjuster* a, int kind, uint32_t id, do
  * values); returns M, 0 when unavailable (the summary's result then reads SolverError) */
 uint32_t ba_adjuster_get_joint_pose_covariance(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids,
                                                int include_calibration, double* cov);
+/* GetJointCovariance (extension): the M x M block of the inverse of the full system over the poses, the calibration
+ * rows (with include_calibration) and the landmarks, columns in that order, M = n_poses PoseSize (+ K) +
+ * n_landmarks LmSize, row-major into cov (room for M^2 values); returns M, 0 when unavailable.
+ * GetPoseLandmarkCrossCovariance: the PoseSize x LmSize block Cov(pose, landmark); returns 0, or 1 when unavailable. */
+uint32_t ba_adjuster_get_joint_covariance(ba_adjuster* a, uint32_t n_poses, const uint32_t* pose_ids, int include_calibration,
+                                          uint32_t n_landmarks, const uint32_t* landmark_ids, double* cov);
+int ba_adjuster_get_pose_landmark_cross_covariance(ba_adjuster* a, uint32_t pose_id, uint32_t landmark_id, double* cov);
 /* Marginalize / AddDensePrior (extension; include/ba_hip.h).  ba_adjuster_marginalize:
  * after a solve, eliminates the poses and landmarks into a dense prior kept by the adjuster; returns 0 and the
  * blanket size, or 1 when refused.  ba_adjuster_get_marginalization reads it: |B| pose ids, |B| x 16 states,

@@ -636,8 +636,40 @@ typedef struct {
 } ba_hip_joint_marginal_stats;
 int ba_hip_get_joint_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* pose_ids, int include_calibration,
                                double* out);
-/* The figures of the last successful ba_hip_get_joint_marginals (zeros before the first). */
+/* The figures of the substitution and the Gram product of the last successful ba_hip_get_joint_marginals or
+ * ba_hip_get_joint_state_marginals (zeros before the first). */
 int ba_hip_get_joint_marginal_stats(ba_hip_engine* e, ba_hip_joint_marginal_stats* out);
+
+/* ---- joint covariance of a mixed set of poses, calibration and landmarks (cross blocks) ----
+ * The M x M block of the inverse of the full system [[U, W], [W^T, V]] over the requested parameters,
+ * M = n_poses D + (include_calibration ? K : 0) + n_landmarks LmSize; columns in that order: the poses in the
+ * caller's order, the calibration rows, the landmarks in the caller's order.  Poses and calibration use the
+ * coordinates of delta_p, landmarks those of delta_l; orderings are invisible.  It holds the pose-landmark cross
+ * blocks Cov(p, l) = -Sigma_pp W_l V_l^-1 and the landmark-landmark blocks V_l^-1 W_l^T Sigma_pp W_l' V_l'^-1
+ * (+ V_l^-1 when l = l'), which no other getter serves.  Same substitution and Gram product as
+ * ba_hip_get_joint_marginals, started from the columns [E | -W_l V_l^-1] instead of unit columns alone; with
+ * n_landmarks == 0 the result is bit for bit that of ba_hip_get_joint_marginals.  The selected inverse is
+ * neither computed nor allocated, ba_hip_get_marginal_stats is untouched.  out is bitwise symmetric and two calls
+ * give the same bits.
+ *   - Preconditions of ba_hip_get_joint_marginals; with n_landmarks > 0 sharded engines are refused as by
+ *     ba_hip_get_landmark_marginals.
+ *   - Errors: an inactive or out-of-range pose or landmark, a repeated pose or landmark id, n_landmarks > 0 with
+ *     LmSize 0, include_calibration without calibration unknowns, M == 0, M > BA_HIP_JOINT_MAX_COLUMNS, NULL.
+ *   - An active landmark without observations reads 1e6 I with exactly zero cross blocks (the convention of
+ *     ba_hip_get_landmark_marginals).
+ *   - The workspace is the joint path's (ba_hip_release_marginals). */
+typedef struct {
+  double rhs_ms;              /* device time of the right-hand-side pass (events) */
+  double seed_ms;             /* device time of the seed pass */
+  uint64_t incidences;        /* valid incidences scattered into the landmark columns */
+  uint32_t landmark_columns;  /* n_landmarks LmSize */
+  uint32_t seed_tiles;        /* tile rows the landmark columns touch */
+} ba_hip_joint_state_stats;
+int ba_hip_get_joint_state_marginals(ba_hip_engine* e, uint32_t n_poses, const uint32_t* pose_ids,
+                                     int include_calibration, uint32_t n_landmarks, const uint32_t* lm_ids,
+                                     double* out);
+/* The figures of the last successful ba_hip_get_joint_state_marginals (zeros before the first). */
+int ba_hip_get_joint_state_stats(ba_hip_engine* e, ba_hip_joint_state_stats* out);
 
 /* ---- sliding-window marginalisation and dense pose priors (extension) ----------------
  * Conventions are the engine's: S delta = rhs (rhs_p_sc), ApplyUpdate(delta) moves a pose by
