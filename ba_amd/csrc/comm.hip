@@ -218,9 +218,7 @@ int ba_hip_comm_init(ba_hip_engine* h, const void* id128, int rank, int nranks) 
   e->coll = native_collective; e->coll_ctx = e;
   e->rank = rank; e->nranks = nranks;
   e->comm_force = nranks == 1;   // one rank: still run the sharded code paths (test of the RCCL calls)
-  e->nzL_valid = false;          // the tile pattern of S is the union over the shards
-  e->dist_plan_version = ~0ull;
-  e->dog_jrhs_valid = false;
+  e->sharding_changed();
   return 0;
 }
 
@@ -229,9 +227,7 @@ int ba_hip_comm_destroy(ba_hip_engine* h) {
   comm_release(e);
   e->allreduce = nullptr; e->allreduce_ctx = nullptr; e->coll = nullptr; e->coll_ctx = nullptr;
   e->rank = 0; e->nranks = 1; e->comm_force = false;
-  e->nzL_valid = false;
-  e->dist_plan_version = ~0ull;
-  e->dog_jrhs_valid = false;
+  e->sharding_changed();
   return 0;
 }
 

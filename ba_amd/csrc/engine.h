@@ -14,6 +14,7 @@
 #include "marg.h"
 #include "pcg.h"
 #include "dist_plan.h"
+#include "lifecycle.h"
 
 namespace bae {
 
@@ -76,7 +77,6 @@ struct Engine {
   DBuf<double> lm_zref;                  // [L][2] reference pixel of every landmark (LandmarkT::z_ref)
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;   // bulk trailing updates of the factorisation (look-ahead)
-  const double* A_cleared = nullptr;  // the allocation of A whose whole square has been zeroed once
   std::vector<hipEvent_t> ev_panel, ev_bulk;
   hipEvent_t ev_imu_start = nullptr, ev_imu_done = nullptr;  // k_imu on stream2 (launch_imu_early)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;           // k_pose_blocks on stream2 (launch_gather_S)
@@ -86,11 +86,9 @@ struct Engine {
   ba_hip_options opt;
   Problem prob;
   Structure st;
-  bool finalized = false;
+  // every "is this still good" flag of what the device holds, and the events that change them (lifecycle.h)
+  Held held;
   int cur = 0;  // current state buffer (0/1)
-  bool has_snapshot = false;
-  bool factored = false;  // A currently holds the Cholesky factor, not S
-  bool factor_foreign = false;  // invdiag holds the factor of a stand-alone solve, not of A (cleared by ba_hip_solve_gn)
   ba_hip_timers timers;
   ba_hip_allreduce_fn allreduce = nullptr;
   void* allreduce_ctx = nullptr;
@@ -150,7 +148,6 @@ struct Engine {
   DBuf<uint32_t> pose_ptr, pose_mid;     // [Pact+1], [Pact]
   DBuf<uint32_t> pose_ent;               // 3 x n_pose_entries: (rowA, rowB, scalar index)
   DBuf<uint8_t> nzL;                     // tile pattern of the factor L (nt x nt bytes, lower), see k_chol.hip
-  bool nzL_valid = false;
   std::vector<uint8_t> nzL_host;         // host copy (flop accounting of the profiled launches)
   uint64_t nzL_version = 0;
   // distributed solve: per panel the row tiles with a structurally nonzero tile (message rows)
@@ -165,6 +162,8 @@ struct Engine {
   // plan of the distributed solve (dist_plan.h): ownership map, per-panel row lists and messages
   DistPlan dist_plan;
   uint64_t dist_plan_version = ~0ull;
+  // who shares the solve changed (ba_hip_set_allreduce, ba_hip_comm_init, ba_hip_comm_destroy)
+  void sharding_changed() { held.sharding_changed(); dist_plan_version = ~0ull; }
   std::string dist_layout_name;
   DBuf<uint32_t> dist_tiles;             // DistPlan::tiles on the device
   // sparse exchange of S (dist_scatter_S_sparse): rectangles per peer (prefix offsets [N + 1]) and their staging offsets
@@ -215,13 +214,11 @@ struct Engine {
   DBuf<double> obs_e, obs_w;             // error for the median, robust weight
   // err_cache: |r|^2 * original weight per observation at the state held in buffer 0 / 1, left behind by the last
   // EvaluateResiduals at that state (k_residuals mode 1); ba_hip_linearize takes its Huber median from it instead of
-  // running the error pass again.  Invalidated by everything that changes a state buffer or the cameras; off with
-  // calibration unknowns (the camera moves with the step) and on request (BA_HIP_NO_ERR_CACHE).
+  // running the error pass again.  Valid while held.obs_e_valid[buffer]; off with calibration unknowns (the camera
+  // moves with the step) and on request (BA_HIP_NO_ERR_CACHE).
   DBuf<double> obs_e_state[2];
-  bool obs_e_valid[2] = {false, false};
   bool err_cache_on() const { return calib_dim == 0 && !err_cache_off; }
   bool err_cache_off = false;
-  void err_cache_clear() { obs_e_valid[0] = obs_e_valid[1] = false; }
   DBuf<double> obs_jl;                   // [O][2*lm] sqrt(w) * dz_dlm (dogleg J_l * rhs_l)
   DBuf<double> diag_blocks;              // [Pact][36] diagonal blocks of S (k_pose_blocks -> k_write_diag)
   DBuf<double> crow;                     // [n_scalars][6] calibration rows, indexed like `scal`: sqrt(w) dz_dtvs
@@ -248,8 +245,7 @@ struct Engine {
   bool defer_active = false;
   int defer_n = 0;
   double* defer_host[40];
-  double dog_h[8];                       // landing place of the dogleg sums (ba_hip_dogleg_terms)
-  bool dog_jrhs_valid = false;           // dog_h[6], dog_h[7] (|J rhs|^2: projection / pose-pose part) belong to the current linearisation
+  double dog_h[8];                       // landing place of the dogleg sums (ba_hip_dogleg_terms); [6], [7] reused while held.dog_jrhs_valid
   double eval_h[4];                      // ... of the evaluation sums (ba_hip_eval_residuals)
   DBuf<unsigned long long> hist;         // selection histograms
   DBuf<int32_t> flags;                   // factorisation status block (k_chol.hip: setup_status_block)
@@ -257,13 +253,11 @@ struct Engine {
   DBuf<double> pivot_floor;              // tol * |S_jj| per row (ba_hip_options::pivot_rel_tolerance)
   // marginal covariances (ba_hip_compute_marginals, k_selinv.hip): the selected inverse of the last factor,
   // computed on request only.  sig: one 64x64 slot per lower tile of nzL (selinv.h); the plan is rebuilt when
-  // the pattern changes; sig_valid: sig belongs to the factor currently in A (cleared by every linearisation
-  // and factorisation)
+  // the pattern changes; held.sig_valid: sig belongs to the factor currently in A
   DBuf<double> sig;
   DBuf<uint32_t> sig_slot, sig_col_ptr, sig_col_rows, sig_level_cols, sig_items;
   SelinvPlan sig_plan;
   uint64_t sig_plan_version = ~0ull;
-  bool sig_valid = false;
   ba_hip_marginal_stats mstats = {};
   // joint covariances of arbitrary pose sets (ba_hip_get_joint_marginals, k_jointcov.hip): the workspace of the
   // forward substitution Y = L^-1 E and the Gram product, allocated by the first request, reused, freed by
@@ -290,27 +284,22 @@ struct Engine {
   DBuf<double> dp_d, dp_J, dp_G, dp_g, dp_w, dp_E, dp_E_eval, dp_jr;
   const double* dp_E_last = nullptr;    // E_p of the last linearisation or evaluation (ba_hip_get_prior_errors)
   double prior_err_h = 0.0, prior_jrhs_h = 0.0;
-  // marginalisation (ba_hip_marginalize): lin_valid = the device holds the last linearisation at the current
-  // state (cleared by every step, rollback, new masks or solve); pp_err_lin: the pose-pose errors of it
-  bool lin_valid = false;
+  // marginalisation (ba_hip_marginalize) needs held.lin_valid: the device holds the last linearisation at the
+  // current state; pp_err_lin: the pose-pose errors of it; the result (while held.marg_valid) in marg_*
   DBuf<double> pp_err_lin;
   std::vector<uint16_t> mask_host;       // the masks of the last ba_hip_set_pose_masks, by pose id
-  bool marg_valid = false;
   std::vector<uint32_t> marg_ids;        // the blanket, by pose id
   std::vector<double> marg_x0, marg_H, marg_b;
   double marg_c = 0.0;
 
   // iterative reduced solve (ba_hip_set_reduced_solver, k_pcg.hip, pcg.h): the mode of the next ba_hip_solve_gn,
-  // its options, the statistics of the last PCG solve (pcg_last: the last ba_hip_solve_gn ran PCG, so A still holds
-  // S), the plan of nzS_host (rebuilt when the pattern's version changes) and the device work space
+  // its options, the statistics of the last PCG solve (held.pcg_last: the last ba_hip_solve_gn ran PCG, so A still
+  // holds S), the plan of nzS_host (rebuilt when the pattern's version changes) and the device work space
   int solver_mode = BA_HIP_SOLVER_DIRECT;
   ba_hip_pcg_options pcg_opt = {};
   ba_hip_pcg_stats pcg_stats = {};
   ba_hip_pcg_coarse_stats pcg_coarse_stats = {};
-  bool pcg_coarse_last = false;   // the last solve (ba_hip_solve_gn or ba_hip_pcg_solve) used the coarse space
   uint32_t pcg_coarse_built = 0;  // coarse_aggregate the tables of pcg_plan were built for
-  bool pcg_last = false;
-  bool pcg_solved = false;   // ... and no linearisation since: gn_p solves the S in A
   bool pcg_refused() const { return allreduce || coll || comm; }
   PcgPlan pcg_plan;
   std::vector<uint32_t> pcg_blk, pcg_blocks;
@@ -407,7 +396,7 @@ int upload_async(Engine* e, DBuf<T>& d, const U* src, size_t count) {
 // signs D and the L_JJ^-T of the diagonal tiles (both in invdiag).  `who` starts the message when there is none.
 inline int kept_factor(Engine* e, const char* who, uint32_t* nt, const double** dsgn, const double** linvT) {
   const uint32_t n = e->st.ld / 64;
-  if (!e->invdiag.p || !e->nzL_valid || e->nzL_host.size() != (size_t)n * n)
+  if (!e->invdiag.p || !e->held.nzL_valid || e->nzL_host.size() != (size_t)n * n)
     return e->fail_msg((std::string(who) + ": no factor of the last ba_hip_solve_gn").c_str());
   *nt = n;
   *dsgn = e->invdiag.p;
@@ -472,7 +461,7 @@ void comm_release(Engine* e);
 int check_solve_residual(Engine* e, const double* dS, const double* dx, const double* db, double* out2);
 int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* status, const uint8_t* nz);
 int trailing_marginals(Engine* e, const double* dA, uint32_t ld, uint32_t first, uint32_t K, double* cov);
-// marginal covariances (k_selinv.hip): the selected inverse of the factor in A (no-op while sig_valid); blocks
+// marginal covariances (k_selinv.hip): the selected inverse of the factor in A (no-op while held.sig_valid); blocks
 // out of it (rows in engine order: out[q] = Sigma[ra[q] .. + Da, rb[q] .. + Db]); landmark blocks (ids: landmark
 // ids, or null for every active landmark by optimisation index); freeing the store
 int marginals_compute(Engine* e);

@@ -279,7 +279,6 @@ static int build_structure(Engine* e) {
     if (st.K)
       for (uint32_t r = st.np / 64; r <= (st.n - 1) / 64; ++r)
         for (uint32_t c = 0; c <= r; ++c) { st.tile_nz[(size_t)r * nt + c] = 1; st.tile_nz[(size_t)c * nt + r] = 1; }
-    e->nzL_valid = false;
   }
 
   stage("tile pattern");
@@ -342,7 +341,7 @@ static int build_structure(Engine* e) {
   if ((rc = upload_cameras(e, false))) return rc;
   // state
   e->cur = 0;
-  e->has_snapshot = false;
+  e->held.structure_rebuilt();   // (nothing since the new tile pattern above has read the old one's flag)
   for (int b = 0; b < 2; ++b) {
     BAE_HIP(e->pose_state[b].alloc(std::max<size_t>((size_t)st.P * kPoseState, 1)));
     BAE_HIP(e->lm_x[b].alloc(std::max<size_t>((size_t)st.L * 4, 1)));
@@ -393,7 +392,6 @@ static int build_structure(Engine* e) {
   BAE_HIP(e->lm_vinv.alloc(L1 * LM1 * LM1)); BAE_HIP(e->lm_bl.alloc(L1 * LM1));
   BAE_HIP(hipMemsetAsync(e->lm_vinv.p, 0, e->lm_vinv.bytes(), e->stream));
   BAE_HIP(hipMemsetAsync(e->lm_bl.p, 0, e->lm_bl.bytes(), e->stream));
-  e->A_cleared = nullptr;  // new structure (possibly a new allocation / leading dimension): clear the square once
   BAE_HIP(e->A.alloc((size_t)(st.ld + 1) * st.ld));
   BAE_HIP(e->rhs_p.alloc(st.ld)); BAE_HIP(e->rhs_sc.alloc(st.ld));
   BAE_HIP(e->gn_p.alloc(st.ld)); BAE_HIP(e->step_p.alloc(st.ld));
@@ -422,7 +420,7 @@ static int build_structure(Engine* e) {
 // tiles in flight on one XCD gather the same pose group's rows out of its L2.
 int build_tile_order(Engine* e) {
   const Structure& st = e->st;
-  if (!e->nzL_valid) {
+  if (!e->held.nzL_valid) {
     int rc = factor_tile_pattern(e);
     if (rc) return rc;
   }
@@ -517,13 +515,13 @@ static int set_masks_device(Engine* e, const std::vector<uint16_t>& by_id) {
 static int kept_factor_ready(Engine* e, const char* who, const char* noun, bool foreign_ok) {
   const std::string w = who, m = w + ": ";
   if (noun && dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
-  if (!e->factored && e->pcg_solved)
+  if (!e->held.factored && e->held.pcg_solved)
     return e->fail_msg((m + "the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor" +
                         (noun ? std::string("; ") + noun + " need a direct solve (ba_hip_set_reduced_solver)" : "")).c_str());
-  if (!e->factored)
+  if (!e->held.factored)
     return e->fail_msg((noun ? m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised since)"
                              : w + " needs the factor of the last ba_hip_solve_gn").c_str());
-  if (e->factor_foreign && !foreign_ok)
+  if (e->held.factor_foreign && !foreign_ok)
     return e->fail_msg((m + "a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has replaced the kept factor "
                             "since the last ba_hip_solve_gn").c_str());
   if (!noun && dist_solve_enabled(e)) return e->fail_msg("calibration marginals: not available with the distributed solve");
@@ -638,7 +636,7 @@ int ba_hip_set_cameras(ba_hip_engine* h, uint32_t n, const double* params4, cons
   e->prob.cam_tvs.assign(t_vs7, t_vs7 + 7 * (size_t)n);
   e->prob.cam_model.assign(n, 0);
   e->prob.cam_w.assign(n, 0.0);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
@@ -652,7 +650,7 @@ int ba_hip_set_camera_models(ba_hip_engine* h, uint32_t n, const int32_t* model,
   e->prob.cam_model.assign(model, model + n);
   e->prob.cam_w.assign(n, 0.0);
   for (uint32_t c = 0; c < n; ++c) if (model[c] == 1) e->prob.cam_w[c] = w[c];
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 int ba_hip_get_camera_fov(ba_hip_engine* h, uint32_t n, double* w) {
@@ -664,7 +662,7 @@ int ba_hip_get_camera_fov(ba_hip_engine* h, uint32_t n, double* w) {
 
 int ba_hip_set_pose_cam_params(ba_hip_engine* h, uint32_t n, const double* params4) {
   ENG(h);
-  e->err_cache_clear();   // (uploaded without a rebuild: the residuals change)
+  e->held.pose_cam_params_changed();
   if (n == 0 || !params4) {
     e->prob.pose_cam_params.clear();
     return 0;
@@ -687,7 +685,7 @@ int ba_hip_set_poses(ba_hip_engine* h, uint32_t n, const double* t_wp7, const do
     if (b6) for (int i = 0; i < 6; ++i) s[10 + i] = b6[(size_t)p * 6 + i];
     if (is_active) pb.pose_active[p] = is_active[p] ? 1 : 0;
   }
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
@@ -702,7 +700,7 @@ int ba_hip_set_landmarks(ba_hip_engine* h, uint32_t n, const double* x_w4, const
   else pb.lm_ref_cam.assign(n, 0);
   if (is_active) pb.lm_active.assign(is_active, is_active + n);
   else pb.lm_active.assign(n, 1);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
@@ -719,14 +717,14 @@ int ba_hip_set_projection_residuals(ba_hip_engine* h, uint32_t n, const double* 
   else pb.proj_cam.assign(n, 0);
   if (weight) pb.proj_w.assign(weight, weight + n);
   else pb.proj_w.assign(n, 1.0);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
 int ba_hip_set_conditioning_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* residual_id) {
   ENG(h);
   e->prob.proj_cond.assign(residual_id, residual_id + n);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
@@ -741,7 +739,7 @@ int ba_hip_set_unary_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* pos
   pb.un_cov_inv.assign(cov_inv36, cov_inv36 + 36 * (size_t)n);
   if (use_rotation) pb.un_rot.assign(use_rotation, use_rotation + n);
   else pb.un_rot.assign(n, 1);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
@@ -761,7 +759,7 @@ int ba_hip_set_binary_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* po
   else pb.bin_w.assign(n, 1.0);
   if (use_rotation) pb.bin_rot.assign(use_rotation, use_rotation + n);
   else pb.bin_rot.assign(n, 1);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
@@ -777,7 +775,7 @@ int ba_hip_set_imu_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* pose1
   pb.imu_meas.assign(meas7, meas7 + 7 * (size_t)(n ? meas_ptr[n] : 0));
   if (weight) pb.imu_w.assign(weight, weight + n);
   else pb.imu_w.assign(n, 1.0);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 
@@ -957,8 +955,7 @@ int ba_hip_set_gravity(ba_hip_engine* h, const double g3[3]) {
 
 int ba_hip_finalize(ba_hip_engine* h) {
   ENG(h);
-  e->dog_jrhs_valid = false;  // the factor rows are rebuilt: no cached sum survives
-  e->err_cache_clear();
+  e->held.finalize_begins();
   BAE_HIP(hipSetDevice(e->device));
   Problem& pb = e->prob;
   if (pb.pose_active.size() != pb.num_poses) pb.pose_active.assign(pb.num_poses, 1);
@@ -968,17 +965,16 @@ int ba_hip_finalize(ba_hip_engine* h) {
   e->opt_of_natural.clear();
   e->group_ptr.clear(); e->group_adj.clear();
   e->order_stats = ba_hip_ordering_stats();
-  e->lin_valid = false;
   e->lev_pos.clear();
   e->mask_host.assign(pb.num_poses, 0);
   int rc = build_structure(e);
   if (rc) return rc;
-  e->finalized = true;
+  e->held.finalize_succeeded();
   return 0;
 }
 
 #define NEED_FINAL() \
-  if (!e->finalized) return e->fail_msg("ba_hip_finalize has not been called")
+  if (!e->held.finalized) return e->fail_msg("ba_hip_finalize has not been called")
 
 int ba_hip_get_conditioning_error(ba_hip_engine* h, double* proj_sq_sum) {
   ENG(h);
@@ -995,10 +991,8 @@ int ba_hip_get_conditioning_error(ba_hip_engine* h, double* proj_sq_sum) {
 int ba_hip_begin_solve(ba_hip_engine* h) {
   ENG(h);
   NEED_FINAL();
-  e->dog_jrhs_valid = false;
-  e->err_cache_clear();   // x_s is re-derived from x_w, the cameras may have been re-uploaded
+  e->held.solve_begins();
   e->err_cache_off = getenv("BA_HIP_NO_ERR_CACHE") != nullptr;
-  e->lin_valid = false;
   BAE_HIP(hipSetDevice(e->device));
   if (!e->prob.pose_cam_params.empty() && e->prob.pose_cam_params.size() != 4 * (size_t)e->prob.num_poses)
     return e->fail_msg("per-pose camera parameters: one [fx,fy,u0,v0] per pose expected");
@@ -1022,8 +1016,7 @@ int ba_hip_set_pose_masks(ba_hip_engine* h, uint32_t n, const uint16_t* masks) {
   ENG(h);
   NEED_FINAL();
   if (n != e->st.P) return e->fail_msg("mask count != pose count");
-  e->dog_jrhs_valid = false;
-  e->lin_valid = false;
+  e->held.masks_changed();
   e->mask_host.assign(masks, masks + n);
   return set_masks_device(e, std::vector<uint16_t>(masks, masks + n));
 }
@@ -1035,12 +1028,12 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   const Structure& st = e->st;
   ba_hip_errors errs = {0, 0, 0, 0};
   int rc;
-  e->dog_jrhs_valid = false;
+  e->held.linearize_begins();
   // projection errors at the linearisation point -> Huber sigma
   EventTimer t_j(e);
   if ((rc = launch_pose_prep(e))) return rc;
   // the errors of the Huber median: left by the last EvaluateResiduals at this state, or computed now
-  const bool cached = e->err_cache_on() && e->obs_e_valid[e->cur] && e->obs_e_state[e->cur].n >= st.O && st.O > 0;
+  const bool cached = e->err_cache_on() && e->held.obs_e_valid[e->cur] && e->obs_e_state[e->cur].n >= st.O && st.O > 0;
   const double* med_in = cached ? e->obs_e_state[e->cur].p : e->obs_e.p;
   if (!cached && (rc = launch_residuals(e, 0))) return rc;
   t_j.mark();
@@ -1082,12 +1075,9 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   if ((rc = sum_partials(e, st.O ? st.n_chunks : 0, 1, hs))) { (void)defer_flush(e); return rc; }
   t_l.mark();
   EventTimer t_s(e);
-  e->factored = false;
-  e->pcg_solved = false;
-  e->sig_valid = false;
+  e->held.linearize_writes_A();
   if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) { (void)defer_flush(e); return rc; }
   // dense priors after k_pp_scatter, in prior order; their E_p is folded into unary_error
-  e->lin_valid = false;
   if ((rc = launch_priors(e, 1, &e->prior_err_h))) { (void)defer_flush(e); return rc; }
   if (e->prob.num_unary + e->prob.num_binary + e->prob.num_imu)  // kept for ba_hip_marginalize (the dogleg reuses pp_err)
     BAE_HIP(hipMemcpyAsync(e->pp_err_lin.p, e->pp_err.p, (size_t)(e->prob.num_unary + e->prob.num_binary + e->prob.num_imu) *
@@ -1103,7 +1093,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
       // (reduce-scatter); the reduced rhs (one row) and rhs_p are summed everywhere
       BAE_HIP(hipStreamSynchronize(e->stream));
       // the union tile pattern decides which tiles of S travel (a collective on first use)
-      if (!e->nzL_valid && (rc = factor_tile_pattern(e))) return rc;
+      if (!e->held.nzL_valid && (rc = factor_tile_pattern(e))) return rc;
       if (shard_allreduce(e, e->rhs_sc.p, st.ld, 0) != 0) return e->fail_msg("allreduce hook failed");
       if (shard_allreduce(e, e->rhs_p.p, st.ld, 0) != 0) return e->fail_msg("allreduce hook failed");
       if ((rc = dist_reduce_scatter_S(e))) return rc;
@@ -1130,7 +1120,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   e->timers.robust_weights = t_r.read_ms();
   e->timers.jtj_schur = t_s.read_ms();
   errs.proj_error = hs[0]; errs.unary_error = hs[1] + e->prior_err_h; errs.binary_error = hs[2]; errs.inertial_error = hs[3];
-  e->lin_valid = true;
+  e->held.linearize_succeeded();
   if (out) *out = errs;
   return 0;
 }
@@ -1145,13 +1135,12 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
   // CalculateGn runs only with active poses (BundleAdjuster.cpp:959-964, 1089-1094): with none, the
   // calibration unknowns are not solved for either (delta_k stays empty in the reference)
   const bool skip = st.K && st.Pact == 0;
-  e->sig_valid = false;
+  e->held.gn_solve_begins();
   if (skip) BAE_HIP(hipMemsetAsync(e->gn_p.p, 0, e->gn_p.bytes(), e->stream));
-  e->pcg_last = e->pcg_solved = e->pcg_coarse_last = false;
   if (st.n > 0 && !skip && e->solver_mode == BA_HIP_SOLVER_PCG) {
     // S stays in A: no factor, no kept copy
     if (e->pcg_refused()) return e->fail_msg("the PCG solver is not available on a sharded engine");
-    if (!e->nzL_valid && (rc = factor_tile_pattern(e))) return rc;
+    if (!e->held.nzL_valid && (rc = factor_tile_pattern(e))) return rc;
     const bool rebuild = e->pcg_plan_version != e->nzL_version || e->pcg_plan.nt != st.ld / 64 || e->pcg_blk.size() != (size_t)2 * st.ld;
     if (rebuild) {
       build_pcg_plan(e->nzS_host, st.ld / 64, e->pcg_plan);
@@ -1175,20 +1164,18 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
     }
     if ((rc = pcg_solve_device(e, e->A.p, st.n, st.ld, e->rhs_sc.p, e->pcg_plan, e->nzS_host, e->pcg_blk, e->pcg_blocks, rebuild,
                                e->pcg_opt, e->gn_p.p, &e->pcg_stats, &status))) return rc;
-    e->factored = false;
-    e->pcg_last = e->pcg_solved = true;
+    e->held.solved_by_pcg();
   } else if (st.n > 0 && !skip) {
     if (e->opt.keep_reduced_system) {
       BAE_HIP(e->A_keep.alloc((size_t)st.ld * st.ld));
       BAE_HIP(hipMemcpyAsync(e->A_keep.p, e->A.p, (size_t)st.ld * st.ld * sizeof(double),
                              hipMemcpyDeviceToDevice, e->stream));
     }
-    if (!e->nzL_valid && (rc = factor_tile_pattern(e))) return rc;
+    if (!e->held.nzL_valid && (rc = factor_tile_pattern(e))) return rc;
     if (dist_solve_enabled(e)) {
       if ((rc = cholesky_solve_dist(e, e->A.p, st.ld, e->gn_p.p, &status, e->nzL.p))) return rc;
     } else if ((rc = cholesky_solve(e, e->A.p, st.n, st.ld, e->gn_p.p, &status, e->nzL.p))) return rc;
-    e->factored = true;
-    e->factor_foreign = false;
+    e->held.solved_directly();
   }
   e->timers.solve = t.stop_ms();
   EventTimer tb(e);
@@ -1206,14 +1193,14 @@ int ba_hip_dogleg_terms(ba_hip_engine* h, int gn_available, ba_hip_dogleg_scalar
   double* dh = e->dog_h;
   // the steepest-descent denominator |J rhs|^2 does not involve the Gauss-Newton step: the second call of
   // an iteration (gn_available, BundleAdjuster.cpp:971-1002) reuses what the first one summed
-  const bool reuse = gn_available && e->dog_jrhs_valid;
+  const bool reuse = gn_available && e->held.dog_jrhs_valid;
   defer_begin(e);
   int rc = launch_dogleg(e, gn_available, dh, reuse);
   if (!rc && !reuse) rc = launch_posepose_jrhs(e, dh + 7);
   if (!rc && !reuse) rc = launch_priors_jrhs(e, &e->prior_jrhs_h);
   const int rf = defer_flush(e);
-  if (rc || rf) { e->dog_jrhs_valid = false; return rc ? rc : rf; }
-  e->dog_jrhs_valid = true;
+  e->held.dogleg_sums(!rc && !rf);
+  if (rc || rf) return rc ? rc : rf;
   out->rhs_p_sq = dh[0]; out->gn_p_sq = dh[1]; out->rhs_gn_p = dh[2];
   out->rhs_l_sq = dh[3]; out->gn_l_sq = dh[4]; out->rhs_gn_l = dh[5];
   out->j_rhs_sq = dh[6] + dh[7] + e->prior_jrhs_h;
@@ -1242,9 +1229,7 @@ int ba_hip_apply_step(ba_hip_engine* h) {
   int rc = launch_apply_step(e);
   if (rc) return rc;
   e->cur = 1 - e->cur;
-  e->has_snapshot = true;
-  e->lin_valid = false;
-  e->obs_e_valid[e->cur] = false;   // a new state in this buffer: no evaluation of it yet
+  e->held.step_applied(e->cur);
   if (e->calib_dim && !e->calib_tvs && e->st.C > 0) {
     // BundleAdjuster.cpp:46-69: params of camera 0 -= delta_k, then every x_s ray is re-derived from
     // the landmark's reference pixel with the new parameters, keeping its length
@@ -1284,11 +1269,10 @@ int ba_hip_apply_step(ba_hip_engine* h) {
 int ba_hip_rollback(ba_hip_engine* h) {
   ENG(h);
   NEED_FINAL();
-  if (!e->has_snapshot) return e->fail_msg("no snapshot to roll back to");
+  if (!e->held.has_snapshot) return e->fail_msg("no snapshot to roll back to");
   BAE_HIP(hipSetDevice(e->device));
   e->cur = 1 - e->cur;
-  e->has_snapshot = false;
-  e->lin_valid = false;
+  e->held.rolled_back();
   int rc;
   if (e->calib_tvs) {
     // the reference restores the poses WITH their cached T_sw but not the rig (:1060-1068): the
@@ -1383,7 +1367,6 @@ uint32_t ba_hip_num_calib_params(const ba_hip_engine* h) {
 }
 int ba_hip_set_calibration(ba_hip_engine* h, int calib_size, int do_tvs) {
   ENG(h);
-  e->dog_jrhs_valid = false;
   if (calib_size != 0 && calib_size != 4 && calib_size != 5)
     return e->fail_msg("CalibSize must be 0, 4 (LinearCamera: fx, fy, u0, v0) or 5 (FovCamera: fx, fy, u0, v0, w)");
   if (calib_size && do_tvs)
@@ -1393,7 +1376,7 @@ int ba_hip_set_calibration(ba_hip_engine* h, int calib_size, int do_tvs) {
     return e->fail_msg("calibration columns need LmSize 1 (parallel_algos.h:102-131)");
   e->calib_dim = do_tvs ? 6 : calib_size;
   e->calib_tvs = do_tvs != 0;
-  e->finalized = false;
+  e->held.calibration_changed();
   return 0;
 }
 int ba_hip_get_calibration_marginals(ba_hip_engine* h, double* cov) {
@@ -1408,7 +1391,7 @@ int ba_hip_get_calibration_marginals(ba_hip_engine* h, double* cov) {
 int ba_hip_set_landmark_ref_pixels(ba_hip_engine* h, uint32_t n, const double* z_ref2) {
   ENG(h);
   e->prob.lm_zref.assign(z_ref2, z_ref2 + 2 * (size_t)n);
-  e->finalized = false;
+  e->held.problem_changed();
   return 0;
 }
 int ba_hip_get_camera_params(ba_hip_engine* h, uint32_t n, double* params4) {
@@ -1451,9 +1434,9 @@ int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
   auto block_of = [&](uint32_t r) { return r < st.np ? r / D : st.Pact; };  // the calibration border is one more block
   std::vector<double> a((size_t)n * ld);
   BAE_HIP(hipStreamSynchronize(e->stream));
-  if (e->factored && !(e->opt.keep_reduced_system && e->A_keep.p))
+  if (e->held.factored && !(e->opt.keep_reduced_system && e->A_keep.p))
     return e->fail_msg("S was factorised in place; set keep_reduced_system to read it after ba_hip_solve_gn");
-  const double* src = e->factored ? e->A_keep.p : e->A.p;
+  const double* src = e->held.factored ? e->A_keep.p : e->A.p;
   if (n) BAE_HIP(hipMemcpy(a.data(), src, a.size() * sizeof(double), hipMemcpyDeviceToHost));
   // lower storage -> the reference's s_: block (i,j) kept for i <= j only when
   // use_triangular_matrices (SparseBlockMatrixOps.h:236-238), full symmetric otherwise
@@ -1475,11 +1458,11 @@ int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
 // ---- marginal covariances (k_selinv.hip) ----------------------------------------------------------
 static int marginals_ready(Engine* e, const char* what, bool landmarks) {
   std::string m = std::string(what) + ": ";
-  if (!e->finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
+  if (!e->held.finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
   if (landmarks && e->sharded() && !dist_solve_enabled(e))   // (the distributed solve refuses first, for every block)
     return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
   int rc;   // (a selected inverse computed before a stand-alone solve stays good)
-  if ((rc = kept_factor_ready(e, what, "marginals", e->sig_valid))) return rc;
+  if ((rc = kept_factor_ready(e, what, "marginals", e->held.sig_valid))) return rc;
   BAE_HIP(hipSetDevice(e->device));
   return marginals_compute(e);
 }
@@ -1603,7 +1586,7 @@ static int joint_state_run(Engine* e, const char* what, bool state, uint32_t n, 
                            int include_calibration, uint32_t nl, const uint32_t* lm_ids, double* out) {
   const std::string m = std::string(what) + ": ";
   if (nl && !e->lm_dim) return e->fail_msg((m + "LmSize 0 has no landmark unknowns").c_str());
-  if (!e->finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
+  if (!e->held.finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
   if (nl && e->sharded() && !dist_solve_enabled(e))   // (the distributed solve refuses first, for every block)
     return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
   int rc;
@@ -1849,11 +1832,11 @@ int ba_hip_check_solve(ba_hip_engine* h, double* residual_norm, double* rhs_norm
   NEED_FINAL();
   BAE_HIP(hipSetDevice(e->device));
   // after a PCG solve A itself still holds S
-  if (!e->pcg_solved && !(e->factored && e->opt.keep_reduced_system && e->A_keep.p))
+  if (!e->held.pcg_solved && !(e->held.factored && e->opt.keep_reduced_system && e->A_keep.p))
     return e->fail_msg("ba_hip_check_solve needs keep_reduced_system and a finished ba_hip_solve_gn");
   if (e->sharded()) return e->fail_msg("ba_hip_check_solve: single shard only");
   double o[2];
-  int rc = check_solve_residual(e, e->pcg_solved ? e->A.p : e->A_keep.p, e->gn_p.p, e->rhs_sc.p, o);
+  int rc = check_solve_residual(e, e->held.pcg_solved ? e->A.p : e->A_keep.p, e->gn_p.p, e->rhs_sc.p, o);
   if (rc) return rc;
   if (residual_norm) *residual_norm = o[0];
   if (rhs_norm) *rhs_norm = o[1];
@@ -1877,17 +1860,17 @@ int ba_hip_get_structure_stats(ba_hip_engine* h, ba_hip_structure_stats* out) {
   out->tile_refs = st.n_tile_refs; out->pose_entries = st.n_pose_entries; out->linearize_waves = st.n_chunks;
   const uint64_t nt = st.ld / 64;
   out->tiles_lower = nt * (nt + 1) / 2;
-  if (!e->nzL_valid && !(e->sharded())) {
+  if (!e->held.nzL_valid && !(e->sharded())) {
     int rc = factor_tile_pattern(e);
     if (rc) return rc;
   }
-  if (e->nzL_valid && e->nzL_host.size() == nt * nt && e->nzS_host.size() == nt * nt)
+  if (e->held.nzL_valid && e->nzL_host.size() == nt * nt && e->nzS_host.size() == nt * nt)
     for (uint64_t i = 0; i < nt; ++i)
       for (uint64_t k = 0; k <= i; ++k) {
         out->tiles_S += e->nzS_host[i * nt + k] ? 1 : 0;
         out->tiles_L += e->nzL_host[i * nt + k] ? 1 : 0;
       }
-  if (e->nzL_valid && e->nzL_host.size() == nt * nt) out->factor_tile_products = factor_tile_products(e->nzL_host, (uint32_t)nt);
+  if (e->held.nzL_valid && e->nzL_host.size() == nt * nt) out->factor_tile_products = factor_tile_products(e->nzL_host, (uint32_t)nt);
   return 0;
 }
 
@@ -1901,9 +1884,9 @@ int ba_hip_debug_set(ba_hip_engine* h, int key, int value) {
       break;
     case 2: e->dbg_tile_order = value; e->tile_order_version = ~0ull; break;
     case 4: e->dbg_linearize_variant = value; break;
-    case 5: e->dbg_host_structure = value; e->finalized = false; break;
+    case 5: e->dbg_host_structure = value; e->held.problem_changed(); break;
     case 6: e->dbg_imu_wave = value; break;
-    case 3: e->dbg_all_tiles = value; e->tile_order_version = ~0ull; e->A_cleared = nullptr; break;
+    case 3: e->dbg_all_tiles = value; e->tile_order_version = ~0ull; e->held.square_dirty(); break;
     default: return e->fail_msg("ba_hip_debug_set: unknown key");
   }
   return 0;
@@ -1980,7 +1963,7 @@ int ba_hip_dist_plan_stats(uint32_t nblk, const uint8_t* nz_lower, int nranks, c
 int ba_hip_get_factor_tile_pattern(ba_hip_engine* h, uint32_t nblk, uint8_t* nz_lower) {
   ENG(h);
   NEED_FINAL();
-  if (!e->nzL_valid) {
+  if (!e->held.nzL_valid) {
     BAE_HIP(hipSetDevice(e->device));
     const int rc = factor_tile_pattern(e);
     if (rc) return rc;
@@ -2024,14 +2007,14 @@ int ba_hip_set_reduced_solver(ba_hip_engine* h, int mode, const ba_hip_pcg_optio
 
 int ba_hip_get_pcg_stats(ba_hip_engine* h, ba_hip_pcg_stats* out) {
   ENG(h);
-  if (!e->pcg_last) return e->fail_msg("ba_hip_get_pcg_stats: the last ba_hip_solve_gn did not run the PCG solver");
+  if (!e->held.pcg_last) return e->fail_msg("ba_hip_get_pcg_stats: the last ba_hip_solve_gn did not run the PCG solver");
   if (out) *out = e->pcg_stats;
   return 0;
 }
 
 int ba_hip_get_pcg_coarse_stats(ba_hip_engine* h, ba_hip_pcg_coarse_stats* out) {
   ENG(h);
-  if (!e->pcg_coarse_last) return e->fail_msg("ba_hip_get_pcg_coarse_stats: the last solve did not use the coarse space");
+  if (!e->held.pcg_coarse_last) return e->fail_msg("ba_hip_get_pcg_coarse_stats: the last solve did not use the coarse space");
   if (out) *out = e->pcg_coarse_stats;
   return 0;
 }
@@ -2039,7 +2022,7 @@ int ba_hip_get_pcg_coarse_stats(ba_hip_engine* h, ba_hip_pcg_coarse_stats* out) 
 int ba_hip_get_pcg_coarse(ba_hip_engine* h, uint32_t nc, double* C, double* Cinv) {
   ENG(h);
   Engine::PcgWork& w = e->pcg;
-  if (!e->pcg_coarse_last || !w.coarse_nc || !w.C.p || !w.Cinv.p)
+  if (!e->held.pcg_coarse_last || !w.coarse_nc || !w.C.p || !w.Cinv.p)
     return e->fail_msg("ba_hip_get_pcg_coarse: the last solve did not use the coarse space");
   if (nc != w.coarse_nc) return e->fail_msg("ba_hip_get_pcg_coarse: nc differs from the coarse unknowns of the last solve");
   BAE_HIP(hipSetDevice(e->device));
@@ -2097,9 +2080,7 @@ int ba_hip_set_allreduce(ba_hip_engine* h, ba_hip_allreduce_fn fn, void* ctx, in
   if (fn && e->solver_mode == BA_HIP_SOLVER_PCG)
     return e->fail_msg("the all-reduce hook needs the direct reduced solver (ba_hip_set_reduced_solver selected PCG)");
   e->allreduce = fn; e->allreduce_ctx = ctx; e->rank = rank; e->nranks = nranks < 1 ? 1 : nranks;
-  e->nzL_valid = false;  // the tile pattern of S is the union over the shards
-  e->dist_plan_version = ~0ull;
-  e->dog_jrhs_valid = false;  // a local sum may have become a cross-shard one
+  e->sharding_changed();
   return 0;
 }
 
@@ -2111,7 +2092,7 @@ int ba_hip_set_dense_priors(ba_hip_engine* h, uint32_t n, const uint32_t* ptr, c
   if (n && (!ptr || !pose_ids || !x0_16 || !H || !b || !c)) return e->fail_msg("ba_hip_set_dense_priors: NULL argument");
   if (n == 0) {  // removes the priors
     e->dpri = DensePriors();
-    e->finalized = false;
+    e->held.problem_changed();
     return 0;
   }
   if (ptr[0] != 0) return e->fail_msg("ba_hip_set_dense_priors: ptr[0] must be 0");
@@ -2137,7 +2118,7 @@ int ba_hip_set_dense_priors(ba_hip_engine* h, uint32_t n, const uint32_t* ptr, c
   pr.b.assign(b, b + (size_t)ktot * D);
   pr.c.assign(c, c + n);
   e->dpri = std::move(pr);
-  e->finalized = false;  // part of the graph: takes effect at the next ba_hip_finalize
+  e->held.problem_changed();
   return 0;
 }
 
@@ -2161,7 +2142,7 @@ int ba_hip_marginalize(ba_hip_engine* h, uint32_t nm, const uint32_t* m_ids, uin
   if ((nm && !m_ids) || (nl && !l_ids)) return e->fail_msg("marginalize: NULL argument");
   if (e->st.K) return e->fail_msg("marginalize: not offered with calibration unknowns");
   if (e->allreduce || e->coll || e->comm) return e->fail_msg("marginalize: not offered on sharded engines or with the distributed solve");
-  if (!e->lin_valid)
+  if (!e->held.lin_valid)
     return e->fail_msg("marginalize: needs the linearisation of the current state (ba_hip_linearize, no step, rollback or "
                        "new masks since)");
   BAE_HIP(hipSetDevice(e->device));
@@ -2178,8 +2159,8 @@ int ba_hip_marginalize(ba_hip_engine* h, uint32_t nm, const uint32_t* m_ids, uin
   const double tol = e->opt.pivot_rel_tolerance > 0 ? e->opt.pivot_rel_tolerance : 1e-10;
   double dev_ms = 0.0;
   const int rc = marginalize_run(e, pl, lmask, tol, &dev_ms);
-  if (rc) {  // the store may hold a partial result
-    e->marg_valid = false;
+  if (rc) {
+    e->held.marginalize_failed();
     return rc;
   }
   // x0: the state of the blanket poses at this linearisation
@@ -2189,7 +2170,7 @@ int ba_hip_marginalize(ba_hip_engine* h, uint32_t nm, const uint32_t* m_ids, uin
   e->marg_x0.resize(e->marg_ids.size() * kPoseState);
   for (size_t i = 0; i < e->marg_ids.size(); ++i)
     for (int k = 0; k < kPoseState; ++k) e->marg_x0[i * kPoseState + k] = state[(size_t)e->marg_ids[i] * kPoseState + k];
-  e->marg_valid = true;
+  e->held.marginalized();
   if (stats) {
     *stats = ba_hip_marginalization_stats();
     stats->blanket_poses = pl.nB;
@@ -2203,7 +2184,7 @@ int ba_hip_marginalize(ba_hip_engine* h, uint32_t nm, const uint32_t* m_ids, uin
 
 int ba_hip_get_marginalization(ba_hip_engine* h, uint32_t* blanket_ids, double* x0_16, double* H, double* b, double* c) {
   ENG(h);
-  if (!e->marg_valid) return e->fail_msg("ba_hip_get_marginalization: no marginalisation result (ba_hip_marginalize)");
+  if (!e->held.marg_valid) return e->fail_msg("ba_hip_get_marginalization: no marginalisation result (ba_hip_marginalize)");
   if (blanket_ids) std::copy(e->marg_ids.begin(), e->marg_ids.end(), blanket_ids);
   if (x0_16) std::copy(e->marg_x0.begin(), e->marg_x0.end(), x0_16);
   if (H) std::copy(e->marg_H.begin(), e->marg_H.end(), H);
@@ -2214,7 +2195,7 @@ int ba_hip_get_marginalization(ba_hip_engine* h, uint32_t* blanket_ids, double* 
 
 int ba_hip_release_marginalization(ba_hip_engine* h) {
   ENG(h);
-  e->marg_valid = false;
+  e->held.marginalization_released();
   std::vector<uint32_t>().swap(e->marg_ids);
   std::vector<double>().swap(e->marg_x0);
   std::vector<double>().swap(e->marg_H);
@@ -2233,7 +2214,7 @@ int ba_hip_dense_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, cons
   BAE_HIP(e->flags.alloc(16));
   BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
   int status = 0;
-  e->factor_foreign = true;  // invdiag is about to hold this system's factor, not the scene's
+  e->held.standalone_factorisation();
   int rc = cholesky_solve(e, dA.p, n, sys.ld, dx.p, &status, nullptr);  // arbitrary matrix: dense
   if (rc) return rc;
   BAE_HIP(download_x(dx, n, x));
@@ -2307,7 +2288,7 @@ int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const
   BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
   BAE_HIP(hipMemcpy(dnz.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
   int status = 0;
-  e->factor_foreign = true;  // invdiag is about to hold this system's factor, not the scene's
+  e->held.standalone_factorisation();
   int rc = cholesky_solve(e, dA.p, n, ld, dx.p, &status, dnz.p);
   if (rc) return rc;
   hipError_t err = hipDeviceSynchronize();  // both streams of the factorisation

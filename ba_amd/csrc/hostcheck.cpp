@@ -840,3 +840,17 @@ extern "C" int ba_hostcheck_pose_pose_leverages(int D, uint32_t P, const uint8_t
   pose_pose_leverage_host(in, variant, cov, lam, lev);
   return 0;
 }
+
+// ---- engine lifecycle record -----------------------------------------------------------------------
+#include "lifecycle.h"
+
+// The events of lifecycle.h (HeldEvent codes) replayed in order on a fresh record: bits[i] = the flags after
+// events[i], one bit per flag in HeldBit order.  Returns 0, or -(i + 1) at the first unknown code.
+extern "C" int ba_hostcheck_lifecycle(uint32_t n, const int32_t* events, uint32_t* bits) {
+  bae::Held h;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!bae::held_apply(h, events[i])) return -(int)(i + 1);
+    bits[i] = bae::held_bits(h);
+  }
+  return 0;
+}

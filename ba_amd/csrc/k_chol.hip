@@ -1564,7 +1564,7 @@ int factor_tile_pattern(Engine* e) {
   BAE_HIP(hipMemcpy(e->nzL.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
   e->nzL_host = nz;
   e->nzL_version++;
-  e->nzL_valid = true;
+  e->held.pattern_built();
   return 0;
 }
 

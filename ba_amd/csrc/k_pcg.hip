@@ -249,7 +249,7 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
   *status = 0;
   if (ld != 64 * nt || blk.size() != (size_t)2 * ld || nz.size() != (size_t)nt * nt)
     return e->fail_msg("pcg_solve_device: plan does not match the system");
-  e->pcg_coarse_last = false;
+  e->held.pcg_run_begins();
   const bool coarse = opt.coarse_aggregate != 0;
   if (coarse && (plan.cmap.size() != (size_t)ld || plan.coarse_req != opt.coarse_aggregate || plan.ncp % 64 || plan.nc > plan.ncp))
     return e->fail_msg("pcg_solve_device: the plan's coarse space does not match the options");
@@ -369,7 +369,7 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
   BAE_HIP(hipMemcpyAsync(dx, w.x.p, (size_t)ld * sizeof(double), hipMemcpyDeviceToDevice, s));
   BAE_HIP(ev.record(5, s));
   BAE_HIP(hipStreamSynchronize(s));
-  e->pcg_coarse_last = coarse;
+  e->held.pcg_run_finished(coarse);
   if (coarse) {
     ba_hip_pcg_coarse_stats& c = e->pcg_coarse_stats;
     memset(&c, 0, sizeof(c));

@@ -250,7 +250,7 @@ int launch_residuals(Engine* e, int mode) {
   if (mode == 1 && e->err_cache_on()) {
     BAE_HIP(e->obs_e_state[e->cur].alloc(std::max<size_t>((size_t)O, 1)));
     err0 = e->obs_e_state[e->cur].p;
-    e->obs_e_valid[e->cur] = true;
+    e->held.residuals_evaluated(e->cur);
   }
 #define BAE_ARGS                                                                          \
   O, (int)e->st.C, mode, e->opt.projection_outlier_threshold, e->obs_z.p, e->obs_pose.p,  \

@@ -541,9 +541,9 @@ int launch_gather_S(Engine* e) {
   const uint32_t n = st.n, ld = st.ld, n_pad = ld;
   // the whole square + rhs row is zeroed once per structure (the tiles above the diagonal are
   // never written afterwards); every iteration k_assemble_tiles rewrites the lower triangle
-  if (e->A_cleared != e->A.p) {
+  if (e->held.A_cleared != e->A.p) {
     BAE_HIP(hipMemsetAsync(e->A.p, 0, (size_t)(n_pad + 1) * ld * sizeof(double), e->stream));
-    e->A_cleared = e->A.p;
+    e->held.square_cleared(e->A.p);
   }
   const uint32_t nt = n_pad / 64;
   {

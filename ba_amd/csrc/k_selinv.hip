@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(256) k_selinv_lm_bare(LmArgs g, uint32_t L, do
 // ---- host side ----------------------------------------------------------------------------------------
 int marginals_compute(Engine* e) {
   const Structure& st = e->st;
-  if (e->sig_valid) return 0;
+  if (e->held.sig_valid) return 0;
   uint32_t nt;
   const double *dsgn, *linvT;
   int rc;
@@ -347,7 +347,7 @@ int marginals_compute(Engine* e) {
   e->mstats.store_bytes = (double)count * sizeof(double);
   e->mstats.levels = levels;
   e->mstats.store_tiles = p.n_slots;
-  e->sig_valid = true;
+  e->held.selinv_computed();
   return 0;
 }
 
@@ -427,7 +427,7 @@ void marginals_release(Engine* e) {   // (ba_hip_release_marginals promises the 
   e->sig_col_rows.release(); e->sig_level_cols.release(); e->sig_items.release();
   e->sig_plan = SelinvPlan();
   e->sig_plan_version = ~0ull;
-  e->sig_valid = false;
+  e->held.selinv_released();
 }
 
 }  // namespace bae
