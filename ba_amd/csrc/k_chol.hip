@@ -389,7 +389,9 @@ k_update2(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uint3
 //     are formed for the whole block — a structurally zero operand tile holds exact zeros;
 //   * one-deep register prefetch (the 128 accumulator registers leave room for one set), chunks of
 //     16, two LDS stages of 2 x 128 x 16, fragments of k-step s + 1 read under the 16 MFMAs of
-//     k-step s, one barrier per chunk (as update_tile_fast);
+//     k-step s, one barrier per chunk (as update_tile_fast); in the K loop every load, LDS store and
+//     fragment read is issued behind an MFMA, one or two per MFMA (BAE_STEP): a block that is alone
+//     on its CU has one wave per SIMD and nothing else to fill a gap between two MFMAs;
 //   * the C block is read and written in the epilogue, one row of MFMA tiles at a time;
 //   * a negative pivot in the K range (indefinite system) sends the block through update_tile,
 //     one 64-tile at a time.
@@ -434,8 +436,10 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
     const uint2* pairs = reinterpret_cast<const uint2*>(((unsigned long long)own.pairs_hi << 32) | own.pairs_lo);
     const uint2 bp = pairs[pr];
     const uint32_t base = c0 / own.G;
-    R = (bp.x - base) * gb + within / gb;
-    C = (bp.y - base) * gb + within % gb;
+    // (the pair comes through a vector load: readfirstlane tells the compiler that the block position, and with it
+    // the operand base addresses of the K loop, is wave-uniform)
+    R = __builtin_amdgcn_readfirstlane((bp.x - base) * gb + within / gb);
+    C = __builtin_amdgcn_readfirstlane((bp.y - base) * gb + within % gb);
     if (C > R || R >= m2) return;
   } else if (RECT) {
     // consecutive workgroups (= the XCDs, round-robin) take the column blocks of one row block:
@@ -489,9 +493,14 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = (double4_t){0.0, 0.0, 0.0, 0.0};
   const int sr = tid >> 3, sc = (tid & 7) * 2;
-  const double* Xg = A + ((size_t)i * NB + sr) * ld + sc;
-  const double* Yg = A + ((size_t)c * NB + sr) * ld + sc;
-  const size_t ld32 = (size_t)32 * ld;
+  // Operand addresses: a wave-uniform base per operand (the first row of tile row i / c; the K offset of a chunk
+  // is added to it on the scalar unit) and one 32-bit byte offset per staged row, shared by X and Y — the
+  // loop holds no 64-bit vector address arithmetic.  (128 rows x ld x 8 bytes stays far below 2^32.)
+  const char* Xrow = reinterpret_cast<const char*>(A + (size_t)i * NB * ld);
+  const char* Yrow = reinterpret_cast<const char*>(A + (size_t)c * NB * ld);
+  uint32_t voff[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) voff[u] = (((uint32_t)sr + 32u * u) * ld + (uint32_t)sc) * 8u;
   double2 px[4], py[4];
   double FA0[4], FB0[4], FA1[4], FB1[4];
 #ifdef BAE_NO_SCHED_PINS_128   // (measurement builds: the compiler schedules the 128x128 loop freely)
@@ -504,35 +513,66 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
 #ifndef BAE_KMASK
 #define BAE_KMASK 0xffffffffu
 #endif
+// (BAE_VOFF_PIN: an empty statement that redefines the row offsets as 32-bit values where it stands.  Without it
+// the compiler widens them to 64 bits once, in front of the loop, and then adds base and offset with a 64-bit
+// vector add per load instead of using the scalar-base + 32-bit-offset form of global_load.)
+#define BAE_VOFF_PIN asm volatile("" : "+v"(voff[0]), "+v"(voff[1]), "+v"(voff[2]), "+v"(voff[3]))
+// one staged row (32 bytes per lane): global -> prefetch register, prefetch register -> LDS stage B
+#define BAE_GLOAD1(P, ROW, U, K0)                                                    \
+  P[U] = *reinterpret_cast<const double2*>(ROW + (size_t)((K0) & BAE_KMASK) * sizeof(double) + (size_t)voff[U]);
+#define BAE_SSTORE1(S, P, B, U)                                                      \
+  { S[B][sr + 32 * (U)][sc] = P[U].x; S[B][sr + 32 * (U)][sc + 1] = P[U].y; }
 #define BAE_GLOAD(K0)                                                                \
   _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                    \
-    px[u] = *reinterpret_cast<const double2*>(Xg + u * ld32 + ((K0) & BAE_KMASK));   \
-    py[u] = *reinterpret_cast<const double2*>(Yg + u * ld32 + ((K0) & BAE_KMASK));   \
+    BAE_GLOAD1(px, Xrow, u, K0) BAE_GLOAD1(py, Yrow, u, K0)                          \
   }
 #define BAE_SSTORE(B)                                                                \
   _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                    \
-    X[B][sr + 32 * u][sc] = px[u].x; X[B][sr + 32 * u][sc + 1] = px[u].y;            \
-    Y[B][sr + 32 * u][sc] = py[u].x; Y[B][sr + 32 * u][sc + 1] = py[u].y;            \
+    BAE_SSTORE1(X, px, B, u) BAE_SSTORE1(Y, py, B, u)                                \
+  }
+// fragment Q of a k-step, in the order the MFMAs of BAE_STEP first need them: A0 B0 B1 B2 B3 A1 A2 A3
+#define BAE_LDF1(FA, FB, B, KS, Q)                                                   \
+  {                                                                                  \
+    if ((Q) == 0 || (Q) >= 5) {                                                      \
+      const int q_ = (Q) == 0 ? 0 : (Q) - 4;                                         \
+      FA[q_] = X[B][rb + 16 * q_ + li][4 * (KS) + lk];                               \
+    } else {                                                                         \
+      FB[(Q) - 1] = Y[B][cb + 16 * ((Q) - 1) + li][4 * (KS) + lk];                   \
+    }                                                                                \
   }
 #define BAE_LDF(FA, FB, B, KS)                                                       \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                    \
-    FA[q] = X[B][rb + 16 * q + li][4 * (KS) + lk];                                   \
-    FB[q] = Y[B][cb + 16 * q + li][4 * (KS) + lk];                                   \
+  _Pragma("unroll") for (int q = 0; q < 8; ++q) BAE_LDF1(FA, FB, B, KS, q)
+// One k-step: 16 MFMAs (ti outer, tj inner: the order per accumulator is k ascending).  A wave alone on its
+// SIMD issues in order, so whatever stands between two MFMAs runs with the matrix pipe draining unless the
+// previous MFMA (64 pipe cycles) covers it.  Every other instruction of the chunk therefore follows an MFMA,
+// one or two per MFMA, each slot closed by a scheduling fence:
+//   slots 0-7              one fragment read of the NEXT k-step (stage RB, k-step RKS) when READ;
+//   slots 8, 10, 12, 14    one staged row when SP is set: the prefetch register P[u] goes to LDS stage SB
+//                          (STORE) and is refilled at once from chunk K0 (LOAD) — the refill of a register
+//                          stands one whole chunk (64 MFMAs) ahead of its store, as before.
+#define BAE_STEP(CA, CB, READ, NA, NBF, RB, RKS, SP, S, P, ROW, SB, STORE, LOAD, K0)             \
+  _Pragma("unroll") for (int t = 0; t < 16; ++t) {                                               \
+    acc[t >> 2][t & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(CA[t >> 2], CB[t & 3], acc[t >> 2][t & 3], 0, 0, 0); \
+    if ((READ) && t < 8) BAE_LDF1(NA, NBF, RB, RKS, t)                                           \
+    if ((SP) && t >= 8 && (t & 1) == 0) {                                                        \
+      if (STORE) BAE_SSTORE1(S, P, SB, (t - 8) >> 1)                                             \
+      if (LOAD) BAE_GLOAD1(P, ROW, (t - 8) >> 1, K0)                                             \
+    }                                                                                            \
+    BAE_SB;                                                                                      \
   }
-#define BAE_MM(FA, FB)                                                               \
-  _Pragma("unroll") for (int ti = 0; ti < 4; ++ti)                                   \
-    _Pragma("unroll") for (int tj = 0; tj < 4; ++tj)                                 \
-      acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(FA[ti], FB[tj], acc[ti][tj], 0, 0, 0);
-#define BAE_CHUNK(J, STORE, LOADK, NEXT)                                             \
-  {                                                                                  \
-    if (STORE) BAE_SSTORE(((J) + 1) & 1);                                            \
-    LOADK;                                                                           \
-    BAE_SB; BAE_LDF(FA1, FB1, (J) & 1, 1); BAE_SB; BAE_MM(FA0, FB0); BAE_SB;         \
-    BAE_LDF(FA0, FB0, (J) & 1, 2); BAE_SB; BAE_MM(FA1, FB1); BAE_SB;                 \
-    BAE_LDF(FA1, FB1, (J) & 1, 3); BAE_SB; BAE_MM(FA0, FB0); BAE_SB;                 \
-    __syncthreads(); BAE_SB;                                                         \
-    if (NEXT) BAE_LDF(FA0, FB0, ((J) + 1) & 1, 0);                                   \
-    BAE_SB; BAE_MM(FA1, FB1); BAE_SB;                                                \
+// One chunk J (stage J & 1): X rows are staged under k-step 0, Y rows under k-step 1; stage (J + 1) & 1 is free
+// from the barrier of chunk J - 1 on and complete (lgkmcnt(0)) at the barrier of this chunk, which stands
+// between k-steps 2 and 3; the first fragments of the next chunk are read behind it, under k-step 3.
+// PRE: statements issued in front of the chunk (the C prefetch of the last chunk).
+#define BAE_CHUNK(J, STORE, LOAD, K0, NEXT, PRE)                                                           \
+  {                                                                                                        \
+    PRE;                                                                                                   \
+    BAE_SB;                                                                                                \
+    BAE_STEP(FA0, FB0, true, FA1, FB1, (J) & 1, 1, true, X, px, Xrow, ((J) + 1) & 1, STORE, LOAD, K0)      \
+    BAE_STEP(FA1, FB1, true, FA0, FB0, (J) & 1, 2, true, Y, py, Yrow, ((J) + 1) & 1, STORE, LOAD, K0)      \
+    BAE_STEP(FA0, FB0, true, FA1, FB1, (J) & 1, 3, false, X, px, Xrow, 0, false, false, 0)                 \
+    __syncthreads(); BAE_SB;                                                                               \
+    BAE_STEP(FA1, FB1, NEXT, FA0, FB0, ((J) + 1) & 1, 0, false, X, px, Xrow, 0, false, false, 0)           \
   }
 #ifdef BAE_TIME128   // measurement build: cycle stamps of one workgroup in 257 (scratch/gpu_r03_time128.sh)
   const unsigned long long tt0 = __builtin_readcyclecounter();
@@ -553,11 +593,12 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
   while (mask) {
     const uint32_t knext = (kb0 + (uint32_t)__builtin_ctzll(mask)) * NB;
     mask &= mask - 1;
+    BAE_VOFF_PIN;
     // stage 0 holds chunk 0 of this tile column, the register set (in flight) chunk 1
-    BAE_CHUNK(0, true, BAE_GLOAD(kcur + 2 * KC2), true);
-    BAE_CHUNK(1, true, BAE_GLOAD(kcur + 3 * KC2), true);
-    BAE_CHUNK(2, true, BAE_GLOAD(knext), true);
-    BAE_CHUNK(3, true, BAE_GLOAD(knext + KC2), true);
+    BAE_CHUNK(0, true, true, kcur + 2 * KC2, true, );
+    BAE_CHUNK(1, true, true, kcur + 3 * KC2, true, );
+    BAE_CHUNK(2, true, true, knext, true, );
+    BAE_CHUNK(3, true, true, knext + KC2, true, );
     kcur = knext;
   }
   // the last tile column; the C block is read and written one row of four MFMA tiles (16 doubles
@@ -576,10 +617,11 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
       const int cc = cb + 16 * tj + li;                                              \
       if (!diag || cc <= r) Aic[(size_t)r * ld + cc] = CV[tj][reg] - acc[TI][tj][reg]; \
     }
-  BAE_CHUNK(0, true, BAE_GLOAD(kcur + 2 * KC2), true);
-  BAE_CHUNK(1, true, BAE_GLOAD(kcur + 3 * KC2), true);
-  BAE_CHUNK(2, true, , true);
-  BAE_CHUNK(3, false, BAE_CLOAD(cva, 0), false);
+  BAE_VOFF_PIN;
+  BAE_CHUNK(0, true, true, kcur + 2 * KC2, true, );
+  BAE_CHUNK(1, true, true, kcur + 3 * KC2, true, );
+  BAE_CHUNK(2, true, false, 0, true, );
+  BAE_CHUNK(3, false, false, 0, false, BAE_CLOAD(cva, 0));
 #ifdef BAE_TIME128
   const unsigned long long tt2 = __builtin_readcyclecounter();
   const unsigned long long tw2 = wall_clock64();
@@ -620,7 +662,11 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
 #undef BAE_GLOAD
 #undef BAE_SSTORE
 #undef BAE_LDF
-#undef BAE_MM
+#undef BAE_GLOAD1
+#undef BAE_VOFF_PIN
+#undef BAE_SSTORE1
+#undef BAE_LDF1
+#undef BAE_STEP
 #undef BAE_CHUNK
 }
 
