@@ -15,6 +15,7 @@
 #include "pcg.h"
 #include "dist_plan.h"
 #include "lifecycle.h"
+#include "chol_launch.h"
 
 namespace bae {
 
@@ -399,8 +400,9 @@ inline int kept_factor(Engine* e, const char* who, uint32_t* nt, const double** 
   if (!e->invdiag.p || !e->held.nzL_valid || e->nzL_host.size() != (size_t)n * n)
     return e->fail_msg((std::string(who) + ": no factor of the last ba_hip_solve_gn").c_str());
   *nt = n;
-  *dsgn = e->invdiag.p;
-  *linvT = *dsgn + (size_t)n * 64;
+  const FactorWork fw(n);
+  *dsgn = e->invdiag.p + fw.dsgn;
+  *linvT = e->invdiag.p + fw.linvT;
   return 0;
 }
 

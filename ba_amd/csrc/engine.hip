@@ -2294,9 +2294,10 @@ int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const
   hipError_t err = hipDeviceSynchronize();  // both streams of the factorisation
   if (err == hipSuccess) err = download_x(dx, n, x);
   if (err == hipSuccess && factor) err = hipMemcpy(factor, dA.p, (size_t)ld * ld * 8, hipMemcpyDeviceToHost);
-  if (err == hipSuccess && dsgn) err = hipMemcpy(dsgn, e->invdiag.p, (size_t)ld * 8, hipMemcpyDeviceToHost);
+  const FactorWork fw(nt);
+  if (err == hipSuccess && dsgn) err = hipMemcpy(dsgn, e->invdiag.p + fw.dsgn, (size_t)ld * 8, hipMemcpyDeviceToHost);
   if (err == hipSuccess && linvT)
-    err = hipMemcpy(linvT, e->invdiag.p + ld, (size_t)nt * 64 * 64 * 8, hipMemcpyDeviceToHost);
+    err = hipMemcpy(linvT, e->invdiag.p + fw.linvT, (size_t)nt * 64 * 64 * 8, hipMemcpyDeviceToHost);
   if (err != hipSuccess) return e->fail(err, "hipMemcpy");
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
 }

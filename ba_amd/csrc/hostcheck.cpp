@@ -854,3 +854,60 @@ extern "C" int ba_hostcheck_lifecycle(uint32_t n, const int32_t* events, uint32_
   }
   return 0;
 }
+
+// ---- switches and launch shapes of the LDL^T solve ---------------------------------------------------
+#include "chol_launch.h"
+
+// chol_launch.h on n rows of integers: row i reads in[i * W_in ...] and writes out[i * W_out ...]; `str` holds the
+// strings of the one row of ops 0 and 5 (null = variable unset).  Returns 0, or -1 for an unknown op.
+//   0  switch parsing   in: nblk; str: NO128 NO_LOOKAHEAD BULK_FULL DENSE NO_DIST_SOLVE SBL BULK_FULL_M | KOUT
+//                       LEFT_MIN_TILES SQUARE SQ_W DIST_LAYOUT DENSE_SCATTER TRACE_FILE; out: the 15 fields in the
+//                       struct's order (the two strings as set / unset)
+//   1  chain_shape      in: nblk left_min_tiles; out: left kin
+//   2  rect128_shape    in: rule nblk c0 ncols G no128 rect_min_rows; out: use128 m2 rect_cols nrow64 grid
+//   3  bulk_shape       in: nblk a_end full own_n own_G have_pairs npairs no128 sbl; out: kernel grid nrow64 m2 sbl swzf
+//   4  FactorWork       in: nblk; out: dsgn linvT opbuf colneg total packet_stride
+//   5  dist_plan_key    in: nzL_version kout pat dense_scatter; str: layout; out: key
+extern "C" int ba_hostcheck_chol_launch(int op, uint32_t n, const int64_t* in, const char* const* str, int64_t* out) {
+  using namespace bae;
+  for (uint32_t i = 0; i < n; ++i) {
+    CholSwitches sw;
+    if (op == 0) {
+      parse_process_switches(&sw, str[0], str[1], str[2], str[3], str[4], str[5], str[6]);
+      parse_call_switches(&sw, (uint32_t)in[0], str[7], str[8], str[9], str[10], str[11], str[12], str[13]);
+      const int64_t v[15] = {sw.no128, sw.no_lookahead, sw.bulk_full, sw.dense, sw.no_dist_solve, sw.sbl,
+                             sw.rect_min_rows, sw.bulk_full_m, sw.kout, sw.left_min_tiles, sw.square, sw.sq_w,
+                             sw.dist_layout != nullptr, sw.dense_scatter, sw.trace_file != nullptr};
+      std::copy(v, v + 15, out);
+    } else if (op == 1) {
+      const int64_t* a = in + (size_t)i * 2;
+      sw.left_min_tiles = (uint32_t)a[1];
+      const ChainShape c = chain_shape((uint32_t)a[0], sw);
+      out[(size_t)i * 2] = c.left; out[(size_t)i * 2 + 1] = c.kin;
+    } else if (op == 2) {
+      const int64_t* a = in + (size_t)i * 7;
+      sw.no128 = a[5] != 0; sw.rect_min_rows = (uint32_t)a[6];
+      const Rect128Shape r = rect128_shape(a[0] ? kRectDist : kRectSingle, (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3],
+                                           (uint32_t)a[4], sw);
+      const int64_t v[5] = {r.use128, r.m2, r.rect_cols, r.nrow64, r.grid};
+      std::copy(v, v + 5, out + (size_t)i * 5);
+    } else if (op == 3) {
+      const int64_t* a = in + (size_t)i * 9;
+      sw.no128 = a[7] != 0; sw.sbl = (uint32_t)a[8];
+      const BulkShape b = bulk_shape((uint32_t)a[0], (uint32_t)a[1], a[2] != 0, (uint32_t)a[3], (uint32_t)a[4], a[5] != 0,
+                                     (uint32_t)a[6], sw);
+      const int64_t v[6] = {b.kernel, b.grid, b.nrow64, b.m2, b.sbl, b.swzf};
+      std::copy(v, v + 6, out + (size_t)i * 6);
+    } else if (op == 4) {
+      const FactorWork fw((uint32_t)in[i]);
+      const int64_t v[6] = {(int64_t)fw.dsgn, (int64_t)fw.linvT, (int64_t)fw.opbuf, (int64_t)fw.colneg, (int64_t)fw.total,
+                            kPacketStride};
+      std::copy(v, v + 6, out + (size_t)i * 6);
+    } else if (op == 5) {
+      out[0] = (int64_t)dist_plan_key((uint64_t)in[0], (uint32_t)in[1], in[2] != 0, str[0], in[3] != 0);
+    } else {
+      return -1;
+    }
+  }
+  return 0;
+}

@@ -1588,12 +1588,15 @@ static void launch_backward(hipStream_t s, double* dA, uint32_t ld, uint32_t nbl
 // triangular solves and the look-ahead skip every tile product with a structurally zero
 // operand — the reference reaches the same saving through Eigen::SimplicialLDLT on
 // s_.sparseView() (BundleAdjuster.cpp:792-799).  BA_HIP_DENSE=1 keeps everything dense.
+// the header's constants are the kernels' (chol_launch.h cannot see them: host only)
+static_assert(kTile == (uint32_t)NB && kPacketStride == (uint32_t)NOPV * 64, "chol_launch.h against the kernels");
+
 int factor_tile_pattern(Engine* e) {
   const Structure& st = e->st;
   const uint32_t nt = st.ld / 64;
   std::vector<uint8_t> nz(st.tile_nz);
   if (nz.size() != (size_t)nt * nt) nz.assign((size_t)nt * nt, 1);
-  static const bool dense = getenv("BA_HIP_DENSE") != nullptr;
+  const bool dense = chol_process_switches().dense;
   if (dense) std::fill(nz.begin(), nz.end(), 1);
   if (e->sharded() && !dense) {
     std::vector<double> cnt(nz.begin(), nz.end());
@@ -1614,11 +1617,7 @@ int factor_tile_pattern(Engine* e) {
   return 0;
 }
 
-uint32_t choose_kout(uint32_t nblk) {
-  const char* ke = getenv("BA_HIP_KOUT");  // (read on every call: tests vary it inside one process)
-  const uint32_t kout_env = ke ? (uint32_t)atoi(ke) : 0;
-  return kout_env ? kout_env : (nblk >= 400 ? 16u : nblk >= 256 ? 8u : 4u);  // measured at 94 / 282 / 469 / 938 tiles
-}
+uint32_t choose_kout(uint32_t nblk) { return kout_from_env(nblk); }
 
 // ---------------------------------------------------------------------------------
 // Distributed reduced solve (replaces CalculateGn,
@@ -1644,8 +1643,7 @@ uint32_t choose_kout(uint32_t nblk) {
 // communicator, more than one rank takes part, and the reduced system need not stay readable
 // (keep_reduced_system).  BA_HIP_DIST_LAYOUT = tri | grid | col | row overrides the layout.
 bool dist_solve_enabled(const Engine* e) {
-  static const bool off = getenv("BA_HIP_NO_DIST_SOLVE") != nullptr;
-  return e->coll && e->sharded() && !e->opt.keep_reduced_system && !off;
+  return e->coll && e->sharded() && !e->opt.keep_reduced_system && !chol_process_switches().no_dist_solve;
 }
 
 // a list of 64-row tiles (then, if the grid says so, the rhs row = row n_pad) x columns [c0, c0 + w) of A
@@ -1673,18 +1671,13 @@ k_copy_panel_rows(double* __restrict__ A, uint32_t ld, const uint32_t* __restric
 // from the panel down; rl_square: the list starts with the panel's own tiles J .. Jend-1 (the square — its
 // diagonal tiles are factorised here); otherwise all its rows lie below the panel and the factor packets
 // of the diagonal tiles are already there (received with the square).
-static const uint32_t KIN = 4;
-static void launch_panel_chain(hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, uint32_t J, uint32_t Jend,
-                               double* dsgn, double* opbuf, int* colneg, int* flags, const uint8_t* nz,
-                               const uint32_t* rl = nullptr, uint32_t rl_n = 0, bool rl_square = false,
-                               bool sq = false) {
-  // Large systems (the chain's tile updates are bandwidth-bound there and cost the bulk update their
-  // full duration): sub-panels of 8, left-looking inside — every column is read and written once
-  // per sub-panel instead of once per earlier column.  Small systems are latency-bound on the
-  // diagonal tile: right-looking keeps its update shallow (K = 64).
-  const char* le = getenv("BA_HIP_LEFT_MIN_TILES");  // (read on every call, like BA_HIP_KOUT: tests lower it)
-  const bool left = nblk >= (le ? (uint32_t)std::max(1, atoi(le)) : 512u);
-  const uint32_t KINv = left ? 2 * KIN : KIN;
+static void launch_panel_chain(const CholSwitches& sw, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
+                               uint32_t J, uint32_t Jend, double* dsgn, double* opbuf, int* colneg, int* flags,
+                               const uint8_t* nz, const uint32_t* rl = nullptr, uint32_t rl_n = 0,
+                               bool rl_square = false, bool sq = false) {
+  const ChainShape cs = chain_shape(nblk, sw);
+  const bool left = cs.left;
+  const uint32_t KINv = cs.kin, SW = sw.sq_w;
   // rows from tile `from` on: the whole range, or the tail of the list
   auto rows_from = [&](uint32_t from, const uint32_t** lp, uint32_t* cnt) {
     if (!rl) { *lp = nullptr; *cnt = nblk - from + 1; return; }
@@ -1695,8 +1688,6 @@ static void launch_panel_chain(hipStream_t s, double* dA, uint32_t ld, uint32_t 
   if (sq) {
     // small systems: the square of every sub-panel in one workgroup (k_square), the rows below it
     // left-looking (k_rowpanel), then the sub-panel applied to the rest of the outer panel
-    const char* swe = getenv("BA_HIP_SQ_W");
-    const uint32_t SW = swe ? std::min(4u, std::max(1u, (uint32_t)atoi(swe))) : KIN;
     for (uint32_t sub = J; sub < Jend; sub += SW) {
       const uint32_t sub_end = std::min(sub + SW, Jend);
       hipLaunchKernelGGL(k_square, dim3(1), dim3(512), sizeof(SquareLds), s, dA, ld, nblk, sub, sub_end - sub, dsgn,
@@ -1740,22 +1731,22 @@ static void launch_panel_chain(hipStream_t s, double* dA, uint32_t ld, uint32_t 
 // chain stream: the panel's own triangle — with the factorisation of tile (c0, c0) in workgroup
 // (0,0) — stays a k_step_update launch; the rectangle below the panel goes to 128x128 blocks when
 // it is big enough.
-static void launch_next_panel_update(hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, uint32_t c0,
-                                     uint32_t ncols, uint32_t kb0, uint32_t kb1, double* dsgn, double* opbuf,
-                                     int* colneg, int* flags, const uint8_t* nz, bool factor = true) {
-  static const bool no128 = getenv("BA_HIP_NO128") != nullptr;
-  const uint32_t r0 = c0 + ncols;
+// The rectangle below the tile columns [c0, c0 + ncols) in 128x128 blocks (rect128_shape said use128).
+static void launch_rect128(const Rect128Shape& r, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, uint32_t c0,
+                           uint32_t ncols, uint32_t kb0, uint32_t kb1, const double* dsgn, const int* colneg,
+                           const uint8_t* nz, const OwnMap& own) {
+  hipLaunchKernelGGL(k_update128<true>, dim3(r.grid), dim3(256), 0, s, dA, ld, nblk, c0, r.m2, kb0, kb1, dsgn, colneg,
+                     0u, nz, own, r.nrow64, c0 + ncols, r.rect_cols);
+}
+static void launch_next_panel_update(const CholSwitches& sw, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
+                                     uint32_t c0, uint32_t ncols, uint32_t kb0, uint32_t kb1, double* dsgn,
+                                     double* opbuf, int* colneg, int* flags, const uint8_t* nz, bool factor = true) {
   auto step_update = factor ? k_step_update<true> : k_step_update<false>;
-  // (a second launch on the serial chain: only where the chain is not the bottleneck)
-  static const uint32_t min_rows =
-      getenv("BA_HIP_BULK_FULL_M") ? (uint32_t)std::max(16, atoi(getenv("BA_HIP_BULK_FULL_M"))) : 128u;
-  if (!no128 && r0 + min_rows <= nblk && ncols % 2u == 0 && c0 % 2u == 0) {
-    const uint32_t m = nblk - r0, m2 = m / 2, rect_cols = ncols / 2;
+  const Rect128Shape r = rect128_shape(kRectSingle, nblk, c0, ncols, 1, sw);
+  if (r.use128) {
     hipLaunchKernelGGL(step_update, dim3(ncols, ncols), dim3(256), 0, s, dA, ld, nblk, c0, kb0, kb1, dsgn, opbuf,
-                       colneg, flags, nz, r0, (const uint32_t*)nullptr);
-    const uint32_t nrow64 = (ncols * (1 + (m & 1u)) + 7) / 8 * 8;
-    hipLaunchKernelGGL(k_update128<true>, dim3(nrow64 + m2 * rect_cols), dim3(256), 0, s, dA, ld, nblk, c0, m2, kb0, kb1,
-                       (const double*)dsgn, (const int*)colneg, 0u, nz, own_map_single(), nrow64, r0, rect_cols);
+                       colneg, flags, nz, c0 + ncols, (const uint32_t*)nullptr);
+    launch_rect128(r, s, dA, ld, nblk, c0, ncols, kb0, kb1, dsgn, colneg, nz, own_map_single());
     return;
   }
   hipLaunchKernelGGL(step_update, dim3(nblk - c0 + 1, ncols), dim3(256), 0, s, dA, ld, nblk, c0, kb0, kb1, dsgn,
@@ -1763,59 +1754,43 @@ static void launch_next_panel_update(hipStream_t s, double* dA, uint32_t ld, uin
 }
 
 // Bulk trailing update of the tile rows / columns >= a_end (and the rhs row) with the tile columns
-// [J, Jend).  Big trailing matrices: 128x128 blocks over the even part (k_update128, XCD-aware 4x4
-// super-blocks = the footprint of the 64-tile kernel's 8x8; the rhs row and an odd last tile row
-// ride along as 64-tiles); otherwise the 64-tile kernel, capped (`full` = false) to leave the
-// serial chain room.  `own`: the tiles this rank updates (distributed solve).
-// One launch, bracketed by the profiling events.
-static void launch_bulk_update(Engine* e, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, uint32_t a_end,
-                                   uint32_t J, uint32_t Jend, const double* dsgn, const int* colneg,
-                                   const uint8_t* nz, bool full, const OwnMap& own, const uint2* pairs = nullptr,
-                                   uint32_t npairs = 0) {
-  static const bool no128 = getenv("BA_HIP_NO128") != nullptr;  // A/B switch
-  static const uint32_t sbl = getenv("BA_HIP_SBL") ? (uint32_t)atoi(getenv("BA_HIP_SBL")) : 3u;
-  const uint32_t m = nblk - a_end;
-  if (full && !no128 && m >= 16 && (a_end % 2u) == 0 && (own.n <= 1 || own.G % 2u == 0)) {
-    const uint32_t m2 = m / 2, sbl2 = 2, sbe2 = 1u << sbl2;
-    const uint32_t nsr = (m2 + sbe2 - 1) / sbe2, nsb = nsr * (nsr + 1) / 2;
-    // leftover 64-tiles first (a multiple of 8 workgroups keeps the XCD phase of the blocks)
-    const uint32_t nrow64 = (m * (1 + (m & 1u)) + 7) / 8 * 8;
-    if (e) e->prof_begin(e->ev_syrk, s);
-    if (pairs && own.n > 1 && a_end % own.G == 0) {
-      // only the block pairs this rank owns (distributed solve)
+// [J, Jend): the kernel and its grid are bulk_shape's.  `own`: the tiles this rank updates, `pairs`: the block
+// pairs it owns (distributed solve).  One launch, bracketed by the profiling events.
+static void launch_bulk_update(const CholSwitches& sw, Engine* e, hipStream_t s, double* dA, uint32_t ld,
+                               uint32_t nblk, uint32_t a_end, uint32_t J, uint32_t Jend, const double* dsgn,
+                               const int* colneg, const uint8_t* nz, bool full, const OwnMap& own,
+                               const uint2* pairs = nullptr, uint32_t npairs = 0) {
+  const BulkShape b = bulk_shape(nblk, a_end, full, own.n, own.G, pairs != nullptr, npairs, sw);
+  const dim3 grid(b.grid), wg(256);
+  e->prof_begin(e->ev_syrk, s);
+  switch (b.kernel) {
+    case kBulkU128List: {
       OwnMap ol = own;
       ol.pairs_lo = (uint32_t)(reinterpret_cast<unsigned long long>(pairs) & 0xffffffffull);
       ol.pairs_hi = (uint32_t)(reinterpret_cast<unsigned long long>(pairs) >> 32);
-      const uint32_t per = (own.G / 2) * (own.G / 2);
-      hipLaunchKernelGGL((k_update128<false, true>), dim3(nrow64 + npairs * per), dim3(256), 0, s, dA, ld, nblk,
-                         a_end, m2, J, Jend, dsgn, colneg, sbl2, nz, ol, nrow64, a_end, 0u);
-    } else {
-      hipLaunchKernelGGL(k_update128<false>, dim3(nrow64 + ((nsb + 7) / 8) * 8 * sbe2 * sbe2), dim3(256), 0, s, dA, ld, nblk,
-                         a_end, m2, J, Jend, dsgn, colneg, sbl2, nz, own, nrow64, a_end, 0u);
+      hipLaunchKernelGGL((k_update128<false, true>), grid, wg, 0, s, dA, ld, nblk, a_end, b.m2, J, Jend, dsgn, colneg,
+                         b.sbl, nz, ol, b.nrow64, a_end, 0u);
+      break;
     }
-    if (e) e->prof_end(e->ev_syrk, s);
-    return;
+    case kBulkU128:
+      hipLaunchKernelGGL(k_update128<false>, grid, wg, 0, s, dA, ld, nblk, a_end, b.m2, J, Jend, dsgn, colneg, b.sbl,
+                         nz, own, b.nrow64, a_end, 0u);
+      break;
+    case kBulkU2Full:
+      hipLaunchKernelGGL(k_update2<false>, grid, wg, 0, s, dA, ld, nblk, a_end, J, Jend, dsgn, colneg, b.swzf, nz, own);
+      break;
+    case kBulkU2Capped:
+      hipLaunchKernelGGL(k_update2<true>, grid, wg, 0, s, dA, ld, nblk, a_end, J, Jend, dsgn, colneg, b.swzf, nz, own);
+      break;
   }
-  // 1-D XCD-aware launch over the 8x8 super-blocks of the (m + 1) x m lower-triangular tile region
-  const uint32_t sbe = 1u << sbl;
-  const uint32_t nsr = (m + 1 + sbe - 1) / sbe, nsb = nsr * (nsr + 1) / 2;
-  const uint32_t grid1 = ((nsb + 7) / 8) * 8 * sbe * sbe;
-  const int swzf = 1 | (int)(sbl << 8);
-  if (e) e->prof_begin(e->ev_syrk, s);
-  if (full)
-    hipLaunchKernelGGL(k_update2<false>, dim3(grid1), dim3(256), 0, s, dA, ld, nblk, a_end, J, Jend, dsgn, colneg,
-                       swzf, nz, own);
-  else
-    hipLaunchKernelGGL(k_update2<true>, dim3(grid1), dim3(256), 0, s, dA, ld, nblk, a_end, J, Jend, dsgn, colneg,
-                       swzf, nz, own);
-  if (e) e->prof_end(e->ev_syrk, s);
+  e->prof_end(e->ev_syrk, s);
 }
 
 // ---- the plan of the distributed solve for the current pattern / communicator ------------------------
-static int ensure_dist_plan(Engine* e, uint32_t nblk, bool pat) {
-  const uint32_t KOUT = choose_kout(nblk);
-  const char* lay_env = getenv("BA_HIP_DIST_LAYOUT");
-  const uint64_t want = (pat ? e->nzL_version : 0) * 1024 + KOUT * 4 + (pat ? 1 : 0);
+static int ensure_dist_plan(const CholSwitches& sw, Engine* e, uint32_t nblk, bool pat) {
+  const uint32_t KOUT = sw.kout;
+  const char* lay_env = sw.dist_layout;
+  const uint64_t want = dist_plan_key(e->nzL_version, KOUT, pat, lay_env, sw.dense_scatter);
   if (e->dist_plan_version == want && e->dist_plan.nblk == nblk && e->dist_plan.map.n == (uint32_t)e->nranks &&
       e->dist_plan.map.rank == (uint32_t)e->rank)
     return 0;
@@ -1869,13 +1844,14 @@ static int ensure_dist_plan(Engine* e, uint32_t nblk, bool pat) {
 // structurally nonzero tile of S on SOME shard travel (the union pattern of factor_tile_pattern, identical
 // on every rank; S itself is half as dense as its factor): the other tiles are zero on every rank already.
 // Chunk of destination rank r: for every panel, the row tiles of that panel whose block r owns.
-int dist_scatter_S_sparse(Engine* e);
+static int dist_scatter_S_sparse(const CholSwitches& sw, Engine* e);
 int dist_reduce_scatter_S(Engine* e) {
   const uint32_t ld = e->st.ld, nblk = ld / NB, N = (uint32_t)e->nranks, rank = (uint32_t)e->rank;
+  const CholSwitches sw = chol_switches(nblk);
   // default: the sparse point-to-point exchange (below); BA_HIP_DENSE_SCATTER=1: one reduce-scatter of the union pattern
-  if (!getenv("BA_HIP_DENSE_SCATTER") && e->nranks > 1) return dist_scatter_S_sparse(e);
+  if (!sw.dense_scatter && e->nranks > 1) return dist_scatter_S_sparse(sw, e);
   const bool pat = e->nzS_host.size() == (size_t)nblk * nblk;
-  { const int prc = ensure_dist_plan(e, nblk, pat && e->nzL_host.size() == (size_t)nblk * nblk); if (prc) return prc; }
+  { const int prc = ensure_dist_plan(sw, e, nblk, pat && e->nzL_host.size() == (size_t)nblk * nblk); if (prc) return prc; }
   const DistPlan& pl = e->dist_plan;
   const uint32_t npanels = pl.nb;
   const uint64_t want = e->dist_plan_version;
@@ -1963,9 +1939,9 @@ k_copy_rects(double* __restrict__ A, uint32_t ld, const uint4* __restrict__ rect
 // (deterministic).  With shards dealt along the trajectory a shard touches a band of S and sends a fraction of what
 // the dense exchange does; with shards that touch everything the volume is the dense one.  The local patterns are
 // all-gathered once per structure (one u64 all-reduce with every rank's bits in its own slot).
-int dist_scatter_S_sparse(Engine* e) {
+static int dist_scatter_S_sparse(const CholSwitches& sw, Engine* e) {
   const uint32_t ld = e->st.ld, nblk = ld / NB, N = (uint32_t)e->nranks, rank = (uint32_t)e->rank;
-  { const int prc = ensure_dist_plan(e, nblk, e->nzL_host.size() == (size_t)nblk * nblk); if (prc) return prc; }
+  { const int prc = ensure_dist_plan(sw, e, nblk, e->nzL_host.size() == (size_t)nblk * nblk); if (prc) return prc; }
   const DistPlan& pl = e->dist_plan;
   if (e->st.tile_nz.size() != (size_t)nblk * nblk) return e->fail_msg("sparse exchange of S: no local tile pattern");
   if (e->dist_sp_version != e->dist_plan_version) {
@@ -2079,9 +2055,10 @@ int dist_scatter_S_sparse(Engine* e) {
 // nt x nt bytes, lower triangle.  Returns 1 if the restriction applies (distributed solve with the sparse exchange).
 int dist_assembly_tiles(Engine* e, std::vector<uint8_t>* need) {
   const uint32_t nt = e->st.ld / NB;
-  if (!dist_solve_enabled(e) || e->nranks <= 1 || getenv("BA_HIP_DENSE_SCATTER")) return 0;
+  const CholSwitches sw = chol_switches(nt);
+  if (!dist_solve_enabled(e) || e->nranks <= 1 || sw.dense_scatter) return 0;
   if (e->nzL_host.size() != (size_t)nt * nt || e->st.tile_nz.size() != (size_t)nt * nt) return 0;
-  if (ensure_dist_plan(e, nt, true)) return -1;
+  if (ensure_dist_plan(sw, e, nt, true)) return -1;
   const DistPlan& pl = e->dist_plan;
   OwnMap me = pl.map;
   me.rank = (uint32_t)e->rank;
@@ -2161,14 +2138,15 @@ __global__ void k_back_apply(double* __restrict__ yrow, const double* __restrict
 
 int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* status, const uint8_t* nz) {
   const uint32_t nblk = ld / NB, rank = (uint32_t)e->rank;
-  BAE_HIP(e->invdiag.alloc((size_t)nblk * NB + (size_t)nblk * NB * NB + (size_t)nblk * NOPV * 64 +
-                           (nblk + 1) / 2));
-  double* dsgn = e->invdiag.p;
-  double* linvT = dsgn + (size_t)nblk * NB;
-  double* opbuf = linvT + (size_t)nblk * NB * NB;
-  int* colneg = reinterpret_cast<int*>(opbuf + (size_t)nblk * NOPV * 64);
+  const CholSwitches sw = chol_switches(nblk);
+  const FactorWork fw(nblk);
+  BAE_HIP(e->invdiag.alloc(fw.total));
+  double* dsgn = e->invdiag.p + fw.dsgn;
+  double* linvT = e->invdiag.p + fw.linvT;
+  double* opbuf = e->invdiag.p + fw.opbuf;
+  int* colneg = reinterpret_cast<int*>(e->invdiag.p + fw.colneg);
   const bool pat = nz && e->nzL_host.size() == (size_t)nblk * nblk;
-  { const int prc = ensure_dist_plan(e, nblk, pat); if (prc) return prc; }
+  { const int prc = ensure_dist_plan(sw, e, nblk, pat); if (prc) return prc; }
   const DistPlan& pl = e->dist_plan;
   const OwnMap& own = pl.map;
   const uint32_t KOUT = own.G, npanels = pl.nb, n_pad = nblk * NB;
@@ -2222,7 +2200,6 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
                        colneg, e->flags.p, nz, nblk + 1u, (const uint32_t*)nullptr);
   // row list of a square: its tiles, then the rhs row — one small device array per plan (ensure_dist_plan)
   DBuf<uint32_t>& sq_list = e->dist_sq_list;
-  static const bool no128 = getenv("BA_HIP_NO128") != nullptr;
   int rc = 0;
   size_t sq_off = 0;
   for (uint32_t J = 0; J < npanels && !rc; ++J) {
@@ -2237,15 +2214,15 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
     double* m_sgn = msg + n_cols;
     double* m_neg = m_sgn + w;
     double* m_op = m_neg + wt;
-    const size_t msg_len = n_cols + w + wt + (size_t)wt * NOPV * 64;
+    const size_t msg_len = n_cols + w + wt + (size_t)wt * kPacketStride;
     if (rank == pn.diag_owner) {
       // (its updates by the earlier panels: bulk of steps <= J-2 and the chain-stream update of step J-1,
       // both ordered before this point by the waits of step J-1)
-      launch_panel_chain(s0, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, sq, wt + 1, true);
+      launch_panel_chain(sw, s0, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, sq, wt + 1, true);
       hipLaunchKernelGGL(k_copy_panel_rows, dim3(w + 1), dim3(256), 0, s0, dA, ld, sq, wt, n_pad, c0 * NB, w, msg, 0);
       BAE_HIP(hipMemcpyAsync(m_sgn, dsgn + (size_t)c0 * NB, w * sizeof(double), hipMemcpyDeviceToDevice, s0));
       BAE_HIP(hipMemcpyAsync(m_neg, colneg + c0, wt * sizeof(int), hipMemcpyDeviceToDevice, s0));
-      BAE_HIP(hipMemcpyAsync(m_op, opbuf + (size_t)c0 * NOPV * 64, (size_t)wt * NOPV * 64 * sizeof(double),
+      BAE_HIP(hipMemcpyAsync(m_op, opbuf + (size_t)c0 * kPacketStride, (size_t)wt * kPacketStride * sizeof(double),
                              hipMemcpyDeviceToDevice, s0));
     }
     BAE_HIP(hipGetLastError());
@@ -2254,7 +2231,7 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
       hipLaunchKernelGGL(k_copy_panel_rows, dim3(w + 1), dim3(256), 0, s0, dA, ld, sq, wt, n_pad, c0 * NB, w, msg, 1);
       BAE_HIP(hipMemcpyAsync(dsgn + (size_t)c0 * NB, m_sgn, w * sizeof(double), hipMemcpyDeviceToDevice, s0));
       BAE_HIP(hipMemcpyAsync(colneg + c0, m_neg, wt * sizeof(int), hipMemcpyDeviceToDevice, s0));
-      BAE_HIP(hipMemcpyAsync(opbuf + (size_t)c0 * NOPV * 64, m_op, (size_t)wt * NOPV * 64 * sizeof(double),
+      BAE_HIP(hipMemcpyAsync(opbuf + (size_t)c0 * kPacketStride, m_op, (size_t)wt * kPacketStride * sizeof(double),
                              hipMemcpyDeviceToDevice, s0));
     }
     if (last) break;
@@ -2262,7 +2239,7 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
     // its tiles took the updates of the panels < J on the panel stream (step J-1: column block J)
     if (pn.own_u_count[rank]) {
       if (J > 0) BAE_HIP(hipStreamWaitEvent(s0, EV(J - 1, 3), 0));
-      launch_panel_chain(s0, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, dtiles + pn.own_u_first[rank],
+      launch_panel_chain(sw, s0, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, dtiles + pn.own_u_first[rank],
                          pn.own_u_count[rank], false);
     }
     auto run_messages = [&](bool urgent, hipStream_t sp, hipStream_t sc, double* sendbuf, double* recvbuf,
@@ -2314,7 +2291,7 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
     BAE_HIP(hipStreamWaitEvent(s1, EV(J, 0), 0));
     if (J > 0) BAE_HIP(hipStreamWaitEvent(s1, EV(J - 1, 2), 0));  // the side staging buffers are free again
     if (pn.own_r_count[rank])
-      launch_panel_chain(s1, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, dtiles + pn.own_r_first[rank],
+      launch_panel_chain(sw, s1, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, dtiles + pn.own_r_first[rank],
                          pn.own_r_count[rank], false);
     if ((rc = run_messages(false, s1, s3, e->dist_ssend.p, e->dist_srecv.p, EV(J, 1)))) break;
     BAE_HIP(hipEventRecord(EV(J, 2), s3));
@@ -2322,14 +2299,12 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
     if (pn.next_needs_side[rank] || own.n <= 1) BAE_HIP(hipStreamWaitEvent(s1, EV(J, 2), 0));  // rows received on the side stream
     if (J > 0) BAE_HIP(hipStreamWaitEvent(s1, EV(J - 1, 4), 0));
     if (n1 < nblk) {
-      const uint32_t ncols = n1 - c1, m = nblk - n1;
+      const uint32_t ncols = n1 - c1;
       OwnMap o1 = own;
       o1.skip_rhs = 1;  // the rhs segment of column block J+1 went with the square's update on the chain stream
-      if (!no128 && m >= 16 && ncols % 2u == 0 && c1 % 2u == 0 && own.G % 2u == 0) {
-        const uint32_t m2 = m / 2, rect_cols = ncols / 2;
-        const uint32_t nrow64 = (ncols * (1 + (m & 1u)) + 7) / 8 * 8;
-        hipLaunchKernelGGL(k_update128<true>, dim3(nrow64 + m2 * rect_cols), dim3(256), 0, s1, dA, ld, nblk, c1, m2, c0, c1,
-                           (const double*)dsgn, (const int*)colneg, 0u, nz, o1, nrow64, n1, rect_cols);
+      const Rect128Shape r = rect128_shape(kRectDist, nblk, c1, ncols, own.G, sw);
+      if (r.use128) {
+        launch_rect128(r, s1, dA, ld, nblk, c1, ncols, c0, c1, dsgn, colneg, nz, o1);
       } else {
         // 64-tiles: exactly the row tiles this rank owns below the square of panel J+1 (its two row lists are
         // adjacent) — a structurally zero tile of L takes no update, so the lists are complete
@@ -2345,7 +2320,7 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
     if (n1 < nblk) {
       BAE_HIP(hipStreamWaitEvent(s2, EV(J, 2), 0));
       BAE_HIP(hipStreamWaitEvent(s2, EV(J, 0), 0));
-      launch_bulk_update(e, s2, dA, ld, nblk, n1, c0, c1, dsgn, colneg, nz, true, own,
+      launch_bulk_update(sw, e, s2, dA, ld, nblk, n1, c0, c1, dsgn, colneg, nz, true, own,
                          e->dist_pairs.p + e->dist_pair_first[J], e->dist_npairs - e->dist_pair_first[J]);
       if (e->profiling) {
         // tile products formed by THIS rank: tiles (i, c), i >= c >= n1, it owns, both operand tiles of the
@@ -2426,8 +2401,9 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
 int trailing_marginals(Engine* e, const double* dA, uint32_t ld, uint32_t first, uint32_t K, double* cov) {
   const uint32_t nblk = ld / NB;
   if (!e->invdiag.p || first + K > ld) return e->fail_msg("no factor to read the marginals from");
-  const double* dsgn = e->invdiag.p;
-  const double* linvT = dsgn + (size_t)nblk * NB;
+  const FactorWork fw(nblk);
+  const double* dsgn = e->invdiag.p + fw.dsgn;
+  const double* linvT = e->invdiag.p + fw.linvT;
   BAE_HIP(hipStreamSynchronize(e->stream));
   const uint32_t t = first / NB, o = first % NB;
   const uint32_t a = std::min(K, NB - o), b = K - a;  // rows in tile t / in tile t + 1
@@ -2461,25 +2437,50 @@ int trailing_marginals(Engine* e, const double* dA, uint32_t ld, uint32_t first,
   return 0;
 }
 
+#ifdef BAE_TIME128  // measurement build: the records of k_update128 are cleared before a solve and written out behind it
+static unsigned long long* t128_dev = nullptr;
+static int time128_begin(Engine* e, const CholSwitches& sw) {
+  if (!sw.trace_file) return 0;
+  if (!t128_dev) {
+    BAE_HIP(hipMalloc(&t128_dev, (size_t)T128_CAP * T128_REC * sizeof(unsigned long long)));
+    BAE_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_t128_buf), &t128_dev, sizeof(t128_dev)));
+  }
+  const unsigned int zero = 0;
+  BAE_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_t128_n), &zero, sizeof(zero)));
+  return 0;
+}
+static int time128_write(Engine* e, const CholSwitches& sw) {
+  if (!t128_dev || !sw.trace_file) return 0;
+  BAE_HIP(hipDeviceSynchronize());
+  unsigned int n = 0;
+  BAE_HIP(hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_t128_n), sizeof(n)));
+  n = std::min(n, T128_CAP);
+  std::vector<unsigned long long> rec((size_t)n * T128_REC);
+  if (n) BAE_HIP(hipMemcpy(rec.data(), t128_dev, rec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (FILE* f = fopen(sw.trace_file, "wb")) {
+    fwrite(rec.data(), sizeof(unsigned long long), rec.size(), f);
+    fclose(f);
+  }
+  return 0;
+}
+#endif
+
 int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, int* status,
                    const uint8_t* nz) {
   (void)n;
   const uint32_t nblk = ld / NB;
-  BAE_HIP(e->invdiag.alloc((size_t)nblk * NB + (size_t)nblk * NB * NB + (size_t)nblk * NOPV * 64 +
-                           (nblk + 1) / 2));
-  double* dsgn = e->invdiag.p;                                  // pivot signs
-  double* linvT = dsgn + (size_t)nblk * NB;                     // inverse-transposed diagonal tiles
-  double* opbuf = linvT + (size_t)nblk * NB * NB;               // factor packets (k_step_update)
-  int* colneg = reinterpret_cast<int*>(opbuf + (size_t)nblk * NOPV * 64);  // per tile column: any d_k < 0
-  static const bool no_lookahead = getenv("BA_HIP_NO_LOOKAHEAD") != nullptr;  // A/B switches
-  static const bool bulk_full = getenv("BA_HIP_BULK_FULL") != nullptr;
-  static const uint32_t bulk_full_m =
-      getenv("BA_HIP_BULK_FULL_M") ? (uint32_t)atoi(getenv("BA_HIP_BULK_FULL_M")) : 128u;
-  hipStream_t s0 = e->stream, s1 = no_lookahead ? e->stream : e->stream2;
+  const CholSwitches sw = chol_switches(nblk);
+  const FactorWork fw(nblk);
+  BAE_HIP(e->invdiag.alloc(fw.total));
+  double* dsgn = e->invdiag.p + fw.dsgn;                         // pivot signs
+  double* linvT = e->invdiag.p + fw.linvT;                       // inverse-transposed diagonal tiles
+  double* opbuf = e->invdiag.p + fw.opbuf;                       // factor packets (k_step_update)
+  int* colneg = reinterpret_cast<int*>(e->invdiag.p + fw.colneg);  // per tile column: any d_k < 0
+  hipStream_t s0 = e->stream, s1 = sw.no_lookahead ? e->stream : e->stream2;
   // Tiles per outer panel: every panel costs one read-modify-write pass over the trailing
   // matrix (8 n^3 / (3 * 64 KOUT) bytes in total), the serial chain inside a panel grows with
   // KOUT.  Small systems are chain-bound (KOUT = 4), large ones HBM-bound on the C tiles.
-  const uint32_t KOUT = choose_kout(nblk);
+  const uint32_t KOUT = sw.kout;
   const uint32_t npanels = (nblk + KOUT - 1) / KOUT;
   while (e->ev_panel.size() < npanels) {
     hipEvent_t a, b;
@@ -2490,23 +2491,14 @@ int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, i
   }
   { const int src = setup_status_block(e, dA, ld, s0); if (src) return src; }
 #ifdef BAE_TIME128
-  static unsigned long long* t128_dev = nullptr;
-  if (getenv("BA_HIP_TRACE_FILE")) {
-    if (!t128_dev) {
-      BAE_HIP(hipMalloc(&t128_dev, (size_t)T128_CAP * T128_REC * sizeof(unsigned long long)));
-      BAE_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_t128_buf), &t128_dev, sizeof(t128_dev)));
-    }
-    const unsigned int zero = 0;
-    BAE_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_t128_n), &zero, sizeof(zero)));
-  }
+  { const int trc = time128_begin(e, sw); if (trc) return trc; }
 #endif
   // BA_HIP_SQUARE=1 (measurement switch, read on every call): the diagonal squares of the sub-panels go to
   // k_square / k_rowpanel — one workgroup per square instead of two launches per tile column.  Measured
   // SLOWER than the per-column chain at configs[1] (5.07 / 4.38 ms at widths 4 / 2 against 3.73 ms: the chain
   // overlaps every factorisation with the other tiles' updates of the same launch, a single workgroup
   // serialises them on one CU's matrix pipes — profiles/r03_square_kernel.txt).
-  const char* sqe = getenv("BA_HIP_SQUARE");
-  const bool sq = nblk < 512 && sqe && atoi(sqe) != 0;
+  const bool sq = sw.square;
   if (sq) {
     if (!e->square_attr_set) {  // (per engine = per device: function attributes belong to the device)
       BAE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_square), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2527,21 +2519,21 @@ int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, i
   uint32_t pj = 0;
   for (uint32_t J = 0; J < nblk; J += KOUT, ++pj) {
     const uint32_t Jend = J + KOUT < nblk ? J + KOUT : nblk;
-    launch_panel_chain(s0, dA, ld, nblk, J, Jend, dsgn, opbuf, colneg, e->flags.p, nz, nullptr, 0, false, sq);
+    launch_panel_chain(sw, s0, dA, ld, nblk, J, Jend, dsgn, opbuf, colneg, e->flags.p, nz, nullptr, 0, false, sq);
     if (Jend >= nblk) break;
     BAE_HIP(hipEventRecord(e->ev_panel[pj], s0));
     const uint32_t a_end = Jend + KOUT < nblk ? Jend + KOUT : nblk;  // columns of the next panel
     // (a) next panel's columns: needs every earlier bulk update of those columns
     if (prev_bulk >= 0) BAE_HIP(hipStreamWaitEvent(s0, e->ev_bulk[prev_bulk], 0));
-    launch_next_panel_update(s0, dA, ld, nblk, Jend, a_end - Jend, J, Jend, dsgn, opbuf, colneg, e->flags.p, nz, !sq);
+    launch_next_panel_update(sw, s0, dA, ld, nblk, Jend, a_end - Jend, J, Jend, dsgn, opbuf, colneg, e->flags.p, nz, !sq);
     // (b) the rest, concurrently with the next panel's factorisation
     if (a_end < nblk) {
       BAE_HIP(hipStreamWaitEvent(s1, e->ev_panel[pj], 0));
       // large trailing matrices (the serial chain is negligible beside them): full occupancy;
       // otherwise the capped variant leaves the chain room
       const uint32_t m = nblk - a_end;
-      launch_bulk_update(e, s1, dA, ld, nblk, a_end, J, Jend, dsgn, colneg, nz,
-                         no_lookahead || bulk_full || m >= bulk_full_m, own_map_single());
+      launch_bulk_update(sw, e, s1, dA, ld, nblk, a_end, J, Jend, dsgn, colneg, nz,
+                         sw.no_lookahead || sw.bulk_full || m >= sw.bulk_full_m, own_map_single());
       BAE_HIP(hipEventRecord(e->ev_bulk[pj], s1));
       prev_bulk = (int)pj;
       if (e->profiling) {
@@ -2570,18 +2562,7 @@ int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, i
   BAE_HIP(hipStreamSynchronize(s0));
   *status = st;
 #ifdef BAE_TIME128
-  if (t128_dev && getenv("BA_HIP_TRACE_FILE")) {
-    BAE_HIP(hipDeviceSynchronize());
-    unsigned int n = 0;
-    BAE_HIP(hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_t128_n), sizeof(n)));
-    n = std::min(n, T128_CAP);
-    std::vector<unsigned long long> rec((size_t)n * T128_REC);
-    if (n) BAE_HIP(hipMemcpy(rec.data(), t128_dev, rec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(getenv("BA_HIP_TRACE_FILE"), "wb")) {
-      fwrite(rec.data(), sizeof(unsigned long long), rec.size(), f);
-      fclose(f);
-    }
-  }
+  return time128_write(e, sw);
 #endif
   return 0;
 }
