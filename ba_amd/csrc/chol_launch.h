@@ -26,6 +26,7 @@ struct CholSwitches {
   // BA_HIP_BULK_FULL_M = v, two readings (both 128 when unset):
   uint32_t rect_min_rows = 128;   //   max(16, v): tile rows below the next panel from which its rectangle goes to k_update128
   uint32_t bulk_full_m = 128;     //   v: trailing tile rows from which the bulk update runs uncapped
+  bool c_rmw = false;             // BA_HIP_C_RMW: k_update128 reads, subtracts and stores C (default: memory-side FP64 adds)
   // --- read on every call (tests vary them inside one process)
   uint32_t kout = 4;              // BA_HIP_KOUT: tiles per outer panel; 0 / unset: by nblk
   uint32_t left_min_tiles = 512;  // BA_HIP_LEFT_MIN_TILES: left-looking sub-panels from this many tiles on
@@ -43,7 +44,7 @@ inline uint32_t parse_kout(const char* v, uint32_t nblk) {
 }
 inline void parse_process_switches(CholSwitches* sw, const char* no128, const char* no_lookahead, const char* bulk_full,
                                    const char* dense, const char* no_dist_solve, const char* sbl,
-                                   const char* bulk_full_m) {
+                                   const char* bulk_full_m, const char* c_rmw = nullptr) {
   sw->no128 = no128 != nullptr;
   sw->no_lookahead = no_lookahead != nullptr;
   sw->bulk_full = bulk_full != nullptr;
@@ -52,6 +53,7 @@ inline void parse_process_switches(CholSwitches* sw, const char* no128, const ch
   sw->sbl = sbl ? (uint32_t)atoi(sbl) : 3u;
   sw->rect_min_rows = bulk_full_m ? (uint32_t)std::max(16, atoi(bulk_full_m)) : 128u;
   sw->bulk_full_m = bulk_full_m ? (uint32_t)atoi(bulk_full_m) : 128u;
+  sw->c_rmw = c_rmw != nullptr;
 }
 inline void parse_call_switches(CholSwitches* sw, uint32_t nblk, const char* kout, const char* left_min_tiles,
                                 const char* square, const char* sq_w, const char* dist_layout,
@@ -70,7 +72,7 @@ inline const CholSwitches& chol_process_switches() {
     CholSwitches sw;
     parse_process_switches(&sw, getenv("BA_HIP_NO128"), getenv("BA_HIP_NO_LOOKAHEAD"), getenv("BA_HIP_BULK_FULL"),
                            getenv("BA_HIP_DENSE"), getenv("BA_HIP_NO_DIST_SOLVE"), getenv("BA_HIP_SBL"),
-                           getenv("BA_HIP_BULK_FULL_M"));
+                           getenv("BA_HIP_BULK_FULL_M"), getenv("BA_HIP_C_RMW"));
     return sw;
   }();
   return once;

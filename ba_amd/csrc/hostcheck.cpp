@@ -859,7 +859,7 @@ extern "C" int ba_hostcheck_lifecycle(uint32_t n, const int32_t* events, uint32_
 #include "chol_launch.h"
 
 // chol_launch.h on n rows of integers: row i reads in[i * W_in ...] and writes out[i * W_out ...]; `str` holds the
-// strings of the one row of ops 0 and 5 (null = variable unset).  Returns 0, or -1 for an unknown op.
+// strings of the one row of ops 0, 5 and 7 (null = variable unset).  Returns 0, or -1 for an unknown op.
 //   0  switch parsing   in: nblk; str: NO128 NO_LOOKAHEAD BULK_FULL DENSE NO_DIST_SOLVE SBL BULK_FULL_M | KOUT
 //                       LEFT_MIN_TILES SQUARE SQ_W DIST_LAYOUT DENSE_SCATTER TRACE_FILE; out: the 15 fields in the
 //                       struct's order (the two strings as set / unset)
@@ -868,6 +868,7 @@ extern "C" int ba_hostcheck_lifecycle(uint32_t n, const int32_t* events, uint32_
 //   3  bulk_shape       in: nblk a_end full own_n own_G have_pairs npairs no128 sbl; out: kernel grid nrow64 m2 sbl swzf
 //   4  FactorWork       in: nblk; out: dsgn linvT opbuf colneg total packet_stride
 //   5  dist_plan_key    in: nzL_version kout pat dense_scatter; str: layout; out: key
+//   7  the epilogue switch of k_update128   str: C_RMW; out: c_rmw   (6 stays unknown: tests/test_chol_launch.py)
 extern "C" int ba_hostcheck_chol_launch(int op, uint32_t n, const int64_t* in, const char* const* str, int64_t* out) {
   using namespace bae;
   for (uint32_t i = 0; i < n; ++i) {
@@ -905,6 +906,9 @@ extern "C" int ba_hostcheck_chol_launch(int op, uint32_t n, const int64_t* in, c
       std::copy(v, v + 6, out + (size_t)i * 6);
     } else if (op == 5) {
       out[0] = (int64_t)dist_plan_key((uint64_t)in[0], (uint32_t)in[1], in[2] != 0, str[0], in[3] != 0);
+    } else if (op == 7) {
+      parse_process_switches(&sw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, str[0]);
+      out[0] = sw.c_rmw;
     } else {
       return -1;
     }

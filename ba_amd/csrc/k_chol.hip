@@ -392,7 +392,8 @@ k_update2(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uint3
 //     k-step s, one barrier per chunk (as update_tile_fast); in the K loop every load, LDS store and
 //     fragment read is issued behind an MFMA, one or two per MFMA (BAE_STEP): a block that is alone
 //     on its CU has one wave per SIMD and nothing else to fill a gap between two MFMAs;
-//   * the C block is read and written in the epilogue, one row of MFMA tiles at a time;
+//   * the epilogue adds -acc to the C block at the memory side (no-return FP64 atomic adds: C is not read);
+//     BA_HIP_C_RMW: C is read and written instead, one row of MFMA tiles at a time;
 //   * a negative pivot in the K range (indefinite system) sends the block through update_tile,
 //     one 64-tile at a time.
 // The blocks cover the even part of the trailing matrix; the rhs row and an odd last tile row are
@@ -403,7 +404,9 @@ __device__ unsigned long long* g_t128_buf = nullptr;
 __device__ unsigned int g_t128_n = 0;
 static const unsigned int T128_CAP = 1u << 21, T128_REC = 6;
 #endif
-template <bool RECT, bool LIST = false>  // RECT: the rectangle variant (separate kernel name in profiles); LIST: own.pairs
+// RECT: the rectangle variant (separate kernel name in profiles); LIST: own.pairs; RMW: the epilogue loads, subtracts
+// and stores C (BA_HIP_C_RMW) instead of adding -acc at the memory side
+template <bool RECT, bool LIST = false, bool RMW = false>
 __global__ void __launch_bounds__(256, 2)
 k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uint32_t m2, uint32_t kb0,
             uint32_t kb1, const double* __restrict__ dsgn, const int* __restrict__ colneg, uint32_t sbl,
@@ -601,11 +604,15 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
     BAE_CHUNK(3, true, true, knext + KC2, true, );
     kcur = knext;
   }
-  // the last tile column; the C block is read and written one row of four MFMA tiles (16 doubles
-  // per lane) at a time, two rows in flight: row 0 is fetched under the last chunk (the prefetch
-  // set is dead by then), row t + 2 when row t has been stored
+  // The last tile column, then the C block.  Default: C -= acc as 64 no-return FP64 adds of -acc per wave
+  // (global_atomic_add_f64: executed at the memory side, C is neither fetched nor kept in L2).  A tile is touched
+  // by one workgroup per launch and fl(C + (-acc)) = fl(C - acc), so the result is that of the read-modify-write
+  // form bit for bit; the wave ends when its adds have issued.
+  // RMW (BA_HIP_C_RMW, the form before): C is read and written one row of four MFMA tiles (16 doubles per lane)
+  // at a time, two rows in flight: row 0 is fetched under the last chunk (the prefetch set is dead by then),
+  // row t + 2 when row t has been stored.
   double* Aic = A + ((size_t)i * NB) * ld + (size_t)c * NB;
-  double4_t cva[4], cvb[4];
+  [[maybe_unused]] double4_t cva[4], cvb[4];
 #define BAE_CLOAD(CV, TI)                                                            \
   _Pragma("unroll") for (int tj = 0; tj < 4; ++tj)                                   \
     _Pragma("unroll") for (int reg = 0; reg < 4; ++reg)                              \
@@ -617,29 +624,64 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
       const int cc = cb + 16 * tj + li;                                              \
       if (!diag || cc <= r) Aic[(size_t)r * ld + cc] = CV[tj][reg] - acc[TI][tj][reg]; \
     }
+#define BAE_CADD(TI)                                                                 \
+  _Pragma("unroll") for (int tj = 0; tj < 4; ++tj)                                   \
+    _Pragma("unroll") for (int reg = 0; reg < 4; ++reg) {                            \
+      const int r = rb + 16 * (TI) + lk + 4 * reg;                                   \
+      const int cc = cb + 16 * tj + li;                                              \
+      if (!diag || cc <= r) unsafeAtomicAdd(&Aic[(size_t)r * ld + cc], -acc[TI][tj][reg]); \
+    }
   BAE_VOFF_PIN;
   BAE_CHUNK(0, true, true, kcur + 2 * KC2, true, );
   BAE_CHUNK(1, true, true, kcur + 3 * KC2, true, );
   BAE_CHUNK(2, true, false, 0, true, );
-  BAE_CHUNK(3, false, false, 0, false, BAE_CLOAD(cva, 0));
+  if constexpr (RMW) {
+    BAE_CHUNK(3, false, false, 0, false, BAE_CLOAD(cva, 0));
+  } else {
+    BAE_CHUNK(3, false, false, 0, false, );
+  }
 #ifdef BAE_TIME128
   const unsigned long long tt2 = __builtin_readcyclecounter();
   const unsigned long long tw2 = wall_clock64();
 #endif
   if (diag && wave == 1) return;  // the strictly upper 64-tile of a diagonal block (computed, not stored)
-  BAE_SB;
-  BAE_CLOAD(cvb, 1);
-  BAE_SB;
-  BAE_CSTORE(cva, 0);
-  BAE_SB;
-  BAE_CLOAD(cva, 2);
-  BAE_SB;
-  BAE_CSTORE(cvb, 1);
-  BAE_SB;
-  BAE_CLOAD(cvb, 3);
-  BAE_SB;
-  BAE_CSTORE(cva, 2);
-  BAE_CSTORE(cvb, 3);
+  if constexpr (RMW) {
+    BAE_SB;
+    BAE_CLOAD(cvb, 1);
+    BAE_SB;
+    BAE_CSTORE(cva, 0);
+    BAE_SB;
+    BAE_CLOAD(cva, 2);
+    BAE_SB;
+    BAE_CSTORE(cvb, 1);
+    BAE_SB;
+    BAE_CLOAD(cvb, 3);
+    BAE_SB;
+    BAE_CSTORE(cva, 2);
+    BAE_CSTORE(cvb, 3);
+  } else {
+    BAE_SB;
+    if (diag) {
+      BAE_CADD(0);
+      BAE_CADD(1);
+      BAE_CADD(2);
+      BAE_CADD(3);
+    } else {
+      // off the diagonal nothing is masked: a wave-uniform address per instruction (scalar unit) and one 32-bit
+      // byte offset per lane, as the operand loads of the K loop
+      const int wv = __builtin_amdgcn_readfirstlane(wave);
+      char* Cw = reinterpret_cast<char*>(Aic + (size_t)(64 * (wv >> 1)) * ld + 64 * (wv & 1));
+      const uint32_t loff = ((uint32_t)lk * ld + (uint32_t)li) * 8u;
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg)
+            unsafeAtomicAdd(reinterpret_cast<double*>(Cw + ((size_t)(16 * ti + 4 * reg) * ld + 16 * tj) * 8 + (size_t)loff),
+                            -acc[ti][tj][reg]);
+    }
+  }
 #ifdef BAE_TIME128
   if (tid == 0 && (blockIdx.x % 257u) == 100u && !RECT) {
     const unsigned long long tt3 = __builtin_readcyclecounter();
@@ -658,6 +700,7 @@ k_update128(double* __restrict__ A, uint32_t ld, uint32_t nblk, uint32_t c0, uin
 #endif
 #undef BAE_CLOAD
 #undef BAE_CSTORE
+#undef BAE_CADD
 #undef BAE_SB
 #undef BAE_GLOAD
 #undef BAE_SSTORE
@@ -1732,10 +1775,11 @@ static void launch_panel_chain(const CholSwitches& sw, hipStream_t s, double* dA
 // (0,0) — stays a k_step_update launch; the rectangle below the panel goes to 128x128 blocks when
 // it is big enough.
 // The rectangle below the tile columns [c0, c0 + ncols) in 128x128 blocks (rect128_shape said use128).
-static void launch_rect128(const Rect128Shape& r, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, uint32_t c0,
-                           uint32_t ncols, uint32_t kb0, uint32_t kb1, const double* dsgn, const int* colneg,
-                           const uint8_t* nz, const OwnMap& own) {
-  hipLaunchKernelGGL(k_update128<true>, dim3(r.grid), dim3(256), 0, s, dA, ld, nblk, c0, r.m2, kb0, kb1, dsgn, colneg,
+static void launch_rect128(const CholSwitches& sw, const Rect128Shape& r, hipStream_t s, double* dA, uint32_t ld,
+                           uint32_t nblk, uint32_t c0, uint32_t ncols, uint32_t kb0, uint32_t kb1, const double* dsgn,
+                           const int* colneg, const uint8_t* nz, const OwnMap& own) {
+  auto kernel = sw.c_rmw ? k_update128<true, false, true> : k_update128<true>;
+  hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(256), 0, s, dA, ld, nblk, c0, r.m2, kb0, kb1, dsgn, colneg,
                      0u, nz, own, r.nrow64, c0 + ncols, r.rect_cols);
 }
 static void launch_next_panel_update(const CholSwitches& sw, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
@@ -1746,7 +1790,7 @@ static void launch_next_panel_update(const CholSwitches& sw, hipStream_t s, doub
   if (r.use128) {
     hipLaunchKernelGGL(step_update, dim3(ncols, ncols), dim3(256), 0, s, dA, ld, nblk, c0, kb0, kb1, dsgn, opbuf,
                        colneg, flags, nz, c0 + ncols, (const uint32_t*)nullptr);
-    launch_rect128(r, s, dA, ld, nblk, c0, ncols, kb0, kb1, dsgn, colneg, nz, own_map_single());
+    launch_rect128(sw, r, s, dA, ld, nblk, c0, ncols, kb0, kb1, dsgn, colneg, nz, own_map_single());
     return;
   }
   hipLaunchKernelGGL(step_update, dim3(nblk - c0 + 1, ncols), dim3(256), 0, s, dA, ld, nblk, c0, kb0, kb1, dsgn,
@@ -1768,14 +1812,17 @@ static void launch_bulk_update(const CholSwitches& sw, Engine* e, hipStream_t s,
       OwnMap ol = own;
       ol.pairs_lo = (uint32_t)(reinterpret_cast<unsigned long long>(pairs) & 0xffffffffull);
       ol.pairs_hi = (uint32_t)(reinterpret_cast<unsigned long long>(pairs) >> 32);
-      hipLaunchKernelGGL((k_update128<false, true>), grid, wg, 0, s, dA, ld, nblk, a_end, b.m2, J, Jend, dsgn, colneg,
-                         b.sbl, nz, ol, b.nrow64, a_end, 0u);
+      auto kernel = sw.c_rmw ? k_update128<false, true, true> : k_update128<false, true>;
+      hipLaunchKernelGGL(kernel, grid, wg, 0, s, dA, ld, nblk, a_end, b.m2, J, Jend, dsgn, colneg, b.sbl, nz, ol,
+                         b.nrow64, a_end, 0u);
       break;
     }
-    case kBulkU128:
-      hipLaunchKernelGGL(k_update128<false>, grid, wg, 0, s, dA, ld, nblk, a_end, b.m2, J, Jend, dsgn, colneg, b.sbl,
-                         nz, own, b.nrow64, a_end, 0u);
+    case kBulkU128: {
+      auto kernel = sw.c_rmw ? k_update128<false, false, true> : k_update128<false>;
+      hipLaunchKernelGGL(kernel, grid, wg, 0, s, dA, ld, nblk, a_end, b.m2, J, Jend, dsgn, colneg, b.sbl, nz, own,
+                         b.nrow64, a_end, 0u);
       break;
+    }
     case kBulkU2Full:
       hipLaunchKernelGGL(k_update2<false>, grid, wg, 0, s, dA, ld, nblk, a_end, J, Jend, dsgn, colneg, b.swzf, nz, own);
       break;
@@ -2304,7 +2351,7 @@ int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* sta
       o1.skip_rhs = 1;  // the rhs segment of column block J+1 went with the square's update on the chain stream
       const Rect128Shape r = rect128_shape(kRectDist, nblk, c1, ncols, own.G, sw);
       if (r.use128) {
-        launch_rect128(r, s1, dA, ld, nblk, c1, ncols, c0, c1, dsgn, colneg, nz, o1);
+        launch_rect128(sw, r, s1, dA, ld, nblk, c1, ncols, c0, c1, dsgn, colneg, nz, o1);
       } else {
         // 64-tiles: exactly the row tiles this rank owns below the square of panel J+1 (its two row lists are
         // adjacent) — a structurally zero tile of L takes no update, so the lists are complete
