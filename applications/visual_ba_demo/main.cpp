@@ -30,6 +30,9 @@
 //                                           pose and the time of the joint call (GetJointPoseCovariance), and the
 //                                           largest correlation between the last pose and the last landmark with
 //                                           the time of that call (GetJointCovariance: the cross blocks)
+//   visual_ba_demo --weakest-modes K        after the solve: the K eigenvalues of smallest magnitude of the reduced
+//                                           system (GetWeakestModes: block inverse iteration on the kept factor)
+//                                           and, per mode, the poses and parameters that carry its largest entries
 //   visual_ba_demo --leverages              after the solve: the median and the smallest redundancy number
 //                                           2 - tr H_aa of the projection residuals (GetProjectionLeverages: hat
 //                                           blocks from the selected inverse) and the five residuals with the
@@ -47,7 +50,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0, weakest_modes = 0; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -295,6 +298,35 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
                 mixed_ms);
     ok = ok && std::isfinite(c(0, 0)) && c(0, 0) > 0 && sl[sl.size() / 2] > 0 && std::isfinite(corr) && corr <= 1.0 + 1e-9;
   }
+  if (shard.weakest_modes) {
+    std::vector<double> ev;
+    ba::MatX modes;
+    ba_hip_mode_stats ms;
+    if (!adjuster.GetWeakestModes(shard.weakest_modes, ev, modes) || !adjuster.GetModeStats(&ms)) {
+      std::printf("weakest modes unavailable\n");
+      return 2;
+    }
+    static const char* names[6] = {"t_x", "t_y", "t_z", "r_x", "r_y", "r_z"};
+    const int np = (int)ba_hip_num_pose_params(adjuster.engine());
+    std::printf("weakest modes: %u of %zu converged in %u iterations (solve %.3f ms, orthonormalisation %.3f ms)\n", ms.converged,
+                ev.size(), ms.iterations, ms.solve_ms, ms.ortho_ms);
+    for (size_t i = 0; i < ev.size(); ++i) {
+      std::vector<int> idx(modes.cols());
+      for (int r = 0; r < modes.cols(); ++r) idx[r] = r;
+      const size_t top = std::min<size_t>(3, idx.size());
+      std::partial_sort(idx.begin(), idx.begin() + top, idx.end(),
+                        [&](int a, int b) { return std::fabs(modes((int)i, a)) > std::fabs(modes((int)i, b)); });
+      std::printf("mode %zu: lambda %.6e, largest entries", i, ev[i]);
+      for (size_t q = 0; q < top; ++q) {
+        const int r = idx[q];
+        // poses 0 and 1 are fixed: active pose a is pose a + 2; the rows behind the poses are the calibration's
+        if (r < np) std::printf("  pose %d %s %+.3f", r / 6 + 2, names[r % 6], modes((int)i, r));
+        else std::printf("  calibration %d %+.3f", r - np, modes((int)i, r));
+      }
+      std::printf("\n");
+      ok = ok && std::isfinite(ev[i]);
+    }
+  }
   if (shard.leverages) {
     const uint32_t nres = adjuster.GetNumProjResiduals();
     std::vector<double> h, red(nres);
@@ -340,7 +372,8 @@ int main(int argc, char** argv) {
       continue;
     }
     if (i + 1 >= argc) break;
-    if (std::strcmp(argv[i], "--pcg-coarse") == 0) shard.pcg_coarse = (unsigned)std::atoi(argv[i + 1]);
+    if (std::strcmp(argv[i], "--weakest-modes") == 0) shard.weakest_modes = (unsigned)std::atoi(argv[i + 1]);
+    else if (std::strcmp(argv[i], "--pcg-coarse") == 0) shard.pcg_coarse = (unsigned)std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--ranks") == 0) shard.ranks = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--rank") == 0) shard.rank = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--device") == 0) shard.device = std::atoi(argv[i + 1]);

@@ -74,6 +74,7 @@ SYMBOLS = [
     "ba_adjuster_get_projection_leverage", "ba_adjuster_get_projection_redundancy",
     "ba_adjuster_get_joint_pose_covariance",
     "ba_adjuster_get_joint_covariance", "ba_adjuster_get_pose_landmark_cross_covariance",
+    "ba_adjuster_solve_with_factor", "ba_adjuster_get_weakest_modes", "ba_adjuster_get_mode_stats",
     "ba_adjuster_get_pose_pose_leverages", "ba_adjuster_get_pose_pose_leverage",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
@@ -459,6 +460,39 @@ class BundleAdjuster:
         if got != m or m == 0:
             raise RuntimeError("joint covariance unavailable (see stderr)")
         return c
+
+    def _reduced_rows(self):
+        eh = self.engine().h
+        return int(self.L.ba_hip_num_pose_params(eh)) + int(self.L.ba_hip_num_calib_params(eh))
+
+    def SolveWithFactor(self, B):
+        """SolveWithFactor: X = S^-1 B with the factor of the last Solve(); B is (n, m), rows as delta_p() then the
+        calibration rows; raises when unavailable."""
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        n = self._reduced_rows()
+        if B.ndim != 2 or B.shape[0] != n:
+            raise RuntimeError("SolveWithFactor: B must be (%d, m)" % n)
+        X = np.zeros_like(B)
+        dp = C.POINTER(C.c_double)
+        if self.L.ba_adjuster_solve_with_factor(self.h, n, B.shape[1], B.ctypes.data_as(dp), X.ctypes.data_as(dp)):
+            raise RuntimeError("solve with the factor unavailable (see stderr)")
+        return X
+
+    def GetWeakestModes(self, k):
+        """GetWeakestModes: (eigenvalues (k,), modes (k, n)) of smallest magnitude of the reduced system of the last
+        Solve(), each mode a unit vector over the rows of SolveWithFactor; raises when unavailable."""
+        n = self._reduced_rows()
+        lam, modes = np.zeros(int(k)), np.zeros((int(k), n))
+        dp = C.POINTER(C.c_double)
+        if self.L.ba_adjuster_get_weakest_modes(self.h, int(k), n, lam.ctypes.data_as(dp), modes.ctypes.data_as(dp)):
+            raise RuntimeError("weakest modes unavailable (see stderr)")
+        return lam, modes
+
+    def GetModeStats(self):
+        st = hipapi.ModeStats()
+        if self.L.ba_adjuster_get_mode_stats(self.h, C.byref(st)):
+            raise RuntimeError("mode statistics unavailable")
+        return {k: getattr(st, k) for k, _ in hipapi.ModeStats._fields_ if k != "reserved"}
 
     def GetPoseLandmarkCrossCovariance(self, pose_id, landmark_id):
         """GetPoseLandmarkCrossCovariance: the (PoseSize, LmSize) block Cov(pose, landmark); raises when unavailable."""

@@ -55,6 +55,9 @@ struct Iface {
   virtual uint32_t joint_state_covariance(uint32_t n, const uint32_t* ids, int include_calibration, uint32_t nl,
                                           const uint32_t* lms, double* out) = 0;
   virtual int pose_landmark_cross_covariance(uint32_t pose_id, uint32_t landmark_id, double* out) = 0;
+  virtual int solve_with_factor(uint32_t n, uint32_t m, const double* B, double* X) = 0;
+  virtual int weakest_modes(uint32_t k, uint32_t n, double* eigenvalues, double* modes) = 0;
+  virtual int mode_stats(ba_hip_mode_stats* out) = 0;
   virtual int pose_pose_leverages(int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev) = 0;
   virtual double pose_pose_leverage(int kind, uint32_t id) = 0;
   virtual int marginalize(uint32_t nm, const uint32_t* m, uint32_t nl, const uint32_t* l, uint32_t* nb) = 0;
@@ -281,6 +284,22 @@ struct Impl : Iface {
     for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
     return 0;
   }
+  int solve_with_factor(uint32_t n, uint32_t m, const double* B, double* X) override {
+    ba::MatX b((int)n, (int)m), x;
+    std::copy(B, B + (size_t)n * m, b.data());
+    if (!ba.SolveWithFactor(b, x)) return 1;
+    std::copy(x.data(), x.data() + (size_t)n * m, X);
+    return 0;
+  }
+  int weakest_modes(uint32_t k, uint32_t n, double* eigenvalues, double* modes) override {
+    std::vector<double> ev;
+    ba::MatX m;
+    if (!ba.GetWeakestModes(k, ev, m) || (uint32_t)m.cols() != n) return 1;
+    std::copy(ev.begin(), ev.end(), eigenvalues);
+    std::copy(m.data(), m.data() + (size_t)k * n, modes);
+    return 0;
+  }
+  int mode_stats(ba_hip_mode_stats* out) override { return ba.GetModeStats(out) ? 0 : 1; }
   int pose_pose_leverages(int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev) override {
     std::vector<double> c, i, l;
     if (!ba.GetPosePoseLeverages(kind, ids ? std::vector<uint32_t>(ids, ids + n) : std::vector<uint32_t>(),
@@ -470,6 +489,15 @@ int ba_adjuster_get_pose_landmark_cross_covariance(ba_adjuster* a, uint32_t pose
   if (!cov) return 1;
   return a->p->pose_landmark_cross_covariance(pose_id, landmark_id, cov);
 }
+int ba_adjuster_solve_with_factor(ba_adjuster* a, uint32_t n, uint32_t m, const double* B, double* X) {
+  if (!B || !X) return 1;
+  return a->p->solve_with_factor(n, m, B, X);
+}
+int ba_adjuster_get_weakest_modes(ba_adjuster* a, uint32_t k, uint32_t n, double* eigenvalues, double* modes) {
+  if (!eigenvalues || !modes) return 1;
+  return a->p->weakest_modes(k, n, eigenvalues, modes);
+}
+int ba_adjuster_get_mode_stats(ba_adjuster* a, ba_hip_mode_stats* out) { return out ? a->p->mode_stats(out) : 1; }
 int ba_adjuster_marginalize(ba_adjuster* a, uint32_t nm, const uint32_t* pose_ids, uint32_t nl,
                             const uint32_t* landmark_ids, uint32_t* blanket_poses) {
   if ((nm && !pose_ids) || (nl && !landmark_ids)) return 1;

@@ -267,6 +267,16 @@ struct Engine {
   DBuf<double> jc_Y, jc_slots, jc_part, jc_out;
   DBuf<uint32_t> jc_lm;                  // landmark columns (ba_hip_get_joint_state_marginals): ids | tile marks | counts
   ba_hip_joint_marginal_stats jstats = {};
+  // solves with the kept factor (ba_hip_factor_solve, k_factorsolve.hip): the plan's tables, one panel per tile
+  // row, the partial tiles of a level and the staging of B / X; allocated by the first request, grown on demand,
+  // freed by ba_hip_release_marginals
+  DBuf<uint32_t> fs_idx;
+  DBuf<double> fs_X, fs_slots, fs_B;
+  ba_hip_factor_solve_stats fsstats = {};
+  // ... and the weakest modes (ba_hip_get_weakest_modes): fs_X then holds three panels of 64 columns; fs_M: the
+  // 64 x 64 matrix of an apply and the Ritz values, fs_part: the partial Gram tiles and their sum
+  DBuf<double> fs_M, fs_part;
+  ba_hip_mode_stats mode_stats = {};
   ba_hip_joint_state_stats jsstats = {};
   ba_hip_leverage_stats lstats = {};     // the last ba_hip_get_projection_leverages (k_lever.hip)
   std::vector<uint32_t> lev_pos;         // its plan (lever.h): sorted position of every residual id, and the block
@@ -483,6 +493,28 @@ int pose_pose_leverages_run(Engine* e, int kind, uint32_t n, const uint32_t* ids
 // invdiag and, for landmarks, the rows of the last linearisation
 int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<uint32_t>& lms, double* out);
 void jointcov_release(Engine* e);
+// the substitution Y <- L^-1 Y of a joint plan whose tables are on the device (k_jointcov.hip), enqueued on `stream`
+struct JointPlan;
+void joint_forward_launch(hipStream_t stream, const JointPlan& p, const uint4* d_chunks, const uint4* d_rows,
+                          const uint32_t* d_src, const uint32_t* d_pos, const double* A, uint32_t ld, const double* linvT,
+                          double* Y, double* slots);
+// X = S^-1 B with a factor on the device (k_factorsolve.hip): the lower storage A (leading dimension ld = 64 nt),
+// its tile pattern on the host, the pivot signs and the L_JJ^-T.  B, X: n x m row-major on the host, rows in the
+// caller's order; rowmap (64 nt entries): the caller's row of every factorised row, kJointNone for padding rows
+struct FactorRef {
+  const double* A;
+  uint32_t ld, nt;
+  const std::vector<uint8_t>* nz;
+  const double *dsgn, *linvT;
+};
+int factor_solve_run(Engine* e, const FactorRef& f, uint32_t n, const uint32_t* rowmap, uint32_t m, const double* B,
+                     double* X);
+void factor_solve_release(Engine* e);
+// the k eigenpairs of smallest magnitude of the factorised S by the block inverse iteration of factorsolve.h on
+// device-resident panels: eigenvalues (k), modes (k x n row-major, rows in the caller's order, unit 2-norm)
+struct ModeOptions;
+int weakest_modes_run(Engine* e, const FactorRef& f, uint32_t n, const uint32_t* rowmap, uint32_t k, const ModeOptions& o,
+                      double* eigenvalues, double* modes);
 // dense priors and marginalisation (k_marg.hip): upload at finalize; linearise (mode 1: into A, rhs_p, rhs_p_sc) or
 // evaluate (mode 0) every prior at the current state, E_p summed into *err_host; the dogleg term; one marginalisation
 int priors_upload(Engine* e);

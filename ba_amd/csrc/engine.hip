@@ -14,6 +14,7 @@
 #include <numeric>
 
 #include "dmath.h"
+#include "factorsolve.h"
 #include "dpose.h"
 
 namespace bae {
@@ -550,6 +551,16 @@ static PaddedSystem pad_system(uint32_t n, const double* a_lower, const double* 
   for (uint32_t r = n; r < ld; ++r) s.A[(size_t)r * ld + r] = 1.0;
   for (uint32_t c = 0; c < n; ++c) s.A[(size_t)ld * ld + c] = b[c];
   return s;
+}
+// the refusals of ba_hip_factor_solve and its test tap that do not depend on the factor
+static int factor_solve_args(Engine* e, const char* what, uint32_t m, const double* B, const double* X) {
+  const std::string w = std::string(what) + ": ";
+  if (m == 0) return e->fail_msg((w + "no columns requested (m == 0)").c_str());
+  if (m > BA_HIP_FACTOR_SOLVE_MAX_COLUMNS)
+    return e->fail_msg((w + std::to_string(m) + " columns requested, the limit is BA_HIP_FACTOR_SOLVE_MAX_COLUMNS (" +
+                        std::to_string(BA_HIP_FACTOR_SOLVE_MAX_COLUMNS) + ")").c_str());
+  if (!B || !X) return e->fail_msg((w + "NULL argument").c_str());
+  return 0;
 }
 // ... and the first n entries of the solution back
 static hipError_t download_x(const DBuf<double>& dx, uint32_t n, double* x) {
@@ -1653,6 +1664,57 @@ int ba_hip_get_joint_marginal_stats(ba_hip_engine* h, ba_hip_joint_marginal_stat
   *out = e->jstats;
   return 0;
 }
+// ---- solves with the kept factor (k_factorsolve.hip): X = S^-1 B, rows in the caller's (natural) order ----
+int ba_hip_factor_solve(ba_hip_engine* h, uint32_t m, const double* B, double* X) {
+  ENG(h);
+  static const char* what = "ba_hip_factor_solve";
+  if (!e->held.finalized) return e->fail_msg("ba_hip_factor_solve: ba_hip_finalize has not been called");
+  int rc;
+  if ((rc = kept_factor_ready(e, what, "solves with the factor", false))) return rc;
+  if ((rc = factor_solve_args(e, what, m, B, X))) return rc;
+  BAE_HIP(hipSetDevice(e->device));
+  FactorRef f = {e->A.p, e->st.ld, 0, &e->nzL_host, nullptr, nullptr};
+  if ((rc = kept_factor(e, "factor solve", &f.nt, &f.dsgn, &f.linvT))) return rc;
+  std::vector<uint32_t> rowmap(e->st.ld, kJointNone);
+  for (uint32_t r = 0; r < e->st.n; ++r) rowmap[int_row(e, r)] = r;
+  return factor_solve_run(e, f, e->st.n, rowmap.data(), m, B, X);
+}
+int ba_hip_get_weakest_modes(ba_hip_engine* h, uint32_t k, const ba_hip_mode_options* o, double* eigenvalues,
+                             double* modes) {
+  ENG(h);
+  static const char* what = "ba_hip_get_weakest_modes";
+  const std::string w = std::string(what) + ": ";
+  if (!e->held.finalized) return e->fail_msg((w + "ba_hip_finalize has not been called").c_str());
+  int rc;
+  if ((rc = kept_factor_ready(e, what, "weakest modes", false))) return rc;
+  const uint32_t n = e->st.n, kmax = std::min(kModeMaxK, n);
+  if (k == 0 || k > kmax)
+    return e->fail_msg((w + std::to_string(k) + " modes requested, k must be between 1 and min(32, n) = " +
+                        std::to_string(kmax)).c_str());
+  if (!eigenvalues || !modes) return e->fail_msg((w + "NULL argument").c_str());
+  ModeOptions mo;
+  if (o && o->tolerance > 0.0) mo.tolerance = o->tolerance;
+  if (o && o->max_iterations) mo.max_iterations = o->max_iterations;
+  if (o && o->seed) mo.seed = o->seed;
+  BAE_HIP(hipSetDevice(e->device));
+  FactorRef f = {e->A.p, e->st.ld, 0, &e->nzL_host, nullptr, nullptr};
+  if ((rc = kept_factor(e, "weakest modes", &f.nt, &f.dsgn, &f.linvT))) return rc;
+  std::vector<uint32_t> rowmap(e->st.ld, kJointNone);
+  for (uint32_t r = 0; r < n; ++r) rowmap[int_row(e, r)] = r;
+  return weakest_modes_run(e, f, n, rowmap.data(), k, mo, eigenvalues, modes);
+}
+int ba_hip_get_mode_stats(ba_hip_engine* h, ba_hip_mode_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_mode_stats: NULL argument");
+  *out = e->mode_stats;
+  return 0;
+}
+int ba_hip_get_factor_solve_stats(ba_hip_engine* h, ba_hip_factor_solve_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_factor_solve_stats: NULL argument");
+  *out = e->fsstats;
+  return 0;
+}
 int ba_hip_get_marginal_stats(ba_hip_engine* h, ba_hip_marginal_stats* out) {
   ENG(h);
   if (!out) return e->fail_msg("ba_hip_get_marginal_stats: NULL argument");
@@ -1665,6 +1727,7 @@ int ba_hip_release_marginals(ba_hip_engine* h) {
   (void)hipStreamSynchronize(e->stream);
   marginals_release(e);
   jointcov_release(e);
+  factor_solve_release(e);
   return 0;
 }
 
@@ -2257,19 +2320,19 @@ int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const 
 // The direct tile-sparse factorisation on a host system with a caller-supplied tile pattern (test entry: the
 // kept factor comes back as the engine holds it).  Uses buffers of its own for the matrix and the pattern; the
 // engine's invdiag work space is shared with ba_hip_solve_gn, so the scene's kept factor is marked gone.
-int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, const uint8_t* tile_map,
-                      double* x, uint8_t* nz_factor, double* factor, double* linvT, double* dsgn) {
-  ENG(h);
-  if (!n || !a_lower || !b || !x) return e->fail_msg("ba_hip_tile_solve: NULL or empty argument");
+// Shared by ba_hip_tile_solve and ba_hip_tile_factor_solve: `who` starts the messages; sys, dA and dx are the
+// caller's and outlive the call (the factor stays in dA, its closed pattern in sys.nz, the solution in dx).
+static int tile_factorise(Engine* e, const char* who, uint32_t n, const double* a_lower, const double* b,
+                          const uint8_t* tile_map, PaddedSystem& sys, DBuf<double>& dA, DBuf<double>& dx, int* status) {
   BAE_HIP(hipSetDevice(e->device));
-  PaddedSystem sys = pad_system(n, a_lower, b, true);
+  sys = pad_system(n, a_lower, b, true);
   const uint32_t ld = sys.ld, nt = sys.nt;
   std::vector<uint8_t>& nz = sys.nz;
   if (tile_map) {
     for (uint32_t r = 0; r < n; ++r)
       for (uint32_t c = 0; c <= r; ++c)
         if (a_lower[(size_t)r * n + c] != 0.0 && r / 64 != c / 64 && !tile_map[(size_t)(r / 64) * nt + c / 64]) {
-          e->err = "ba_hip_tile_solve: entry (" + std::to_string(r) + ", " + std::to_string(c) + ") is nonzero but tile (" +
+          e->err = std::string(who) + ": entry (" + std::to_string(r) + ", " + std::to_string(c) + ") is nonzero but tile (" +
                    std::to_string(r / 64) + ", " + std::to_string(c / 64) + ") is not in the tile map";
           return -1;
         }
@@ -2278,8 +2341,6 @@ int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const
   }
   for (uint32_t i = 0; i < nt; ++i) nz[(size_t)i * nt + i] = 1;  // diagonal tiles always
   tile_symbolic_factor(nz, nt);
-  if (nz_factor) std::copy(nz.begin(), nz.end(), nz_factor);
-  DBuf<double> dA, dx;
   DBuf<uint8_t> dnz;
   BAE_HIP(dA.alloc(sys.A.size()));
   BAE_HIP(dx.alloc(ld));
@@ -2287,12 +2348,23 @@ int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const
   BAE_HIP(e->flags.alloc(16));
   BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
   BAE_HIP(hipMemcpy(dnz.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
-  int status = 0;
   e->held.standalone_factorisation();
-  int rc = cholesky_solve(e, dA.p, n, ld, dx.p, &status, dnz.p);
+  int rc = cholesky_solve(e, dA.p, n, ld, dx.p, status, dnz.p);
   if (rc) return rc;
-  hipError_t err = hipDeviceSynchronize();  // both streams of the factorisation
-  if (err == hipSuccess) err = download_x(dx, n, x);
+  BAE_HIP(hipDeviceSynchronize());  // both streams of the factorisation (dnz goes with this scope)
+  return 0;
+}
+int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, const uint8_t* tile_map,
+                      double* x, uint8_t* nz_factor, double* factor, double* linvT, double* dsgn) {
+  ENG(h);
+  if (!n || !a_lower || !b || !x) return e->fail_msg("ba_hip_tile_solve: NULL or empty argument");
+  PaddedSystem sys;
+  DBuf<double> dA, dx;
+  int status = 0;
+  if (int rc = tile_factorise(e, "ba_hip_tile_solve", n, a_lower, b, tile_map, sys, dA, dx, &status)) return rc;
+  const uint32_t ld = sys.ld, nt = sys.nt;
+  if (nz_factor) std::copy(sys.nz.begin(), sys.nz.end(), nz_factor);
+  hipError_t err = download_x(dx, n, x);
   if (err == hipSuccess && factor) err = hipMemcpy(factor, dA.p, (size_t)ld * ld * 8, hipMemcpyDeviceToHost);
   const FactorWork fw(nt);
   if (err == hipSuccess && dsgn) err = hipMemcpy(dsgn, e->invdiag.p + fw.dsgn, (size_t)ld * 8, hipMemcpyDeviceToHost);
@@ -2300,6 +2372,25 @@ int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const
     err = hipMemcpy(linvT, e->invdiag.p + fw.linvT, (size_t)nt * 64 * 64 * 8, hipMemcpyDeviceToHost);
   if (err != hipSuccess) return e->fail(err, "hipMemcpy");
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
+}
+
+int ba_hip_tile_factor_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const uint8_t* tile_map, uint32_t m,
+                             const double* B, double* X) {
+  ENG(h);
+  static const char* what = "ba_hip_tile_factor_solve";
+  if (!n || !a_lower) return e->fail_msg("ba_hip_tile_factor_solve: NULL or empty argument");
+  if (int rc = factor_solve_args(e, what, m, B, X)) return rc;
+  PaddedSystem sys;
+  DBuf<double> dA, dx;
+  int status = 0;
+  const std::vector<double> b(n, 0.0);
+  if (int rc = tile_factorise(e, what, n, a_lower, b.data(), tile_map, sys, dA, dx, &status)) return rc;
+  if (status) return BA_HIP_FACTORIZATION_ERROR;
+  const FactorWork fw(sys.nt);
+  const FactorRef f = {dA.p, sys.ld, sys.nt, &sys.nz, e->invdiag.p + fw.dsgn, e->invdiag.p + fw.linvT};
+  std::vector<uint32_t> rowmap(sys.ld, kJointNone);
+  for (uint32_t r = 0; r < n; ++r) rowmap[r] = r;
+  return factor_solve_run(e, f, n, rowmap.data(), m, B, X);
 }
 
 int ba_hip_select_kth(ba_hip_engine* h, uint32_t n, const double* values, uint32_t k, double* out) {

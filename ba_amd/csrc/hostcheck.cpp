@@ -332,15 +332,20 @@ extern "C" uint64_t ba_hostcheck_group_order_products(uint32_t Pact, int D, uint
 #include "selinv.h"
 
 // Pattern and factor of a dense symmetric S for the two harnesses below: the closed tile pattern, L (lower
-// storage, ld = 64 nt), the pivot signs and linvT; -1 on a zero pivot
+// storage, ld = 64 nt), the pivot signs and linvT; -1 on a zero pivot.  tile_map (optional, nt x nt): tiles to
+// count as non-zero besides those that hold a non-zero of S
 static int host_tile_factor(uint32_t n, const double* S, std::vector<uint8_t>& nz, std::vector<double>& L,
-                            std::vector<double>& d, std::vector<double>& linvT) {
+                            std::vector<double>& d, std::vector<double>& linvT, const uint8_t* tile_map = nullptr) {
   const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
   nz.assign((size_t)nt * nt, 0);
   for (uint32_t r = 0; r < n; ++r)
     for (uint32_t c = 0; c < n; ++c)
       if (S[(size_t)r * n + c] != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
   for (uint32_t t = 0; t < nt; ++t) nz[(size_t)t * nt + t] = 1;
+  if (tile_map)
+    for (uint32_t i = 0; i < nt; ++i)
+      for (uint32_t k = 0; k <= i; ++k)
+        if (tile_map[(size_t)i * nt + k]) nz[(size_t)i * nt + k] = nz[(size_t)k * nt + i] = 1;
   bae::tile_symbolic_factor(nz, nt);
   L.assign((size_t)ld * ld, 0.0);
   d.assign(ld, 1.0);
@@ -474,6 +479,65 @@ extern "C" int ba_hostcheck_joint_rhs(uint32_t n, const double* S, uint32_t m, c
   std::copy(nz.begin(), nz.end(), nzL_out);
   *products = p.products;
   *levels = p.levels();
+  return 0;
+}
+
+// ---- solves with the kept factor (factorsolve.h) ---------------------------------------------------------
+#include "factorsolve.h"
+
+// X = S^-1 B for a dense symmetric S (n x n) and B (n x m, row-major), factorised as for ba_hostcheck_selinv on
+// the pattern of S's non-zeros and the optional lower tile map (nt x nt), by build_factor_solve_plan +
+// factor_solve_host.  variant: FactorSolveVariant (0 is the computation).  Out: X (n x m), nzL (nt x nt), the
+// backward level of every tile column (nt), levels2 = (forward, backward) launch pairs, products2 = the tile
+// products of the two passes.  Returns -1 on a zero pivot, -2 on m == 0.
+extern "C" int ba_hostcheck_factor_solve(uint32_t n, const double* S, const uint8_t* tile_map, uint32_t m, const double* B,
+                                         int variant, double* X, uint8_t* nzL_out, uint32_t* backward_level_of,
+                                         uint32_t* levels2, uint64_t* products2) {
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  if (!m) return -2;
+  std::vector<uint8_t> nz;
+  std::vector<double> L, d, linvT;
+  if (host_tile_factor(n, S, nz, L, d, linvT, tile_map)) return -1;
+  bae::FactorSolvePlan p;
+  bae::build_factor_solve_plan(nz, nt, m, p);
+  const uint32_t mp = p.fwd.m_pad;
+  std::vector<double> P(p.fwd.y_count(), 0.0);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c < m; ++c) P[(size_t)r * mp + c] = B[(size_t)r * m + c];
+  bae::factor_solve_host(p, L.data(), ld, linvT.data(), d.data(), P.data(), variant);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c < m; ++c) X[(size_t)r * m + c] = P[(size_t)r * mp + c];
+  std::copy(nz.begin(), nz.end(), nzL_out);
+  for (uint32_t J = 0; J < nt; ++J) backward_level_of[J] = p.backward_level_of(J);
+  levels2[0] = p.fwd.levels();
+  levels2[1] = p.bwd.levels();
+  products2[0] = p.fwd.products;
+  products2[1] = p.bwd.products;
+  return 0;
+}
+
+// The k eigenpairs of smallest magnitude of a dense symmetric S by weakest_modes_host, factorised as for
+// ba_hostcheck_factor_solve.  pad_nonzero: the wrong variant of factorsolve.h.  Out: eigenvalues (k, ascending
+// magnitude), modes (k x n), out_u32 = (iterations, converged, block), the largest relative residual of the k
+// pairs.  Returns -1 on a zero pivot, -2 on k out of range.
+extern "C" int ba_hostcheck_weakest_modes(uint32_t n, const double* S, const uint8_t* tile_map, uint32_t k, double tolerance,
+                                          uint32_t max_iterations, uint32_t seed, int pad_nonzero, double* eigenvalues,
+                                          double* modes, uint32_t* out_u32, double* residual_max) {
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  if (k == 0 || k > std::min(bae::kModeMaxK, n)) return -2;
+  std::vector<uint8_t> nz;
+  std::vector<double> L, d, linvT;
+  if (host_tile_factor(n, S, nz, L, d, linvT, tile_map)) return -1;
+  bae::ModeOptions o;
+  o.tolerance = tolerance;
+  o.max_iterations = max_iterations;
+  o.seed = seed;
+  bae::ModeResult r;
+  bae::weakest_modes_host(nz, nt, L.data(), ld, linvT.data(), d.data(), n, k, o, pad_nonzero != 0, eigenvalues, modes, r);
+  out_u32[0] = r.iterations;
+  out_u32[1] = r.converged;
+  out_u32[2] = r.block;
+  *residual_max = r.residual_max;
   return 0;
 }
 

@@ -118,17 +118,10 @@ struct JointEntry {
   double v;
 };
 
-// Host restatement of k_joint_init (+ k_joint_rhs), k_joint_fsolve + k_joint_epilogue per level, k_joint_gram and
-// k_joint_combine, with the device's order of summation over chunks, slots and groups.  L: the factor in the
-// engine's lower storage (row-major, leading dimension ld >= 64 nt; only tiles of the pattern are read),
-// linvT: nt tiles L_JJ^-T (row-major), dsgn: 64 nt pivot signs.  The right-hand side B (64 nt x m) starts from
-// zero and takes the `ne` entries in their order (entries that share a place add up); every entry's tile row must
-// be one the plan was seeded with.  Y: reach x 64 x m_pad (the panels), cov = B^T S^-1 B: m x m row-major.
-inline void jointcov_host_rhs(const JointPlan& p, const double* L, size_t ld, const double* linvT, const double* dsgn,
-                              const JointEntry* ent, size_t ne, double* Y, double* cov) {
-  const uint32_t m = p.m, mp = p.m_pad, nr = (uint32_t)p.reach.size();
-  std::fill(Y, Y + p.y_count(), 0.0);
-  for (size_t i = 0; i < ne; ++i) Y[((size_t)p.pos[ent[i].row / 64] * 64 + ent[i].row % 64) * mp + ent[i].col] += ent[i].v;
+// The substitution alone (k_joint_fsolve + k_joint_epilogue per level): the panels Y hold the right-hand side and
+// take L^-1 of it.  Shared with the multi-RHS solve of factorsolve.h.
+inline void joint_forward_host(const JointPlan& p, const double* L, size_t ld, const double* linvT, double* Y) {
+  const uint32_t m = p.m, mp = p.m_pad;
   std::vector<double> part((size_t)64 * mp), T((size_t)64 * mp);
   for (uint32_t v = 0; v < p.levels(); ++v)
     for (uint32_t e = p.level_ptr[v]; e < p.level_ptr[v + 1]; ++e) {
@@ -157,6 +150,20 @@ inline void jointcov_host_rhs(const JointPlan& p, const double* L, size_t ld, co
           YI[(size_t)r * mp + x] = s;
         }
     }
+}
+
+// Host restatement of k_joint_init (+ k_joint_rhs), k_joint_fsolve + k_joint_epilogue per level, k_joint_gram and
+// k_joint_combine, with the device's order of summation over chunks, slots and groups.  L: the factor in the
+// engine's lower storage (row-major, leading dimension ld >= 64 nt; only tiles of the pattern are read),
+// linvT: nt tiles L_JJ^-T (row-major), dsgn: 64 nt pivot signs.  The right-hand side B (64 nt x m) starts from
+// zero and takes the `ne` entries in their order (entries that share a place add up); every entry's tile row must
+// be one the plan was seeded with.  Y: reach x 64 x m_pad (the panels), cov = B^T S^-1 B: m x m row-major.
+inline void jointcov_host_rhs(const JointPlan& p, const double* L, size_t ld, const double* linvT, const double* dsgn,
+                              const JointEntry* ent, size_t ne, double* Y, double* cov) {
+  const uint32_t m = p.m, mp = p.m_pad, nr = (uint32_t)p.reach.size();
+  std::fill(Y, Y + p.y_count(), 0.0);
+  for (size_t i = 0; i < ne; ++i) Y[((size_t)p.pos[ent[i].row / 64] * 64 + ent[i].row % 64) * mp + ent[i].col] += ent[i].v;
+  joint_forward_host(p, L, ld, linvT, Y);
   std::vector<double> acc((size_t)m * m, 0.0), grp((size_t)m * m);
   for (uint32_t g = 0; g < p.gram_groups; ++g) {
     std::fill(grp.begin(), grp.end(), 0.0);

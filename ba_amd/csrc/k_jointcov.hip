@@ -265,6 +265,23 @@ k_joint_lmdiag(const uint32_t* __restrict__ lm_ptr, const double* __restrict__ l
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
+// The substitution Y <- L^-1 Y over the plan's reach, two launches per level (engine.h; also the forward half of
+// the multi-RHS solve in k_factorsolve.hip).  The tables are the plan's chunks, rows, src and pos on the device.
+void joint_forward_launch(hipStream_t stream, const JointPlan& p, const uint4* d_chunks, const uint4* d_rows,
+                          const uint32_t* d_src, const uint32_t* d_pos, const double* A, uint32_t ld, const double* linvT,
+                          double* Y, double* slots) {
+  const uint32_t mp = p.m_pad, ncb = p.ncb;
+  for (uint32_t v = 0; v < p.levels(); ++v) {
+    const uint32_t c0 = p.chunk_level_ptr[v], c1 = p.chunk_level_ptr[v + 1];
+    if (c1 > c0)
+      hipLaunchKernelGGL(k_joint_fsolve, dim3(c1 - c0, ncb), dim3(256), 0, stream, d_chunks + c0, d_src, d_pos, A, ld,
+                         (const double*)Y, mp, slots);
+    const uint32_t r0 = p.level_ptr[v], r1 = p.level_ptr[v + 1];
+    hipLaunchKernelGGL(k_joint_epilogue, dim3(r1 - r0, ncb), dim3(256), 0, stream, d_rows + r0, d_pos, linvT, Y, mp,
+                       (const double*)slots);
+  }
+}
+
 // sel: the requested rows of S in the engine's (factorised) numbering (unit columns), lms: the requested landmarks
 // (active, checked by the caller), whose LM columns each follow those of sel; out: M x M on the host
 int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<uint32_t>& lms, double* out) {
@@ -356,15 +373,8 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<
     else hipLaunchKernelGGL(k_joint_rhs<3>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, Ms, d_idx + o_pos, e->jc_Y.p, mp);
     (void)ev.record(4, e->stream);
   }
-  for (uint32_t v = 0; v < p.levels(); ++v) {
-    const uint32_t c0 = p.chunk_level_ptr[v], c1 = p.chunk_level_ptr[v + 1];
-    if (c1 > c0)
-      hipLaunchKernelGGL(k_joint_fsolve, dim3(c1 - c0, ncb), dim3(256), 0, e->stream, d_chunks + c0, d_idx + o_src,
-                         d_idx + o_pos, (const double*)e->A.p, st.ld, (const double*)e->jc_Y.p, mp, e->jc_slots.p);
-    const uint32_t r0 = p.level_ptr[v], r1 = p.level_ptr[v + 1];
-    hipLaunchKernelGGL(k_joint_epilogue, dim3(r1 - r0, ncb), dim3(256), 0, e->stream, d_rows + r0, d_idx + o_pos, linvT,
-                       e->jc_Y.p, mp, (const double*)e->jc_slots.p);
-  }
+  joint_forward_launch(e->stream, p, d_chunks, d_rows, d_idx + o_src, d_idx + o_pos, e->A.p, st.ld, linvT, e->jc_Y.p,
+                       e->jc_slots.p);
   (void)ev.record(1, e->stream);
   if (p.gram_groups)
     hipLaunchKernelGGL(k_joint_gram, dim3(p.gram_groups, ntl), dim3(256), 0, e->stream, (const double*)e->jc_Y.p, mp,

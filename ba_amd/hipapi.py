@@ -133,6 +133,26 @@ class PosePoseLeverageStats(C.Structure):
 JOINT_MAX_COLUMNS = 512  # BA_HIP_JOINT_MAX_COLUMNS
 
 
+class FactorSolveStats(C.Structure):
+    _fields_ = [("forward_ms", C.c_double), ("backward_ms", C.c_double), ("workspace_bytes", C.c_double),
+                ("tile_products", C.c_uint64), ("columns", C.c_uint32), ("tiles", C.c_uint32),
+                ("forward_levels", C.c_uint32), ("backward_levels", C.c_uint32)]
+
+
+FACTOR_SOLVE_MAX_COLUMNS = 512  # BA_HIP_FACTOR_SOLVE_MAX_COLUMNS
+
+
+class ModeOptions(C.Structure):
+    _fields_ = [("tolerance", C.c_double), ("max_iterations", C.c_uint32), ("seed", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class ModeStats(C.Structure):
+    _fields_ = [("solve_ms", C.c_double), ("ortho_ms", C.c_double), ("residual_max", C.c_double),
+                ("workspace_bytes", C.c_double), ("iterations", C.c_uint32), ("converged", C.c_uint32),
+                ("block", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MarginalizationStats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("blanket_poses", "absorbed_projection", "absorbed_unary", "absorbed_binary",
                                           "absorbed_inertial", "absorbed_priors", "dropped_projection", "reserved")] + \
@@ -193,6 +213,8 @@ SYMBOLS = [
     "ba_hip_get_projection_leverages", "ba_hip_get_leverage_stats", "ba_hip_device_bytes_live",
     "ba_hip_get_pose_pose_leverages", "ba_hip_get_pose_pose_leverage_stats", "ba_hip_num_pose_pose_residuals",
     "ba_hip_get_joint_state_marginals", "ba_hip_get_joint_state_stats",
+    "ba_hip_factor_solve", "ba_hip_get_factor_solve_stats", "ba_hip_tile_factor_solve",
+    "ba_hip_get_weakest_modes", "ba_hip_get_mode_stats",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -533,6 +555,43 @@ class Engine:
         self._chk(self.L.ba_hip_get_joint_marginal_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in JointMarginalStats._fields_ if k != "reserved"}
 
+    # ---- solves with the kept factor: X = S^-1 B for the caller's right-hand sides ----
+    def factor_solve(self, B):
+        """X = S^-1 B with the factor the last direct solve_gn left: B is (n,) or (n, m), n = pose + calibration
+        parameters, rows in the order of get_delta_gn; X has B's shape."""
+        B = _d(B)
+        n = self.num_pose_params() + self.num_calib_params()
+        if B.ndim not in (1, 2) or B.shape[0] != n:
+            raise ValueError("B must have %d rows" % n)
+        m = 1 if B.ndim == 1 else B.shape[1]
+        X = np.empty_like(B)
+        self._chk(self.L.ba_hip_factor_solve(self.h, m, _p(B, dp), _p(X, dp)))
+        return X
+
+    def factor_solve_stats(self):
+        st = FactorSolveStats()
+        self._chk(self.L.ba_hip_get_factor_solve_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in FactorSolveStats._fields_}
+
+    # ---- weakest modes: the eigenpairs of S of smallest magnitude, from the kept factor ----
+    def weakest_modes(self, k, tolerance=None, max_iterations=None, seed=None):
+        """(eigenvalues (k,), modes (k, n)): the k eigenpairs of the factorised S of smallest magnitude, ascending in
+        magnitude; each mode is a unit vector over the rows of get_delta_gn.  None takes the engine's defaults
+        (1e-8, 50 iterations, seed 1); when the cap is reached the last Ritz pairs come back and mode_stats() shows
+        converged < k."""
+        n = self.num_pose_params() + self.num_calib_params()
+        lam, modes = np.zeros(int(k)), np.zeros((int(k), n))
+        o = None
+        if tolerance is not None or max_iterations is not None or seed is not None:
+            o = C.byref(ModeOptions(float(tolerance or 0.0), int(max_iterations or 0), int(seed or 0)))
+        self._chk(self.L.ba_hip_get_weakest_modes(self.h, int(k), o, _p(lam, dp), _p(modes, dp)))
+        return lam, modes
+
+    def mode_stats(self):
+        st = ModeStats()
+        self._chk(self.L.ba_hip_get_mode_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in ModeStats._fields_ if k != "reserved"}
+
     # ---- joint covariance of poses, calibration and landmarks (the cross blocks included) ----
     def joint_state_marginals(self, pose_ids, lm_ids, include_calibration=False):
         """(M, M) block of the inverse of the full system over the poses `pose_ids`, the calibration rows when asked
@@ -831,6 +890,24 @@ class Engine:
         rc = self._chk(self.L.ba_hip_tile_solve(self.h, n, _p(a, dp), _p(b, dp), _p(tm, u8p), _p(x, dp), _p(nzl, u8p),
                                                 _p(st, dp), _p(li, dp), _p(sg, dp)), positive_ok=True)
         return (x, rc, nzl, st, li, sg) if keep_factor else (x, rc, nzl)
+
+    def tile_factor_solve(self, a_lower, B, tile_map=None):
+        """The factorisation of tile_solve on (a_lower, tile_map), then X = A^-1 B (n x m) by the substitution of
+        factor_solve on the factor it leaves: (X, rc)."""
+        a, B = _d(a_lower), _d(B)
+        n = a.shape[0]
+        nt = max((n + 63) // 64, 1)
+        tm = None
+        if tile_map is not None:
+            tm = np.ascontiguousarray(tile_map, dtype=np.uint8)
+            if tm.shape != (nt, nt):
+                raise ValueError("tile_map must be %d x %d" % (nt, nt))
+        if B.ndim != 2 or B.shape[0] != n:
+            raise ValueError("B must be %d x m" % n)
+        X = np.zeros_like(B)
+        rc = self._chk(self.L.ba_hip_tile_factor_solve(self.h, n, _p(a, dp), _p(tm, u8p), B.shape[1], _p(B, dp), _p(X, dp)),
+                       positive_ok=True)
+        return X, rc
 
     def select_kth(self, values, k):
         v = _d(values)

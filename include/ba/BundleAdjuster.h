@@ -521,6 +521,47 @@ class BundleAdjuster {
     }
     return true;
   }
+  // X = S^-1 B with the factor the last Solve() left (extension; include/ba_hip.h ba_hip_factor_solve, DESIGN.md
+  // section 19): B and X are n x m, n = active poses * kPoseDim + kCalibDim, m <= BA_HIP_FACTOR_SOLVE_MAX_COLUMNS.
+  // Row r belongs to the (r / kPoseDim)-th active pose in the order the poses were added, parameter r % kPoseDim
+  // of its tangent step (translation, rotation, then velocity and biases); the calibration rows come last.  false,
+  // reported through Check(), and a 0 x 0 X when unavailable (no solve yet, the PCG or the distributed solve, a
+  // wrong row count, no or too many columns).
+  bool SolveWithFactor(const MatrixXt& B, MatrixXt& X) {
+    const uint32_t n = engine_ ? ba_hip_num_pose_params(engine_) + ba_hip_num_calib_params(engine_) : 0;
+    if (!engine_ || (uint32_t)B.rows() != n) {
+      std::cerr << "ba::BundleAdjuster::SolveWithFactor: B must have " << n << " rows" << std::endl;
+      X = MatX();
+      return false;
+    }
+    X = MatX(B.rows(), B.cols());
+    if (!Check(ba_hip_factor_solve(engine_, (uint32_t)B.cols(), B.data(), X.data()), "ba_hip_factor_solve")) {
+      X = MatX();
+      return false;
+    }
+    return true;
+  }
+  // The k eigenpairs of smallest magnitude of the reduced system of the last Solve() (extension; include/ba_hip.h
+  // ba_hip_get_weakest_modes): the weakly determined directions - a free scale, yaw about gravity, a bias.
+  // eigenvalues: k values by ascending magnitude (negative with an indefinite S); modes: k x n, row i the unit
+  // vector of mode i over the rows of SolveWithFactor (entry r: active pose r / kPoseDim, parameter r % kPoseDim;
+  // calibration last).  GetModeStats tells whether the k pairs converged.  false, reported through Check(), when
+  // unavailable (as SolveWithFactor; k == 0 or k > min(32, n)).
+  bool GetWeakestModes(uint32_t k, std::vector<Scalar>& eigenvalues, MatrixXt& modes) {
+    const uint32_t n = engine_ ? ba_hip_num_pose_params(engine_) + ba_hip_num_calib_params(engine_) : 0;
+    std::vector<double> ev(k, 0.0);
+    modes = MatX((int)k, (int)n);
+    if (!engine_ || !Check(ba_hip_get_weakest_modes(engine_, k, nullptr, ev.data(), modes.data()), "ba_hip_get_weakest_modes")) {
+      eigenvalues.clear();
+      modes = MatX();
+      return false;
+    }
+    eigenvalues.assign(ev.begin(), ev.end());
+    return true;
+  }
+  bool GetModeStats(ba_hip_mode_stats* out) {
+    return engine_ && out && Check(ba_hip_get_mode_stats(engine_, out), "ba_hip_get_mode_stats");
+  }
   // Joint covariance of the poses `pose_ids`, the calibration rows (with include_calibration) and the landmarks
   // `landmark_ids`, columns in that order (extension; include/ba_hip.h ba_hip_get_joint_state_marginals, DESIGN.md
   // section 17): the block of the inverse of the full system, pose-landmark and landmark-landmark cross blocks

@@ -156,6 +156,14 @@ uint32_t ba_adjuster_get_joint_pose_covariance(ba_adjuster* a, uint32_t n, const
 uint32_t ba_adjuster_get_joint_covariance(ba_adjuster* a, uint32_t n_poses, const uint32_t* pose_ids, int include_calibration,
                                           uint32_t n_landmarks, const uint32_t* landmark_ids, double* cov);
 int ba_adjuster_get_pose_landmark_cross_covariance(ba_adjuster* a, uint32_t pose_id, uint32_t landmark_id, double* cov);
+/* SolveWithFactor (extension): X = S^-1 B with the factor of the last solve; B and X are n x m row-major, n = the
+ * pose and calibration parameters of the reduced system (rows as ba_hip_get_delta_gn).  GetWeakestModes: the k
+ * eigenpairs of smallest magnitude of that system, eigenvalues (k) and modes (k x n row-major, unit vectors); n must
+ * be the same row count.  GetModeStats: the figures of the last GetWeakestModes.  All return 0, or 1 when
+ * unavailable (the summary's result then reads SolverError). */
+int ba_adjuster_solve_with_factor(ba_adjuster* a, uint32_t n, uint32_t m, const double* B, double* X);
+int ba_adjuster_get_weakest_modes(ba_adjuster* a, uint32_t k, uint32_t n, double* eigenvalues, double* modes);
+int ba_adjuster_get_mode_stats(ba_adjuster* a, ba_hip_mode_stats* out);
 /* Marginalize / AddDensePrior (extension; include/ba_hip.h).  ba_adjuster_marginalize:
  * after a solve, eliminates the poses and landmarks into a dense prior kept by the adjuster; returns 0 and the
  * blanket size, or 1 when refused.  ba_adjuster_get_marginalization reads it: |B| pose ids, |B| x 16 states,

@@ -640,6 +640,70 @@ int ba_hip_get_joint_marginals(ba_hip_engine* e, uint32_t n, const uint32_t* pos
  * ba_hip_get_joint_state_marginals (zeros before the first). */
 int ba_hip_get_joint_marginal_stats(ba_hip_engine* e, ba_hip_joint_marginal_stats* out);
 
+/* ---- solves with the kept factor: X = S^-1 B for a caller's right-hand sides ----------
+ * S is the reduced system that the last direct ba_hip_solve_gn factorised (S = L D L^T, tile-sparse, left on the
+ * device); B holds m columns of the caller's own.  Both passes of the substitution run over every tile row, by
+ * levels of the factor's pattern, on the matrix cores.
+ *   - n = ba_hip_num_pose_params + ba_hip_num_calib_params.  B and X are n x m, row-major, on the host; their rows
+ *     are in the order and coordinates of ba_hip_get_delta_gn (natural pose order whatever the pose ordering, the
+ *     calibration rows last).  X may be B.
+ *   - Preconditions of ba_hip_get_joint_marginals: a direct solve since the last linearisation, not the PCG
+ *     solver, not the distributed solve, no stand-alone solve since.  Replicated sharded engines are served.
+ *   - Refused with a message: m == 0, m > BA_HIP_FACTOR_SOLVE_MAX_COLUMNS, NULL arguments.
+ *   - Reads the factor only: the Sigma store, its validity and the statistics of the other getters stay untouched.
+ *     No atomics: two calls give the same bits.
+ *   - The workspace is allocated by the first call, grown on demand and freed by ba_hip_release_marginals. */
+#define BA_HIP_FACTOR_SOLVE_MAX_COLUMNS 512
+typedef struct {
+  double forward_ms;        /* Y = L^-1 B */
+  double backward_ms;       /* X = L^-T D Y */
+  double workspace_bytes;   /* device bytes the solve holds */
+  uint64_t tile_products;   /* 64 x 64 x 64 products of both passes */
+  uint32_t columns;         /* m */
+  uint32_t tiles;           /* tile rows of the factor */
+  uint32_t forward_levels;  /* launch pairs of the forward pass */
+  uint32_t backward_levels; /* ... of the backward pass */
+} ba_hip_factor_solve_stats;
+int ba_hip_factor_solve(ba_hip_engine* e, uint32_t m, const double* B, double* X);
+/* The figures of the last successful ba_hip_factor_solve or ba_hip_tile_factor_solve (zeros before the first). */
+int ba_hip_get_factor_solve_stats(ba_hip_engine* e, ba_hip_factor_solve_stats* out);
+
+/* ---- weakest modes: the eigenpairs of S of smallest magnitude ---------------------------
+ * Which directions of the problem are weakly determined (a free scale, yaw about gravity, a bias ...): the k
+ * eigenpairs of the S that the last direct ba_hip_solve_gn factorised whose eigenvalues are smallest in magnitude,
+ * by block inverse iteration with Rayleigh-Ritz on min(64, n) vectors.  Only S^-1 is needed (ba_hip_factor_solve on
+ * panels that stay on the device), so the in-place factorisation does not stand in the way.
+ *   - 1 <= k <= min(32, n).  eigenvalues: k values by ascending magnitude; with negative pivots S is indefinite and
+ *     the sign is reported.  modes: k x n row-major, each row a unit vector in the rows and coordinates of
+ *     ba_hip_factor_solve (6 or more consecutive entries per active pose in natural order, calibration last).
+ *   - Options: NULL, or a zero field, takes the default: tolerance 1e-8, max_iterations 50, seed 1.  Pair i has
+ *     converged when |S^-1 v_i - theta_i v_i| <= tolerance |theta_i|, theta_i = 1 / lambda_i.
+ *   - Returns 0 also when the cap is reached with converged < k (ba_hip_get_mode_stats): eigenvalues and modes are
+ *     then the last Ritz pairs, not converged ones.
+ *   - The start block is counter based (splitmix64 of seed, row and column, stated in factorsolve.h), no atomics:
+ *     a second call returns the same bits.
+ *   - Preconditions, refusals and workspace as for ba_hip_factor_solve; besides k == 0, k > min(32, n), NULL. */
+typedef struct {
+  double tolerance;
+  uint32_t max_iterations;
+  uint32_t seed;
+  uint32_t reserved[3];
+} ba_hip_mode_options;
+typedef struct {
+  double solve_ms;          /* applying S^-1, all iterations (host clock around the drained stream) */
+  double ortho_ms;          /* orthonormalisation, Gram products and host eigenproblems included */
+  double residual_max;      /* largest |S^-1 v - theta v| / |theta| over the k pairs at return */
+  double workspace_bytes;
+  uint32_t iterations;
+  uint32_t converged;       /* pairs among the k that met the tolerance */
+  uint32_t block;           /* vectors iterated: min(64, n) */
+  uint32_t reserved;
+} ba_hip_mode_stats;
+int ba_hip_get_weakest_modes(ba_hip_engine* e, uint32_t k, const ba_hip_mode_options* o, double* eigenvalues,
+                             double* modes);
+/* The figures of the last successful ba_hip_get_weakest_modes (zeros before the first). */
+int ba_hip_get_mode_stats(ba_hip_engine* e, ba_hip_mode_stats* out);
+
 /* ---- joint covariance of a mixed set of poses, calibration and landmarks (cross blocks) ----
  * The M x M block of the inverse of the full system [[U, W], [W^T, V]] over the requested parameters,
  * M = n_poses D + (include_calibration ? K : 0) + n_landmarks LmSize; columns in that order: the poses in the
@@ -824,6 +888,11 @@ int ba_hip_dense_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, cons
  * ba_hip_solve_gn is gone afterwards: the marginal covariances are refused until the next ba_hip_solve_gn. */
 int ba_hip_tile_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const double* b, const uint8_t* tile_map,
                       double* x, uint8_t* nz_factor, double* factor, double* linvT, double* dsgn);
+/* Test tap of ba_hip_factor_solve: the factorisation of ba_hip_tile_solve on (a_lower, tile_map), then X = A^-1 B
+ * (n x m row-major, host; m <= BA_HIP_FACTOR_SOLVE_MAX_COLUMNS) by the substitution kernels of ba_hip_factor_solve
+ * on the factor it leaves.  Returns and lifecycle effects as ba_hip_tile_solve. */
+int ba_hip_tile_factor_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const uint8_t* tile_map, uint32_t m,
+                             const double* B, double* X);
 /* exact k-th smallest (0-based) of n non-negative doubles — the device selection behind
  * the Huber sigma (std::nth_element at floor(N/2), BundleAdjuster.cpp:1356-1358) */
 int ba_hip_select_kth(ba_hip_engine* e, uint32_t n, const double* values, uint32_t k, double* out);
