@@ -23,6 +23,9 @@
 //                                           iterations and the true residual of every Gauss-Newton step
 //   visual_ba_demo --pcg [tol] --pcg-coarse G   ... with the two-level preconditioner over aggregates of G poses
 //                                           (Options::pcg_coarse_aggregate); prints the coarse space of every step
+//   visual_ba_demo --pcg [tol] --joint-cov A,B   after the solve: the joint covariance of the poses A and B without a
+//                                           factor (GetJointPoseCovarianceIterative: the panel PCG on the twelve unit
+//                                           columns), printed as a 12 x 12 block with the passes and the time
 //   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
 //                                           GetLandmarkCovariance: selected inverse of the reduced system), then
@@ -50,7 +53,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0, weakest_modes = 0; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0, weakest_modes = 0; int joint_a = -1, joint_b = -1; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -298,6 +301,23 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
                 mixed_ms);
     ok = ok && std::isfinite(c(0, 0)) && c(0, 0) > 0 && sl[sl.size() / 2] > 0 && std::isfinite(corr) && corr <= 1.0 + 1e-9;
   }
+  if (shard.joint_a >= 0) {
+    ba::MatX joint;
+    ba_hip_pcg_panel_stats ps;
+    if (!adjuster.GetJointPoseCovarianceIterative({(uint32_t)shard.joint_a, (uint32_t)shard.joint_b}, joint, shard.pcg_tol) ||
+        joint.rows() != 12 || !adjuster.GetPcgPanelStats(&ps)) {
+      std::printf("iterative joint covariance unavailable (it needs --pcg and two different active poses)\n");
+      return 2;
+    }
+    std::printf("joint covariance of poses %d and %d by the panel PCG: %u columns, %u passes, %u converged, largest residual %.2e, "
+                "%.3f ms\n", shard.joint_a, shard.joint_b, ps.columns, ps.passes, ps.converged, ps.max_rel_residual_true, ps.solve_ms);
+    for (int i = 0; i < 12; ++i) {
+      for (int j = 0; j < 12; ++j) std::printf(" % .3e", joint(i, j));
+      std::printf("\n");
+    }
+    for (int i = 0; i < 12; ++i) ok = ok && std::isfinite(joint(i, i)) && joint(i, i) > 0;
+    ok = ok && ps.converged == 12;
+  }
   if (shard.weakest_modes) {
     std::vector<double> ev;
     ba::MatX modes;
@@ -374,6 +394,12 @@ int main(int argc, char** argv) {
     if (i + 1 >= argc) break;
     if (std::strcmp(argv[i], "--weakest-modes") == 0) shard.weakest_modes = (unsigned)std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--pcg-coarse") == 0) shard.pcg_coarse = (unsigned)std::atoi(argv[i + 1]);
+    else if (std::strcmp(argv[i], "--joint-cov") == 0) {
+      if (std::sscanf(argv[i + 1], "%d,%d", &shard.joint_a, &shard.joint_b) != 2 || shard.joint_a < 0 || shard.joint_b < 0) {
+        std::printf("bad --joint-cov (two pose ids: A,B)\n");
+        return 3;
+      }
+    }
     else if (std::strcmp(argv[i], "--ranks") == 0) shard.ranks = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--rank") == 0) shard.rank = std::atoi(argv[i + 1]);
     else if (std::strcmp(argv[i], "--device") == 0) shard.device = std::atoi(argv[i + 1]);

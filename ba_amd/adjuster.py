@@ -75,6 +75,7 @@ SYMBOLS = [
     "ba_adjuster_get_joint_pose_covariance",
     "ba_adjuster_get_joint_covariance", "ba_adjuster_get_pose_landmark_cross_covariance",
     "ba_adjuster_solve_with_factor", "ba_adjuster_get_weakest_modes", "ba_adjuster_get_mode_stats",
+    "ba_adjuster_solve_with_pcg", "ba_adjuster_get_joint_pose_covariance_iterative", "ba_adjuster_get_pcg_panel_stats",
     "ba_adjuster_get_pose_pose_leverages", "ba_adjuster_get_pose_pose_leverage",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
@@ -477,6 +478,39 @@ class BundleAdjuster:
         if self.L.ba_adjuster_solve_with_factor(self.h, n, B.shape[1], B.ctypes.data_as(dp), X.ctypes.data_as(dp)):
             raise RuntimeError("solve with the factor unavailable (see stderr)")
         return X
+
+    def SolveWithPcg(self, B, tol=0.0):
+        """SolveWithPcg: X = S^-1 B without a factor, after a Solve() with reduced_solver = Pcg; B as in
+        SolveWithFactor, tol the relative residual per column (0: Options.pcg_tolerance); raises when unavailable."""
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        n = self._reduced_rows()
+        if B.ndim != 2 or B.shape[0] != n:
+            raise RuntimeError("SolveWithPcg: B must be (%d, m)" % n)
+        X = np.zeros_like(B)
+        dp = C.POINTER(C.c_double)
+        if self.L.ba_adjuster_solve_with_pcg(self.h, n, B.shape[1], B.ctypes.data_as(dp), C.c_double(tol), X.ctypes.data_as(dp)):
+            raise RuntimeError("solve with the panel PCG unavailable (see stderr)")
+        return X
+
+    def GetJointPoseCovarianceIterative(self, ids, tol=0.0, include_calibration=False):
+        """GetJointPoseCovarianceIterative: GetJointPoseCovariance after a Solve() with reduced_solver = Pcg."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32).ravel()
+        k = self.L.ba_hip_num_calib_params(self.engine().h) if include_calibration else 0
+        m = len(ids) * self.pose_dim + k
+        c = np.zeros((m, m))
+        self.L.ba_adjuster_get_joint_pose_covariance_iterative.restype = C.c_uint32
+        got = self.L.ba_adjuster_get_joint_pose_covariance_iterative(
+            self.h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_uint32)), int(bool(include_calibration)), C.c_double(tol),
+            c.ctypes.data_as(C.POINTER(C.c_double)))
+        if got != m or m == 0:
+            raise RuntimeError("iterative joint pose covariance unavailable (see stderr)")
+        return c
+
+    def GetPcgPanelStats(self):
+        st = hipapi.PcgPanelStats()
+        if self.L.ba_adjuster_get_pcg_panel_stats(self.h, C.byref(st)):
+            return None
+        return {k: getattr(st, k) for k, _ in hipapi.PcgPanelStats._fields_}
 
     def GetWeakestModes(self, k):
         """GetWeakestModes: (eigenvalues (k,), modes (k, n)) of smallest magnitude of the reduced system of the last

@@ -56,6 +56,9 @@ struct Iface {
                                           const uint32_t* lms, double* out) = 0;
   virtual int pose_landmark_cross_covariance(uint32_t pose_id, uint32_t landmark_id, double* out) = 0;
   virtual int solve_with_factor(uint32_t n, uint32_t m, const double* B, double* X) = 0;
+  virtual int solve_with_pcg(uint32_t n, uint32_t m, const double* B, double tol, double* X) = 0;
+  virtual uint32_t joint_covariance_iterative(uint32_t n, const uint32_t* ids, int include_calibration, double tol, double* out) = 0;
+  virtual int pcg_panel_stats(ba_hip_pcg_panel_stats* out) = 0;
   virtual int weakest_modes(uint32_t k, uint32_t n, double* eigenvalues, double* modes) = 0;
   virtual int mode_stats(ba_hip_mode_stats* out) = 0;
   virtual int pose_pose_leverages(int kind, uint32_t n, const uint32_t* ids, double* cov, double* info, double* lev) = 0;
@@ -291,6 +294,20 @@ struct Impl : Iface {
     std::copy(x.data(), x.data() + (size_t)n * m, X);
     return 0;
   }
+  int solve_with_pcg(uint32_t n, uint32_t m, const double* B, double tol, double* X) override {
+    ba::MatX b((int)n, (int)m), x;
+    std::copy(B, B + (size_t)n * m, b.data());
+    if (!ba.SolveWithPcg(b, x, tol)) return 1;
+    std::copy(x.data(), x.data() + (size_t)n * m, X);
+    return 0;
+  }
+  uint32_t joint_covariance_iterative(uint32_t n, const uint32_t* ids, int include_calibration, double tol, double* out) override {
+    ba::MatX m;
+    if (!ba.GetJointPoseCovarianceIterative(std::vector<uint32_t>(ids, ids + n), m, tol, include_calibration != 0)) return 0;
+    for (int i = 0; i < m.rows() * m.cols(); ++i) out[i] = m.data()[i];
+    return (uint32_t)m.rows();
+  }
+  int pcg_panel_stats(ba_hip_pcg_panel_stats* out) override { return ba.GetPcgPanelStats(out) ? 0 : 1; }
   int weakest_modes(uint32_t k, uint32_t n, double* eigenvalues, double* modes) override {
     std::vector<double> ev;
     ba::MatX m;
@@ -492,6 +509,19 @@ int ba_adjuster_get_pose_landmark_cross_covariance(ba_adjuster* a, uint32_t pose
 int ba_adjuster_solve_with_factor(ba_adjuster* a, uint32_t n, uint32_t m, const double* B, double* X) {
   if (!B || !X) return 1;
   return a->p->solve_with_factor(n, m, B, X);
+}
+int ba_adjuster_solve_with_pcg(ba_adjuster* a, uint32_t n, uint32_t m, const double* B, double tol, double* X) {
+  if (!B || !X) return 1;
+  return a->p->solve_with_pcg(n, m, B, tol, X);
+}
+uint32_t ba_adjuster_get_joint_pose_covariance_iterative(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids,
+                                                         int include_calibration, double tol, double* cov) {
+  if ((n && !pose_ids) || !cov) return 0;
+  return a->p->joint_covariance_iterative(n, pose_ids, include_calibration, tol, cov);
+}
+int ba_adjuster_get_pcg_panel_stats(ba_adjuster* a, ba_hip_pcg_panel_stats* out) {
+  if (!out) return 1;
+  return a->p->pcg_panel_stats(out);
 }
 int ba_adjuster_get_weakest_modes(ba_adjuster* a, uint32_t k, uint32_t n, double* eigenvalues, double* modes) {
   if (!eigenvalues || !modes) return 1;

@@ -327,6 +327,23 @@ struct Engine {
     DBuf<double> C, Lc, Wc, Cinv, rc, yc, ryc_part;
     uint32_t coarse_key = 0, coarse_nc = 0, coarse_ncp = 0;   // aggregate the tables were uploaded for; size of the last C
   } pcg;
+  // panel PCG (ba_hip_pcg_panel_solve_system, k_pcg_panel.hip, pcg_panel.h): a work space of its own — the tables
+  // and vectors of `pcg` belong to the next ba_hip_solve_gn and are not touched — allocated by the first call, grown
+  // on demand; the statistics and the per-column record of the last call
+  struct PcgPanelWork {
+    DBuf<uint32_t> idx;       // chunks | src | blk | blocks | chunk_ptr | rowmap
+    DBuf<uint8_t> nz;
+    DBuf<double> stage, B, X, P, Z, Q, R, slots, minv, parts, colv;
+    DBuf<uint32_t> colu;      // act | run | flags (two copies)
+    DBuf<PcgState> state;     // two copies of m_pad states
+    DBuf<int32_t> status;
+    size_t bytes() const {
+      return idx.bytes() + nz.bytes() + stage.bytes() + B.bytes() + X.bytes() + P.bytes() + Z.bytes() + Q.bytes() + R.bytes() +
+             slots.bytes() + minv.bytes() + parts.bytes() + colv.bytes() + colu.bytes() + state.bytes() + status.bytes();
+    }
+  } pcgp;
+  ba_hip_pcg_panel_stats pcgp_stats = {};
+  std::vector<PcgState> pcgp_cols;
 
   // optional per-kernel timing (ba_hip_set_profiling)
   bool profiling = false;
@@ -529,6 +546,14 @@ int pcg_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const
 // launches of a pass on the residual r
 int pcg_coarse_setup_device(Engine* e, const double* dA, uint32_t ld, const PcgPlan& plan);
 void pcg_coarse_apply_device(Engine* e, const PcgPlan& plan, const PcgState* st, const double* r);
+// panel PCG on the system in dA (k_pcg_panel.hip): X = S^-1 B for the first n unknowns of the padded system, m
+// columns.  B, X: n x m row-major on the host, rows in the caller's order; rowmap (ld entries): the caller's row of
+// every matrix row, kPcgNone for padding rows.  Fills e->pcgp_stats and e->pcgp_cols, touches no validity flag;
+// *status != 0 when some column broke down
+int pcg_panel_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld, const PcgPlan& plan,
+                           const std::vector<uint8_t>& nz, const std::vector<uint32_t>& blk, const std::vector<uint32_t>& blocks,
+                           const uint32_t* rowmap, uint32_t m, const double* B, double* X, const ba_hip_pcg_options& opt,
+                           int* status);
 int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& lmask, double tol, double* dev_ms);
 
 }  // namespace bae

@@ -2098,6 +2098,118 @@ int ba_hip_get_pcg_coarse(ba_hip_engine* h, uint32_t nc, double* C, double* Cinv
   return 0;
 }
 
+// ---- panel PCG (k_pcg_panel.hip): S^-1 on a block of columns after a PCG solve, A holds S ----
+// The refusals the two entry points share; `who` starts the messages.
+static int pcg_panel_ready(Engine* e, const char* who, const ba_hip_pcg_options* o) {
+  const std::string m = std::string(who) + ": ";
+  if (e->pcg_refused() || dist_solve_enabled(e))
+    return e->fail_msg((m + "not available on a sharded engine (all-reduce hook, collectives hook or communicator set)").c_str());
+  if (!e->held.finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
+  if (!e->held.pcg_solved) {
+    if (e->held.factored)
+      return e->fail_msg((m + "the last ba_hip_solve_gn ran the direct solver, A holds its factor and not S; panel solves need "
+                              "a PCG solve (ba_hip_set_reduced_solver, BA_HIP_SOLVER_PCG); ba_hip_factor_solve serves the factor").c_str());
+    if (e->held.pcg_last)
+      return e->fail_msg((m + "the system was re-linearised since the PCG solve of the last ba_hip_solve_gn").c_str());
+    return e->fail_msg((m + "needs a PCG solve by the last ba_hip_solve_gn (BA_HIP_SOLVER_PCG; none yet, or the system was "
+                            "re-linearised since)").c_str());
+  }
+  if (!o) return e->fail_msg((m + "NULL argument").c_str());
+  if (o->coarse_aggregate)
+    return e->fail_msg((m + "coarse_aggregate must be 0: the coarse space is not available in panel solves").c_str());
+  if (!(o->rel_tolerance > 0.0) || !(o->rel_tolerance < 1.0)) return e->fail_msg((m + "rel_tolerance must lie in (0, 1)").c_str());
+  if (e->pcg_plan.nt != e->st.ld / 64 || e->pcg_blk.size() != (size_t)2 * e->st.ld)
+    return e->fail_msg((m + "the plan of the last PCG solve does not match the system").c_str());
+  return 0;
+}
+static int pcg_panel_args(Engine* e, const char* who, uint32_t m, const void* a, const void* b) {
+  const std::string w = std::string(who) + ": ";
+  if (m == 0) return e->fail_msg((w + "no columns requested (m == 0)").c_str());
+  if (m > BA_HIP_PCG_PANEL_MAX_COLUMNS)
+    return e->fail_msg((w + std::to_string(m) + " columns requested, the limit is BA_HIP_PCG_PANEL_MAX_COLUMNS (" +
+                        std::to_string(BA_HIP_PCG_PANEL_MAX_COLUMNS) + ")").c_str());
+  if (!a || !b) return e->fail_msg((w + "NULL argument").c_str());
+  return 0;
+}
+// rows in the caller's (natural) order, as ba_hip_factor_solve
+static int pcg_panel_on_S(Engine* e, uint32_t m, const double* B, double* X, const ba_hip_pcg_options& o) {
+  BAE_HIP(hipSetDevice(e->device));
+  std::vector<uint32_t> rowmap(e->st.ld, kPcgNone);
+  for (uint32_t r = 0; r < e->st.n; ++r) rowmap[int_row(e, r)] = r;
+  int status = 0;
+  int rc = pcg_panel_solve_device(e, e->A.p, e->st.n, e->st.ld, e->pcg_plan, e->nzS_host, e->pcg_blk, e->pcg_blocks, rowmap.data(),
+                                  m, B, X, o, &status);
+  if (rc) return rc;
+  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
+}
+int ba_hip_pcg_panel_solve_system(ba_hip_engine* h, uint32_t m, const double* B, double* X, const ba_hip_pcg_options* o) {
+  ENG(h);
+  static const char* what = "ba_hip_pcg_panel_solve_system";
+  int rc;
+  if ((rc = pcg_panel_ready(e, what, o))) return rc;
+  if ((rc = pcg_panel_args(e, what, m, B, X))) return rc;
+  return pcg_panel_on_S(e, m, B, X, *o);
+}
+int ba_hip_get_joint_marginals_pcg(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,
+                                   const ba_hip_pcg_options* o, double* out) {
+  ENG(h);
+  static const char* what = "ba_hip_get_joint_marginals_pcg";
+  const std::string msg = std::string(what) + ": ";
+  int rc;
+  if ((rc = pcg_panel_ready(e, what, o))) return rc;
+  if ((n && !pose_ids) || !out) return e->fail_msg((msg + "NULL argument").c_str());
+  const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K;
+  if (include_calibration && !K)
+    return e->fail_msg((msg + "include_calibration without calibration unknowns (ba_hip_set_calibration)").c_str());
+  const uint64_t M = (uint64_t)n * D + (include_calibration ? K : 0);
+  if ((rc = pcg_panel_args(e, what, (uint32_t)std::min<uint64_t>(M, 0xffffffffu), out, out))) return rc;
+  std::vector<uint32_t> seen(pose_ids, pose_ids + n);
+  std::sort(seen.begin(), seen.end());
+  for (uint32_t i = 0; i + 1 < n; ++i)
+    if (seen[i] == seen[i + 1])
+      return e->fail_msg((msg + "pose " + std::to_string(seen[i]) + " is repeated (the joint block would be singular)").c_str());
+  std::vector<uint32_t> nat_of_int(e->st.ld, kPcgNone), sel;   // the selected rows in the caller's numbering
+  for (uint32_t r = 0; r < e->st.n; ++r) nat_of_int[int_row(e, r)] = r;
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t r;
+    if ((rc = pose_row(e, pose_ids[i], &r, what))) return rc;
+    for (uint32_t x = 0; x < D; ++x) sel.push_back(nat_of_int[r + x]);
+  }
+  if (include_calibration)
+    for (uint32_t x = 0; x < K; ++x) sel.push_back(e->st.np + x);
+  const uint32_t m = (uint32_t)M, N = e->st.n;
+  std::vector<double> E((size_t)N * m, 0.0), X((size_t)N * m, 0.0);
+  for (uint32_t c = 0; c < m; ++c) E[(size_t)sel[c] * m + c] = 1.0;
+  rc = pcg_panel_on_S(e, m, E.data(), X.data(), *o);
+  if (rc && rc != BA_HIP_FACTORIZATION_ERROR) return rc;
+  for (uint32_t a = 0; a < m; ++a)
+    for (uint32_t c = 0; c < m; ++c)
+      out[(size_t)a * m + c] = 0.5 * (X[(size_t)sel[a] * m + c] + X[(size_t)sel[c] * m + a]);
+  return rc;
+}
+int ba_hip_get_pcg_panel_stats(ba_hip_engine* h, ba_hip_pcg_panel_stats* out) {
+  ENG(h);
+  if (!out) return e->fail_msg("ba_hip_get_pcg_panel_stats: NULL argument");
+  *out = e->pcgp_stats;
+  return 0;
+}
+int ba_hip_get_pcg_panel_columns(ba_hip_engine* h, uint32_t m, uint32_t* iterations, uint32_t* converged, uint32_t* breakdown,
+                                 double* rel_residual_true) {
+  ENG(h);
+  if (e->pcgp_cols.empty()) return e->fail_msg("ba_hip_get_pcg_panel_columns: no panel solve yet");
+  if (m != e->pcgp_cols.size())
+    return e->fail_msg(("ba_hip_get_pcg_panel_columns: m differs from the " + std::to_string(e->pcgp_cols.size()) +
+                        " columns of the last panel solve").c_str());
+  for (uint32_t j = 0; j < m; ++j) {
+    const PcgState& c = e->pcgp_cols[j];
+    if (iterations) iterations[j] = c.iterations;
+    if (converged) converged[j] = c.converged;
+    if (breakdown) breakdown[j] = c.breakdown;
+    if (rel_residual_true) rel_residual_true[j] = c.bb > 0.0 ? sqrt(c.rr_true / c.bb) : 0.0;
+  }
+  return 0;
+}
+
 int ba_hip_set_pose_permutation(ba_hip_engine* h, const uint32_t* opt_of_natural, uint32_t n) {
   ENG(h);
   if (n && !opt_of_natural) return e->fail_msg("ba_hip_set_pose_permutation: NULL permutation");
@@ -2314,6 +2426,38 @@ int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const 
   if (rc) return rc;
   BAE_HIP(download_x(dx, n, x));
   if (stats) *stats = st;
+  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
+}
+
+int ba_hip_pcg_panel_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, uint32_t m, const double* B, uint32_t block,
+                           const ba_hip_pcg_options* o, double* X, ba_hip_pcg_panel_stats* stats) {
+  ENG(h);
+  static const char* what = "ba_hip_pcg_panel_solve";
+  if (!n || !a_lower || !o) return e->fail_msg("ba_hip_pcg_panel_solve: NULL or empty argument");
+  int rc;
+  if ((rc = pcg_panel_args(e, what, m, B, X))) return rc;
+  if (block < 1 || block > kPcgMaxBlock) return e->fail_msg("ba_hip_pcg_panel_solve: block must lie in 1 .. 16");
+  if (!(o->rel_tolerance > 0.0) || !(o->rel_tolerance < 1.0)) return e->fail_msg("ba_hip_pcg_panel_solve: rel_tolerance must lie in (0, 1)");
+  if (o->coarse_aggregate)
+    return e->fail_msg("ba_hip_pcg_panel_solve: coarse_aggregate must be 0: the coarse space is not available in panel solves");
+  BAE_HIP(hipSetDevice(e->device));
+  const std::vector<double> zero(n, 0.0);
+  const PaddedSystem sys = pad_system(n, a_lower, zero.data(), true);
+  const uint32_t ld = sys.ld;
+  PcgPlan plan;
+  build_pcg_plan(sys.nz, sys.nt, plan);
+  std::vector<uint32_t> blk, blocks, rowmap(ld, kPcgNone);
+  pcg_row_blocks(n, block, 0, ld, blk, blocks);
+  for (uint32_t r = 0; r < n; ++r) rowmap[r] = r;
+  DBuf<double> dA;
+  BAE_HIP(dA.alloc(sys.A.size()));
+  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
+  int status = 0;
+  e->held.pcg_run_begins();   // a stand-alone PCG run without the coarse space, as ba_hip_pcg_solve
+  rc = pcg_panel_solve_device(e, dA.p, n, ld, plan, sys.nz, blk, blocks, rowmap.data(), m, B, X, *o, &status);
+  if (rc) return rc;
+  e->held.pcg_run_finished(false);
+  if (stats) *stats = e->pcgp_stats;
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
 }
 

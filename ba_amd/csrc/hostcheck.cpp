@@ -979,3 +979,64 @@ extern "C" int ba_hostcheck_chol_launch(int op, uint32_t n, const int64_t* in, c
   }
   return 0;
 }
+
+// ---- panel PCG (pcg_panel.h) --------------------------------------------------------------------------------
+#include "pcg_panel.h"
+
+// One product Q = S P by the panel plan on the lower storage A (row-major, 64 nt x 64 nt; tiles outside nz and the
+// strict upper triangle of diagonal tiles are not read).  P, Q: (64 nt) x m row-major.  variant: 0, or one of the
+// deliberately wrong ones of pcg_panel.h.  out_u32: sources, chunks.
+extern "C" int ba_hostcheck_pcg_spmm(uint32_t nt, const uint8_t* nz, const double* A, uint32_t m, const double* P, double* Q,
+                                     int variant, uint32_t* out_u32) {
+  if (!nt || !m || m > bae::kPcgPanelMaxColumns) return -1;
+  std::vector<uint8_t> z(nz, nz + (size_t)nt * nt);
+  bae::PcgPlan pl;
+  bae::build_pcg_plan(z, nt, pl);
+  bae::PcgPanelPlan pp;
+  bae::build_pcg_panel_plan(pl, m, pp);
+  bae::pcg_panel_spmm_host(pp, A, (size_t)64 * nt, P, m, nullptr, Q, nullptr, variant);
+  if (out_u32) { out_u32[0] = pp.n_src(); out_u32[1] = pp.n_chunks(); }
+  return 0;
+}
+
+// pcg_panel_host on a symmetric n x n system given dense (row-major n x n; the LOWER triangle is read), padded like
+// the engine pads A.  tile_map (optional, nt x nt bytes): tiles that belong to the pattern beside those of the
+// nonzeros.  np rows in blocks of D, then one block of K = n - np.  B, X: n x m row-major.  Per column j: out_u32[4 j
+// ..] = iterations, converged, breakdown, residual replacements; out_f64[2 j ..] = relative residual, true and of
+// the recurrence.  out_scalar: passes, tiles, sources, chunks.
+extern "C" int ba_hostcheck_pcg_panel(uint32_t n, const double* S, const uint8_t* tile_map, uint32_t m, const double* B,
+                                      uint32_t np, uint32_t D, double rel_tolerance, uint32_t max_iterations, int variant,
+                                      double* X, uint32_t* out_u32, double* out_f64, uint32_t* out_scalar) {
+  if (!n || np > n || D < 1 || D > bae::kPcgMaxBlock || n - np > bae::kPcgMaxBlock || !m || m > bae::kPcgPanelMaxColumns) return -1;
+  const uint32_t nt = (n + 63) / 64, ld = 64 * nt;
+  std::vector<double> A((size_t)ld * ld, 0.0), Bp((size_t)ld * m, 0.0), Xp((size_t)ld * m, 0.0);
+  std::vector<uint8_t> nz((size_t)nt * nt, 0);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c <= r; ++c) {
+      const double v = S[(size_t)r * n + c];
+      A[(size_t)r * ld + c] = v;
+      if (v != 0.0) nz[(size_t)(r / 64) * nt + c / 64] = 1;
+    }
+  if (tile_map)
+    for (size_t i = 0; i < nz.size(); ++i) nz[i] |= tile_map[i] ? 1 : 0;
+  for (uint32_t r = n; r < ld; ++r) A[(size_t)r * ld + r] = 1.0;
+  std::copy(B, B + (size_t)n * m, Bp.begin());
+  bae::PcgPlan pl;
+  bae::build_pcg_plan(nz, nt, pl);
+  bae::PcgPanelPlan pp;
+  bae::build_pcg_panel_plan(pl, m, pp);
+  std::vector<uint32_t> blk, blocks;
+  bae::pcg_row_blocks(np, D, n - np, ld, blk, blocks);
+  bae::PcgPanelResult res;
+  const int rc = bae::pcg_panel_host(pl, pp, A.data(), ld, Bp.data(), m, n, nz, blk, blocks, rel_tolerance, max_iterations,
+                                     Xp.data(), &res, variant);
+  std::copy(Xp.begin(), Xp.begin() + (size_t)n * m, X);
+  for (uint32_t j = 0; j < m; ++j) {
+    const bae::PcgResult& c = res.col[j];
+    out_u32[4 * j] = c.iterations; out_u32[4 * j + 1] = c.converged; out_u32[4 * j + 2] = c.breakdown; out_u32[4 * j + 3] = c.replacements;
+    out_f64[2 * j] = c.bb > 0.0 ? std::sqrt(c.rr_true / c.bb) : 0.0;
+    out_f64[2 * j + 1] = c.bb > 0.0 ? std::sqrt(c.rr_recur / c.bb) : 0.0;
+  }
+  if (out_scalar) { out_scalar[0] = res.passes; out_scalar[1] = pl.n_tiles; out_scalar[2] = pp.n_src(); out_scalar[3] = pp.n_chunks(); }
+  return rc;
+}

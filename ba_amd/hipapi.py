@@ -176,6 +176,15 @@ class PcgCoarseStats(C.Structure):
                [(n, C.c_double) for n in ("setup_ms", "apply_ms", "coarse_bytes")]
 
 
+class PcgPanelStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("columns", "column_blocks", "passes", "converged", "capped", "broken_down")] + \
+               [(n, C.c_double) for n in ("max_rel_residual_true", "solve_ms", "spmm_ms", "tile_products_per_pass",
+                                          "bytes_read_per_product", "workspace_bytes")]
+
+
+PCG_PANEL_MAX_COLUMNS = 512  # BA_HIP_PCG_PANEL_MAX_COLUMNS
+
+
 def _pcg_stats_dict(st):
     return {k: getattr(st, k) for k, _ in type(st)._fields_ if k != "reserved"}
 
@@ -215,6 +224,8 @@ SYMBOLS = [
     "ba_hip_get_joint_state_marginals", "ba_hip_get_joint_state_stats",
     "ba_hip_factor_solve", "ba_hip_get_factor_solve_stats", "ba_hip_tile_factor_solve",
     "ba_hip_get_weakest_modes", "ba_hip_get_mode_stats",
+    "ba_hip_pcg_panel_solve_system", "ba_hip_get_joint_marginals_pcg", "ba_hip_get_pcg_panel_stats",
+    "ba_hip_get_pcg_panel_columns", "ba_hip_pcg_panel_solve",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -862,6 +873,56 @@ class Engine:
         rc = self._chk(self.L.ba_hip_pcg_solve(self.h, b.shape[0], _p(a, dp), _p(b, dp), int(block), C.byref(o), _p(x, dp),
                                                C.byref(st)), positive_ok=True)
         return x, rc, _pcg_stats_dict(st)
+
+    # ---- panel PCG: S^-1 on a block of columns after a PCG solve (no factor) ----
+    def pcg_panel_solve_system(self, B, rel_tolerance=1e-8, max_iterations=0, check_every=0, coarse_aggregate=0):
+        """(X, rc): X = S^-1 B by the panel PCG after a PCG solve_gn; B is (n,) or (n, m), rows in the order of
+        get_delta_gn.  rc is 0 or 4 (some column broke down: pcg_panel_columns names it)."""
+        B = _d(B)
+        n = self.num_pose_params() + self.num_calib_params()
+        if B.ndim not in (1, 2) or B.shape[0] != n:
+            raise ValueError("B must have %d rows" % n)
+        m = 1 if B.ndim == 1 else B.shape[1]
+        X = np.zeros_like(B)
+        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every), int(coarse_aggregate))
+        rc = self._chk(self.L.ba_hip_pcg_panel_solve_system(self.h, m, _p(B, dp), _p(X, dp), C.byref(o)), positive_ok=True)
+        return X, rc
+
+    def joint_marginals_pcg(self, ids, include_calibration=False, rel_tolerance=1e-8, max_iterations=0, check_every=0,
+                            coarse_aggregate=0):
+        """The block of joint_marginals without a factor: the panel PCG on unit columns, symmetrised."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.uint32).ravel()
+        m = len(ids) * self.pose_dim + (self.num_calib_params() if include_calibration else 0)
+        out = np.zeros((m, m))
+        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every), int(coarse_aggregate))
+        self._chk(self.L.ba_hip_get_joint_marginals_pcg(self.h, len(ids), _p(ids, u32p), int(bool(include_calibration)),
+                                                        C.byref(o), _p(out, dp)))
+        return out
+
+    def pcg_panel_stats(self):
+        st = PcgPanelStats()
+        self._chk(self.L.ba_hip_get_pcg_panel_stats(self.h, C.byref(st)))
+        return _pcg_stats_dict(st)
+
+    def pcg_panel_columns(self, m):
+        """The per-column record of the last panel solve: dict of (m,) arrays."""
+        it, cv, bd = (np.zeros(int(m), dtype=np.uint32) for _ in range(3))
+        rel = np.zeros(int(m))
+        self._chk(self.L.ba_hip_get_pcg_panel_columns(self.h, int(m), _p(it, u32p), _p(cv, u32p), _p(bd, u32p), _p(rel, dp)))
+        return dict(iterations=it, converged=cv, breakdown=bd, rel_residual_true=rel)
+
+    def pcg_panel_solve(self, a_lower, B, block, rel_tolerance, max_iterations=0, check_every=0, coarse_aggregate=0):
+        """Stand-alone panel PCG on an SPD system given by its lower triangle: (X, rc, stats dict); B is (n, m)."""
+        a, B = _d(a_lower), _d(B)
+        if B.ndim == 1:
+            B = B[:, None]
+        B = np.ascontiguousarray(B)
+        X = np.zeros_like(B)
+        o = PcgOptions(float(rel_tolerance), int(max_iterations), int(check_every), int(coarse_aggregate))
+        st = PcgPanelStats()
+        rc = self._chk(self.L.ba_hip_pcg_panel_solve(self.h, B.shape[0], _p(a, dp), B.shape[1], _p(B, dp), int(block),
+                                                     C.byref(o), _p(X, dp), C.byref(st)), positive_ok=True)
+        return X, rc, _pcg_stats_dict(st)
 
     def dense_solve(self, a_lower, b):
         a, b = _d(a_lower), _d(b)

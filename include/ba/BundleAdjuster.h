@@ -541,6 +541,48 @@ class BundleAdjuster {
     }
     return true;
   }
+  // X = S^-1 B without a factor, after a Solve() with Options::reduced_solver = Pcg (extension; include/ba_hip.h
+  // ba_hip_pcg_panel_solve_system): one block-Jacobi PCG recurrence per column, run in
+  // lock-step, to the relative residual `tol` (<= 0: Options::pcg_tolerance).  B, X and their rows as SolveWithFactor.
+  // false, reported through Check(), and a 0 x 0 X when unavailable (the last solve was direct, a wrong row count, no
+  // or more than BA_HIP_PCG_PANEL_MAX_COLUMNS columns) or when a column broke down.
+  bool SolveWithPcg(const MatrixXt& B, MatrixXt& X, Scalar tol = 0) {
+    const uint32_t n = engine_ ? ba_hip_num_pose_params(engine_) + ba_hip_num_calib_params(engine_) : 0;
+    if (!engine_ || (uint32_t)B.rows() != n) {
+      std::cerr << "ba::BundleAdjuster::SolveWithPcg: B must have " << n << " rows" << std::endl;
+      X = MatX();
+      return false;
+    }
+    ba_hip_pcg_options po = {};
+    po.rel_tolerance = tol > 0 ? tol : options_.pcg_tolerance;
+    po.max_iterations = options_.pcg_max_iterations;
+    X = MatX(B.rows(), B.cols());
+    if (!Check(ba_hip_pcg_panel_solve_system(engine_, (uint32_t)B.cols(), B.data(), X.data(), &po),
+               "ba_hip_pcg_panel_solve_system")) {
+      X = MatX();
+      return false;
+    }
+    return true;
+  }
+  // GetJointPoseCovariance without a factor, after a Solve() with Options::reduced_solver = Pcg: the same block in
+  // the same layout, from the panel PCG on unit columns (ba_hip_get_joint_marginals_pcg); its relative accuracy is
+  // about cond(S) * tol (tol <= 0: Options::pcg_tolerance).
+  bool GetJointPoseCovarianceIterative(const std::vector<uint32_t>& ids, MatrixXt& cov, Scalar tol = 0,
+                                       bool include_calibration = false) {
+    const int M = (int)(ids.size() * kPoseDim + (include_calibration ? kCalibDim : 0));
+    ba_hip_pcg_options po = {};
+    po.rel_tolerance = tol > 0 ? tol : options_.pcg_tolerance;
+    po.max_iterations = options_.pcg_max_iterations;
+    cov = MatX(M, M);
+    if (!engine_ || !Check(ba_hip_get_joint_marginals_pcg(engine_, (uint32_t)ids.size(), ids.data(), include_calibration ? 1 : 0,
+                                                          &po, cov.data()),
+                           "ba_hip_get_joint_marginals_pcg")) {
+      cov = MatX();
+      return false;
+    }
+    return true;
+  }
+  bool GetPcgPanelStats(ba_hip_pcg_panel_stats* out) const { return engine_ && ba_hip_get_pcg_panel_stats(engine_, out) == 0; }
   // The k eigenpairs of smallest magnitude of the reduced system of the last Solve() (extension; include/ba_hip.h
   // ba_hip_get_weakest_modes): the weakly determined directions - a free scale, yaw about gravity, a bias.
   // eigenvalues: k values by ascending magnitude (negative with an indefinite S); modes: k x n, row i the unit

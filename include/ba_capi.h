@@ -164,6 +164,14 @@ int ba_adjuster_get_pose_landmark_cross_covariance(ba_adjuster* a, uint32_t pose
 int ba_adjuster_solve_with_factor(ba_adjuster* a, uint32_t n, uint32_t m, const double* B, double* X);
 int ba_adjuster_get_weakest_modes(ba_adjuster* a, uint32_t k, uint32_t n, double* eigenvalues, double* modes);
 int ba_adjuster_get_mode_stats(ba_adjuster* a, ba_hip_mode_stats* out);
+/* SolveWithPcg / GetJointPoseCovarianceIterative (extension): the two calls above without a
+ * factor, after a solve with reduced_solver = Pcg, by the panel PCG to the relative residual tol (<= 0: the options'
+ * pcg_tolerance).  Layouts and returns as ba_adjuster_solve_with_factor and ba_adjuster_get_joint_pose_covariance.
+ * GetPcgPanelStats: the figures of the last of them; 0, or 1 when unavailable. */
+int ba_adjuster_solve_with_pcg(ba_adjuster* a, uint32_t n, uint32_t m, const double* B, double tol, double* X);
+uint32_t ba_adjuster_get_joint_pose_covariance_iterative(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids,
+                                                         int include_calibration, double tol, double* cov);
+int ba_adjuster_get_pcg_panel_stats(ba_adjuster* a, ba_hip_pcg_panel_stats* out);
 /* Marginalize / AddDensePrior (extension; include/ba_hip.h).  ba_adjuster_marginalize:
  * after a solve, eliminates the poses and landmarks into a dense prior kept by the adjuster; returns 0 and the
  * blanket size, or 1 when refused.  ba_adjuster_get_marginalization reads it: |B| pose ids, |B| x 16 states,

@@ -865,12 +865,62 @@ int ba_hip_get_pcg_coarse_stats(ba_hip_engine* e, ba_hip_pcg_coarse_stats* out);
  * either pointer may be NULL. */
 int ba_hip_get_pcg_coarse(ba_hip_engine* e, uint32_t nc, double* C, double* Cinv);
 
+/* ---- panel PCG: S^-1 applied to a block of columns after a PCG solve (extension) ----------------------
+ * After a PCG solve there is no factor, but A still holds S.  ba_hip_pcg_panel_solve_system computes X = S^-1 B for
+ * 1 <= m <= BA_HIP_PCG_PANEL_MAX_COLUMNS right-hand sides by m INDEPENDENT block-Jacobi PCG recurrences run in
+ * lock-step (not block CG: no m x m systems, dependent columns are no problem).  Every column has the stopping
+ * rule, the true-residual verification, the residual replacement and the breakdown codes of the solver above, its
+ * own alpha and beta and its own iteration count; a finished column is frozen while the others go on.  Only the
+ * tiles of S are shared: a pass reads them once per block of 64 columns and multiplies on the FP64 matrix cores.
+ * FP64, no atomics, fixed summation order: a second call returns the same bits, and column j of X has the same bits
+ * whatever the other columns hold and wherever in B it sits.
+ *   B, X   n x m row-major (host), n = pose + calibration parameters; rows in the order and coordinates of
+ *          ba_hip_factor_solve (natural pose order under every pose ordering, the calibration rows last).
+ *   o      rel_tolerance in (0, 1), max_iterations and check_every as above; coarse_aggregate must be 0 (the coarse
+ *          space is not available in panel solves).
+ * Precondition: the last ba_hip_solve_gn ran PCG and the system has not been linearised since.  Refused with a
+ * message otherwise, and for a direct solver, a sharded engine, m == 0, m > the limit, NULL arguments and
+ * coarse_aggregate != 0.  Reads A only: delta_gn, the statistics of the last ba_hip_solve_gn and every validity
+ * flag of the engine stay as they are.
+ * Returns 0 when no column broke down (columns that ran into max_iterations are reported per column, not as an
+ * error) and BA_HIP_FACTORIZATION_ERROR when some column did; X then holds every column's last finite iterate. */
+#define BA_HIP_PCG_PANEL_MAX_COLUMNS 512
+int ba_hip_pcg_panel_solve_system(ba_hip_engine* e, uint32_t m, const double* B, double* X, const ba_hip_pcg_options* o);
+/* The block of S^-1 that ba_hip_get_joint_marginals returns, in the same layout (the poses in the caller's order,
+ * the calibration rows last), computed without a factor: G = E^T (S^-1 E) by the panel solve on unit columns,
+ * returned as (G + G^T) / 2.  Preconditions and refusals of ba_hip_pcg_panel_solve_system; the accuracy is that of
+ * the options' rel_tolerance (relative error about cond(S) * rel_tolerance). */
+int ba_hip_get_joint_marginals_pcg(ba_hip_engine* e, uint32_t n, const uint32_t* pose_ids, int include_calibration,
+                                   const ba_hip_pcg_options* o, double* out);
+typedef struct {
+  uint32_t columns, column_blocks;  /* m, ceil(m / 64) */
+  uint32_t passes;                  /* passes enqueued until every column was done (or the cap) */
+  uint32_t converged, capped, broken_down;   /* columns; they add up to `columns` */
+  double max_rel_residual_true;     /* the largest ||b_j - S x_j|| / ||b_j|| over the converged and capped columns */
+  double solve_ms;                  /* the whole call on the device, block inverses included */
+  double spmm_ms;                   /* mean device time of one product Q = S P (sampled once per check_every) */
+  double tile_products_per_pass;    /* 64 x 64 x 64 products of one pass (all column blocks) */
+  double bytes_read_per_product;    /* of one product Q = S P: tiles, panel tiles and partial-tile slots */
+  double workspace_bytes;           /* device memory of the panel solver */
+} ba_hip_pcg_panel_stats;
+/* Of the last panel solve (either entry point above, or the test tap). */
+int ba_hip_get_pcg_panel_stats(ba_hip_engine* e, ba_hip_pcg_panel_stats* out);
+/* The per-column record of the last panel solve; m must be its column count; every pointer may be NULL.
+ * breakdown: the codes of ba_hip_pcg_stats. */
+int ba_hip_get_pcg_panel_columns(ba_hip_engine* e, uint32_t m, uint32_t* iterations, uint32_t* converged,
+                                 uint32_t* breakdown, double* rel_residual_true);
+
 /* ---- stand-alone kernels exposed for tests and benchmarks ------------------------- */
 /* The PCG solver on an SPD system given by its LOWER triangle (row-major n x n, host memory); `block`: size of the
  * preconditioner's diagonal blocks (1 .. 16; the last block is shorter when it does not divide n).  The tile
  * pattern is that of the nonzeros of a_lower.  Returns 0 or BA_HIP_FACTORIZATION_ERROR as described above. */
 int ba_hip_pcg_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const double* b, uint32_t block,
                      const ba_hip_pcg_options* o, double* x, ba_hip_pcg_stats* stats);
+/* Test tap of the panel PCG: X = A^-1 B (n x m row-major, host) on the system of ba_hip_pcg_solve — lower triangle,
+ * pattern of its nonzeros, one block size — by the kernels of ba_hip_pcg_panel_solve_system.  stats may be NULL.
+ * Returns and lifecycle effects as ba_hip_pcg_solve; the per-column record is read with ba_hip_get_pcg_panel_columns. */
+int ba_hip_pcg_panel_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, uint32_t m, const double* B, uint32_t block,
+                           const ba_hip_pcg_options* o, double* X, ba_hip_pcg_panel_stats* stats);
 /* Dense Cholesky solve of an SPD system given by its LOWER triangle (row-major n x n,
  * host memory): x = A^-1 b.  Runs the same kernels ba_hip_solve_gn uses. */
 int ba_hip_dense_solve(ba_hip_engine* e, uint32_t n, const double* a_lower, const double* b, double* x);
