@@ -420,6 +420,34 @@ int upload_async(Engine* e, DBuf<T>& d, const U* src, size_t count) {
   return 0;
 }
 
+// The index tables of a plan, packed into one device buffer.  add() appends a section and returns its offset in
+// words, first padded with zeros to a multiple of `align` words (4 for a section read as uint4, 2 for uint2);
+// after an upload into `buf`, at<T>(offset) is the section on the device.
+struct IndexPack {
+  std::vector<uint32_t> w;
+  const uint32_t* d = nullptr;
+  template <class It>
+  size_t add(It first, It last, size_t align = 1) {
+    w.resize((w.size() + align - 1) / align * align, 0);
+    const size_t o = w.size();
+    w.insert(w.end(), first, last);
+    return o;
+  }
+  size_t add(const std::vector<uint32_t>& v, size_t align = 1) { return add(v.begin(), v.end(), align); }
+  size_t size() const { return w.size(); }
+  hipError_t upload(const DBuf<uint32_t>& buf) {   // synchronous, into a buffer the caller allocated with size() words
+    d = buf.p;
+    return w.empty() ? hipSuccess : hipMemcpy(buf.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  }
+  int upload_async(Engine* e, DBuf<uint32_t>& buf) {   // on e->stream: the pack must outlive its next synchronisation
+    const int rc = bae::upload_async(e, buf, w.data(), w.size());
+    d = buf.p;
+    return rc;
+  }
+  template <class T = uint32_t>
+  const T* at(size_t offset) const { return reinterpret_cast<const T*>(d + offset); }
+};
+
 // The factor that the last ba_hip_solve_gn left behind, for the kernels that read it: its tile count, the pivot
 // signs D and the L_JJ^-T of the diagonal tiles (both in invdiag).  `who` starts the message when there is none.
 inline int kept_factor(Engine* e, const char* who, uint32_t* nt, const double** dsgn, const double** linvT) {
@@ -510,11 +538,23 @@ int pose_pose_leverages_run(Engine* e, int kind, uint32_t n, const uint32_t* ids
 // invdiag and, for landmarks, the rows of the last linearisation
 int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<uint32_t>& lms, double* out);
 void jointcov_release(Engine* e);
-// the substitution Y <- L^-1 Y of a joint plan whose tables are on the device (k_jointcov.hip), enqueued on `stream`
+// the substitution of a joint plan whose tables are on the device (k_jointcov.hip), enqueued on `stream`, one level
+// after the other: Y <- L^-1 Y (dsgn unused), or with `transposed` and the plan of the mirrored pattern, which holds
+// every tile row (panel t = tile t, pos unused), Y <- L^-T D Y
 struct JointPlan;
-void joint_forward_launch(hipStream_t stream, const JointPlan& p, const uint4* d_chunks, const uint4* d_rows,
-                          const uint32_t* d_src, const uint32_t* d_pos, const double* A, uint32_t ld, const double* linvT,
-                          double* Y, double* slots);
+struct SubstTables {
+  const uint4 *chunks, *rows;
+  const uint32_t *src, *pos;
+};
+void joint_subst_launch(hipStream_t stream, const JointPlan& p, const SubstTables& t, bool transposed, const double* A,
+                        uint32_t ld, const double* linvT, const double* dsgn, double* Y, double* slots);
+// B (n x m row-major, the caller's row order) -> a panel of `count` = rows x mp doubles through rowmap (the caller's
+// row of every panel row, kJointNone = kPcgNone for a padding row), zeros in padding rows and columns; and back
+// (k_factorsolve.hip).  Enqueued on `stream`.
+void panel_scatter_launch(hipStream_t stream, const double* B, uint32_t m, const uint32_t* rowmap, uint64_t count,
+                          uint32_t mp, double* X);
+void panel_gather_launch(hipStream_t stream, const double* X, uint32_t mp, const uint32_t* rowmap, uint64_t count,
+                         uint32_t m, double* out);
 // X = S^-1 B with a factor on the device (k_factorsolve.hip): the lower storage A (leading dimension ld = 64 nt),
 // its tile pattern on the host, the pivot signs and the L_JJ^-T.  B, X: n x m row-major on the host, rows in the
 // caller's order; rowmap (64 nt entries): the caller's row of every factorised row, kJointNone for padding rows

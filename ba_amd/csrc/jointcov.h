@@ -15,12 +15,14 @@
 #pragma once
 #include <stdint.h>
 
+#include "none_row.h"
+
 #include <algorithm>
 #include <vector>
 
 namespace bae {
 
-static const uint32_t kJointNone = 0xffffffffu;
+static const uint32_t kJointNone = kNoneRow;
 static const uint32_t kJointChunk = 4;      // sources per chunk: the K loop of a row is split into
                                             // ceil(sources / 4) workgroups, their partial tiles summed in order
 static const uint32_t kJointGramGroup = 8;  // reach rows per partial sum of the Gram product

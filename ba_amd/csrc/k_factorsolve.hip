@@ -1,15 +1,12 @@
 // Solves with the factor that ba_hip_solve_gn leaves behind (ba_hip_factor_solve): X = S^-1 B for a caller's block
-// of m <= 512 right-hand sides, S = L D L^T tile-sparse.  One 64 x m_pad panel per tile row; the forward pass
-// Y = L^-1 B runs through k_joint_fsolve / k_joint_epilogue of k_jointcov.hip (joint_forward_launch) seeded with
-// every tile row, the backward pass X_J = L_JJ^-T (D_J Y_J - sum_{I > J} L_IJ^T X_I) is its mirror, in place:
+// of m <= 512 right-hand sides, S = L D L^T tile-sparse.  One 64 x m_pad panel per tile row, solved in place by the
+// substitution of k_jointcov.hip (joint_subst_launch) seeded with every tile row: the forward pass Y = L^-1 B
+// (k_joint_fsolve / k_joint_epilogue), then its mirror on the mirrored plan, the backward pass
+// X_J = L_JJ^-T (D_J Y_J - sum_{I > J} L_IJ^T X_I) (k_fsol_bsolve / k_fsol_bepilogue, also there).  Here are
 //
-//   k_fsol_scatter    B (n x m, the caller's row order) -> panels in the factorised row order, zeros in padding rows
-//                     and padding columns
-//   k_fsol_bsolve     partial tile sum_{I in chunk} L_IJ^T X_I, one workgroup per (column J, chunk of <= 4 sources,
-//                     block of 64 columns); one launch per level
-//   k_fsol_bepilogue  X_J = L_JJ^-T (D_J Y_J - the column's partial tiles in chunk order), one workgroup per
-//                     (column J, block of 64 columns); one launch per level
-//   k_fsol_gather     panels -> X (n x m, the caller's row order)
+//   k_panel_scatter   B (n x m, the caller's row order) -> panels in the factorised row order, zeros in padding rows
+//                     and padding columns (also the panels of k_pcg_panel.hip)
+//   k_panel_gather    panels -> X (n x m, the caller's row order)
 //
 // and the weakest modes of S (ba_hip_get_weakest_modes): the block inverse iteration of factorsolve.h on three
 // panels of 64 columns that stay on the device, S^-1 applied by the kernels above, the 64 x 64 matrices on the host:
@@ -24,9 +21,7 @@
 // pivot signs D from invdiag.  FP64, no atomics: every partial tile and every panel element has one writer and the
 // sums run in the plan's order, so two calls give the same bits.
 //
-// The tile products run on v_mfma_f64_16x16x4_f64 with the staging of tile_mma.h, as in k_jointcov.hip.  In the
-// backward pass L_IJ is read as it lies in memory, rows = k: it is the k-major operand, and linvT[J] = L_JJ^-T the
-// index-major one.
+// The tile products run on v_mfma_f64_16x16x4_f64 with the staging of tile_mma.h, as in k_jointcov.hip.
 #include "engine.h"
 #include "factorsolve.h"
 #include "tile_mma.h"
@@ -39,10 +34,10 @@ namespace bae {
 
 using namespace tile64;
 
-// rowmap[i]: the caller's row of factorised row i (kJointNone for a padding row), i < rows
+// rowmap[i]: the caller's row of panel row i (kJointNone for a padding row), i < count / mp
 __global__ void __launch_bounds__(256)
-k_fsol_scatter(const double* __restrict__ B, uint32_t m, const uint32_t* __restrict__ rowmap, uint64_t count, uint32_t mp,
-               double* __restrict__ X) {
+k_panel_scatter(const double* __restrict__ B, uint32_t m, const uint32_t* __restrict__ rowmap, uint64_t count, uint32_t mp,
+                double* __restrict__ X) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count) return;
   const uint32_t c = (uint32_t)(t % mp), r = rowmap[t / mp];
@@ -50,86 +45,21 @@ k_fsol_scatter(const double* __restrict__ B, uint32_t m, const uint32_t* __restr
 }
 
 __global__ void __launch_bounds__(256)
-k_fsol_gather(const double* __restrict__ X, uint32_t mp, const uint32_t* __restrict__ rowmap, uint64_t count, uint32_t m,
-              double* __restrict__ out) {
+k_panel_gather(const double* __restrict__ X, uint32_t mp, const uint32_t* __restrict__ rowmap, uint64_t count, uint32_t m,
+               double* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count) return;
   const uint32_t c = (uint32_t)(t % mp), r = rowmap[t / mp];
   if (c < m && r != kJointNone) out[(size_t)r * m + c] = X[t];
 }
 
-// chunks: (J, J, first source, end source) of one level; slot (blockIdx.x, blockIdx.y) = the partial tile
-// sum_{I in chunk} L_IJ^T X_I[:, 64 b .. 64 b + 64)
-__global__ void __launch_bounds__(256)
-k_fsol_bsolve(const uint4* __restrict__ chunks, const uint32_t* __restrict__ src, const double* __restrict__ A, uint32_t ld,
-              const double* __restrict__ X, uint32_t mp, double* __restrict__ slots) {
-  __shared__ Lds s;
-  const uint4 c = chunks[blockIdx.x];
-  const uint32_t J = c.x, s0 = c.z, b = blockIdx.y;
-  const uint32_t nch = 2 * (c.w - s0);
-  double4_t acc[2][2];
-  zero_acc(acc);
-  Chunk ca, cb;
-  auto fetch = [&](uint32_t ch) {
-    const uint32_t I = src[s0 + (ch >> 1)];
-    const int k0 = KCH * (int)(ch & 1);
-    load_kmajor(ca, A + (size_t)I * TB * ld + (size_t)J * TB, ld, k0);   // X[k][r] = L_IJ[k][r]
-    load_kmajor(cb, X + (size_t)I * TB * mp + (size_t)b * TB, mp, k0);   // Y[k][x] = X_I[k][x]
-  };
-  if (nch) fetch(0);
-  for (uint32_t ch = 0; ch < nch; ++ch) {
-    store_kmajor(ca, s.X);
-    store_kmajor(cb, s.Y);
-    __syncthreads();
-    if (ch + 1 < nch) fetch(ch + 1);
-    mma_chunk(acc, s);
-    __syncthreads();
-  }
-  store_tile(slots + ((size_t)blockIdx.x * gridDim.y + b) * (TB * TB), TB, acc);
+void panel_scatter_launch(hipStream_t stream, const double* B, uint32_t m, const uint32_t* rowmap, uint64_t count,
+                          uint32_t mp, double* X) {
+  hipLaunchKernelGGL(k_panel_scatter, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, B, m, rowmap, count, mp, X);
 }
-
-// rows: (J, first chunk, end chunk, first chunk of the level) of one level.
-// X_J = L_JJ^-T T, T = D_J Y_J - the column's partial tiles in chunk order; Y_J is what the panel holds.
-__global__ void __launch_bounds__(256)
-k_fsol_bepilogue(const uint4* __restrict__ rows, const double* __restrict__ linvT, const double* __restrict__ dsgn,
-                 double* __restrict__ X, uint32_t mp, const double* __restrict__ slots) {
-  __shared__ Lds s;
-  const uint4 r = rows[blockIdx.x];
-  const uint32_t J = r.x, b = blockIdx.y, ncb = gridDim.y;
-  double* XJ = X + (size_t)J * TB * mp + (size_t)b * TB;
-  const double* G = linvT + (size_t)J * TB * TB;  // G[i][k] = (L_JJ^-T)[i][k]: X[k][i], read index-major
-  const double* d = dsgn + (size_t)J * TB;
-  const int tid = threadIdx.x;
-  // thread t owns elements e = t + 256 q of the 64 x 64 tile, as in k_joint_epilogue: the 16 loads of a slot are in
-  // flight together; the sign of row k goes on while Y_J is read
-  double v[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int k = (tid + 256 * q) / TB;
-    v[q] = XJ[(size_t)k * mp + tid % TB] * d[k];
-  }
-  const double* sl = slots + ((size_t)(r.y - r.w) * ncb + b) * (TB * TB) + tid;
-  for (uint32_t c = r.y; c < r.z; ++c, sl += (size_t)ncb * (TB * TB)) {
-    double w[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) w[q] = sl[256 * q];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) v[q] -= w[q];
-  }
-  double4_t out[2][2];
-  zero_acc(out);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    Chunk cg;
-    load_imajor(cg, G, TB, KCH * h);
-    store_imajor(cg, s.X);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) s.Y[(tid + 256 * q) / TB][tid % TB] = v[8 * h + q];
-    __syncthreads();
-    mma_chunk(out, s);
-    __syncthreads();
-  }
-  store_tile(XJ, mp, out);
+void panel_gather_launch(hipStream_t stream, const double* X, uint32_t mp, const uint32_t* rowmap, uint64_t count,
+                         uint32_t m, double* out) {
+  hipLaunchKernelGGL(k_panel_gather, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, X, mp, rowmap, count, m, out);
 }
 
 // part[g] = sum_{t in group g} X_t^T Y_t: both panels are k-major operands as they lie (rows = k)
@@ -138,7 +68,6 @@ k_mode_gram(const double* __restrict__ X, const double* __restrict__ Y, uint32_t
   __shared__ Lds s;
   const uint32_t g = blockIdx.x;
   const uint32_t t0 = g * kModeGramGroup, t1 = min(nt, t0 + kModeGramGroup);
-  const uint32_t nch = 2 * (t1 - t0);
   double4_t acc[2][2];
   zero_acc(acc);
   Chunk ca, cb;
@@ -148,15 +77,10 @@ k_mode_gram(const double* __restrict__ X, const double* __restrict__ Y, uint32_t
     load_kmajor(ca, X + off, kModeBlock, k0);
     load_kmajor(cb, Y + off, kModeBlock, k0);
   };
-  if (nch) fetch(0);
-  for (uint32_t ch = 0; ch < nch; ++ch) {
+  accumulate_chunks(acc, s, 2 * (t1 - t0), fetch, [&](uint32_t) {
     store_kmajor(ca, s.X);
     store_kmajor(cb, s.Y);
-    __syncthreads();
-    if (ch + 1 < nch) fetch(ch + 1);
-    mma_chunk(acc, s);
-    __syncthreads();
-  }
+  });
   store_tile(part + (size_t)g * (TB * TB), TB, acc);
 }
 
@@ -203,29 +127,19 @@ k_mode_residual(const double* __restrict__ W, const double* __restrict__ Q, cons
 // ---- host side ----------------------------------------------------------------------------------------
 namespace {
 
-// the plan's tables on the device, one buffer: forward chunks | forward rows | backward chunks | backward rows
-// (all read as uint4) | forward src | backward src | pos (the identity) | rowmap
+// the plan's tables on the device, one buffer; pos is the identity and serves both passes
 struct FsolTables {
-  const uint4 *f_chunks, *f_rows, *b_chunks, *b_rows;
-  const uint32_t *f_src, *b_src, *pos, *rowmap;
+  SubstTables fwd, bwd;
+  const uint32_t* rowmap;
 };
 
 int fsol_prepare(Engine* e, const FactorRef& f, const uint32_t* rowmap, const FactorSolvePlan& p, size_t n_stage,
                  FsolTables* t, uint32_t panels = 1) {
   const JointPlan &pf = p.fwd, &pb = p.bwd;
   const uint32_t nt = f.nt, rows = nt * (uint32_t)TB;
-  std::vector<uint32_t> idx;
-  const size_t o_fc = 0, o_fr = o_fc + pf.chunks.size(), o_bc = o_fr + pf.rows.size(), o_br = o_bc + pb.chunks.size(),
-               o_fs = o_br + pb.rows.size(), o_bs = o_fs + pf.src.size(), o_pos = o_bs + pb.src.size(), o_map = o_pos + nt;
-  idx.reserve(o_map + rows);
-  idx.insert(idx.end(), pf.chunks.begin(), pf.chunks.end());
-  idx.insert(idx.end(), pf.rows.begin(), pf.rows.end());
-  idx.insert(idx.end(), pb.chunks.begin(), pb.chunks.end());
-  idx.insert(idx.end(), pb.rows.begin(), pb.rows.end());
-  idx.insert(idx.end(), pf.src.begin(), pf.src.end());
-  idx.insert(idx.end(), pb.src.begin(), pb.src.end());
-  idx.insert(idx.end(), pf.pos.begin(), pf.pos.end());
-  idx.insert(idx.end(), rowmap, rowmap + rows);
+  IndexPack idx;
+  const size_t o_fc = idx.add(pf.chunks, 4), o_fr = idx.add(pf.rows, 4), o_bc = idx.add(pb.chunks, 4), o_br = idx.add(pb.rows, 4),
+               o_fs = idx.add(pf.src), o_bs = idx.add(pb.src), o_pos = idx.add(pf.pos), o_map = idx.add(rowmap, rowmap + rows);
   const size_t n_x = panels * pf.y_count(), n_slots = (size_t)std::max(p.max_level_chunks(), 1u) * pf.ncb * TB * TB;
   if (e->fs_idx.alloc(idx.size()) != hipSuccess || e->fs_X.alloc(n_x) != hipSuccess ||
       e->fs_slots.alloc(n_slots) != hipSuccess || e->fs_B.alloc(n_stage) != hipSuccess) {
@@ -236,34 +150,18 @@ int fsol_prepare(Engine* e, const FactorRef& f, const uint32_t* rowmap, const Fa
              (n_x + n_slots + n_stage) * sizeof(double) + idx.size() * sizeof(uint32_t), nt, pf.m);
     return e->fail_msg(msg);
   }
-  BAE_HIP(hipMemcpy(e->fs_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  const uint32_t* d = e->fs_idx.p;
-  t->f_chunks = reinterpret_cast<const uint4*>(d + o_fc);
-  t->f_rows = reinterpret_cast<const uint4*>(d + o_fr);
-  t->b_chunks = reinterpret_cast<const uint4*>(d + o_bc);
-  t->b_rows = reinterpret_cast<const uint4*>(d + o_br);
-  t->f_src = d + o_fs;
-  t->b_src = d + o_bs;
-  t->pos = d + o_pos;
-  t->rowmap = d + o_map;
+  BAE_HIP(idx.upload(e->fs_idx));
+  t->fwd = {idx.at<uint4>(o_fc), idx.at<uint4>(o_fr), idx.at(o_fs), idx.at(o_pos)};
+  t->bwd = {idx.at<uint4>(o_bc), idx.at<uint4>(o_br), idx.at(o_bs), idx.at(o_pos)};
+  t->rowmap = idx.at(o_map);
   return 0;
 }
 
 // X <- S^-1 X on the panels, enqueued on e->stream; ev (optional): events 1 and 2 after the two passes
 void fsol_apply(Engine* e, const FactorRef& f, const FactorSolvePlan& p, const FsolTables& t, double* X, Events<4>* ev) {
-  joint_forward_launch(e->stream, p.fwd, t.f_chunks, t.f_rows, t.f_src, t.pos, f.A, f.ld, f.linvT, X, e->fs_slots.p);
+  joint_subst_launch(e->stream, p.fwd, t.fwd, false, f.A, f.ld, f.linvT, nullptr, X, e->fs_slots.p);
   if (ev) (void)ev->record(1, e->stream);
-  const JointPlan& pb = p.bwd;
-  const uint32_t mp = pb.m_pad, ncb = pb.ncb;
-  for (uint32_t v = 0; v < pb.levels(); ++v) {
-    const uint32_t c0 = pb.chunk_level_ptr[v], c1 = pb.chunk_level_ptr[v + 1];
-    if (c1 > c0)
-      hipLaunchKernelGGL(k_fsol_bsolve, dim3(c1 - c0, ncb), dim3(256), 0, e->stream, t.b_chunks + c0, t.b_src, f.A, f.ld,
-                         (const double*)X, mp, e->fs_slots.p);
-    const uint32_t r0 = pb.level_ptr[v], r1 = pb.level_ptr[v + 1];
-    hipLaunchKernelGGL(k_fsol_bepilogue, dim3(r1 - r0, ncb), dim3(256), 0, e->stream, t.b_rows + r0, f.linvT, f.dsgn, X, mp,
-                       (const double*)e->fs_slots.p);
-  }
+  joint_subst_launch(e->stream, p.bwd, t.bwd, true, f.A, f.ld, f.linvT, f.dsgn, X, e->fs_slots.p);
   if (ev) (void)ev->record(2, e->stream);
 }
 
@@ -281,13 +179,10 @@ int factor_solve_run(Engine* e, const FactorRef& f, uint32_t n, const uint32_t* 
   BAE_HIP(hipMemcpyAsync(e->fs_B.p, B, n_io * sizeof(double), hipMemcpyHostToDevice, e->stream));
   Events<4> ev;   // start, forward done, backward done, end
   BAE_HIP(ev.create());
-  const unsigned nb = (unsigned)((n_x + 255) / 256);
-  hipLaunchKernelGGL(k_fsol_scatter, dim3(nb), dim3(256), 0, e->stream, (const double*)e->fs_B.p, m, t.rowmap, n_x, mp,
-                     e->fs_X.p);
+  panel_scatter_launch(e->stream, e->fs_B.p, m, t.rowmap, n_x, mp, e->fs_X.p);
   (void)ev.record(0, e->stream);
   fsol_apply(e, f, p, t, e->fs_X.p, &ev);
-  hipLaunchKernelGGL(k_fsol_gather, dim3(nb), dim3(256), 0, e->stream, (const double*)e->fs_X.p, mp, t.rowmap, n_x, m,
-                     e->fs_B.p);
+  panel_gather_launch(e->stream, e->fs_X.p, mp, t.rowmap, n_x, m, e->fs_B.p);
   (void)ev.record(3, e->stream);
   const hipError_t lerr = hipGetLastError();
   const hipError_t serr = hipEventSynchronize(ev[3]);
@@ -333,8 +228,7 @@ struct DeviceModeOps {
       for (uint32_t c = 0; c < pcols; ++c) B[(size_t)r * kModeBlock + c] = mode_start_value(seed, r, c);
     if (err != hipSuccess) return;
     keep(hipMemcpyAsync(e->fs_B.p, B.data(), B.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_fsol_scatter, dim3((unsigned)((panel + 255) / 256)), dim3(256), 0, e->stream,
-                       (const double*)e->fs_B.p, kModeBlock, t.rowmap, (uint64_t)panel, kModeBlock, P(a));
+    panel_scatter_launch(e->stream, e->fs_B.p, kModeBlock, t.rowmap, (uint64_t)panel, kModeBlock, P(a));
     drain();
   }
   void gram(int a, int b, double* G) {
@@ -397,9 +291,7 @@ int weakest_modes_run(Engine* e, const FactorRef& f, uint32_t n, const uint32_t*
   ModeResult r;
   weakest_modes_iterate(ops, n, k, o, r);
   if (ops.err != hipSuccess) return e->fail(ops.err, "k_mode");
-  const unsigned nb = (unsigned)((ops.panel + 255) / 256);
-  hipLaunchKernelGGL(k_fsol_gather, dim3(nb), dim3(256), 0, e->stream, (const double*)ops.P(r.panel), kModeBlock, t.rowmap,
-                     (uint64_t)ops.panel, kModeBlock, e->fs_B.p);
+  panel_gather_launch(e->stream, ops.P(r.panel), kModeBlock, t.rowmap, (uint64_t)ops.panel, kModeBlock, e->fs_B.p);
   std::vector<double> Qv(n_io);
   BAE_HIP(hipGetLastError());
   BAE_HIP(hipMemcpyAsync(Qv.data(), e->fs_B.p, n_io * sizeof(double), hipMemcpyDeviceToHost, e->stream));

@@ -11,6 +11,10 @@
 //                     block of 64 columns); one launch per level
 //   k_joint_epilogue  Y_I = L_II^-1 (E_I - sum of the row's partial tiles in chunk order), one workgroup per
 //                     (row I, block of 64 columns); one launch per level
+//   k_fsol_bsolve     the same two with L^T, the backward pass of the multi-RHS solve (k_factorsolve.hip launches
+//   k_fsol_bepilogue  it): partial tile sum_{I in chunk} L_IJ^T X_I per (column J, chunk, block of 64 columns), and
+//                     X_J = L_JJ^-T (D_J Y_J - the column's partial tiles in chunk order).  L_IJ is then read as it
+//                     lies in memory, rows = k: it is the k-major operand, and linvT[J] = L_JJ^-T the index-major one
 //   k_joint_gram      partial tile sum_{I in group} Y_I^T D_I Y_I, one workgroup per (group of <= 8 reach rows,
 //                     lower 64 x 64 tile of the output)
 //   k_joint_combine   the groups summed in order, the lower half mirrored into the upper one
@@ -45,58 +49,73 @@ k_joint_init(double* __restrict__ Y, uint64_t count, uint32_t mp, const uint32_t
   Y[t] = col_key[t % mp] == (uint32_t)(t / mp) ? 1.0 : 0.0;
 }
 
-// chunks: (I, position of I, first source, end source) of one level; slot (blockIdx.x, blockIdx.y) = the
-// partial tile sum_{J in chunk} L_IJ Y_J[:, 64 b .. 64 b + 64)
-__global__ void __launch_bounds__(256)
-k_joint_fsolve(const uint4* __restrict__ chunks, const uint32_t* __restrict__ src, const uint32_t* __restrict__ pos,
-               const double* __restrict__ A, uint32_t ld, const double* __restrict__ Y, uint32_t mp,
-               double* __restrict__ slots) {
-  __shared__ Lds s;
+// The substitution with L (T = false: forward, rows I, sources J < I) or with L^T (T = true: the backward pass of
+// the multi-RHS solve, columns J, sources I > J; k_factorsolve.hip launches it).  Panel of tile t: pos[t]; the
+// transposed pass visits every tile row, its panel t is tile t and it has no pos.
+// chunks: (R, position of R, first source, end source) of one level, R the row (column) being solved; slot
+// (blockIdx.x, blockIdx.y) = the partial tile sum_{S in chunk} L_RS Y_S (L_SR^T Y_S) of columns [64 b, 64 b + 64)
+template <bool T>
+__device__ __forceinline__ void subst_partial(Lds& s, const uint4* __restrict__ chunks, const uint32_t* __restrict__ src,
+                                              const uint32_t* __restrict__ pos, const double* __restrict__ A, uint32_t ld,
+                                              const double* __restrict__ Y, uint32_t mp, double* __restrict__ slots) {
   const uint4 c = chunks[blockIdx.x];
-  const uint32_t I = c.x, s0 = c.z, b = blockIdx.y;
-  const uint32_t nch = 2 * (c.w - s0);
+  const uint32_t R = c.x, s0 = c.z, b = blockIdx.y;
   double4_t acc[2][2];
   zero_acc(acc);
   Chunk ca, cb;
   auto fetch = [&](uint32_t ch) {
-    const uint32_t J = src[s0 + (ch >> 1)];
+    const uint32_t S = src[s0 + (ch >> 1)];
     const int k0 = KCH * (int)(ch & 1);
-    load_imajor(ca, A + (size_t)I * TB * ld + (size_t)J * TB, ld, k0);              // X[k][r] = L_IJ[r][k]
-    load_kmajor(cb, Y + (size_t)pos[J] * TB * mp + (size_t)b * TB, mp, k0);         // Y[k][x] = Y_J[k][x]
+    uint32_t panel = S;
+    if constexpr (T) {
+      load_kmajor(ca, A + (size_t)S * TB * ld + (size_t)R * TB, ld, k0);   // X[k][r] = L_SR[k][r], as it lies
+    } else {
+      load_imajor(ca, A + (size_t)R * TB * ld + (size_t)S * TB, ld, k0);   // X[k][r] = L_RS[r][k]
+      panel = pos[S];
+    }
+    load_kmajor(cb, Y + (size_t)panel * TB * mp + (size_t)b * TB, mp, k0);   // Y[k][x] = Y_S[k][x]
   };
-  if (nch) fetch(0);
-  for (uint32_t ch = 0; ch < nch; ++ch) {
-    store_imajor(ca, s.X);
+  accumulate_chunks(acc, s, 2 * (c.w - s0), fetch, [&](uint32_t) {
+    if constexpr (T) store_kmajor(ca, s.X);
+    else store_imajor(ca, s.X);
     store_kmajor(cb, s.Y);
-    __syncthreads();
-    if (ch + 1 < nch) fetch(ch + 1);
-    mma_chunk(acc, s);
-    __syncthreads();
-  }
+  });
   store_tile(slots + ((size_t)blockIdx.x * gridDim.y + b) * (TB * TB), TB, acc);
 }
 
-// rows: (I, first chunk, end chunk, first chunk of the level) of one level.
-// Y_I = L_II^-1 T, T = Y_I (the unit entries) - the row's partial tiles in chunk order.
-__global__ void __launch_bounds__(256)
-k_joint_epilogue(const uint4* __restrict__ rows, const uint32_t* __restrict__ pos, const double* __restrict__ linvT,
-                 double* __restrict__ Y, uint32_t mp, const double* __restrict__ slots) {
-  __shared__ Lds s;
+// rows: (R, first chunk, end chunk, first chunk of the level) of one level.
+// Y_R = G V with V = Y_R (T: D_R Y_R, the sign of row k going on while Y_R is read) - the row's partial tiles in
+// chunk order, and G = L_RR^-1, linvT[R] read k-major (T: L_RR^-T, linvT[R] read index-major).  The sign is a
+// compile-time choice: a run-time test would put a branch around each of the 16 first loads.
+template <bool T>
+__device__ __forceinline__ void subst_epilogue(Lds& s, const uint4* __restrict__ rows, const uint32_t* __restrict__ pos,
+                                               const double* __restrict__ linvT, const double* __restrict__ dsgn,
+                                               double* __restrict__ Y, uint32_t mp, const double* __restrict__ slots) {
   const uint4 r = rows[blockIdx.x];
-  const uint32_t I = r.x, b = blockIdx.y, ncb = gridDim.y;
-  double* YI = Y + (size_t)pos[I] * TB * mp + (size_t)b * TB;
-  const double* G = linvT + (size_t)I * TB * TB;  // G[c][x] = (L_II^-1)[x][c]: X[k = c][i = x]
+  const uint32_t R = r.x, b = blockIdx.y, ncb = gridDim.y;
+  uint32_t panel = R;
+  if constexpr (!T) panel = pos[R];
+  double* YR = Y + (size_t)panel * TB * mp + (size_t)b * TB;
+  const double* G = linvT + (size_t)R * TB * TB;  // linvT[R][c][x] = (L_RR^-1)[x][c]
   const int tid = threadIdx.x;
-  // T first, both 32-row halves at once.  Thread t owns elements e = t + 256 q of the 64 x 64 tile: the 16 loads
-  // of a slot are independent and in flight together; each element subtracts its slots in chunk order
+  // V first, both 32-row halves at once.  Thread t owns elements e = t + 256 q of the 64 x 64 tile; each element
+  // subtracts its slots in chunk order
   double v[16];
 #pragma unroll
-  for (int q = 0; q < 16; ++q) v[q] = YI[(size_t)((tid + 256 * q) / TB) * mp + tid % TB];
+  for (int q = 0; q < 16; ++q) {
+    const int k = (tid + 256 * q) / TB;
+    v[q] = YR[(size_t)k * mp + tid % TB];
+    if constexpr (T) v[q] *= dsgn[(size_t)R * TB + k];
+  }
   const double* sl = slots + ((size_t)(r.y - r.w) * ncb + b) * (TB * TB) + tid;
   for (uint32_t c = r.y; c < r.z; ++c, sl += (size_t)ncb * (TB * TB)) {
     double w[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) w[q] = sl[256 * q];
+    // The 16 loads of a slot are independent and must be in flight together.  Without the barrier the compiler pulls
+    // the first two adds, and the wait they need, in front of the other fourteen loads: a memory round trip more per
+    // slot, 24 % of the substitution where a row has 50 slots.
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < 16; ++q) v[q] -= w[q];
   }
@@ -105,15 +124,46 @@ k_joint_epilogue(const uint4* __restrict__ rows, const uint32_t* __restrict__ po
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     Chunk cg;
-    load_kmajor(cg, G, TB, KCH * h);
-    store_kmajor(cg, s.X);
+    if constexpr (T) {
+      load_imajor(cg, G, TB, KCH * h);
+      store_imajor(cg, s.X);
+    } else {
+      load_kmajor(cg, G, TB, KCH * h);
+      store_kmajor(cg, s.X);
+    }
 #pragma unroll
     for (int q = 0; q < 8; ++q) s.Y[(tid + 256 * q) / TB][tid % TB] = v[8 * h + q];
     __syncthreads();
     mma_chunk(out, s);
     __syncthreads();
   }
-  store_tile(YI, mp, out);
+  store_tile(YR, mp, out);
+}
+
+__global__ void __launch_bounds__(256)
+k_joint_fsolve(const uint4* __restrict__ chunks, const uint32_t* __restrict__ src, const uint32_t* __restrict__ pos,
+               const double* __restrict__ A, uint32_t ld, const double* __restrict__ Y, uint32_t mp,
+               double* __restrict__ slots) {
+  __shared__ Lds s;
+  subst_partial<false>(s, chunks, src, pos, A, ld, Y, mp, slots);
+}
+__global__ void __launch_bounds__(256)
+k_joint_epilogue(const uint4* __restrict__ rows, const uint32_t* __restrict__ pos, const double* __restrict__ linvT,
+                 double* __restrict__ Y, uint32_t mp, const double* __restrict__ slots) {
+  __shared__ Lds s;
+  subst_epilogue<false>(s, rows, pos, linvT, nullptr, Y, mp, slots);
+}
+__global__ void __launch_bounds__(256)
+k_fsol_bsolve(const uint4* __restrict__ chunks, const uint32_t* __restrict__ src, const double* __restrict__ A, uint32_t ld,
+              const double* __restrict__ X, uint32_t mp, double* __restrict__ slots) {
+  __shared__ Lds s;
+  subst_partial<true>(s, chunks, src, nullptr, A, ld, X, mp, slots);
+}
+__global__ void __launch_bounds__(256)
+k_fsol_bepilogue(const uint4* __restrict__ rows, const double* __restrict__ linvT, const double* __restrict__ dsgn,
+                 double* __restrict__ X, uint32_t mp, const double* __restrict__ slots) {
+  __shared__ Lds s;
+  subst_epilogue<true>(s, rows, nullptr, linvT, dsgn, X, mp, slots);
 }
 
 // part[(g, t)] = sum_{q in group g} Y_q[:, bi]^T D_q Y_q[:, bj], t = bi (bi + 1) / 2 + bj, bi >= bj
@@ -126,7 +176,6 @@ k_joint_gram(const double* __restrict__ Y, uint32_t mp, const uint32_t* __restri
   while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
   const uint32_t bj = t - bi * (bi + 1) / 2;
   const uint32_t q0 = g * kJointGramGroup, q1 = min(nr, q0 + kJointGramGroup);
-  const uint32_t nch = 2 * (q1 - q0);
   const int tid = threadIdx.x;
   double4_t acc[2][2];
   zero_acc(acc);
@@ -145,15 +194,10 @@ k_joint_gram(const double* __restrict__ Y, uint32_t mp, const uint32_t* __restri
       ca.v[x].y *= dk;
     }
   };
-  if (nch) fetch(0);
-  for (uint32_t ch = 0; ch < nch; ++ch) {
+  accumulate_chunks(acc, s, 2 * (q1 - q0), fetch, [&](uint32_t) {
     store_kmajor(ca, s.X);
     store_kmajor(cb, s.Y);
-    __syncthreads();
-    if (ch + 1 < nch) fetch(ch + 1);
-    mma_chunk(acc, s);
-    __syncthreads();
-  }
+  });
   store_tile(part + ((size_t)g * gridDim.y + t) * (TB * TB), TB, acc);
 }
 
@@ -265,20 +309,27 @@ k_joint_lmdiag(const uint32_t* __restrict__ lm_ptr, const double* __restrict__ l
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-// The substitution Y <- L^-1 Y over the plan's reach, two launches per level (engine.h; also the forward half of
-// the multi-RHS solve in k_factorsolve.hip).  The tables are the plan's chunks, rows, src and pos on the device.
-void joint_forward_launch(hipStream_t stream, const JointPlan& p, const uint4* d_chunks, const uint4* d_rows,
-                          const uint32_t* d_src, const uint32_t* d_pos, const double* A, uint32_t ld, const double* linvT,
-                          double* Y, double* slots) {
+// The substitution over the levels of a plan, two launches per level (engine.h): Y <- L^-1 Y over the plan's reach
+// (dsgn unused), or with `transposed` the backward pass Y <- L^-T D Y of the multi-RHS solve in k_factorsolve.hip,
+// whose plan holds every tile row.
+void joint_subst_launch(hipStream_t stream, const JointPlan& p, const SubstTables& t, bool transposed, const double* A,
+                        uint32_t ld, const double* linvT, const double* dsgn, double* Y, double* slots) {
   const uint32_t mp = p.m_pad, ncb = p.ncb;
   for (uint32_t v = 0; v < p.levels(); ++v) {
     const uint32_t c0 = p.chunk_level_ptr[v], c1 = p.chunk_level_ptr[v + 1];
-    if (c1 > c0)
-      hipLaunchKernelGGL(k_joint_fsolve, dim3(c1 - c0, ncb), dim3(256), 0, stream, d_chunks + c0, d_src, d_pos, A, ld,
+    if (c1 > c0 && transposed)
+      hipLaunchKernelGGL(k_fsol_bsolve, dim3(c1 - c0, ncb), dim3(256), 0, stream, t.chunks + c0, t.src, A, ld,
+                         (const double*)Y, mp, slots);
+    else if (c1 > c0)
+      hipLaunchKernelGGL(k_joint_fsolve, dim3(c1 - c0, ncb), dim3(256), 0, stream, t.chunks + c0, t.src, t.pos, A, ld,
                          (const double*)Y, mp, slots);
     const uint32_t r0 = p.level_ptr[v], r1 = p.level_ptr[v + 1];
-    hipLaunchKernelGGL(k_joint_epilogue, dim3(r1 - r0, ncb), dim3(256), 0, stream, d_rows + r0, d_pos, linvT, Y, mp,
-                       (const double*)slots);
+    if (transposed)
+      hipLaunchKernelGGL(k_fsol_bepilogue, dim3(r1 - r0, ncb), dim3(256), 0, stream, t.rows + r0, linvT, dsgn, Y, mp,
+                         (const double*)slots);
+    else
+      hipLaunchKernelGGL(k_joint_epilogue, dim3(r1 - r0, ncb), dim3(256), 0, stream, t.rows + r0, t.pos, linvT, Y, mp,
+                         (const double*)slots);
   }
 }
 
@@ -331,17 +382,11 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<
   JointPlan p;
   build_joint_plan(e->nzL_host, nt, tiles, M, p);
   const uint32_t nr = (uint32_t)p.reach.size(), mp = p.m_pad, ncb = p.ncb, ntl = ncb * (ncb + 1) / 2;
-  // one index buffer: chunks | rows (both read as uint4) | src | pos | reach | col_key
-  std::vector<uint32_t> idx;
-  const size_t o_chunks = 0, o_rows = p.chunks.size(), o_src = o_rows + p.rows.size(), o_pos = o_src + p.src.size(),
-               o_reach = o_pos + nt, o_key = o_reach + nr;
-  idx.reserve(o_key + mp);
-  idx.insert(idx.end(), p.chunks.begin(), p.chunks.end());
-  idx.insert(idx.end(), p.rows.begin(), p.rows.end());
-  idx.insert(idx.end(), p.src.begin(), p.src.end());
-  idx.insert(idx.end(), p.pos.begin(), p.pos.end());
-  idx.insert(idx.end(), p.reach.begin(), p.reach.end());
-  for (uint32_t c = 0; c < mp; ++c) idx.push_back(c < Ms ? p.pos[sel[c] / TB] * TB + sel[c] % TB : kJointNone);
+  std::vector<uint32_t> key(mp, kJointNone);
+  for (uint32_t c = 0; c < Ms; ++c) key[c] = p.pos[sel[c] / TB] * TB + sel[c] % TB;
+  IndexPack idx;   // one index buffer
+  const size_t o_chunks = idx.add(p.chunks, 4), o_rows = idx.add(p.rows, 4), o_src = idx.add(p.src), o_pos = idx.add(p.pos),
+               o_reach = idx.add(p.reach), o_key = idx.add(key);
   const size_t n_y = p.y_count(), n_slots = (size_t)std::max(p.max_level_chunks, 1u) * ncb * TB * TB,
                n_part = (size_t)p.gram_groups * ntl * TB * TB, n_out = (size_t)M * M;
   const size_t bytes = (n_y + n_slots + n_part + n_out) * sizeof(double) + idx.size() * sizeof(uint32_t);
@@ -355,30 +400,27 @@ int jointcov_run(Engine* e, const std::vector<uint32_t>& sel, const std::vector<
              bytes, nr, M);
     return e->fail_msg(msg);
   }
-  BAE_HIP(hipMemcpy(e->jc_idx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  const uint32_t* d_idx = e->jc_idx.p;
-  const uint4* d_chunks = reinterpret_cast<const uint4*>(d_idx + o_chunks);
-  const uint4* d_rows = reinterpret_cast<const uint4*>(d_idx + o_rows);
+  BAE_HIP(idx.upload(e->jc_idx));
+  const SubstTables tab = {idx.at<uint4>(o_chunks), idx.at<uint4>(o_rows), idx.at(o_src), idx.at(o_pos)};
   Events<5> ev;   // start, substitution done, end; around the right-hand-side pass
   BAE_HIP(ev.create());
   (void)ev.record(0, e->stream);
   // (a request whose columns are all zero has an empty reach: nothing to initialise, solve or multiply)
   if (n_y)
     hipLaunchKernelGGL(k_joint_init, dim3((unsigned)((n_y + 255) / 256)), dim3(256), 0, e->stream, e->jc_Y.p, (uint64_t)n_y,
-                       mp, d_idx + o_key);
+                       mp, idx.at(o_key));
   const bool rhs = nl && nr;
   if (rhs) {
     (void)ev.record(3, e->stream);
-    if (LM == 1) hipLaunchKernelGGL(k_joint_rhs<1>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, Ms, d_idx + o_pos, e->jc_Y.p, mp);
-    else hipLaunchKernelGGL(k_joint_rhs<3>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, Ms, d_idx + o_pos, e->jc_Y.p, mp);
+    if (LM == 1) hipLaunchKernelGGL(k_joint_rhs<1>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, Ms, tab.pos, e->jc_Y.p, mp);
+    else hipLaunchKernelGGL(k_joint_rhs<3>, dim3((nl + 3) / 4), dim3(256), 0, e->stream, g, nl, d_ids, Ms, tab.pos, e->jc_Y.p, mp);
     (void)ev.record(4, e->stream);
   }
-  joint_forward_launch(e->stream, p, d_chunks, d_rows, d_idx + o_src, d_idx + o_pos, e->A.p, st.ld, linvT, e->jc_Y.p,
-                       e->jc_slots.p);
+  joint_subst_launch(e->stream, p, tab, false, e->A.p, st.ld, linvT, nullptr, e->jc_Y.p, e->jc_slots.p);
   (void)ev.record(1, e->stream);
   if (p.gram_groups)
     hipLaunchKernelGGL(k_joint_gram, dim3(p.gram_groups, ntl), dim3(256), 0, e->stream, (const double*)e->jc_Y.p, mp,
-                       d_idx + o_reach, nr, dsgn, e->jc_part.p);
+                       idx.at(o_reach), nr, dsgn, e->jc_part.p);
   hipLaunchKernelGGL(k_joint_combine, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, e->stream,
                      (const double*)e->jc_part.p, p.gram_groups, ntl, M, e->jc_out.p);
   if (nl) {

@@ -11,10 +11,11 @@
 //                         all-done word and one word per column block
 //   k_pcgp_update2        x += alpha_j p, p = z + beta_j p (p = z, p = x), every column masked by its action bits
 //
-// and k_pcgp_scatter / k_pcgp_gather move the caller's B and X between the host layout and the panels.  Every kernel
-// of a pass but k_pcgp_decide returns at once when the all-done word (or the word of its column block) is set, so
-// the host enqueues check_every passes blind and reads one word back per batch.  FP64; the tile products run on
-// v_mfma_f64_16x16x4_f64 with the staging of tile_mma.h; no atomics, no memory-side adds, every sum in a fixed order.
+// and k_panel_scatter / k_panel_gather (k_factorsolve.hip) move the caller's B and X between the host layout and the
+// panels.  Every kernel of a pass but k_pcgp_decide returns at once when the all-done word (or the word of its column
+// block) is set, so the host enqueues check_every passes blind and reads one word back per batch.  FP64; the tile
+// products run on v_mfma_f64_16x16x4_f64 with the staging of tile_mma.h; no atomics, no memory-side adds, every sum
+// in a fixed order.
 #include "engine.h"
 #include "pcg_panel.h"
 #include "tile_mma.h"
@@ -35,25 +36,6 @@ __global__ void k_pcg_blocks(const double* __restrict__ A, uint32_t ld, const ui
 // flags: [0] every column is done, [1 + b] every column of block b is done
 static __device__ __forceinline__ bool pcgp_idle(const uint32_t* __restrict__ flags, uint32_t b) {
   return flags[0] != 0 || flags[1 + b] != 0;
-}
-
-// rowmap[i]: the caller's row of matrix row i (kPcgNone for a padding row)
-__global__ void __launch_bounds__(256)
-k_pcgp_scatter(const double* __restrict__ B, uint32_t m, const uint32_t* __restrict__ rowmap, uint64_t count, uint32_t mp,
-               double* __restrict__ X) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= count) return;
-  const uint32_t c = (uint32_t)(t % mp), r = rowmap[t / mp];
-  X[t] = (c < m && r != kPcgNone) ? B[(size_t)r * m + c] : 0.0;
-}
-
-__global__ void __launch_bounds__(256)
-k_pcgp_gather(const double* __restrict__ X, uint32_t mp, const uint32_t* __restrict__ rowmap, uint64_t count, uint32_t m,
-              double* __restrict__ out) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= count) return;
-  const uint32_t c = (uint32_t)(t % mp), r = rowmap[t / mp];
-  if (c < m && r != kPcgNone) out[(size_t)r * m + c] = X[t];
 }
 
 // 32 k-columns of the symmetric diagonal tile in the index-major layout of load_imajor, from its lower triangle:
@@ -91,6 +73,8 @@ k_pcgp_spmm(const uint4* __restrict__ chunks, const uint2* __restrict__ src, con
     else load_diag_sym(ca, A + (size_t)I * TB * ld + (size_t)I * TB, ld, k0);
     load_kmajor(cb, P + (size_t)sr.x * TB * mp + (size_t)b * TB, mp, k0);                               // Y[k][j] = P_T[k][j]
   };
+  // (not accumulate_chunks: through it the same instructions come out in another order, and a product that takes
+  // 84 us at 1000 poses and up to 64 columns takes 87 to 90; profiles/tile_pipeline_ab.txt has the three-library run)
   if (nch) fetch(0);
   for (uint32_t ch = 0; ch < nch; ++ch) {
     if (src[s0 + (ch >> 1)].y == kPanelCol) store_kmajor(ca, s.X);
@@ -297,22 +281,13 @@ int pcg_panel_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld,
   build_pcg_panel_plan(plan, m, pp);
   const uint32_t mp = pp.m_pad, ncb = pp.ncb, nflag = 1 + ncb;
   const size_t N = (size_t)ld * mp, n_io = (size_t)n * m;
-  // the tables in one buffer: chunks (uint4) | src (uint2) | blk (uint2) | blocks (uint2) | chunk_ptr | rowmap
-  std::vector<uint32_t> idx;
-  const size_t o_ch = 0, o_src = o_ch + pp.chunks.size(), o_blk = o_src + pp.src.size(), o_blocks = o_blk + blk.size(),
-               o_cp = o_blocks + ((blocks.size() + 3) / 4) * 4, o_map = o_cp + pp.chunk_ptr.size();
-  idx.reserve(o_map + ld);
-  idx.insert(idx.end(), pp.chunks.begin(), pp.chunks.end());
-  idx.insert(idx.end(), pp.src.begin(), pp.src.end());
-  idx.insert(idx.end(), blk.begin(), blk.end());
-  idx.insert(idx.end(), blocks.begin(), blocks.end());
-  idx.resize(o_cp, 0);
-  idx.insert(idx.end(), pp.chunk_ptr.begin(), pp.chunk_ptr.end());
-  idx.insert(idx.end(), rowmap, rowmap + ld);
+  IndexPack idx;   // the tables in one buffer
+  const size_t o_ch = idx.add(pp.chunks, 4), o_src = idx.add(pp.src, 2), o_blk = idx.add(blk, 2), o_blocks = idx.add(blocks, 2),
+               o_cp = idx.add(pp.chunk_ptr, 4), o_map = idx.add(rowmap, rowmap + ld);
   Events<4> ev;   // 0 / 3 the solve, 1 / 2 one product of a batch
   BAE_HIP(ev.create());
   int rc;
-  if ((rc = upload_async(e, w.idx, idx.data(), idx.size())) || (rc = upload_async(e, w.nz, nz.data(), nz.size()))) return rc;
+  if ((rc = idx.upload_async(e, w.idx)) || (rc = upload_async(e, w.nz, nz.data(), nz.size()))) return rc;
   BAE_HIP(w.stage.alloc(n_io));
   BAE_HIP(w.B.alloc(N)); BAE_HIP(w.X.alloc(N)); BAE_HIP(w.P.alloc(N)); BAE_HIP(w.Z.alloc(N)); BAE_HIP(w.Q.alloc(N));
   BAE_HIP(w.R.alloc(2 * N));
@@ -323,13 +298,9 @@ int pcg_panel_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld,
   BAE_HIP(w.colu.alloc((size_t)2 * mp + 2 * nflag));
   BAE_HIP(w.state.alloc((size_t)2 * mp));
   BAE_HIP(w.status.alloc(2));
-  const uint32_t* d = w.idx.p;
-  const uint4* d_chunks = reinterpret_cast<const uint4*>(d + o_ch);
-  const uint2* d_src = reinterpret_cast<const uint2*>(d + o_src);
-  const uint2* d_blk = reinterpret_cast<const uint2*>(d + o_blk);
-  const uint2* d_blocks = reinterpret_cast<const uint2*>(d + o_blocks);
-  const uint32_t* d_cp = d + o_cp;
-  const uint32_t* d_map = d + o_map;
+  const uint4* d_chunks = idx.at<uint4>(o_ch);
+  const uint2 *d_src = idx.at<uint2>(o_src), *d_blk = idx.at<uint2>(o_blk), *d_blocks = idx.at<uint2>(o_blocks);
+  const uint32_t *d_cp = idx.at(o_cp), *d_map = idx.at(o_map);
   double *pq_part = w.parts.p, *rz_part = pq_part + (size_t)nt * mp, *rr_part = rz_part + (size_t)nt * mp;
   double *pq = w.colv.p, *alpha1 = pq + mp, *alpha2 = alpha1 + mp, *beta = alpha2 + mp;
   uint32_t *act = w.colu.p, *run = act + mp, *flags = run + mp;   // flags: two copies of nflag words
@@ -348,8 +319,7 @@ int pcg_panel_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld,
   BAE_HIP(hipMemsetAsync(w.X.p, 0, N * sizeof(double), s));
   BAE_HIP(hipMemsetAsync(w.P.p, 0, N * sizeof(double), s));
   BAE_HIP(hipMemsetAsync(w.minv.p, 0, (size_t)ld * 16 * sizeof(double), s));
-  const unsigned nb_io = (unsigned)((N + 255) / 256);
-  hipLaunchKernelGGL(k_pcgp_scatter, dim3(nb_io), dim3(256), 0, s, (const double*)w.stage.p, m, d_map, (uint64_t)N, mp, w.B.p);
+  panel_scatter_launch(s, w.stage.p, m, d_map, (uint64_t)N, mp, w.B.p);
   if (nblocks)
     hipLaunchKernelGGL(k_pcg_blocks, dim3((nblocks + 3) / 4), dim3(64), 0, s, dA, ld, (const uint8_t*)w.nz.p, nt, d_blocks,
                        nblocks, w.minv.p, w.status.p);
@@ -397,7 +367,7 @@ int pcg_panel_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld,
     }
     if (done) break;
   }
-  hipLaunchKernelGGL(k_pcgp_gather, dim3(nb_io), dim3(256), 0, s, (const double*)w.X.p, mp, d_map, (uint64_t)N, m, w.stage.p);
+  panel_gather_launch(s, w.X.p, mp, d_map, (uint64_t)N, m, w.stage.p);
   BAE_HIP(ev.record(3, s));
   BAE_HIP(hipGetLastError());
   std::vector<PcgState> cols(mp);

@@ -40,7 +40,6 @@ __device__ __forceinline__ void k_loop(double4_t (&acc)[2][2], Lds& s, uint32_t 
                                        uint32_t m, const double* __restrict__ A, size_t ld,
                                        const uint32_t* __restrict__ slot, uint32_t nt,
                                        const double* __restrict__ store) {
-  const uint32_t nch = 2 * m;
   Chunk ca, cb;
   bool a_imajor = false;
   auto fetch = [&](uint32_t ch) {
@@ -58,16 +57,11 @@ __device__ __forceinline__ void k_loop(double4_t (&acc)[2][2], Lds& s, uint32_t 
     }
     load_kmajor(cb, A + (size_t)K * TB * ld + (size_t)J * TB, ld, k0);
   };
-  if (nch) fetch(0);
-  for (uint32_t ch = 0; ch < nch; ++ch) {
+  accumulate_chunks(acc, s, 2 * m, fetch, [&](uint32_t) {
     if (a_imajor) store_imajor(ca, s.X);
     else store_kmajor(ca, s.X);
     store_kmajor(cb, s.Y);
-    __syncthreads();
-    if (ch + 1 < nch) fetch(ch + 1);
-    mma_chunk(acc, s);
-    __syncthreads();
-  }
+  });
 }
 
 // Epilogue product: out = M x L_JJ^-1 with M[r][x] = sgn * T[r][x] (+ L_JJ^-T[r][x] d_x when DIAG), T in acc.

@@ -27,6 +27,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "none_row.h"
+
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -41,7 +43,7 @@ namespace bae {
 
 static const uint32_t kPcgMaxBlock = 16;   // largest preconditioner block (PoseSize 15)
 static const uint32_t kPcgCoarseMax = 1024;   // BA_HIP_PCG_COARSE_MAX: coarse unknowns
-static const uint32_t kPcgNone = 0xffffffffu;
+static const uint32_t kPcgNone = kNoneRow;
 enum : uint32_t { kPcgInit = 0, kPcgIter = 1, kPcgVerify = 2 };
 enum : uint32_t { kPcgStep = 1 /* x += alpha p */, kPcgDir = 2 /* p = z + beta p */, kPcgRestart = 4 /* p = z */ };
 

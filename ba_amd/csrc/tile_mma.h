@@ -1,5 +1,6 @@
-// The 64 x 64 FP64 tile product of the kernels that read the kept factor (k_selinv.hip, k_jointcov.hip; the
-// accumulator layout also serves k_pcg_coarse.hip).  Device only.
+// The 64 x 64 FP64 tile product of the kernels that read the kept factor or the assembled S (k_selinv.hip,
+// k_jointcov.hip, k_factorsolve.hip, k_pcg_panel.hip; the accumulator layout also serves k_pcg_coarse.hip): the
+// loads and stores of a chunk and the pipelined K loop (accumulate_chunks).  Device only.
 //
 // One workgroup of 256 threads forms one output tile on v_mfma_f64_16x16x4_f64.  Wave w owns the 32 x 32 quarter
 // at rows rb = 32 (w >> 1), columns cb = 32 (w & 1), as 2 x 2 MFMA blocks acc[ti][tj] of 16 x 16.  Lane l holds of
@@ -88,6 +89,21 @@ __device__ __forceinline__ void mma_chunk(double4_t (&acc)[2][2], const Lds& s) 
     acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
     acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
     acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+  }
+}
+
+// The pipelined K loop of every tile product: acc += sum over nch chunks of X^T Y.  fetch(ch) loads chunk ch into the
+// caller's Chunk registers, stage(ch) stores those registers to s.X and s.Y; chunk ch + 1 is fetched while the
+// matrix cores work on chunk ch.  Every thread of the workgroup calls it with the same nch (it owns the barriers).
+template <class Fetch, class Stage>
+__device__ __forceinline__ void accumulate_chunks(double4_t (&acc)[2][2], Lds& s, uint32_t nch, Fetch fetch, Stage stage) {
+  if (nch) fetch(0);
+  for (uint32_t ch = 0; ch < nch; ++ch) {
+    stage(ch);
+    __syncthreads();
+    if (ch + 1 < nch) fetch(ch + 1);
+    mma_chunk(acc, s);
+    __syncthreads();
   }
 }
 
