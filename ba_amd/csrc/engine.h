@@ -124,6 +124,13 @@ struct Engine {
   const double* pose_cam_ptr() const { return prob.pose_cam_params.empty() ? nullptr : pose_cam.p; }
   DBuf<int32_t> pose_opt, lm_opt;
   DBuf<uint16_t> pose_mask;
+  // pose_mask holds the masks of the last ba_hip_set_pose_masks.  What reads the Jacobians of the last linearisation
+  // after the fact (k_pplever.hip) needs the masks that linearisation ran with: pose_mask itself while
+  // mask_version == lin_mask_version, afterwards pose_mask_lin, which ba_hip_set_pose_masks fills before it overwrites
+  // pose_mask for the first time since that linearisation.  (Version counters: beside the record of lifecycle.h.)
+  DBuf<uint16_t> pose_mask_lin;
+  uint64_t mask_version = 0, lin_mask_version = 0;
+  const uint16_t* lin_pose_mask() const { return mask_version == lin_mask_version ? pose_mask.p : pose_mask_lin.p; }
   DBuf<uint32_t> lm_ref_pose, lm_ref_cam;
   DBuf<uint32_t> lm_ptr;            // [L+1] CSR over sorted observations
   DBuf<double> obs_z;               // [O][2]

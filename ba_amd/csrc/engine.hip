@@ -361,6 +361,8 @@ static int build_structure(Engine* e) {
   BAE_HIP(e->twp.alloc(std::max<size_t>((size_t)st.P * kRt, 1)));
   BAE_HIP(e->pose_mask.alloc(std::max<size_t>((size_t)st.P + st.Pact, 1)));
   BAE_HIP(hipMemsetAsync(e->pose_mask.p, 0, e->pose_mask.bytes(), e->stream));
+  BAE_HIP(e->pose_mask_lin.alloc(std::max<size_t>((size_t)st.P + st.Pact, 1)));
+  e->lin_mask_version = e->mask_version;   // no linearisation yet: nothing reads the copy
   BAE_HIP(e->lm_outliers.alloc(std::max<size_t>(st.L, 1)));
   BAE_HIP(hipMemsetAsync(e->lm_outliers.p, 0, e->lm_outliers.bytes(), e->stream));
   // per-iteration buffers
@@ -498,6 +500,12 @@ int upload_cameras(Engine* e, bool eval_only) {
 
 static int set_masks_device(Engine* e, const std::vector<uint16_t>& by_id) {
   const Structure& st = e->st;
+  // the factor in A stays readable (lifecycle.h: masks_changed) and so do the pose-pose Jacobians of its linearisation:
+  // keep the masks they were built with for ba_hip_get_pose_pose_leverages
+  if (e->mask_version == e->lin_mask_version)
+    BAE_HIP(hipMemcpyAsync(e->pose_mask_lin.p, e->pose_mask.p, ((size_t)st.P + st.Pact) * sizeof(uint16_t),
+                           hipMemcpyDeviceToDevice, e->stream));
+  ++e->mask_version;
   std::vector<uint16_t> m((size_t)st.P + st.Pact, 0);
   for (uint32_t p = 0; p < st.P; ++p) {
     m[p] = by_id[p];
@@ -1087,6 +1095,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   t_l.mark();
   EventTimer t_s(e);
   e->held.linearize_writes_A();
+  e->lin_mask_version = e->mask_version;   // the rows above and the system about to be gathered carry the current masks
   if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) { (void)defer_flush(e); return rc; }
   // dense priors after k_pp_scatter, in prior order; their E_p is folded into unary_error
   if ((rc = launch_priors(e, 1, &e->prior_err_h))) { (void)defer_flush(e); return rc; }

@@ -141,7 +141,7 @@ int pose_pose_leverages_run(Engine* e, int kind, uint32_t n, const uint32_t* ids
   if (n == 0) return 0;
   PPLevArgs v;
   v.res_p1 = e->pp_res_p1.p; v.res_p2 = e->pp_res_p2.p;
-  v.pose_opt = e->pose_opt.p; v.pose_mask = e->pose_mask.p;
+  v.pose_opt = e->pose_opt.p; v.pose_mask = e->lin_pose_mask();   // the masks of the linearisation whose Jacobians pp_dz holds
   v.pp_dz = e->pp_dz.p; v.pp_info = e->pp_info.p;
   v.bin_s = e->bin_cov_inv_sqrt.p; v.bin_w = e->bin_w.p;
   v.slot = e->sig_slot.p; v.store = e->sig.p;

@@ -1,6 +1,7 @@
 """The engine's lifecycle record (ba_amd/csrc/lifecycle.h) on the CPU: ba_hostcheck_lifecycle replays a list of
 events on a fresh record and returns the flags after each one.  The sequences below are the event table of DESIGN.md
-("What the engine holds and what drops it") stated as a test."""
+("What the engine holds and what drops it") stated as a test.  The second half derives the event x reader matrix of
+lifecycle_cases.py from the same record: what test_lifecycle_gpu.py then asks of the engine."""
 import ctypes
 
 import numpy as np
@@ -8,16 +9,8 @@ import pytest
 
 from helpers import hostcheck_lib
 
-# the enums HeldBit and HeldEvent of lifecycle.h, in their order
-BITS = ("finalized", "snapshot", "err0", "err1", "lin", "dog_jrhs", "factored", "foreign", "pcg_solved", "pcg_last",
-        "pcg_coarse_last", "sig", "pattern", "marg", "square_cleared")
-EVENTS = ("problem_changed", "calibration_changed", "pose_cam_params_changed", "finalize_begins", "structure_rebuilt",
-          "finalize_succeeded", "sharding_changed", "pattern_built", "solve_begins", "masks_changed", "linearize_begins",
-          "linearize_writes_A", "linearize_succeeded", "gn_solve_begins", "solved_by_pcg", "solved_directly",
-          "standalone_factorisation", "pcg_run_begins", "pcg_run_finished_plain", "pcg_run_finished_coarse",
-          "dogleg_sums_ok", "dogleg_sums_failed", "step_applied_to_0", "step_applied_to_1", "rolled_back",
-          "residuals_evaluated_at_0", "residuals_evaluated_at_1", "selinv_computed", "selinv_released",
-          "marginalize_failed", "marginalized", "marginalization_released", "square_cleared", "square_dirty")
+from lifecycle_cases import BITS, EVENTS   # the enums HeldBit and HeldEvent of lifecycle.h, in their order
+import lifecycle_cases as lcs
 
 FINALIZE = ("finalize_begins", "structure_rebuilt", "finalize_succeeded", "solve_begins", "masks_changed")
 LINEARIZE = ("linearize_begins", "linearize_writes_A", "pattern_built", "square_cleared", "linearize_succeeded")
@@ -160,3 +153,201 @@ def test_single_drops(event, drops):
     held = after(*seq)
     assert drops <= held
     assert after(*seq, event) == held - drops
+
+
+# ---- the event x reader matrix (lifecycle_cases.py; the device side is test_lifecycle_gpu.py) ------------------
+def test_the_tables_name_codes_of_the_header():
+    for ev in lcs.EVENT_LIST:
+        assert set(ev.codes) <= set(EVENTS), ev.name
+    for r in lcs.READERS + [lcs.CALIBRATION_READER]:
+        assert set(r.reads) <= set(BITS) and set(r.before_codes) <= set(EVENTS), r.name
+    assert len({ev.name for ev in lcs.EVENT_LIST}) == len(lcs.EVENT_LIST)
+    assert len({r.name for r in lcs.READERS}) == len(lcs.READERS)
+
+
+def test_every_cell_is_decided_by_the_bits_its_reader_reads():
+    """For every event sequence of the table the replayed bits give the reader's rule all it needs: the outcome does
+    not move when any bit outside reader.reads is flipped, and it is a refusal with a message or a plain serve."""
+    cells = lcs.table()
+    assert len(cells) == len(lcs.EVENT_LIST) * len(lcs.READERS)
+    for c in cells:
+        r = lcs.READER[c.reader]
+        base = r.rule(c.bits)
+        assert base[0] in ("serve", "refuse") and (base[0] == "serve" or (base[1] in lcs.KINDS and base[2]))
+        for b in set(BITS) - set(r.reads):
+            assert r.rule(c.bits ^ {b}) == base, (c, b)
+
+
+def test_every_reader_is_reached_in_every_way_its_rule_allows():
+    """refuse, serve a new system, serve unchanged: each at least once per reader; a kind that no event / reader pair
+    reaches is reported."""
+    cells = lcs.table()
+    missing = [(r.name, k) for r in lcs.READERS for k in ("refuse", "new", "unchanged")
+               if not any(c.reader == r.name and c.kind == k for c in cells)]
+    assert not missing, missing
+
+
+# the refusal kinds each reader's guard can produce (the sharded / distributed branches are out of scope)
+CAN_REFUSE = {
+    "kept factor": ("not finalized", "no factor", "PCG left no factor", "foreign factor"),
+    "panel": ("not finalized", "no PCG solve", "direct solver holds the factor", "re-linearised since the PCG solve"),
+    "marginalize": ("not finalized", "no linearisation"),
+    "check_solve": ("not finalized", "no finished solve"),
+    "get_S": ("not finalized",),
+    "pcg_stats": ("no PCG statistics",),
+}
+
+
+def _guard(name):
+    if name in ("marginalize", "check_solve", "get_S", "pcg_stats"):
+        return name
+    return "panel" if name in ("pcg_panel_solve_system", "joint_marginals_pcg") else "kept factor"
+
+
+def test_every_refusal_kind_is_reached():
+    """not finalized, no factor, PCG left no factor, foreign factor, no linearisation, no PCG solve, direct solver
+    holds the factor (and the third message of pcg_panel_ready): by at least one cell per reader that can produce
+    it.  The marginal readers reach "foreign factor" through their cold variant or after release_marginals."""
+    cells = lcs.table()
+    got = {}
+    for c in cells:
+        if c.kind == "refuse":
+            got.setdefault(c.reader[:-5] if c.reader.endswith("_cold") else c.reader, set()).add(c.refusal)
+    # the leverages have no cold variant of their own: after release_marginals + a stand-alone solve they refuse too
+    t = lcs.Tracker(lcs.SETUP + ("standalone_factorisation", "selinv_released"))
+    for r in lcs.READERS:
+        if r.reads == lcs.READER["pose_marginals"].reads and not r.before:
+            out, _ = t.expect(r)
+            assert out[:2] == ("refuse", "foreign factor"), r.name
+            got.setdefault(r.name, set()).add(out[1])
+    for r in lcs.READERS:
+        if r.before:
+            continue
+        want = set(CAN_REFUSE[_guard(r.name)])
+        assert want <= got.get(r.name, set()), (r.name, want - got.get(r.name, set()))
+    for kind in ("not finalized", "no factor", "PCG left no factor", "foreign factor", "no linearisation", "no PCG solve",
+                 "direct solver holds the factor"):
+        assert any(c.refusal == kind for c in cells), kind
+
+
+@pytest.mark.parametrize("drop,readers", [
+    ("foreign", ("joint_marginals", "factor_solve", "weakest_modes", "joint_state_marginals", "pose_marginals_cold")),
+    ("factored", ("pose_marginals", "factor_solve")),
+    ("pcg_solved", ("landmark_marginals", "joint_marginals")),
+    ("finalized", ("projection_leverages", "weakest_modes")),
+    ("lin", ("marginalize",)),
+])
+def test_a_rule_that_ignores_a_flag_is_noticed(drop, readers):
+    """The negative check: a reader rule that does not look at factor_foreign, lin_valid (or factored, pcg_solved,
+    finalized) derives a matrix that differs from the table's in at least one cell of that reader."""
+    want = {(c.event, c.reader): (c.kind, c.refusal) for c in lcs.table()}
+    for name in readers:
+        r = lcs.READER[name]
+        if name == "marginalize":
+            blind = lcs.rule_marginalize(honour=tuple(b for b in ("finalized", "lin") if b != drop))
+        else:
+            honour = tuple(b for b in ("finalized", "factored", "pcg_solved", "foreign") if b != drop)
+            who = "x"
+            blind = (lcs.rule_marginals if "sig" in r.reads else lcs.rule_kept_factor)(who, honour=honour)
+        got = {(c.event, c.reader): (c.kind, c.refusal) for c in lcs.table(rules={name: blind})}
+        differ = [k for k in want if k[1] == name and want[k] != got[k]]
+        assert differ, "no cell of %s notices a rule without %s" % (name, drop)
+
+
+def test_documented_matrix_is_the_derived_one():
+    """DESIGN.md section 18 holds the matrix as lifecycle_cases.matrix_markdown() prints it"""
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "DESIGN.md"), encoding="utf-8") as f:
+        doc = f.read()
+    assert lcs.matrix_markdown() in doc
+
+
+# ---- states A and B are far enough apart (the oracle on the CPU) ------------------------------------------------
+def _oracle_system(sc, pa, obs, poses, terms):
+    import copy
+    from oracle import pyoracle as po
+    from helpers import gn_options
+    import pplever_cases as pc
+    ba = po.OracleBundleAdjuster(1, 6)
+    ba.Init(gn_options(po, apply_results=0))
+    ba.AddCamera(sc.cam_params)
+    ba.add_poses(poses, is_active=pa)
+    ba.add_landmarks(sc.landmarks, sc.lm_ref_pose)
+    ba.add_projection_residuals(*obs)
+    s2 = copy.copy(sc)
+    s2.poses = poses
+    pc.add_to_oracle(ba, s2, terms)
+    ba.Solve(1)
+    S = ba.S()
+    S = np.where(S == 0.0, S.T, S)
+    dz = pc.oracle_jacobians(ba, terms)[0]
+    return S, ba.rhs(), dz, ba.proj_jacobians()
+
+
+def test_states_are_separated():
+    """The dense references of states A and B, from the oracle's S on the CPU: for the fixed perturbation SHIFT every
+    reader's reference at B lies more than 100 tolerances from the one at A, in the reader's own error measure — a
+    stale read of A's numbers cannot pass B's check.  (The device test asserts the same on the engine's numbers.)"""
+    import leverage_cases as lc
+    import pplever_cases as pc
+    sc, pa, obs, poses_a, poses_b = lcs.scene_AB()
+    terms = pc.helper_terms(sc, lcs.P)
+    (Sa, ra, dza, ja), (Sb, rb, dzb, jb) = (_oracle_system(sc, pa, obs, p, terms) for p in (poses_a, poses_b))
+    assert Sa.shape == Sb.shape == (72, 72)
+    tol = max(lc.tolerance(Sa), lc.tolerance(Sb))
+    cond = max(np.linalg.cond(Sa), np.linalg.cond(Sb))
+    pcg_bound = cond * lcs.PCG_TOL + 4.5 * np.finfo(np.float64).eps * cond
+    Ia, Ib = np.linalg.inv(Sa), np.linalg.inv(Sb)
+    d = np.sqrt(np.diag(Ib))
+    rows = lc.natural_rows(pa)
+    rr = lambda ids: np.array([rows[p] + x for p in ids for x in range(6)])
+    corr = lambda r, c: float((np.abs(Ia - Ib)[np.ix_(r, c)] / np.outer(d[r], d[c])).max())
+    sep = {}
+    sep["pose_marginals"] = min(corr(rr([p]), rr([p])) for p in lcs.POSE_IDS) / tol
+    sep["pose_pair_marginals"] = min(corr(rr([a]), rr([b])) for a, b in zip(lcs.PAIR_A, lcs.PAIR_B)) / tol
+    sep["joint_marginals"] = corr(rr(lcs.JOINT_IDS), rr(lcs.JOINT_IDS)) / tol
+    Xa, Xb = Ia @ lcs.RHS, Ib @ lcs.RHS
+    rel = float((np.linalg.norm(Xa - Xb, axis=0) / np.linalg.norm(Xb, axis=0)).min())
+    sep["factor_solve"] = rel / tol
+    sep["pcg_panel_solve_system"] = rel / pcg_bound
+    r = rr(lcs.JOINT_IDS)
+    sep["joint_marginals_pcg"] = np.linalg.norm((Ia - Ib)[np.ix_(r, r)], 2) / np.linalg.norm(Ib[np.ix_(r, r)], 2) / pcg_bound
+    wa, wb = (np.sort(np.abs(np.linalg.eigvalsh(S)))[:lcs.MODES] for S in (Sa, Sb))
+    sep["weakest_modes"] = float(np.max(np.abs(wa - wb) / wb)) / tol
+    sep["get_S"] = float(np.abs(Sa - Sb).max() / np.abs(Sb).max()) / tol
+    sep["check_solve"] = abs(np.linalg.norm(ra) - np.linalg.norm(rb)) / np.linalg.norm(rb) / tol
+    # hat blocks of the pose-pose residuals, whitened with the information the engine starts from (unary scale 1)
+    info, w = pc.informations(terms)
+    lam = info * w[:, None, None]
+    masks = np.zeros(lcs.P, dtype=np.uint16)
+    G = pc.whitened_rows(terms, 6, dzb, lam, pa, masks)[2]
+    R = pc.res_dim(terms, 6)
+    ca, cb = pc.reference_cov(terms, 6, dza, pa, masks, Ia), pc.reference_cov(terms, 6, dzb, pa, masks, Ib)
+    for kind, name in ((0, "pose_pose_leverages_unary"), (1, "pose_pose_leverages_binary")):
+        sl = terms.kind_slice(kind)
+        sep[name] = pc.block_err(pc.whiten(ca[sl], G[sl], R[sl]), pc.whiten(cb[sl], G[sl], R[sl])) / tol
+    # hat blocks of the projection residuals and the landmark blocks, from the oracle's whitened Jacobians
+    nres = len(obs[1])
+    ids = [0, 7, nres // 2, nres - 1]
+    la = np.ones(lcs.L, dtype=np.uint8)
+    hat, lmk, jst = [], [], []
+    for S, (jm, jr, jl) in ((Sa, ja), (Sb, jb)):
+        assert len(jm) == nres
+        J, n = lc.dense_jacobian(1, 6, 0, pa, la, sc.lm_ref_pose, obs[1], obs[2], jm, jr, jl)
+        H = J.T @ J
+        full = np.linalg.inv(np.block([[S + H[:n, n:] @ np.linalg.solve(H[n:, n:], H[n:, :n]), H[:n, n:]], [H[n:, :n], H[n:, n:]]]))
+        rows2 = np.concatenate([[2 * a, 2 * a + 1] for a in ids])
+        Ja = J[rows2]
+        hat.append(np.stack([Ja[2 * q:2 * q + 2] @ full @ Ja[2 * q:2 * q + 2].T for q in range(len(ids))]))
+        lmk.append(np.array([full[n + l, n + l] for l in lcs.LM_IDS]))
+        sel = np.concatenate([rr(lcs.POSE_IDS), n + np.array(lcs.LM_IDS)])
+        jst.append(full[np.ix_(sel, sel)])
+    sep["projection_leverages"] = float(np.abs(hat[0] - hat[1]).max()) / tol
+    sep["landmark_marginals"] = float((np.abs(lmk[0] - lmk[1]) / lmk[1]).min()) / tol
+    dj = np.sqrt(np.diag(jst[1]))
+    sep["joint_state_marginals"] = float((np.abs(jst[0] - jst[1]) / np.outer(dj, dj)).max()) / tol
+    print("separation of state B from state A in tolerances (tol %.3g, cond %.3g): %s"
+          % (tol, cond, {k: "%.3g" % v for k, v in sep.items()}))
+    for name, v in sep.items():
+        assert v > 100.0, (name, v)
