@@ -490,6 +490,22 @@ int select_kth(Engine* e, const double* d_values, uint32_t n_local, uint64_t k, 
 int sum_partials(Engine* e, uint32_t nparts, uint32_t ncomp, double* host_out, bool cross_shard = true);
 void defer_begin(Engine* e);   // k_reduce.hip
 int defer_flush(Engine* e);
+// The deferred-sum scope of one phase call (Engine::defer_active).  flush(): the ONE copy and synchronisation, where
+// the call wants its sums.  A scope that ends without it (an error return) is cancelled: nothing is copied and
+// nothing is written through the host pointers the reductions registered.
+struct DeferScope {
+  Engine* e;
+  bool flushed = false;
+  explicit DeferScope(Engine* eng) : e(eng) { defer_begin(e); }
+  DeferScope(const DeferScope&) = delete;
+  DeferScope& operator=(const DeferScope&) = delete;
+  int flush() { flushed = true; return defer_flush(e); }
+  ~DeferScope() {
+    if (flushed) return;
+    e->defer_active = false;
+    e->defer_n = 0;
+  }
+};
 int launch_imu_early(Engine* e, double c_huber_proj);
 int launch_posepose_build(Engine* e, double c_huber_proj, double* h3);
 int launch_posepose_eval(Engine* e, double* h3);

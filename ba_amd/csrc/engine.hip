@@ -1,7 +1,7 @@
 // Host side of the gfx950 engine: C-ABI entry points of include/ba_hip.h, the
 // per-Solve structure build (observation CSR, incidences, gather lists) and the phase
 // drivers that enqueue the kernels of k_proj.hip / k_reduce.hip / k_chol.hip.
-#include "engine.h"
+#include "entry.h"
 #include <chrono>
 #include <functional>
 #include <memory>
@@ -517,64 +517,6 @@ static int set_masks_device(Engine* e, const std::vector<uint16_t>& by_id) {
   return 0;
 }
 
-// Is the factor that the last ba_hip_solve_gn left in A there to be read?  The one statement of it, for everything
-// that reads the factor: `who` starts the message, `noun` names what was asked for.  foreign_ok: a stand-alone solve
-// since then does not matter to the caller.  ba_hip_get_calibration_marginals (noun == nullptr) is older than the
-// rest and keeps its shorter wording, and its later place for the distributed solve.
-static int kept_factor_ready(Engine* e, const char* who, const char* noun, bool foreign_ok) {
-  const std::string w = who, m = w + ": ";
-  if (noun && dist_solve_enabled(e)) return e->fail_msg((m + "not available with the distributed solve").c_str());
-  if (!e->held.factored && e->held.pcg_solved)
-    return e->fail_msg((m + "the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor" +
-                        (noun ? std::string("; ") + noun + " need a direct solve (ba_hip_set_reduced_solver)" : "")).c_str());
-  if (!e->held.factored)
-    return e->fail_msg((noun ? m + "needs the factor of the last ba_hip_solve_gn (none yet, or the system was re-linearised since)"
-                             : w + " needs the factor of the last ba_hip_solve_gn").c_str());
-  if (e->held.factor_foreign && !foreign_ok)
-    return e->fail_msg((m + "a stand-alone solve (ba_hip_tile_solve / ba_hip_dense_solve) has replaced the kept factor "
-                            "since the last ba_hip_solve_gn").c_str());
-  if (!noun && dist_solve_enabled(e)) return e->fail_msg("calibration marginals: not available with the distributed solve");
-  return 0;
-}
-
-// The host work that ba_hip_dense_solve, ba_hip_pcg_solve and ba_hip_tile_solve share.  pad_system: the caller's
-// n x n lower triangle in (ld + 1) x ld storage, ones on the padded diagonal, the right-hand side as row ld; with
-// want_nz also the nt x nt map of the tiles that hold a nonzero entry.
-struct PaddedSystem {
-  uint32_t ld = 0, nt = 0;
-  std::vector<double> A;
-  std::vector<uint8_t> nz;
-};
-static PaddedSystem pad_system(uint32_t n, const double* a_lower, const double* b, bool want_nz) {
-  PaddedSystem s;
-  const uint32_t ld = s.ld = std::max(((n + 63) / 64) * 64, 64u), nt = s.nt = ld / 64;
-  s.A.assign((size_t)(ld + 1) * ld, 0.0);
-  if (want_nz) s.nz.assign((size_t)nt * nt, 0);
-  for (uint32_t r = 0; r < n; ++r)
-    for (uint32_t c = 0; c <= r; ++c) {
-      const double v = a_lower[(size_t)r * n + c];
-      s.A[(size_t)r * ld + c] = v;
-      if (want_nz && v != 0.0) s.nz[(size_t)(r / 64) * nt + c / 64] = 1;
-    }
-  for (uint32_t r = n; r < ld; ++r) s.A[(size_t)r * ld + r] = 1.0;
-  for (uint32_t c = 0; c < n; ++c) s.A[(size_t)ld * ld + c] = b[c];
-  return s;
-}
-// the refusals of ba_hip_factor_solve and its test tap that do not depend on the factor
-static int factor_solve_args(Engine* e, const char* what, uint32_t m, const double* B, const double* X) {
-  const std::string w = std::string(what) + ": ";
-  if (m == 0) return e->fail_msg((w + "no columns requested (m == 0)").c_str());
-  if (m > BA_HIP_FACTOR_SOLVE_MAX_COLUMNS)
-    return e->fail_msg((w + std::to_string(m) + " columns requested, the limit is BA_HIP_FACTOR_SOLVE_MAX_COLUMNS (" +
-                        std::to_string(BA_HIP_FACTOR_SOLVE_MAX_COLUMNS) + ")").c_str());
-  if (!B || !X) return e->fail_msg((w + "NULL argument").c_str());
-  return 0;
-}
-// ... and the first n entries of the solution back
-static hipError_t download_x(const DBuf<double>& dx, uint32_t n, double* x) {
-  return hipMemcpy(x, dx.p, (size_t)n * 8, hipMemcpyDeviceToHost);
-}
-
 }  // namespace bae
 
 using namespace bae;
@@ -624,12 +566,9 @@ int ba_hip_create(int lm_dim, int pose_dim, int device, void* stream, ba_hip_eng
   return 0;
 }
 
-// (every entry point starts outside a deferred-sum scope, whatever an earlier call's error path left behind)
-#define ENG(h) Engine* e = reinterpret_cast<Engine*>(h); e->defer_active = false; e->defer_n = 0
-
 void ba_hip_destroy(ba_hip_engine* h) {
   if (!h) return;
-  ENG(h);
+  Engine* e = reinterpret_cast<Engine*>(h);
   (void)hipSetDevice(e->device);
   (void)hipStreamSynchronize(e->stream);   // nothing of the engine's in flight when the communicator goes
   comm_release(e);
@@ -643,13 +582,13 @@ const char* ba_hip_last_error(const ba_hip_engine* h) {
 }
 
 int ba_hip_set_options(ba_hip_engine* h, const ba_hip_options* o) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   e->opt = *o;
   return 0;
 }
 
 int ba_hip_set_cameras(ba_hip_engine* h, uint32_t n, const double* params4, const double* t_vs7) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   e->prob.num_cams = n;
   e->prob.cam_params.assign(params4, params4 + 4 * (size_t)n);
   e->prob.cam_tvs.assign(t_vs7, t_vs7 + 7 * (size_t)n);
@@ -660,7 +599,7 @@ int ba_hip_set_cameras(ba_hip_engine* h, uint32_t n, const double* params4, cons
 }
 
 int ba_hip_set_camera_models(ba_hip_engine* h, uint32_t n, const int32_t* model, const double* w) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   if (n != e->prob.num_cams) return e->fail_msg("ba_hip_set_camera_models: one entry per camera of ba_hip_set_cameras expected");
   for (uint32_t c = 0; c < n; ++c) {
     if (model[c] != 0 && model[c] != 1) return e->fail_msg("camera model: 0 (LinearCamera) or 1 (FovCamera)");
@@ -673,14 +612,14 @@ int ba_hip_set_camera_models(ba_hip_engine* h, uint32_t n, const int32_t* model,
   return 0;
 }
 int ba_hip_get_camera_fov(ba_hip_engine* h, uint32_t n, double* w) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   if (!w || n != e->prob.cam_w.size()) return e->fail_msg("ba_hip_get_camera_fov: camera count mismatch");
   for (size_t c = 0; c < e->prob.cam_w.size(); ++c) w[c] = e->prob.cam_w[c];
   return 0;
 }
 
 int ba_hip_set_pose_cam_params(ba_hip_engine* h, uint32_t n, const double* params4) {
-  ENG(h);
+  BA_ENTRY_DEVICE(h);
   e->held.pose_cam_params_changed();
   if (n == 0 || !params4) {
     e->prob.pose_cam_params.clear();
@@ -692,7 +631,7 @@ int ba_hip_set_pose_cam_params(ba_hip_engine* h, uint32_t n, const double* param
 
 int ba_hip_set_poses(ba_hip_engine* h, uint32_t n, const double* t_wp7, const double* v_w3,
                      const double* b6, const uint8_t* is_active) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   Problem& pb = e->prob;
   pb.num_poses = n;
   pb.pose_state.assign((size_t)n * kPoseState, 0.0);
@@ -710,7 +649,7 @@ int ba_hip_set_poses(ba_hip_engine* h, uint32_t n, const double* t_wp7, const do
 
 int ba_hip_set_landmarks(ba_hip_engine* h, uint32_t n, const double* x_w4, const uint32_t* ref_pose_id,
                          const uint32_t* ref_cam_id, const uint8_t* is_active) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   Problem& pb = e->prob;
   pb.num_lms = n;
   pb.lm_xw.assign(x_w4, x_w4 + 4 * (size_t)n);
@@ -726,7 +665,7 @@ int ba_hip_set_landmarks(ba_hip_engine* h, uint32_t n, const double* x_w4, const
 int ba_hip_set_projection_residuals(ba_hip_engine* h, uint32_t n, const double* z2,
                                     const uint32_t* meas_pose_id, const uint32_t* landmark_id,
                                     const uint32_t* cam_id, const double* weight) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   Problem& pb = e->prob;
   pb.num_proj = n;
   pb.proj_z.assign(z2, z2 + 2 * (size_t)n);
@@ -741,7 +680,7 @@ int ba_hip_set_projection_residuals(ba_hip_engine* h, uint32_t n, const double* 
 }
 
 int ba_hip_set_conditioning_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* residual_id) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   e->prob.proj_cond.assign(residual_id, residual_id + n);
   e->held.problem_changed();
   return 0;
@@ -750,7 +689,7 @@ int ba_hip_set_conditioning_residuals(ba_hip_engine* h, uint32_t n, const uint32
 int ba_hip_set_unary_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_id,
                                const double* t_wp7, const double* cov_inv36,
                                const uint8_t* use_rotation) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   Problem& pb = e->prob;
   pb.num_unary = n;
   pb.un_pose.assign(pose_id, pose_id + n);
@@ -766,7 +705,7 @@ int ba_hip_set_binary_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* po
                                 const uint32_t* pose2_id, const double* t_12_7,
                                 const double* cov_inv36, const double* cov_inv_sqrt36,
                                 const double* weight, const uint8_t* use_rotation) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   Problem& pb = e->prob;
   pb.num_binary = n;
   pb.bin_p1.assign(pose1_id, pose1_id + n);
@@ -785,7 +724,7 @@ int ba_hip_set_binary_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* po
 int ba_hip_set_imu_residuals(ba_hip_engine* h, uint32_t n, const uint32_t* pose1_id,
                              const uint32_t* pose2_id, const uint32_t* meas_ptr, const double* meas7,
                              const double* weight) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   Problem& pb = e->prob;
   pb.num_imu = n;
   pb.imu_p1.assign(pose1_id, pose1_id + n);
@@ -950,7 +889,7 @@ int ba_hip_lie(int op, const double* a, const double* b, double* out) {
 }
 
 int ba_hip_set_imu_noise(ba_hip_engine* h, const double r6[6], const double rb6[6]) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   e->prob.imu_noise.clear();
   if (r6 && rb6) {
     e->prob.imu_noise.assign(r6, r6 + 6);
@@ -960,22 +899,21 @@ int ba_hip_set_imu_noise(ba_hip_engine* h, const double r6[6], const double rb6[
 }
 
 int ba_hip_set_inertial_covariance_once(ba_hip_engine* h, int on, int reset) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   e->imu_cov_once = on != 0;
   if (reset || !on) e->imu_cov_count = 0;
   return 0;
 }
 
 int ba_hip_set_gravity(ba_hip_engine* h, const double g3[3]) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   for (int i = 0; i < 3; ++i) e->prob.gravity[i] = g3[i];
   return 0;
 }
 
 int ba_hip_finalize(ba_hip_engine* h) {
-  ENG(h);
+  BA_ENTRY_DEVICE(h);
   e->held.finalize_begins();
-  BAE_HIP(hipSetDevice(e->device));
   Problem& pb = e->prob;
   if (pb.pose_active.size() != pb.num_poses) pb.pose_active.assign(pb.num_poses, 1);
   if (pb.lm_active.size() != pb.num_lms) pb.lm_active.assign(pb.num_lms, 1);
@@ -992,13 +930,8 @@ int ba_hip_finalize(ba_hip_engine* h) {
   return 0;
 }
 
-#define NEED_FINAL() \
-  if (!e->held.finalized) return e->fail_msg("ba_hip_finalize has not been called")
-
 int ba_hip_get_conditioning_error(ba_hip_engine* h, double* proj_sq_sum) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_FINAL(h);
   *proj_sq_sum = 0.0;
   if (e->prob.proj_cond.empty() || e->st.O == 0) return 0;
   int rc = launch_pose_prep(e);
@@ -1008,11 +941,9 @@ int ba_hip_get_conditioning_error(ba_hip_engine* h, double* proj_sq_sum) {
 }
 
 int ba_hip_begin_solve(ba_hip_engine* h) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   e->held.solve_begins();
   e->err_cache_off = getenv("BA_HIP_NO_ERR_CACHE") != nullptr;
-  BAE_HIP(hipSetDevice(e->device));
   if (!e->prob.pose_cam_params.empty() && e->prob.pose_cam_params.size() != 4 * (size_t)e->prob.num_poses)
     return e->fail_msg("per-pose camera parameters: one [fx,fy,u0,v0] per pose expected");
   if (!e->prob.pose_cam_params.empty() && e->has_fov)
@@ -1032,8 +963,7 @@ int ba_hip_begin_solve(ba_hip_engine* h) {
 }
 
 int ba_hip_set_pose_masks(ba_hip_engine* h, uint32_t n, const uint16_t* masks) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   if (n != e->st.P) return e->fail_msg("mask count != pose count");
   e->held.masks_changed();
   e->mask_host.assign(masks, masks + n);
@@ -1041,9 +971,7 @@ int ba_hip_set_pose_masks(ba_hip_engine* h, uint32_t n, const uint16_t* masks) {
 }
 
 int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_FINAL(h);
   const Structure& st = e->st;
   ba_hip_errors errs = {0, 0, 0, 0};
   int rc;
@@ -1082,23 +1010,23 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   const bool imu_late = e->prob.imu_meas.size() / 7 > 4096;
   if (!imu_late && (rc = launch_imu_early(e, c_huber))) return rc;
   EventTimer t_l(e);
-  // from here on every sum stays on the device until ONE copy at the end of the call (defer_flush): the
+  // from here on every sum stays on the device until ONE copy at the end of the call (sums.flush()): the
   // assembly and the pose-pose kernels are enqueued without waiting for the linearisation to finish
   double* hs = e->eval_h;  // proj | unary | binary | inertial
   for (int i = 0; i < 4; ++i) hs[i] = 0.0;
-  defer_begin(e);
+  DeferScope sums(e);
   if ((rc = launch_landmarks(e, c_huber, e->opt.use_robust_norm_for_proj_residuals))) return rc;
-  if (imu_late && (rc = launch_imu_early(e, c_huber))) { (void)defer_flush(e); return rc; }
+  if (imu_late && (rc = launch_imu_early(e, c_huber))) return rc;
   // proj_error_ of BuildProblem (BundleAdjuster.cpp:1386): sum of w |r|^2 with the new weights, one
   // partial per linearisation wave
-  if ((rc = sum_partials(e, st.O ? st.n_chunks : 0, 1, hs))) { (void)defer_flush(e); return rc; }
+  if ((rc = sum_partials(e, st.O ? st.n_chunks : 0, 1, hs))) return rc;
   t_l.mark();
   EventTimer t_s(e);
   e->held.linearize_writes_A();
   e->lin_mask_version = e->mask_version;   // the rows above and the system about to be gathered carry the current masks
-  if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) { (void)defer_flush(e); return rc; }
+  if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) return rc;
   // dense priors after k_pp_scatter, in prior order; their E_p is folded into unary_error
-  if ((rc = launch_priors(e, 1, &e->prior_err_h))) { (void)defer_flush(e); return rc; }
+  if ((rc = launch_priors(e, 1, &e->prior_err_h))) return rc;
   if (e->prob.num_unary + e->prob.num_binary + e->prob.num_imu)  // kept for ba_hip_marginalize (the dogleg reuses pp_err)
     BAE_HIP(hipMemcpyAsync(e->pp_err_lin.p, e->pp_err.p, (size_t)(e->prob.num_unary + e->prob.num_binary + e->prob.num_imu) *
                            sizeof(double), hipMemcpyDeviceToDevice, e->stream));
@@ -1135,7 +1063,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
     }
   }
   t_s.mark();
-  if ((rc = defer_flush(e))) return rc;
+  if ((rc = sums.flush())) return rc;
   e->timers.j_evaluation = t_j.read_ms() + t_l.read_ms();
   e->timers.robust_weights = t_r.read_ms();
   e->timers.jtj_schur = t_s.read_ms();
@@ -1146,9 +1074,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
 }
 
 int ba_hip_solve_gn(ba_hip_engine* h) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_FINAL(h);
   const Structure& st = e->st;
   int status = 0, rc;
   EventTimer t(e);
@@ -1205,46 +1131,39 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
 }
 
 int ba_hip_dogleg_terms(ba_hip_engine* h, int gn_available, ba_hip_dogleg_scalars* out) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
-  // every sum of this call stays on the device until ONE copy at the end (defer_flush)
+  BA_ENTRY_FINAL(h);
+  // every sum of this call stays on the device until ONE copy at the end (sums.flush())
   memset(out, 0, sizeof(*out));
   double* dh = e->dog_h;
   // the steepest-descent denominator |J rhs|^2 does not involve the Gauss-Newton step: the second call of
   // an iteration (gn_available, BundleAdjuster.cpp:971-1002) reuses what the first one summed
   const bool reuse = gn_available && e->held.dog_jrhs_valid;
-  defer_begin(e);
+  DeferScope sums(e);
   int rc = launch_dogleg(e, gn_available, dh, reuse);
   if (!rc && !reuse) rc = launch_posepose_jrhs(e, dh + 7);
   if (!rc && !reuse) rc = launch_priors_jrhs(e, &e->prior_jrhs_h);
-  const int rf = defer_flush(e);
-  e->held.dogleg_sums(!rc && !rf);
-  if (rc || rf) return rc ? rc : rf;
+  if (!rc) rc = sums.flush();
+  e->held.dogleg_sums(!rc);
+  if (rc) return rc;
   out->rhs_p_sq = dh[0]; out->gn_p_sq = dh[1]; out->rhs_gn_p = dh[2];
   out->rhs_l_sq = dh[3]; out->gn_l_sq = dh[4]; out->rhs_gn_l = dh[5];
   out->j_rhs_sq = dh[6] + dh[7] + e->prior_jrhs_h;
-  if (e->st.K && (rc = launch_calib_dogleg(e, gn_available, out))) return rc;
-  return 0;
+  return e->st.K ? launch_calib_dogleg(e, gn_available, out) : 0;
 }
 
 int ba_hip_compose_step(ba_hip_engine* h, double coef_rhs, double coef_gn, ba_hip_step_norms* out) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_FINAL(h);
   double n2[2];
-  defer_begin(e);  // both norms in one copy
+  DeferScope sums(e);  // both norms in one copy; declared after n2, which the reductions register
   int rc = launch_compose_step(e, coef_rhs, coef_gn, n2);
-  const int rf = defer_flush(e);
-  if (rc || rf) return rc ? rc : rf;
+  if (!rc) rc = sums.flush();
+  if (rc) return rc;
   if (out) { out->step_p_norm = std::sqrt(n2[0]); out->step_l_norm = std::sqrt(n2[1]); }
   return 0;
 }
 
 int ba_hip_apply_step(ba_hip_engine* h) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_FINAL(h);
   EventTimer t(e);
   int rc = launch_apply_step(e);
   if (rc) return rc;
@@ -1287,10 +1206,8 @@ int ba_hip_apply_step(ba_hip_engine* h) {
 }
 
 int ba_hip_rollback(ba_hip_engine* h) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   if (!e->held.has_snapshot) return e->fail_msg("no snapshot to roll back to");
-  BAE_HIP(hipSetDevice(e->device));
   e->cur = 1 - e->cur;
   e->held.rolled_back();
   int rc;
@@ -1312,20 +1229,18 @@ int ba_hip_rollback(ba_hip_engine* h) {
 }
 
 int ba_hip_eval_residuals(ba_hip_engine* h, ba_hip_errors* out) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_FINAL(h);
   ba_hip_errors errs = {0, 0, 0, 0};
   EventTimer t(e);
-  double* hs = e->eval_h;  // proj | unary | binary | inertial: one copy for the four sums (defer_flush)
+  double* hs = e->eval_h;  // proj | unary | binary | inertial: one copy for the four sums (sums.flush())
   for (int i = 0; i < 4; ++i) hs[i] = 0.0;
-  defer_begin(e);
+  DeferScope sums(e);
   int rc = launch_residuals(e, 1);
   if (!rc) rc = sum_partials(e, (e->st.O + 255) / 256, 1, hs);
   if (!rc) rc = launch_posepose_eval(e, hs + 1);
   if (!rc) rc = launch_priors(e, 0, &e->prior_err_h);
-  const int rf = defer_flush(e);
-  if (rc || rf) return rc ? rc : rf;
+  if (!rc) rc = sums.flush();
+  if (rc) return rc;
   errs.proj_error = hs[0]; errs.unary_error = hs[1] + e->prior_err_h; errs.binary_error = hs[2]; errs.inertial_error = hs[3];
   e->timers.evaluate_residuals = t.stop_ms();
   if (out) *out = errs;
@@ -1333,9 +1248,7 @@ int ba_hip_eval_residuals(ba_hip_engine* h, ba_hip_errors* out) {
 }
 
 int ba_hip_end_solve(ba_hip_engine* h) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_FINAL(h);
   int rc = launch_end_solve(e);
   if (rc) return rc;
   BAE_HIP(hipStreamSynchronize(e->stream));
@@ -1344,8 +1257,7 @@ int ba_hip_end_solve(ba_hip_engine* h) {
 
 // ---- results --------------------------------------------------------------------------
 int ba_hip_get_poses(ba_hip_engine* h, double* t_wp7, double* v_w3, double* b6) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   const uint32_t P = e->st.P;
   std::vector<double> s((size_t)P * kPoseState);
   BAE_HIP(hipStreamSynchronize(e->stream));
@@ -1360,8 +1272,7 @@ int ba_hip_get_poses(ba_hip_engine* h, double* t_wp7, double* v_w3, double* b6) 
 }
 
 int ba_hip_get_landmarks(ba_hip_engine* h, double* x_w4) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   BAE_HIP(hipStreamSynchronize(e->stream));
   const double* src = e->lm_dim == 1 ? e->lm_xw.p : e->lm_x[e->cur].p;
   if (e->st.L) BAE_HIP(hipMemcpy(x_w4, src, (size_t)e->st.L * 4 * sizeof(double), hipMemcpyDeviceToHost));
@@ -1369,8 +1280,7 @@ int ba_hip_get_landmarks(ba_hip_engine* h, double* x_w4) {
 }
 
 int ba_hip_get_landmark_flags(ba_hip_engine* h, uint8_t* is_reliable, uint32_t* num_outliers) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   BAE_HIP(hipStreamSynchronize(e->stream));
   if (e->st.L && is_reliable)
     BAE_HIP(hipMemcpy(is_reliable, e->lm_reliable[e->cur].p, e->st.L, hipMemcpyDeviceToHost));
@@ -1386,7 +1296,7 @@ uint32_t ba_hip_num_calib_params(const ba_hip_engine* h) {
   return reinterpret_cast<const Engine*>(h)->st.K;
 }
 int ba_hip_set_calibration(ba_hip_engine* h, int calib_size, int do_tvs) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   if (calib_size != 0 && calib_size != 4 && calib_size != 5)
     return e->fail_msg("CalibSize must be 0, 4 (LinearCamera: fx, fy, u0, v0) or 5 (FovCamera: fx, fy, u0, v0, w)");
   if (calib_size && do_tvs)
@@ -1400,29 +1310,26 @@ int ba_hip_set_calibration(ba_hip_engine* h, int calib_size, int do_tvs) {
   return 0;
 }
 int ba_hip_get_calibration_marginals(ba_hip_engine* h, double* cov) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   if (!e->st.K) return e->fail_msg("no calibration columns (ba_hip_set_calibration)");
-  int rc;
-  if ((rc = kept_factor_ready(e, "ba_hip_get_calibration_marginals", nullptr, false))) return rc;
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ASK(guard_kept_factor(e->held, guard_facts(e), "ba_hip_get_calibration_marginals", nullptr, false));
   return trailing_marginals(e, e->A.p, e->st.ld, e->st.np, e->st.K, cov);
 }
 int ba_hip_set_landmark_ref_pixels(ba_hip_engine* h, uint32_t n, const double* z_ref2) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   e->prob.lm_zref.assign(z_ref2, z_ref2 + 2 * (size_t)n);
   e->held.problem_changed();
   return 0;
 }
 int ba_hip_get_camera_params(ba_hip_engine* h, uint32_t n, double* params4) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   const std::vector<double>& p = e->prob.cam_params;
   if (!params4 || (size_t)n * 4 != p.size()) return e->fail_msg("ba_hip_get_camera_params: camera count mismatch");
   for (size_t i = 0; i < p.size(); ++i) params4[i] = p[i];
   return 0;
 }
 int ba_hip_get_cameras(ba_hip_engine* h, uint32_t n, double* t_vs7) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   const std::vector<double>& t = e->prob.cam_tvs;
   if (!t_vs7 || (size_t)n * 7 != t.size()) return e->fail_msg("ba_hip_get_cameras: camera count mismatch");
   for (size_t i = 0; i < t.size(); ++i) t_vs7[i] = t[i];
@@ -1433,29 +1340,15 @@ uint32_t ba_hip_num_lm_params(const ba_hip_engine* h) {
   return e->st.Lact * e->lm_dim;
 }
 
-// Public outputs are indexed by the NATURAL optimisation index: row r of the caller's numbering is row
-// int_row(r) of the engine's (the pose ordering of ba_hip_set_pose_ordering; the calibration border stays last).
-static inline uint32_t int_row(const Engine* e, uint32_t r) {
-  const uint32_t D = (uint32_t)e->pose_dim;
-  if (e->opt_of_natural.empty() || r >= e->st.np) return r;
-  return e->opt_of_natural[r / D] * D + r % D;
-}
-static void unpermute_vec(const Engine* e, double* v) {
-  if (e->opt_of_natural.empty() || !v) return;
-  std::vector<double> tmp(v, v + e->st.np);
-  for (uint32_t r = 0; r < e->st.np; ++r) v[r] = tmp[int_row(e, r)];
-}
-
 int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   const Structure& st = e->st;
   const uint32_t n = st.n, ld = st.ld, D = e->pose_dim;
+  const StructureView sv = structure_view(e);
   auto block_of = [&](uint32_t r) { return r < st.np ? r / D : st.Pact; };  // the calibration border is one more block
   std::vector<double> a((size_t)n * ld);
   BAE_HIP(hipStreamSynchronize(e->stream));
-  if (e->held.factored && !(e->opt.keep_reduced_system && e->A_keep.p))
-    return e->fail_msg("S was factorised in place; set keep_reduced_system to read it after ba_hip_solve_gn");
+  BA_ASK(guard_get_S(e->held, guard_facts(e)));
   const double* src = e->held.factored ? e->A_keep.p : e->A.p;
   if (n) BAE_HIP(hipMemcpy(a.data(), src, a.size() * sizeof(double), hipMemcpyDeviceToHost));
   // lower storage -> the reference's s_: block (i,j) kept for i <= j only when
@@ -1463,7 +1356,7 @@ int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
   // (r, c) in the caller's numbering, (ri, ci) in the engine's; the triangle kept is the caller's
   for (uint32_t r = 0; r < n; ++r)
     for (uint32_t c = 0; c < n; ++c) {
-      const uint32_t ri = int_row(e, r), ci = int_row(e, c);
+      const uint32_t ri = int_row(sv, r), ci = int_row(sv, c);
       const uint32_t bi = block_of(ri), bj = block_of(ci);
       double v;
       if (bi == bj) v = a[(size_t)ri * ld + ci];
@@ -1475,760 +1368,16 @@ int ba_hip_get_S(ba_hip_engine* h, double* s_nxn) {
   return 0;
 }
 
-// ---- marginal covariances (k_selinv.hip) ----------------------------------------------------------
-static int marginals_ready(Engine* e, const char* what, bool landmarks) {
-  std::string m = std::string(what) + ": ";
-  if (!e->held.finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
-  if (landmarks && e->sharded() && !dist_solve_enabled(e))   // (the distributed solve refuses first, for every block)
-    return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
-  int rc;   // (a selected inverse computed before a stand-alone solve stays good)
-  if ((rc = kept_factor_ready(e, what, "marginals", e->held.sig_valid))) return rc;
-  BAE_HIP(hipSetDevice(e->device));
-  return marginals_compute(e);
-}
-static int pose_row(Engine* e, uint32_t id, uint32_t* row, const char* what) {
-  if (id >= e->st.P || e->st.pose_opt[id] < 0) {
-    e->err = std::string(what) + ": pose " + std::to_string(id) + " is not an active pose (it has no columns in S)";
-    return -1;
-  }
-  *row = (uint32_t)e->st.pose_opt[id] * (uint32_t)e->pose_dim;
-  return 0;
-}
-int ba_hip_compute_marginals(ba_hip_engine* h) {
-  ENG(h);
-  return marginals_ready(e, "ba_hip_compute_marginals", false);
-}
-int ba_hip_get_pose_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, double* out) {
-  ENG(h);
-  static const char* what = "ba_hip_get_pose_marginals";
-  int rc;
-  if ((rc = marginals_ready(e, what, false))) return rc;
-  if (n && (!pose_ids || !out)) return e->fail_msg("ba_hip_get_pose_marginals: NULL argument");
-  std::vector<uint32_t> r(n);
-  for (uint32_t i = 0; i < n; ++i)
-    if ((rc = pose_row(e, pose_ids[i], &r[i], what))) return rc;
-  return marginals_gather(e, n, r, r, e->pose_dim, e->pose_dim, out);
-}
-int ba_hip_get_pose_pair_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* a_ids, const uint32_t* b_ids, double* out) {
-  ENG(h);
-  static const char* what = "ba_hip_get_pose_pair_marginals";
-  int rc;
-  if ((rc = marginals_ready(e, what, false))) return rc;
-  if (n && (!a_ids || !b_ids || !out)) return e->fail_msg("ba_hip_get_pose_pair_marginals: NULL argument");
-  std::vector<uint32_t> ra(n), rb(n);
-  for (uint32_t i = 0; i < n; ++i)
-    if ((rc = pose_row(e, a_ids[i], &ra[i], what)) || (rc = pose_row(e, b_ids[i], &rb[i], what))) return rc;
-  return marginals_gather(e, n, ra, rb, e->pose_dim, e->pose_dim, out);
-}
-int ba_hip_get_calibration_block_marginals(ba_hip_engine* h, double* out) {
-  ENG(h);
-  if (!e->st.K) return e->fail_msg("no calibration columns (ba_hip_set_calibration)");
-  int rc;
-  if ((rc = marginals_ready(e, "ba_hip_get_calibration_block_marginals", false))) return rc;
-  std::vector<uint32_t> r(1, e->st.np);
-  return marginals_gather(e, 1, r, r, (int)e->st.K, (int)e->st.K, out);
-}
-int ba_hip_get_landmark_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* lm_ids, double* out) {
-  ENG(h);
-  int rc;
-  if ((rc = marginals_ready(e, "ba_hip_get_landmark_marginals", true))) return rc;
-  if (n && !out) return e->fail_msg("ba_hip_get_landmark_marginals: NULL argument");
-  if (!lm_ids && n != e->st.Lact)
-    return e->fail_msg("ba_hip_get_landmark_marginals: with NULL ids n must be the active landmark count");
-  if (lm_ids)
-    for (uint32_t i = 0; i < n; ++i)
-      if (lm_ids[i] >= e->st.L || e->st.lm_opt[lm_ids[i]] < 0) {
-        e->err = "ba_hip_get_landmark_marginals: landmark " + std::to_string(lm_ids[i]) + " is not an active landmark";
-        return -1;
-      }
-  return marginals_landmarks(e, n, lm_ids, out);
-}
-// ---- leverages of projection residuals (k_lever.hip) ----
-int ba_hip_get_projection_leverages(ba_hip_engine* h, uint32_t n, const uint32_t* residual_ids, double* out) {
-  ENG(h);
-  static const char* what = "ba_hip_get_projection_leverages";
-  const std::string m = std::string(what) + ": ";
-  if (e->lm_dim == 0) return e->fail_msg((m + "LmSize 0 has no projection residuals").c_str());
-  int rc;
-  if ((rc = marginals_ready(e, what, true))) return rc;
-  if (n && !out) return e->fail_msg((m + "NULL argument").c_str());
-  if (!residual_ids && n != e->st.O)
-    return e->fail_msg((m + "with NULL ids n must be the projection residual count").c_str());
-  if (residual_ids)
-    for (uint32_t i = 0; i < n; ++i)
-      if (residual_ids[i] >= e->st.O)
-        return e->fail_msg((m + "id " + std::to_string(residual_ids[i]) + " is not a projection residual (there are " +
-                            std::to_string(e->st.O) + ")").c_str());
-  return leverages_run(e, n, residual_ids, out);
-}
-int ba_hip_get_leverage_stats(ba_hip_engine* h, ba_hip_leverage_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_leverage_stats: NULL argument");
-  *out = e->lstats;
-  return 0;
-}
-// ---- leverages of unary, binary and inertial residuals (k_pplever.hip) ----
-int ba_hip_get_pose_pose_leverages(ba_hip_engine* h, int kind, uint32_t n, const uint32_t* ids, double* cov, double* info,
-                                   double* leverage) {
-  ENG(h);
-  static const char* what = "ba_hip_get_pose_pose_leverages";
-  const std::string m = std::string(what) + ": ";
-  if (kind != BA_HIP_RES_UNARY && kind != BA_HIP_RES_BINARY && kind != BA_HIP_RES_IMU)
-    return e->fail_msg((m + "kind " + std::to_string(kind) + " is none of BA_HIP_RES_UNARY, _BINARY, _IMU").c_str());
-  int rc;
-  if ((rc = marginals_ready(e, what, false))) return rc;
-  static const char* names[3] = {"a unary", "a binary", "an inertial"};
-  const Problem& pb = e->prob;
-  const uint32_t count = kind == BA_HIP_RES_UNARY ? pb.num_unary : kind == BA_HIP_RES_BINARY ? pb.num_binary : pb.num_imu;
-  if (n && !cov && !info && !leverage) return e->fail_msg((m + "every output is NULL").c_str());
-  if (!ids && n != count)
-    return e->fail_msg((m + "with NULL ids n must be the residual count of the kind (" + std::to_string(count) + ")").c_str());
-  if (ids)
-    for (uint32_t i = 0; i < n; ++i)
-      if (ids[i] >= count)
-        return e->fail_msg((m + "id " + std::to_string(ids[i]) + " is not " + names[kind] + " residual (there are " +
-                            std::to_string(count) + ")").c_str());
-  return pose_pose_leverages_run(e, kind, n, ids, cov, info, leverage);
-}
-uint32_t ba_hip_num_pose_pose_residuals(const ba_hip_engine* h, int kind) {
-  const Problem& pb = reinterpret_cast<const Engine*>(h)->prob;
-  return kind == BA_HIP_RES_UNARY ? pb.num_unary : kind == BA_HIP_RES_BINARY ? pb.num_binary : kind == BA_HIP_RES_IMU ? pb.num_imu : 0;
-}
-int ba_hip_get_pose_pose_leverage_stats(ba_hip_engine* h, ba_hip_pose_pose_leverage_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_pose_pose_leverage_stats: NULL argument");
-  *out = e->ppl_stats;
-  return 0;
-}
-// ---- joint covariance of a pose set (k_jointcov.hip): Y = L^-1 E over the reach, Sigma = Y^T D Y; with landmarks
-// the columns [E | -W V^-1] and V^-1 on their diagonal blocks.  One path for both getters: `what` starts the messages.
-static int joint_state_run(Engine* e, const char* what, bool state, uint32_t n, const uint32_t* pose_ids,
-                           int include_calibration, uint32_t nl, const uint32_t* lm_ids, double* out) {
-  const std::string m = std::string(what) + ": ";
-  if (nl && !e->lm_dim) return e->fail_msg((m + "LmSize 0 has no landmark unknowns").c_str());
-  if (!e->held.finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
-  if (nl && e->sharded() && !dist_solve_enabled(e))   // (the distributed solve refuses first, for every block)
-    return e->fail_msg((m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)").c_str());
-  int rc;
-  if ((rc = kept_factor_ready(e, what, "joint marginals", false))) return rc;
-  if ((n && !pose_ids) || (nl && !lm_ids) || !out) return e->fail_msg((m + "NULL argument").c_str());
-  const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K, LM = (uint32_t)e->lm_dim;
-  if (include_calibration && !K)
-    return e->fail_msg((m + "include_calibration without calibration unknowns (ba_hip_set_calibration)").c_str());
-  const uint64_t M = (uint64_t)n * D + (include_calibration ? K : 0) + (uint64_t)nl * LM;
-  if (M == 0)
-    return e->fail_msg((m + (state ? "no pose, no calibration rows and no landmark requested"
-                                   : "no pose and no calibration rows requested")).c_str());
-  if (M > BA_HIP_JOINT_MAX_COLUMNS)
-    return e->fail_msg((m + std::to_string(M) + " columns requested, the limit is BA_HIP_JOINT_MAX_COLUMNS (" +
-                        std::to_string(BA_HIP_JOINT_MAX_COLUMNS) + ")").c_str());
-  std::vector<uint32_t> sel;
-  sel.reserve(M);
-  std::vector<uint32_t> seen(pose_ids, pose_ids + n);
-  std::sort(seen.begin(), seen.end());
-  for (uint32_t i = 0; i + 1 < n; ++i)
-    if (seen[i] == seen[i + 1])
-      return e->fail_msg((m + "pose " + std::to_string(seen[i]) + " is repeated (the joint block would be singular)").c_str());
-  for (uint32_t i = 0; i < n; ++i) {
-    uint32_t r;
-    if ((rc = pose_row(e, pose_ids[i], &r, what))) return rc;
-    for (uint32_t x = 0; x < D; ++x) sel.push_back(r + x);
-  }
-  if (include_calibration)
-    for (uint32_t x = 0; x < K; ++x) sel.push_back(e->st.np + x);
-  std::vector<uint32_t> lms(lm_ids, lm_ids + nl);
-  seen = lms;
-  std::sort(seen.begin(), seen.end());
-  for (uint32_t i = 0; i + 1 < nl; ++i)
-    if (seen[i] == seen[i + 1])
-      return e->fail_msg((m + "landmark " + std::to_string(seen[i]) + " is repeated (the joint block would be singular)").c_str());
-  for (uint32_t i = 0; i < nl; ++i)
-    if (lms[i] >= e->st.L || e->st.lm_opt[lms[i]] < 0)
-      return e->fail_msg((m + "landmark " + std::to_string(lms[i]) + " is not an active landmark").c_str());
-  BAE_HIP(hipSetDevice(e->device));
-  if ((rc = jointcov_run(e, sel, lms, out))) return rc;
-  if (state && !nl) e->jsstats = ba_hip_joint_state_stats{};
-  return 0;
-}
-int ba_hip_get_joint_marginals(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,
-                               double* out) {
-  ENG(h);
-  return joint_state_run(e, "ba_hip_get_joint_marginals", false, n, pose_ids, include_calibration, 0, nullptr, out);
-}
-int ba_hip_get_joint_state_marginals(ba_hip_engine* h, uint32_t n_poses, const uint32_t* pose_ids, int include_calibration,
-                                     uint32_t n_landmarks, const uint32_t* lm_ids, double* out) {
-  ENG(h);
-  return joint_state_run(e, "ba_hip_get_joint_state_marginals", true, n_poses, pose_ids, include_calibration, n_landmarks,
-                         lm_ids, out);
-}
-int ba_hip_get_joint_state_stats(ba_hip_engine* h, ba_hip_joint_state_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_joint_state_stats: NULL argument");
-  *out = e->jsstats;
-  return 0;
-}
-int ba_hip_get_joint_marginal_stats(ba_hip_engine* h, ba_hip_joint_marginal_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_joint_marginal_stats: NULL argument");
-  *out = e->jstats;
-  return 0;
-}
-// ---- solves with the kept factor (k_factorsolve.hip): X = S^-1 B, rows in the caller's (natural) order ----
-int ba_hip_factor_solve(ba_hip_engine* h, uint32_t m, const double* B, double* X) {
-  ENG(h);
-  static const char* what = "ba_hip_factor_solve";
-  if (!e->held.finalized) return e->fail_msg("ba_hip_factor_solve: ba_hip_finalize has not been called");
-  int rc;
-  if ((rc = kept_factor_ready(e, what, "solves with the factor", false))) return rc;
-  if ((rc = factor_solve_args(e, what, m, B, X))) return rc;
-  BAE_HIP(hipSetDevice(e->device));
-  FactorRef f = {e->A.p, e->st.ld, 0, &e->nzL_host, nullptr, nullptr};
-  if ((rc = kept_factor(e, "factor solve", &f.nt, &f.dsgn, &f.linvT))) return rc;
-  std::vector<uint32_t> rowmap(e->st.ld, kJointNone);
-  for (uint32_t r = 0; r < e->st.n; ++r) rowmap[int_row(e, r)] = r;
-  return factor_solve_run(e, f, e->st.n, rowmap.data(), m, B, X);
-}
-int ba_hip_get_weakest_modes(ba_hip_engine* h, uint32_t k, const ba_hip_mode_options* o, double* eigenvalues,
-                             double* modes) {
-  ENG(h);
-  static const char* what = "ba_hip_get_weakest_modes";
-  const std::string w = std::string(what) + ": ";
-  if (!e->held.finalized) return e->fail_msg((w + "ba_hip_finalize has not been called").c_str());
-  int rc;
-  if ((rc = kept_factor_ready(e, what, "weakest modes", false))) return rc;
-  const uint32_t n = e->st.n, kmax = std::min(kModeMaxK, n);
-  if (k == 0 || k > kmax)
-    return e->fail_msg((w + std::to_string(k) + " modes requested, k must be between 1 and min(32, n) = " +
-                        std::to_string(kmax)).c_str());
-  if (!eigenvalues || !modes) return e->fail_msg((w + "NULL argument").c_str());
-  ModeOptions mo;
-  if (o && o->tolerance > 0.0) mo.tolerance = o->tolerance;
-  if (o && o->max_iterations) mo.max_iterations = o->max_iterations;
-  if (o && o->seed) mo.seed = o->seed;
-  BAE_HIP(hipSetDevice(e->device));
-  FactorRef f = {e->A.p, e->st.ld, 0, &e->nzL_host, nullptr, nullptr};
-  if ((rc = kept_factor(e, "weakest modes", &f.nt, &f.dsgn, &f.linvT))) return rc;
-  std::vector<uint32_t> rowmap(e->st.ld, kJointNone);
-  for (uint32_t r = 0; r < n; ++r) rowmap[int_row(e, r)] = r;
-  return weakest_modes_run(e, f, n, rowmap.data(), k, mo, eigenvalues, modes);
-}
-int ba_hip_get_mode_stats(ba_hip_engine* h, ba_hip_mode_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_mode_stats: NULL argument");
-  *out = e->mode_stats;
-  return 0;
-}
-int ba_hip_get_factor_solve_stats(ba_hip_engine* h, ba_hip_factor_solve_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_factor_solve_stats: NULL argument");
-  *out = e->fsstats;
-  return 0;
-}
-int ba_hip_get_marginal_stats(ba_hip_engine* h, ba_hip_marginal_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_marginal_stats: NULL argument");
-  *out = e->mstats;
-  return 0;
-}
-int ba_hip_release_marginals(ba_hip_engine* h) {
-  ENG(h);
-  (void)hipSetDevice(e->device);
-  (void)hipStreamSynchronize(e->stream);
-  marginals_release(e);
-  jointcov_release(e);
-  factor_solve_release(e);
-  return 0;
-}
-
-int ba_hip_get_rhs(ba_hip_engine* h, double* rhs_p_sc, double* rhs_p, double* rhs_l) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  if (rhs_p_sc && st.n) BAE_HIP(hipMemcpy(rhs_p_sc, e->rhs_sc.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
-  if (rhs_p && st.n) BAE_HIP(hipMemcpy(rhs_p, e->rhs_p.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
-  unpermute_vec(e, st.n ? rhs_p_sc : nullptr);
-  unpermute_vec(e, st.n ? rhs_p : nullptr);
-  if (rhs_l && st.Lact) {
-    std::vector<double> bl((size_t)st.L * e->lm_dim);
-    BAE_HIP(hipMemcpy(bl.data(), e->lm_bl.p, bl.size() * 8, hipMemcpyDeviceToHost));
-    for (uint32_t l = 0; l < st.L; ++l)
-      if (st.lm_opt[l] >= 0)
-        for (int k = 0; k < e->lm_dim; ++k)
-          rhs_l[(size_t)st.lm_opt[l] * e->lm_dim + k] = bl[(size_t)l * e->lm_dim + k];
-  }
-  return 0;
-}
-
-int ba_hip_get_delta_gn(ba_hip_engine* h, double* delta_p, double* delta_l) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  if (delta_p && st.n) BAE_HIP(hipMemcpy(delta_p, e->gn_p.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
-  unpermute_vec(e, st.n ? delta_p : nullptr);
-  if (delta_l && st.Lact) BAE_HIP(hipMemcpy(delta_l, e->gn_l.p, (size_t)st.Lact * e->lm_dim * 8, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int ba_hip_get_step(ba_hip_engine* h, double* delta_p, double* delta_l) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  if (delta_p && st.n) BAE_HIP(hipMemcpy(delta_p, e->step_p.p, (size_t)st.n * 8, hipMemcpyDeviceToHost));
-  unpermute_vec(e, st.n ? delta_p : nullptr);
-  if (delta_l && st.Lact) BAE_HIP(hipMemcpy(delta_l, e->step_l.p, (size_t)st.Lact * e->lm_dim * 8, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int ba_hip_get_proj_weights(ba_hip_engine* h, double* weight) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  std::vector<double> w(st.O);
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  if (st.O) BAE_HIP(hipMemcpy(w.data(), e->obs_w.p, (size_t)st.O * 8, hipMemcpyDeviceToHost));
-  for (uint32_t s = 0; s < st.O; ++s) weight[st.obs_perm[s]] = w[s];
-  return 0;
-}
-
-int ba_hip_get_proj_residuals(ba_hip_engine* h, double* residual2) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  if (st.O == 0) return 0;
-  BAE_HIP(hipSetDevice(e->device));
-  DBuf<double> d;
-  BAE_HIP(d.alloc((size_t)2 * st.O));
-  int rc = launch_residual_vectors(e, d.p);
-  if (rc) return rc;
-  std::vector<double> r((size_t)2 * st.O);
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  BAE_HIP(hipMemcpy(r.data(), d.p, r.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (uint32_t s = 0; s < st.O; ++s) {
-    residual2[2 * (size_t)st.obs_perm[s]] = r[2 * (size_t)s];
-    residual2[2 * (size_t)st.obs_perm[s] + 1] = r[2 * (size_t)s + 1];
-  }
-  return 0;
-}
-
-int ba_hip_get_proj_jacobians(ba_hip_engine* h, double* j_meas12, double* j_ref12, double* j_lm, double* r2) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  if (st.O == 0) return 0;
-  BAE_HIP(hipSetDevice(e->device));
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  const int LM = e->lm_dim, R = rows_per_obs(LM);
-  std::vector<double> rows((size_t)st.O * R * kRow), jl((size_t)st.O * 2 * LM), sc((size_t)2 * st.O);
-  BAE_HIP(hipMemcpy(rows.data(), e->frow.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
-  BAE_HIP(hipMemcpy(jl.data(), e->obs_jl.p, jl.size() * sizeof(double), hipMemcpyDeviceToHost));
-  BAE_HIP(hipMemcpy(sc.data(), e->scal.p, sc.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (uint32_t s = 0; s < st.O; ++s) {
-    const size_t a = st.obs_perm[s];
-    const double* rr = &rows[(size_t)s * R * kRow];
-    if (j_meas12) for (int i = 0; i < 12; ++i) j_meas12[12 * a + i] = rr[i];
-    if (j_ref12) for (int i = 0; i < 12; ++i) j_ref12[12 * a + i] = LM == 1 ? rr[12 + i] : 0.0;
-    if (j_lm) for (int i = 0; i < 2 * LM; ++i) j_lm[2 * LM * a + i] = jl[(size_t)s * 2 * LM + i];
-    if (r2) { r2[2 * a] = sc[2 * (size_t)s]; r2[2 * a + 1] = sc[2 * (size_t)s + 1]; }
-  }
-  return 0;
-}
-
-// 6 doubles per row: with CalibSize 4 / 5 the last two / the last column are zero
-int ba_hip_get_calib_jacobians(ba_hip_engine* h, double* j_k12) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  if (!st.K) return e->fail_msg("no calibration columns (ba_hip_set_calibration)");
-  if (st.O == 0) return 0;
-  BAE_HIP(hipSetDevice(e->device));
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  std::vector<double> rows((size_t)2 * st.O * kRow);
-  BAE_HIP(hipMemcpy(rows.data(), e->crow.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (uint32_t s = 0; s < st.O; ++s)
-    for (int i = 0; i < 12; ++i) j_k12[12 * (size_t)st.obs_perm[s] + i] = rows[12 * (size_t)s + i];
-  return 0;
-}
-
-int ba_hip_get_imu_residuals(ba_hip_engine* h, double* residual15) {
-  ENG(h);
-  NEED_FINAL();
-  const uint32_t ni = e->prob.num_imu;
-  if (ni == 0) return 0;
-  BAE_HIP(hipSetDevice(e->device));
-  DBuf<double> d;
-  BAE_HIP(d.alloc((size_t)15 * ni));
-  int rc = launch_imu_residual_vectors(e, d.p);
-  if (rc) return rc;
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  BAE_HIP(hipMemcpy(residual15, d.p, (size_t)15 * ni * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int ba_hip_get_imu_errors(ba_hip_engine* h, double* mahalanobis) {
-  ENG(h);
-  NEED_FINAL();
-  const Problem& pb = e->prob;
-  if (pb.num_imu == 0) return 0;
-  BAE_HIP(hipSetDevice(e->device));
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  BAE_HIP(hipMemcpy(mahalanobis, e->pp_err.p + pb.num_unary + pb.num_binary, (size_t)pb.num_imu * sizeof(double),
-                    hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int ba_hip_set_unary_scales(ba_hip_engine* h, uint32_t n, const double* scale) {
-  ENG(h);
-  NEED_FINAL();
-  if (n != e->prob.num_unary || (n && !scale)) return e->fail_msg("ba_hip_set_unary_scales: one scale per unary residual expected");
-  if (!n) return 0;
-  BAE_HIP(hipSetDevice(e->device));
-  BAE_HIP(hipMemcpyAsync(e->un_scale.p, scale, n * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  return 0;
-}
-
-int ba_hip_get_unary_scales(ba_hip_engine* h, double* scale) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  if (e->prob.num_unary)
-    BAE_HIP(hipMemcpy(scale, e->un_scale.p, (size_t)e->prob.num_unary * 8, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int ba_hip_check_solve(ba_hip_engine* h, double* residual_norm, double* rhs_norm) {
-  ENG(h);
-  NEED_FINAL();
-  BAE_HIP(hipSetDevice(e->device));
-  // after a PCG solve A itself still holds S
-  if (!e->held.pcg_solved && !(e->held.factored && e->opt.keep_reduced_system && e->A_keep.p))
-    return e->fail_msg("ba_hip_check_solve needs keep_reduced_system and a finished ba_hip_solve_gn");
-  if (e->sharded()) return e->fail_msg("ba_hip_check_solve: single shard only");
-  double o[2];
-  int rc = check_solve_residual(e, e->held.pcg_solved ? e->A.p : e->A_keep.p, e->gn_p.p, e->rhs_sc.p, o);
-  if (rc) return rc;
-  if (residual_norm) *residual_norm = o[0];
-  if (rhs_norm) *rhs_norm = o[1];
-  return 0;
-}
-
-int ba_hip_get_timers(ba_hip_engine* h, ba_hip_timers* t) {
-  ENG(h);
-  *t = e->timers;
-  return 0;
-}
-
-int ba_hip_get_structure_stats(ba_hip_engine* h, ba_hip_structure_stats* out) {
-  ENG(h);
-  NEED_FINAL();
-  const Structure& st = e->st;
-  memset(out, 0, sizeof(*out));
-  out->poses_active = st.Pact; out->landmarks_active = st.Lact; out->observations = st.O;
-  out->incidences = st.n_inc; out->factor_rows = st.n_rows;
-  out->pair_blocks = st.n_pairs; out->pair_entries = st.n_pair_entries;
-  out->tile_refs = st.n_tile_refs; out->pose_entries = st.n_pose_entries; out->linearize_waves = st.n_chunks;
-  const uint64_t nt = st.ld / 64;
-  out->tiles_lower = nt * (nt + 1) / 2;
-  if (!e->held.nzL_valid && !(e->sharded())) {
-    int rc = factor_tile_pattern(e);
-    if (rc) return rc;
-  }
-  if (e->held.nzL_valid && e->nzL_host.size() == nt * nt && e->nzS_host.size() == nt * nt)
-    for (uint64_t i = 0; i < nt; ++i)
-      for (uint64_t k = 0; k <= i; ++k) {
-        out->tiles_S += e->nzS_host[i * nt + k] ? 1 : 0;
-        out->tiles_L += e->nzL_host[i * nt + k] ? 1 : 0;
-      }
-  if (e->held.nzL_valid && e->nzL_host.size() == nt * nt) out->factor_tile_products = factor_tile_products(e->nzL_host, (uint32_t)nt);
-  return 0;
-}
-
-int ba_hip_debug_set(ba_hip_engine* h, int key, int value) {
-  ENG(h);
-  switch (key) {
-    case 1:
-      if (value != 0 && value != 1 && value != 2 && value != 5 && value != 6)
-        return e->fail_msg("ba_hip_debug_set: key 1 takes the assembly variants 0, 1, 2, 5 and 6");
-      e->dbg_assemble_variant = value;
-      break;
-    case 2: e->dbg_tile_order = value; e->tile_order_version = ~0ull; break;
-    case 4: e->dbg_linearize_variant = value; break;
-    case 5: e->dbg_host_structure = value; e->held.problem_changed(); break;
-    case 6: e->dbg_imu_wave = value; break;
-    case 3: e->dbg_all_tiles = value; e->tile_order_version = ~0ull; e->held.square_dirty(); break;
-    default: return e->fail_msg("ba_hip_debug_set: unknown key");
-  }
-  return 0;
-}
-
-int ba_hip_set_profiling(ba_hip_engine* h, int enable) {
-  ENG(h);
-  e->prof_collect();
-  e->profiling = enable != 0;
-  memset(&e->kstats, 0, sizeof(e->kstats));
-  return 0;
-}
-int ba_hip_get_kernel_stats(ba_hip_engine* h, ba_hip_kernel_stats* out) {
-  ENG(h);
-  (void)hipStreamSynchronize(e->stream);
-  e->prof_collect();
-  *out = e->kstats;
-  return 0;
-}
-
-int ba_hip_device_buffer(ba_hip_engine* h, int which, void** dev_ptr, size_t* num_doubles) {
-  ENG(h);
-  NEED_FINAL();
-  if (which == 0) { *dev_ptr = e->A.p; *num_doubles = (size_t)(e->st.ld + 1) * e->st.ld; return 0; }
-  if (which == 1) { *dev_ptr = e->scalars_out.p; *num_doubles = e->scalars_out.n; return 0; }
-  return e->fail_msg("unknown buffer id");
-}
-
-int ba_hip_allreduce_host(ba_hip_engine* h, void* host, size_t count, int dtype) {
-  ENG(h);
-  if (!e->sharded() || count == 0) return 0;  // single shard: the values are already the totals
-  BAE_HIP(hipSetDevice(e->device));
-  DBuf<double> d;  // both element types are 8 bytes
-  BAE_HIP(d.alloc(count));
-  hipError_t err = hipMemcpy(d.p, host, count * 8, hipMemcpyHostToDevice);
-  int rc = 0;
-  if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
-  if (!rc && shard_allreduce(e, d.p, count, dtype) != 0) rc = e->fail_msg("allreduce hook failed");
-  if (!rc && (err = hipMemcpy(host, d.p, count * 8, hipMemcpyDeviceToHost)) != hipSuccess) rc = e->fail(err, "hipMemcpy");
-  return rc;
-}
-
-int ba_hip_get_comm_stats(ba_hip_engine* h, ba_hip_comm_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("null output");
-  *out = e->cstats;
-  return 0;
-}
-
-int ba_hip_reset_comm_stats(ba_hip_engine* h) {
-  ENG(h);
-  memset(&e->cstats, 0, sizeof(e->cstats));
-  return 0;
-}
-
-int ba_hip_dist_plan_stats(uint32_t nblk, const uint8_t* nz_lower, int nranks, const char* layout, uint32_t kout,
-                           ba_hip_dist_plan_stats_t* out) {
-  if (!out || nranks < 1 || nblk == 0) return -1;
-  const uint32_t G = kout ? kout : choose_kout(nblk);
-  OwnMap map;
-  std::string name;
-  if (!build_own_map((uint32_t)nranks, layout, G, &map, &name)) return -1;
-  const DistPlanStats s = dist_plan_stats(build_dist_plan(nblk, map, nz_lower));
-  out->factor_bytes = s.factor_bytes;
-  out->chain_recv_max = s.chain_recv_max; out->chain_recv_total = s.chain_recv_total;
-  out->side_recv_max = s.side_recv_max; out->side_recv_total = s.side_recv_total;
-  out->chain_sent_total = s.chain_sent_total; out->side_sent_total = s.side_sent_total;
-  out->recv_max = s.recv_max; out->backward_allreduce_bytes = s.backward_allreduce_bytes;
-  out->messages_chain = s.messages_chain; out->messages_side = s.messages_side;
-  out->panels = s.panels; out->ranks = s.ranks; out->classes = s.classes; out->kout = G;
-  return 0;
-}
-
-int ba_hip_get_factor_tile_pattern(ba_hip_engine* h, uint32_t nblk, uint8_t* nz_lower) {
-  ENG(h);
-  NEED_FINAL();
-  if (!e->held.nzL_valid) {
-    BAE_HIP(hipSetDevice(e->device));
-    const int rc = factor_tile_pattern(e);
-    if (rc) return rc;
-  }
-  if (e->nzL_host.size() != (size_t)nblk * nblk) return e->fail_msg("tile count mismatch");
-  memcpy(nz_lower, e->nzL_host.data(), e->nzL_host.size());
-  return 0;
-}
-
-int ba_hip_solve_is_distributed(ba_hip_engine* h) {
-  if (!h) return 0;
-  return dist_solve_enabled(reinterpret_cast<Engine*>(h)) ? 1 : 0;
-}
-
-int ba_hip_set_pose_ordering(ba_hip_engine* h, int mode) {
-  ENG(h);
-  if (mode != kOrderNatural && mode != kOrderAuto && mode != kOrderUser)
-    return e->fail_msg("ba_hip_set_pose_ordering: unknown mode");
-  if (mode != kOrderNatural && e->ordering_refused())
-    return e->fail_msg("pose ordering is not available on a sharded engine (all-reduce hook, collectives hook or communicator set)");
-  e->order_mode = mode;
-  return 0;
-}
-
-int ba_hip_set_reduced_solver(ba_hip_engine* h, int mode, const ba_hip_pcg_options* o) {
-  ENG(h);
-  if (mode != BA_HIP_SOLVER_DIRECT && mode != BA_HIP_SOLVER_PCG) return e->fail_msg("ba_hip_set_reduced_solver: unknown mode");
-  if (mode == BA_HIP_SOLVER_PCG) {
-    if (e->pcg_refused())
-      return e->fail_msg("the PCG solver is not available on a sharded engine (all-reduce hook, collectives hook or communicator set)");
-    ba_hip_pcg_options v = {};
-    v.rel_tolerance = 1e-6;
-    if (o) v = *o;
-    if (!(v.rel_tolerance > 0.0) || !(v.rel_tolerance < 1.0))
-      return e->fail_msg("ba_hip_set_reduced_solver: rel_tolerance must lie in (0, 1)");
-    e->pcg_opt = v;
-  }
-  e->solver_mode = mode;
-  return 0;
-}
-
-int ba_hip_get_pcg_stats(ba_hip_engine* h, ba_hip_pcg_stats* out) {
-  ENG(h);
-  if (!e->held.pcg_last) return e->fail_msg("ba_hip_get_pcg_stats: the last ba_hip_solve_gn did not run the PCG solver");
-  if (out) *out = e->pcg_stats;
-  return 0;
-}
-
-int ba_hip_get_pcg_coarse_stats(ba_hip_engine* h, ba_hip_pcg_coarse_stats* out) {
-  ENG(h);
-  if (!e->held.pcg_coarse_last) return e->fail_msg("ba_hip_get_pcg_coarse_stats: the last solve did not use the coarse space");
-  if (out) *out = e->pcg_coarse_stats;
-  return 0;
-}
-
-int ba_hip_get_pcg_coarse(ba_hip_engine* h, uint32_t nc, double* C, double* Cinv) {
-  ENG(h);
-  Engine::PcgWork& w = e->pcg;
-  if (!e->held.pcg_coarse_last || !w.coarse_nc || !w.C.p || !w.Cinv.p)
-    return e->fail_msg("ba_hip_get_pcg_coarse: the last solve did not use the coarse space");
-  if (nc != w.coarse_nc) return e->fail_msg("ba_hip_get_pcg_coarse: nc differs from the coarse unknowns of the last solve");
-  BAE_HIP(hipSetDevice(e->device));
-  const double* src[2] = {w.C.p, w.Cinv.p};
-  double* dst[2] = {C, Cinv};
-  for (int i = 0; i < 2; ++i)
-    if (dst[i])
-      BAE_HIP(hipMemcpy2D(dst[i], (size_t)nc * sizeof(double), src[i], (size_t)w.coarse_ncp * sizeof(double),
-                          (size_t)nc * sizeof(double), nc, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// ---- panel PCG (k_pcg_panel.hip): S^-1 on a block of columns after a PCG solve, A holds S ----
-// The refusals the two entry points share; `who` starts the messages.
-static int pcg_panel_ready(Engine* e, const char* who, const ba_hip_pcg_options* o) {
-  const std::string m = std::string(who) + ": ";
-  if (e->pcg_refused() || dist_solve_enabled(e))
-    return e->fail_msg((m + "not available on a sharded engine (all-reduce hook, collectives hook or communicator set)").c_str());
-  if (!e->held.finalized) return e->fail_msg((m + "ba_hip_finalize has not been called").c_str());
-  if (!e->held.pcg_solved) {
-    if (e->held.factored)
-      return e->fail_msg((m + "the last ba_hip_solve_gn ran the direct solver, A holds its factor and not S; panel solves need "
-                              "a PCG solve (ba_hip_set_reduced_solver, BA_HIP_SOLVER_PCG); ba_hip_factor_solve serves the factor").c_str());
-    if (e->held.pcg_last)
-      return e->fail_msg((m + "the system was re-linearised since the PCG solve of the last ba_hip_solve_gn").c_str());
-    return e->fail_msg((m + "needs a PCG solve by the last ba_hip_solve_gn (BA_HIP_SOLVER_PCG; none yet, or the system was "
-                            "re-linearised since)").c_str());
-  }
-  if (!o) return e->fail_msg((m + "NULL argument").c_str());
-  if (o->coarse_aggregate)
-    return e->fail_msg((m + "coarse_aggregate must be 0: the coarse space is not available in panel solves").c_str());
-  if (!(o->rel_tolerance > 0.0) || !(o->rel_tolerance < 1.0)) return e->fail_msg((m + "rel_tolerance must lie in (0, 1)").c_str());
-  if (e->pcg_plan.nt != e->st.ld / 64 || e->pcg_blk.size() != (size_t)2 * e->st.ld)
-    return e->fail_msg((m + "the plan of the last PCG solve does not match the system").c_str());
-  return 0;
-}
-static int pcg_panel_args(Engine* e, const char* who, uint32_t m, const void* a, const void* b) {
-  const std::string w = std::string(who) + ": ";
-  if (m == 0) return e->fail_msg((w + "no columns requested (m == 0)").c_str());
-  if (m > BA_HIP_PCG_PANEL_MAX_COLUMNS)
-    return e->fail_msg((w + std::to_string(m) + " columns requested, the limit is BA_HIP_PCG_PANEL_MAX_COLUMNS (" +
-                        std::to_string(BA_HIP_PCG_PANEL_MAX_COLUMNS) + ")").c_str());
-  if (!a || !b) return e->fail_msg((w + "NULL argument").c_str());
-  return 0;
-}
-// rows in the caller's (natural) order, as ba_hip_factor_solve
-static int pcg_panel_on_S(Engine* e, uint32_t m, const double* B, double* X, const ba_hip_pcg_options& o) {
-  BAE_HIP(hipSetDevice(e->device));
-  std::vector<uint32_t> rowmap(e->st.ld, kPcgNone);
-  for (uint32_t r = 0; r < e->st.n; ++r) rowmap[int_row(e, r)] = r;
-  int status = 0;
-  int rc = pcg_panel_solve_device(e, e->A.p, e->st.n, e->st.ld, e->pcg_plan, e->nzS_host, e->pcg_blk, e->pcg_blocks, rowmap.data(),
-                                  m, B, X, o, &status);
-  if (rc) return rc;
-  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
-}
-int ba_hip_pcg_panel_solve_system(ba_hip_engine* h, uint32_t m, const double* B, double* X, const ba_hip_pcg_options* o) {
-  ENG(h);
-  static const char* what = "ba_hip_pcg_panel_solve_system";
-  int rc;
-  if ((rc = pcg_panel_ready(e, what, o))) return rc;
-  if ((rc = pcg_panel_args(e, what, m, B, X))) return rc;
-  return pcg_panel_on_S(e, m, B, X, *o);
-}
-int ba_hip_get_joint_marginals_pcg(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, int include_calibration,
-                                   const ba_hip_pcg_options* o, double* out) {
-  ENG(h);
-  static const char* what = "ba_hip_get_joint_marginals_pcg";
-  const std::string msg = std::string(what) + ": ";
-  int rc;
-  if ((rc = pcg_panel_ready(e, what, o))) return rc;
-  if ((n && !pose_ids) || !out) return e->fail_msg((msg + "NULL argument").c_str());
-  const uint32_t D = (uint32_t)e->pose_dim, K = e->st.K;
-  if (include_calibration && !K)
-    return e->fail_msg((msg + "include_calibration without calibration unknowns (ba_hip_set_calibration)").c_str());
-  const uint64_t M = (uint64_t)n * D + (include_calibration ? K : 0);
-  if ((rc = pcg_panel_args(e, what, (uint32_t)std::min<uint64_t>(M, 0xffffffffu), out, out))) return rc;
-  std::vector<uint32_t> seen(pose_ids, pose_ids + n);
-  std::sort(seen.begin(), seen.end());
-  for (uint32_t i = 0; i + 1 < n; ++i)
-    if (seen[i] == seen[i + 1])
-      return e->fail_msg((msg + "pose " + std::to_string(seen[i]) + " is repeated (the joint block would be singular)").c_str());
-  std::vector<uint32_t> nat_of_int(e->st.ld, kPcgNone), sel;   // the selected rows in the caller's numbering
-  for (uint32_t r = 0; r < e->st.n; ++r) nat_of_int[int_row(e, r)] = r;
-  for (uint32_t i = 0; i < n; ++i) {
-    uint32_t r;
-    if ((rc = pose_row(e, pose_ids[i], &r, what))) return rc;
-    for (uint32_t x = 0; x < D; ++x) sel.push_back(nat_of_int[r + x]);
-  }
-  if (include_calibration)
-    for (uint32_t x = 0; x < K; ++x) sel.push_back(e->st.np + x);
-  const uint32_t m = (uint32_t)M, N = e->st.n;
-  std::vector<double> E((size_t)N * m, 0.0), X((size_t)N * m, 0.0);
-  for (uint32_t c = 0; c < m; ++c) E[(size_t)sel[c] * m + c] = 1.0;
-  rc = pcg_panel_on_S(e, m, E.data(), X.data(), *o);
-  if (rc && rc != BA_HIP_FACTORIZATION_ERROR) return rc;
-  for (uint32_t a = 0; a < m; ++a)
-    for (uint32_t c = 0; c < m; ++c)
-      out[(size_t)a * m + c] = 0.5 * (X[(size_t)sel[a] * m + c] + X[(size_t)sel[c] * m + a]);
-  return rc;
-}
-int ba_hip_get_pcg_panel_stats(ba_hip_engine* h, ba_hip_pcg_panel_stats* out) {
-  ENG(h);
-  if (!out) return e->fail_msg("ba_hip_get_pcg_panel_stats: NULL argument");
-  *out = e->pcgp_stats;
-  return 0;
-}
-int ba_hip_get_pcg_panel_columns(ba_hip_engine* h, uint32_t m, uint32_t* iterations, uint32_t* converged, uint32_t* breakdown,
-                                 double* rel_residual_true) {
-  ENG(h);
-  if (e->pcgp_cols.empty()) return e->fail_msg("ba_hip_get_pcg_panel_columns: no panel solve yet");
-  if (m != e->pcgp_cols.size())
-    return e->fail_msg(("ba_hip_get_pcg_panel_columns: m differs from the " + std::to_string(e->pcgp_cols.size()) +
-                        " columns of the last panel solve").c_str());
-  for (uint32_t j = 0; j < m; ++j) {
-    const PcgState& c = e->pcgp_cols[j];
-    if (iterations) iterations[j] = c.iterations;
-    if (converged) converged[j] = c.converged;
-    if (breakdown) breakdown[j] = c.breakdown;
-    if (rel_residual_true) rel_residual_true[j] = c.bb > 0.0 ? sqrt(c.rr_true / c.bb) : 0.0;
-  }
-  return 0;
-}
-
 int ba_hip_set_pose_permutation(ba_hip_engine* h, const uint32_t* opt_of_natural, uint32_t n) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   if (n && !opt_of_natural) return e->fail_msg("ba_hip_set_pose_permutation: NULL permutation");
   e->order_user.assign(opt_of_natural, opt_of_natural + n);
   return 0;
 }
 
 int ba_hip_get_pose_ordering(ba_hip_engine* h, uint32_t* opt_of_natural, ba_hip_ordering_stats* out) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_HOST(h);
+  if (!e->held.finalized) return e->fail_msg(kNotFinalized);
   if (opt_of_natural)
     for (uint32_t i = 0; i < e->st.Pact; ++i) opt_of_natural[i] = e->opt_of_natural.empty() ? i : e->opt_of_natural[i];
   if (out) *out = e->order_stats;
@@ -2236,8 +1385,8 @@ int ba_hip_get_pose_ordering(ba_hip_engine* h, uint32_t* opt_of_natural, ba_hip_
 }
 
 int ba_hip_get_pose_group_graph(ba_hip_engine* h, uint32_t* ptr, uint32_t* adj, uint32_t* num_groups, uint32_t* num_edges) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_HOST(h);
+  if (!e->held.finalized) return e->fail_msg(kNotFinalized);
   const uint32_t ng = e->group_ptr.empty() ? 0 : (uint32_t)e->group_ptr.size() - 1;
   if (num_groups) *num_groups = ng;
   if (num_edges) *num_edges = (uint32_t)e->group_adj.size();
@@ -2247,7 +1396,7 @@ int ba_hip_get_pose_group_graph(ba_hip_engine* h, uint32_t* ptr, uint32_t* adj, 
 }
 
 int ba_hip_set_collectives(ba_hip_engine* h, ba_hip_collective_fn fn, void* ctx) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   if (fn && e->order_mode != kOrderNatural)
     return e->fail_msg("the collectives hook needs natural pose order (ba_hip_set_pose_ordering is set)");
   if (fn && e->solver_mode == BA_HIP_SOLVER_PCG)
@@ -2258,7 +1407,7 @@ int ba_hip_set_collectives(ba_hip_engine* h, ba_hip_collective_fn fn, void* ctx)
 }
 
 int ba_hip_set_allreduce(ba_hip_engine* h, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   if (fn && e->order_mode != kOrderNatural)
     return e->fail_msg("the all-reduce hook needs natural pose order (ba_hip_set_pose_ordering is set)");
   if (fn && e->solver_mode == BA_HIP_SOLVER_PCG)
@@ -2271,7 +1420,7 @@ int ba_hip_set_allreduce(ba_hip_engine* h, ba_hip_allreduce_fn fn, void* ctx, in
 // ---- dense pose priors and marginalisation (k_marg.hip, marg.h) --------------------------------------
 int ba_hip_set_dense_priors(ba_hip_engine* h, uint32_t n, const uint32_t* ptr, const uint32_t* pose_ids,
                             const double* x0_16, const double* H, const double* b, const double* c) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   const int D = e->pose_dim;
   if (n && (!ptr || !pose_ids || !x0_16 || !H || !b || !c)) return e->fail_msg("ba_hip_set_dense_priors: NULL argument");
   if (n == 0) {  // removes the priors
@@ -2307,11 +1456,9 @@ int ba_hip_set_dense_priors(ba_hip_engine* h, uint32_t n, const uint32_t* ptr, c
 }
 
 int ba_hip_get_prior_errors(ba_hip_engine* h, uint32_t n, double* out) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   if (n != e->dpri.count() || (n && !out)) return e->fail_msg("ba_hip_get_prior_errors: one entry per dense prior expected");
   if (!n) return 0;
-  BAE_HIP(hipSetDevice(e->device));
   BAE_HIP(hipStreamSynchronize(e->stream));
   if (!e->dp_E_last) { for (uint32_t q = 0; q < n; ++q) out[q] = 0.0; return 0; }
   BAE_HIP(hipMemcpy(out, e->dp_E_last, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -2320,16 +1467,10 @@ int ba_hip_get_prior_errors(ba_hip_engine* h, uint32_t n, double* out) {
 
 int ba_hip_marginalize(ba_hip_engine* h, uint32_t nm, const uint32_t* m_ids, uint32_t nl, const uint32_t* l_ids,
                        ba_hip_marginalization_stats* stats) {
-  ENG(h);
-  NEED_FINAL();
+  BA_ENTRY_FINAL(h);
   const auto t0 = std::chrono::steady_clock::now();
   if ((nm && !m_ids) || (nl && !l_ids)) return e->fail_msg("marginalize: NULL argument");
-  if (e->st.K) return e->fail_msg("marginalize: not offered with calibration unknowns");
-  if (e->allreduce || e->coll || e->comm) return e->fail_msg("marginalize: not offered on sharded engines or with the distributed solve");
-  if (!e->held.lin_valid)
-    return e->fail_msg("marginalize: needs the linearisation of the current state (ba_hip_linearize, no step, rollback or "
-                       "new masks since)");
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ASK(guard_marginalize(e->held, guard_facts(e), e->st.K != 0));
   const Structure& st = e->st;
   MargPlan pl;
   std::string err;
@@ -2367,7 +1508,7 @@ int ba_hip_marginalize(ba_hip_engine* h, uint32_t nm, const uint32_t* m_ids, uin
 }
 
 int ba_hip_get_marginalization(ba_hip_engine* h, uint32_t* blanket_ids, double* x0_16, double* H, double* b, double* c) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   if (!e->held.marg_valid) return e->fail_msg("ba_hip_get_marginalization: no marginalisation result (ba_hip_marginalize)");
   if (blanket_ids) std::copy(e->marg_ids.begin(), e->marg_ids.end(), blanket_ids);
   if (x0_16) std::copy(e->marg_x0.begin(), e->marg_x0.end(), x0_16);
@@ -2378,7 +1519,7 @@ int ba_hip_get_marginalization(ba_hip_engine* h, uint32_t* blanket_ids, double* 
 }
 
 int ba_hip_release_marginalization(ba_hip_engine* h) {
-  ENG(h);
+  BA_ENTRY_HOST(h);
   e->held.marginalization_released();
   std::vector<uint32_t>().swap(e->marg_ids);
   std::vector<double>().swap(e->marg_x0);
@@ -2388,173 +1529,13 @@ int ba_hip_release_marginalization(ba_hip_engine* h) {
   return 0;
 }
 
-int ba_hip_dense_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, double* x) {
-  ENG(h);
-  BAE_HIP(hipSetDevice(e->device));
-  const PaddedSystem sys = pad_system(n, a_lower, b, false);
-  DBuf<double> dA, dx;
-  BAE_HIP(dA.alloc(sys.A.size()));
-  BAE_HIP(dx.alloc(sys.ld));
-  BAE_HIP(e->flags.alloc(16));
-  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
-  int status = 0;
-  e->held.standalone_factorisation();
-  int rc = cholesky_solve(e, dA.p, n, sys.ld, dx.p, &status, nullptr);  // arbitrary matrix: dense
-  if (rc) return rc;
-  BAE_HIP(download_x(dx, n, x));
-  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
-}
-
-int ba_hip_pcg_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, uint32_t block,
-                     const ba_hip_pcg_options* o, double* x, ba_hip_pcg_stats* stats) {
-  ENG(h);
-  if (!n || !a_lower || !b || !o || !x) return e->fail_msg("ba_hip_pcg_solve: NULL or empty argument");
-  if (block < 1 || block > kPcgMaxBlock) return e->fail_msg("ba_hip_pcg_solve: block must lie in 1 .. 16");
-  if (!(o->rel_tolerance > 0.0) || !(o->rel_tolerance < 1.0)) return e->fail_msg("ba_hip_pcg_solve: rel_tolerance must lie in (0, 1)");
-  BAE_HIP(hipSetDevice(e->device));
-  const PaddedSystem sys = pad_system(n, a_lower, b, true);
-  const uint32_t ld = sys.ld;
-  PcgPlan plan;
-  build_pcg_plan(sys.nz, sys.nt, plan);
-  std::vector<uint32_t> blk, blocks;
-  pcg_row_blocks(n, block, 0, ld, blk, blocks);
-  if (o->coarse_aggregate) {
-    std::vector<uint32_t> nat;
-    uint32_t nblk = 0;
-    pcg_natural_rows(n, block, 0, ld, nat, nblk);
-    build_pcg_coarse(plan, nat, nblk, block, 0, o->coarse_aggregate);
-  }
-  DBuf<double> dA, dx;
-  BAE_HIP(dA.alloc(sys.A.size()));
-  BAE_HIP(dx.alloc(ld));
-  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
-  int status = 0;
-  ba_hip_pcg_stats st;
-  e->pcg_plan_version = ~0ull;   // the work space now holds this system's plan, not the engine's
-  int rc = pcg_solve_device(e, dA.p, n, ld, dA.p + (size_t)ld * ld, plan, sys.nz, blk, blocks, true, *o, dx.p, &st, &status);
-  if (rc) return rc;
-  BAE_HIP(download_x(dx, n, x));
-  if (stats) *stats = st;
-  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
-}
-
-int ba_hip_pcg_panel_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, uint32_t m, const double* B, uint32_t block,
-                           const ba_hip_pcg_options* o, double* X, ba_hip_pcg_panel_stats* stats) {
-  ENG(h);
-  static const char* what = "ba_hip_pcg_panel_solve";
-  if (!n || !a_lower || !o) return e->fail_msg("ba_hip_pcg_panel_solve: NULL or empty argument");
-  int rc;
-  if ((rc = pcg_panel_args(e, what, m, B, X))) return rc;
-  if (block < 1 || block > kPcgMaxBlock) return e->fail_msg("ba_hip_pcg_panel_solve: block must lie in 1 .. 16");
-  if (!(o->rel_tolerance > 0.0) || !(o->rel_tolerance < 1.0)) return e->fail_msg("ba_hip_pcg_panel_solve: rel_tolerance must lie in (0, 1)");
-  if (o->coarse_aggregate)
-    return e->fail_msg("ba_hip_pcg_panel_solve: coarse_aggregate must be 0: the coarse space is not available in panel solves");
-  BAE_HIP(hipSetDevice(e->device));
-  const std::vector<double> zero(n, 0.0);
-  const PaddedSystem sys = pad_system(n, a_lower, zero.data(), true);
-  const uint32_t ld = sys.ld;
-  PcgPlan plan;
-  build_pcg_plan(sys.nz, sys.nt, plan);
-  std::vector<uint32_t> blk, blocks, rowmap(ld, kPcgNone);
-  pcg_row_blocks(n, block, 0, ld, blk, blocks);
-  for (uint32_t r = 0; r < n; ++r) rowmap[r] = r;
-  DBuf<double> dA;
-  BAE_HIP(dA.alloc(sys.A.size()));
-  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
-  int status = 0;
-  e->held.pcg_run_begins();   // a stand-alone PCG run without the coarse space, as ba_hip_pcg_solve
-  rc = pcg_panel_solve_device(e, dA.p, n, ld, plan, sys.nz, blk, blocks, rowmap.data(), m, B, X, *o, &status);
-  if (rc) return rc;
-  e->held.pcg_run_finished(false);
-  if (stats) *stats = e->pcgp_stats;
-  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
-}
-
-// The direct tile-sparse factorisation on a host system with a caller-supplied tile pattern (test entry: the
-// kept factor comes back as the engine holds it).  Uses buffers of its own for the matrix and the pattern; the
-// engine's invdiag work space is shared with ba_hip_solve_gn, so the scene's kept factor is marked gone.
-// Shared by ba_hip_tile_solve and ba_hip_tile_factor_solve: `who` starts the messages; sys, dA and dx are the
-// caller's and outlive the call (the factor stays in dA, its closed pattern in sys.nz, the solution in dx).
-static int tile_factorise(Engine* e, const char* who, uint32_t n, const double* a_lower, const double* b,
-                          const uint8_t* tile_map, PaddedSystem& sys, DBuf<double>& dA, DBuf<double>& dx, int* status) {
-  BAE_HIP(hipSetDevice(e->device));
-  sys = pad_system(n, a_lower, b, true);
-  const uint32_t ld = sys.ld, nt = sys.nt;
-  std::vector<uint8_t>& nz = sys.nz;
-  if (tile_map) {
-    for (uint32_t r = 0; r < n; ++r)
-      for (uint32_t c = 0; c <= r; ++c)
-        if (a_lower[(size_t)r * n + c] != 0.0 && r / 64 != c / 64 && !tile_map[(size_t)(r / 64) * nt + c / 64]) {
-          e->err = std::string(who) + ": entry (" + std::to_string(r) + ", " + std::to_string(c) + ") is nonzero but tile (" +
-                   std::to_string(r / 64) + ", " + std::to_string(c / 64) + ") is not in the tile map";
-          return -1;
-        }
-    for (uint32_t i = 0; i < nt; ++i)
-      for (uint32_t k = 0; k <= i; ++k) nz[(size_t)i * nt + k] |= tile_map[(size_t)i * nt + k] ? 1 : 0;
-  }
-  for (uint32_t i = 0; i < nt; ++i) nz[(size_t)i * nt + i] = 1;  // diagonal tiles always
-  tile_symbolic_factor(nz, nt);
-  DBuf<uint8_t> dnz;
-  BAE_HIP(dA.alloc(sys.A.size()));
-  BAE_HIP(dx.alloc(ld));
-  BAE_HIP(dnz.alloc(nz.size()));
-  BAE_HIP(e->flags.alloc(16));
-  BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
-  BAE_HIP(hipMemcpy(dnz.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
-  e->held.standalone_factorisation();
-  int rc = cholesky_solve(e, dA.p, n, ld, dx.p, status, dnz.p);
-  if (rc) return rc;
-  BAE_HIP(hipDeviceSynchronize());  // both streams of the factorisation (dnz goes with this scope)
-  return 0;
-}
-int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, const uint8_t* tile_map,
-                      double* x, uint8_t* nz_factor, double* factor, double* linvT, double* dsgn) {
-  ENG(h);
-  if (!n || !a_lower || !b || !x) return e->fail_msg("ba_hip_tile_solve: NULL or empty argument");
-  PaddedSystem sys;
-  DBuf<double> dA, dx;
-  int status = 0;
-  if (int rc = tile_factorise(e, "ba_hip_tile_solve", n, a_lower, b, tile_map, sys, dA, dx, &status)) return rc;
-  const uint32_t ld = sys.ld, nt = sys.nt;
-  if (nz_factor) std::copy(sys.nz.begin(), sys.nz.end(), nz_factor);
-  hipError_t err = download_x(dx, n, x);
-  if (err == hipSuccess && factor) err = hipMemcpy(factor, dA.p, (size_t)ld * ld * 8, hipMemcpyDeviceToHost);
-  const FactorWork fw(nt);
-  if (err == hipSuccess && dsgn) err = hipMemcpy(dsgn, e->invdiag.p + fw.dsgn, (size_t)ld * 8, hipMemcpyDeviceToHost);
-  if (err == hipSuccess && linvT)
-    err = hipMemcpy(linvT, e->invdiag.p + fw.linvT, (size_t)nt * 64 * 64 * 8, hipMemcpyDeviceToHost);
-  if (err != hipSuccess) return e->fail(err, "hipMemcpy");
-  return status ? BA_HIP_FACTORIZATION_ERROR : 0;
-}
-
-int ba_hip_tile_factor_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const uint8_t* tile_map, uint32_t m,
-                             const double* B, double* X) {
-  ENG(h);
-  static const char* what = "ba_hip_tile_factor_solve";
-  if (!n || !a_lower) return e->fail_msg("ba_hip_tile_factor_solve: NULL or empty argument");
-  if (int rc = factor_solve_args(e, what, m, B, X)) return rc;
-  PaddedSystem sys;
-  DBuf<double> dA, dx;
-  int status = 0;
-  const std::vector<double> b(n, 0.0);
-  if (int rc = tile_factorise(e, what, n, a_lower, b.data(), tile_map, sys, dA, dx, &status)) return rc;
-  if (status) return BA_HIP_FACTORIZATION_ERROR;
-  const FactorWork fw(sys.nt);
-  const FactorRef f = {dA.p, sys.ld, sys.nt, &sys.nz, e->invdiag.p + fw.dsgn, e->invdiag.p + fw.linvT};
-  std::vector<uint32_t> rowmap(sys.ld, kJointNone);
-  for (uint32_t r = 0; r < n; ++r) rowmap[r] = r;
-  return factor_solve_run(e, f, n, rowmap.data(), m, B, X);
-}
-
 int ba_hip_select_kth(ba_hip_engine* h, uint32_t n, const double* values, uint32_t k, double* out) {
-  ENG(h);
-  BAE_HIP(hipSetDevice(e->device));
+  BA_ENTRY_DEVICE(h);
   DBuf<double> dv;
   BAE_HIP(dv.alloc(std::max<uint32_t>(n, 1)));
   BAE_HIP(e->hist.alloc(2048 + 8));
   if (n) BAE_HIP(hipMemcpy(dv.p, values, (size_t)n * 8, hipMemcpyHostToDevice));
-  int rc = select_kth(e, dv.p, n, k, out);
-  return rc;
+  return select_kth(e, dv.p, n, k, out);
 }
 
 }  // extern "C"

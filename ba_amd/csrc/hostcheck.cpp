@@ -1040,3 +1040,90 @@ extern "C" int ba_hostcheck_pcg_panel(uint32_t n, const double* S, const uint8_t
   if (out_scalar) { out_scalar[0] = res.passes; out_scalar[1] = pl.n_tiles; out_scalar[2] = pp.n_src(); out_scalar[3] = pp.n_chunks(); }
   return rc;
 }
+
+// ---- the request layer (requests.h) ---------------------------------------------------------------------------
+#include "requests.h"
+
+// the message into msg (cap bytes with the terminator); 0 = served, 1 = refused
+static int put_message(const std::string& m, char* msg, uint32_t cap) {
+  if (msg && cap) {
+    const size_t k = std::min<size_t>(m.size(), cap - 1);
+    std::copy(m.begin(), m.begin() + k, msg);
+    msg[k] = 0;
+  }
+  return m.empty() ? 0 : 1;
+}
+
+// The events replayed on a fresh record as ba_hostcheck_lifecycle does, then one named guard of requests.h.
+// facts: bit 0 distributed solve, 1 sharded, 2 hooked, 3 kept copy, 4 the PCG plan fits.  flags: bit 0 foreign_ok
+// (kept_factor), bit 1 landmarks (kept_factor, marginals), bit 2 the caller passed PCG options (pcg_panel), bit 3
+// calibration unknowns (marginalize).  noun: kept_factor only, null for the calibration wording.
+// Returns 0 (served), 1 (refused, the message in msg), -(i + 1) at the first unknown event code, -1000 for an
+// unknown guard.
+extern "C" int ba_hostcheck_guard(uint32_t n, const int32_t* events, const char* guard, const char* who, const char* noun,
+                                  uint32_t facts, uint32_t flags, double rel_tolerance, uint32_t coarse_aggregate, char* msg,
+                                  uint32_t cap) {
+  using namespace bae;
+  Held h;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!held_apply(h, events[i])) return -(int)(i + 1);
+  const GuardFacts f = {(facts & 1) != 0, (facts & 2) != 0, (facts & 4) != 0, (facts & 8) != 0, (facts & 16) != 0};
+  const PcgAsk ask = {rel_tolerance, coarse_aggregate};
+  const std::string g = guard;
+  if (g == "kept_factor") return put_message(guard_kept_factor(h, f, who, noun, flags & 1, (flags & 2) != 0), msg, cap);
+  if (g == "marginals") return put_message(guard_marginals(h, f, who, (flags & 2) != 0), msg, cap);
+  if (g == "pcg_panel") return put_message(guard_pcg_panel(h, f, who, flags & 4 ? &ask : nullptr), msg, cap);
+  if (g == "check_solve") return put_message(guard_check_solve(h, f), msg, cap);
+  if (g == "get_S") return put_message(guard_get_S(h, f), msg, cap);
+  if (g == "pcg_stats") return put_message(guard_pcg_stats(h), msg, cap);
+  if (g == "pcg_coarse_stats") return put_message(guard_pcg_coarse_stats(h), msg, cap);
+  if (g == "marginalize") return put_message(guard_marginalize(h, f, (flags & 8) != 0), msg, cap);
+  return -1000;
+}
+
+// select_rows on a structure given by its tables (n = np + K; n_perm entries of opt_of_natural, 0 = no ordering).
+// rows_out (room for the request's columns) and lms_out (n_lms) receive the selection, counts[0 .. 1] their sizes.
+extern "C" int ba_hostcheck_selection(uint32_t P, const int32_t* pose_opt, uint32_t L, const int32_t* lm_opt, uint32_t np,
+                                      uint32_t K, uint32_t D, uint32_t LM, uint32_t ld, uint32_t n_perm,
+                                      const uint32_t* opt_of_natural, const char* who, uint32_t n_poses, const uint32_t* pose_ids,
+                                      int include_calibration, uint32_t n_lms, const uint32_t* lm_ids, int have_out,
+                                      uint64_t limit, const char* limit_name, const char* nothing, int caller_numbering,
+                                      uint32_t* rows_out, uint32_t* lms_out, uint32_t* counts, char* msg, uint32_t cap) {
+  using namespace bae;
+  const std::vector<int32_t> po(pose_opt, pose_opt + P), lo(lm_opt, lm_opt + L);
+  const std::vector<uint32_t> perm(opt_of_natural, opt_of_natural + n_perm);
+  const StructureView v = {P, L, np, K, np + K, ld, D, LM, &po, &lo, &perm};
+  RowSelection s;
+  const int rc = put_message(select_rows(v, {who, n_poses, pose_ids, include_calibration != 0, n_lms, lm_ids, have_out != 0, limit,
+                                             limit_name, nothing, caller_numbering != 0}, &s), msg, cap);
+  if (rc) return rc;
+  std::copy(s.rows.begin(), s.rows.end(), rows_out);
+  std::copy(s.lms.begin(), s.lms.end(), lms_out);
+  counts[0] = (uint32_t)s.rows.size(); counts[1] = (uint32_t)s.lms.size();
+  return 0;
+}
+
+// The small checks: op 0 ids_or_all (u: have ids, n, count; name: the count's name), 1 pcg_options_ok (d: tolerance;
+// u: coarse_aggregate, the PcgCoarse mode), 2 block_ok (u: block), 3 columns_ok (u: m, limit; name: the limit's).
+extern "C" int ba_hostcheck_request_check(int op, const char* who, const char* name, const uint64_t* u, const double* d, char* msg,
+                                          uint32_t cap) {
+  using namespace bae;
+  if (op == 0) return put_message(ids_or_all(who, u[0] ? who : nullptr, (uint32_t)u[1], (uint32_t)u[2], name), msg, cap);
+  if (op == 1) return put_message(pcg_options_ok(who, {d[0], (uint32_t)u[0]}, (PcgCoarse)u[1]), msg, cap);
+  if (op == 2) return put_message(block_ok(who, (uint32_t)u[0]), msg, cap);
+  if (op == 3) return put_message(columns_ok(who, u[0], u[1], name), msg, cap);
+  return -1000;
+}
+
+// natural_rowmap of np pose rows in blocks of D under opt_of_natural (n_perm entries, 0 = none) and K border rows, and
+// identity_rowmap(np + K, ld): ld entries each
+extern "C" void ba_hostcheck_rowmaps(uint32_t np, uint32_t K, uint32_t D, uint32_t ld, uint32_t n_perm,
+                                     const uint32_t* opt_of_natural, uint32_t* natural_out, uint32_t* identity_out) {
+  using namespace bae;
+  const std::vector<int32_t> none;
+  const std::vector<uint32_t> perm(opt_of_natural, opt_of_natural + n_perm);
+  const StructureView v = {0, 0, np, K, np + K, ld, D, 0, &none, &none, &perm};
+  const std::vector<uint32_t> a = natural_rowmap(v), b = identity_rowmap(np + K, ld);
+  std::copy(a.begin(), a.end(), natural_out);
+  std::copy(b.begin(), b.end(), identity_out);
+}

@@ -4,8 +4,8 @@ drops it").
 
 Two tables and one scene.  An EVENT is a short driver on hipapi.Engine plus the HeldEvent codes the engine fires while
 it runs; a READER is a call on the engine plus the rule that says, from the Held bits, whether the engine serves it or
-refuses it and with which message (the rules restate kept_factor_ready, pcg_panel_ready, the marginalize guard and
-the guards of check_solve / get_S / get_pcg_stats of engine.hip).  The expected outcome of a cell is not written
+refuses it and with which message (the rules restate guard_kept_factor, guard_pcg_panel, the marginalize guard and
+the guards of check_solve / get_S / get_pcg_stats of requests.h; test_lifecycle.py holds those guards to the rules).  The expected outcome of a cell is not written
 down: walk() replays the codes fired so far through ba_hostcheck_lifecycle (the record of lifecycle.h itself, compiled
 for the host) and applies the reader's rule to the bits that come back.  A cell is one of
 
@@ -78,7 +78,7 @@ def scene_AB():
     return sc, pa, obs, poses_a, poses_b
 
 
-# ---- messages: the wording of engine.hip as regular expressions ----------------------------------------------------
+# ---- messages: the wording of requests.h as regular expressions ----------------------------------------------------
 NOT_FINALIZED = "ba_hip_finalize has not been called"
 NO_FACTOR = "needs the factor of the last ba_hip_solve_gn \\(none yet, or the system was re-linearised since\\)"
 NO_FACTOR_SHORT = "ba_hip_get_calibration_marginals needs the factor of the last ba_hip_solve_gn"
@@ -106,9 +106,9 @@ def refuse(kind, who=None, short=False):
     return ("refuse", kind, (who + ": " if who else "") + msg)
 
 
-# ---- the rules: outcome from the Held bits, one per guard of engine.hip --------------------------------------------
+# ---- the rules: outcome from the Held bits, one per guard of requests.h -------------------------------------------
 def rule_kept_factor(who, foreign_ok=lambda bits: False, short=False, honour=("finalized", "factored", "pcg_solved", "foreign")):
-    """kept_factor_ready behind the caller's own finalized check.  honour: the bits the rule looks at — the negative
+    """guard_kept_factor (with its finalized check).  honour: the bits the rule looks at — the negative
     check of test_lifecycle.py leaves one out and must see a cell change."""
     def rule(bits):
         has = lambda b: b in bits and b in honour
@@ -125,7 +125,7 @@ def rule_kept_factor(who, foreign_ok=lambda bits: False, short=False, honour=("f
 
 
 def rule_marginals(who, **kw):
-    """marginals_ready: a selected inverse computed before a stand-alone solve stays good"""
+    """guard_marginals: a selected inverse computed before a stand-alone solve stays good"""
     return rule_kept_factor(who, foreign_ok=lambda bits: "sig" in bits, **kw)
 
 

@@ -263,6 +263,134 @@ def test_documented_matrix_is_the_derived_one():
     assert lcs.matrix_markdown() in doc
 
 
+# ---- the guards of requests.h themselves (ba_hostcheck_guard) against the readers' rules -------------------------
+KEPT_COPY, PLAN_FITS = 8, 16                 # facts: every engine of these tests keeps the reduced system
+FOREIGN_OK, LANDMARKS, HAS_OPTIONS = 1, 2, 4   # flags
+
+
+def _guard_of(reader):
+    """(guard, who, noun, facts, flags) of ba_hostcheck_guard for a reader of the table"""
+    name = reader.name[:-5] if reader.name.endswith("_cold") else reader.name
+    kept = {"joint_marginals": ("ba_hip_get_joint_marginals", "joint marginals", 0),
+            "joint_state_marginals": ("ba_hip_get_joint_state_marginals", "joint marginals", LANDMARKS),
+            "factor_solve": ("ba_hip_factor_solve", "solves with the factor", 0),
+            "weakest_modes": ("ba_hip_get_weakest_modes", "weakest modes", 0)}
+    marginals = {"pose_marginals": ("ba_hip_get_pose_marginals", 0), "pose_pair_marginals": ("ba_hip_get_pose_pair_marginals", 0),
+                 "landmark_marginals": ("ba_hip_get_landmark_marginals", LANDMARKS),
+                 "projection_leverages": ("ba_hip_get_projection_leverages", LANDMARKS),
+                 "pose_pose_leverages_unary": ("ba_hip_get_pose_pose_leverages", 0),
+                 "pose_pose_leverages_binary": ("ba_hip_get_pose_pose_leverages", 0)}
+    panel = {"pcg_panel_solve_system": "ba_hip_pcg_panel_solve_system", "joint_marginals_pcg": "ba_hip_get_joint_marginals_pcg"}
+    if name in kept:
+        return ("kept_factor", kept[name][0], kept[name][1], 0, kept[name][2])
+    if name in marginals:
+        return ("marginals", marginals[name][0], None, 0, marginals[name][1])
+    if name in panel:
+        return ("pcg_panel", panel[name], None, PLAN_FITS, HAS_OPTIONS)
+    if name == "calibration_marginals":
+        return ("kept_factor", "ba_hip_get_calibration_marginals", None, 0, 0)
+    assert name in ("check_solve", "get_S", "marginalize", "pcg_stats"), name
+    return (name, "", None, KEPT_COPY, 0)
+
+
+def _ask_guard(codes, guard, who, noun, facts, flags):
+    """the message of the C++ guard after the events `codes` on a fresh record ("" = served)"""
+    hc = hostcheck_lib()
+    hc.ba_hostcheck_guard.restype = ctypes.c_int
+    ev = np.array([EVENTS.index(c) for c in codes], dtype=np.int32)
+    msg = ctypes.create_string_buffer(512)
+    rc = hc.ba_hostcheck_guard(ctypes.c_uint32(len(ev)), ev.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), guard.encode(),
+                               who.encode(), noun.encode() if noun else None, ctypes.c_uint32(facts), ctypes.c_uint32(flags),
+                               ctypes.c_double(lcs.PCG_TOL), ctypes.c_uint32(0), msg, ctypes.c_uint32(512))
+    assert rc in (0, 1), (rc, guard)
+    assert bool(rc) == bool(msg.value)
+    return msg.value.decode()
+
+
+def test_the_guards_decide_every_cell_as_the_rules_do():
+    """Every cell of the event x reader matrix, and beyond it every prefix of every event's code sequence: the guard
+    of requests.h that the reader's entry point asks serves exactly where the reader's rule serves, and where it
+    refuses its message matches the rule's regular expression.  (The rules remain the statement the matrix of
+    DESIGN.md is derived from; this holds the product code to them without a device.)"""
+    import re
+    cells = 0
+    for ev in lcs.EVENT_LIST:
+        t = lcs.Tracker(lcs.SETUPS[ev.setup])
+        for r in lcs.READERS:
+            t.expect(r)
+        t.fire(*ev.codes)
+        for r in lcs.READERS:
+            codes = list(t.codes) + list(r.before_codes)      # what has fired when the reader's guard looks
+            out, bits = t.expect(r)
+            got = _ask_guard(codes, *_guard_of(r))
+            assert (got == "") == (out[0] == "serve"), (ev.name, r.name, out, got)
+            if got:
+                assert re.search(out[2], got), (ev.name, r.name, out[2], got)
+            cells += 1
+        # every prefix of everything this engine has fired by now, for every reader and the calibration getter
+        history = lcs.replay(*t.codes)
+        for k in range(len(t.codes) + 1):
+            bits = history[k - 1] if k else frozenset()
+            for r in lcs.READERS + [lcs.CALIBRATION_READER]:
+                out = r.rule(bits)
+                got = _ask_guard(t.codes[:k], *_guard_of(r))
+                assert (got == "") == (out[0] == "serve"), (ev.name, k, r.name, out, got)
+                if got:
+                    assert re.search(out[2], got), (ev.name, k, r.name, out[2], got)
+    assert cells == len(lcs.EVENT_LIST) * len(lcs.READERS) == 437
+
+
+def test_the_guards_read_the_engine_facts():
+    """the branches of the guards that no single-GPU engine reaches: sharded engines, the distributed solve, a system
+    factorised in place, a PCG plan of another system, missing or unusable PCG options"""
+    import re
+    direct, pcg = lcs.SETUP, lcs.SETUP_PCG
+    DIST, SHARDED, HOOKED = 1, 2, 4
+    who = "ba_hip_get_joint_state_marginals"
+    assert _ask_guard(direct, "kept_factor", who, "joint marginals", SHARDED, LANDMARKS) == \
+        who + ": landmark blocks are not available on sharded engines (each rank holds one landmark shard)"
+    assert _ask_guard(direct, "kept_factor", who, "joint marginals", SHARDED, 0) == ""
+    assert _ask_guard(direct, "kept_factor", who, "joint marginals", SHARDED | DIST, LANDMARKS) == \
+        who + ": not available with the distributed solve"
+    assert _ask_guard(direct, "marginals", "w", None, DIST, 0) == "w: not available with the distributed solve"
+    # the calibration getter's wording, and its later place for the distributed solve
+    cal = "ba_hip_get_calibration_marginals"
+    assert _ask_guard(direct, "kept_factor", cal, None, DIST, 0) == "calibration marginals: not available with the distributed solve"
+    assert _ask_guard(lcs.UPLOAD + lcs.FINALIZE, "kept_factor", cal, None, DIST, 0) == cal + " needs the factor of the last ba_hip_solve_gn"
+    assert _ask_guard((), "kept_factor", cal, None, 0, 0) == "ba_hip_finalize has not been called"
+    foreign = direct + ("selinv_released", "standalone_factorisation")
+    assert re.search(lcs.FOREIGN, _ask_guard(foreign, "kept_factor", "w", "weakest modes", 0, 0))
+    assert _ask_guard(foreign, "kept_factor", "w", "weakest modes", 0, FOREIGN_OK) == ""
+    # the reduced system
+    assert _ask_guard(direct, "get_S", "", None, 0, 0).startswith("S was factorised in place")
+    assert _ask_guard(direct, "get_S", "", None, KEPT_COPY, 0) == "" and _ask_guard(pcg, "get_S", "", None, 0, 0) == ""
+    assert re.search(lcs.NO_CHECK, _ask_guard(direct, "check_solve", "", None, 0, 0))
+    assert _ask_guard(pcg, "check_solve", "", None, 0, 0) == ""
+    assert _ask_guard(pcg, "check_solve", "", None, SHARDED, 0) == "ba_hip_check_solve: single shard only"
+    # panel PCG
+    w = "ba_hip_pcg_panel_solve_system"
+    assert _ask_guard(pcg, "pcg_panel", w, None, PLAN_FITS, HAS_OPTIONS) == ""
+    assert _ask_guard(pcg, "pcg_panel", w, None, 0, HAS_OPTIONS) == w + ": the plan of the last PCG solve does not match the system"
+    assert _ask_guard(pcg, "pcg_panel", w, None, PLAN_FITS, 0) == w + ": NULL argument"
+    for facts in (HOOKED, DIST):
+        assert _ask_guard((), "pcg_panel", w, None, facts | PLAN_FITS, HAS_OPTIONS) == \
+            w + ": not available on a sharded engine (all-reduce hook, collectives hook or communicator set)"
+    # marginalize and the coarse statistics
+    assert _ask_guard(direct, "marginalize", "", None, 0, 0) == ""
+    assert _ask_guard(direct, "marginalize", "", None, 0, 8) == "marginalize: not offered with calibration unknowns"
+    assert _ask_guard(direct, "marginalize", "", None, HOOKED, 0) == "marginalize: not offered on sharded engines or with the distributed solve"
+    coarse = lcs.UPLOAD + lcs.FINALIZE + ("gn_solve_begins", "pcg_run_begins", "pcg_run_finished_coarse", "solved_by_pcg")
+    assert _ask_guard(coarse, "pcg_coarse_stats", "", None, 0, 0) == ""
+    assert _ask_guard(pcg, "pcg_coarse_stats", "", None, 0, 0) == "ba_hip_get_pcg_coarse_stats: the last solve did not use the coarse space"
+    hc = hostcheck_lib()
+    hc.ba_hostcheck_guard.restype = ctypes.c_int
+    bad = np.array([len(EVENTS)], dtype=np.int32)
+    msg = ctypes.create_string_buffer(8)
+    args = (b"w", None, ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_double(0.5), ctypes.c_uint32(0), msg, ctypes.c_uint32(8))
+    assert hc.ba_hostcheck_guard(ctypes.c_uint32(1), bad.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), b"get_S", *args) == -1
+    assert hc.ba_hostcheck_guard(ctypes.c_uint32(0), None, b"no_such_guard", *args) == -1000
+
+
 # ---- states A and B are far enough apart (the oracle on the CPU) ------------------------------------------------
 def _oracle_system(sc, pa, obs, poses, terms):
     import copy
