@@ -1,7 +1,8 @@
-// Host decisions of the LDL^T solve (k_chol.hip): its environment switches, the shapes of its launches, the layout
-// of its work space and the key of the distributed plan.  Integers in, small structs out — no HIP type, so
-// hostcheck.cpp evaluates the same functions on the CPU (ba_hostcheck_chol_launch, tests/test_chol_launch.py).
-// These are the only getenv calls of the solve (DESIGN.md 9.1a has the table).
+// Host decisions of the LDL^T solve (k_chol.hip, and its distributed driver dist_solve.hip): its environment
+// switches, the shapes of its launches, the layout of its work space and the key of the distributed plan (the plan
+// and its tables: dist_plan.h).  Integers in, small structs out — no HIP type, so hostcheck.cpp evaluates the same
+// functions on the CPU (ba_hostcheck_chol_launch, tests/test_chol_launch.py).  These are the only getenv calls of the
+// solve (DESIGN.md 9.1a has the table).
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -77,7 +78,7 @@ inline const CholSwitches& chol_process_switches() {
   }();
   return once;
 }
-// Every switch, for a solve of nblk tiles: the entry points of k_chol.hip call this once and hand it down.
+// Every switch, for a solve of nblk tiles: the entry points of k_chol.hip / dist_solve.hip call this once and hand it down.
 inline CholSwitches chol_switches(uint32_t nblk) {
   CholSwitches sw = chol_process_switches();
   parse_call_switches(&sw, nblk, getenv("BA_HIP_KOUT"), getenv("BA_HIP_LEFT_MIN_TILES"), getenv("BA_HIP_SQUARE"),
@@ -154,7 +155,7 @@ struct FactorWork {
         colneg(opbuf + (size_t)nblk * kPacketStride), total(colneg + (nblk + 1) / 2) {}  // colneg: one int per tile column
 };
 
-// ---- key of the cached distributed plan (Engine::dist_plan_version; ~0 = none) -------------------------------------
+// ---- key of the cached distributed plan and its tables (Engine::dist.key; ~0 = none) -------------------------------
 // Everything ensure_dist_plan's result depends on besides nblk and the communicator: the pattern version (if the
 // plan uses the pattern), the panel width, the layout and the kind of S exchange.  Layouts that cannot give a plan
 // share one code: build_own_map rejects them and nothing is cached.

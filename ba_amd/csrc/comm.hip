@@ -125,7 +125,7 @@ int dist_exchange(Engine* e, const std::vector<DistXfer>& x, bool side, hipStrea
   }
   if (e->comm && e->coll == native_collective) {
     RcclApi* a = rccl();
-    ncclComm_t comm = static_cast<ncclComm_t>(side && e->comm2 ? e->comm2 : e->comm);
+    ncclComm_t comm = static_cast<ncclComm_t>(side && e->dist.comm2 ? e->dist.comm2 : e->comm);
     ncclResult_t r = a->GroupStart();
     if (r != ncclSuccess) return rccl_fail(e, "ncclGroupStart", r);
     for (const DistXfer& t : x) {
@@ -164,11 +164,11 @@ int dist_allreduce_stream(Engine* e, double* buf, size_t count, hipStream_t s) {
 void comm_release(Engine* e) {
   if (!e->comm) return;
   if (RcclApi* a = rccl()) {
-    if (e->comm2) (void)a->CommDestroy(static_cast<ncclComm_t>(e->comm2));
+    if (e->dist.comm2) (void)a->CommDestroy(static_cast<ncclComm_t>(e->dist.comm2));
     (void)a->CommDestroy(static_cast<ncclComm_t>(e->comm));
   }
   e->comm = nullptr;
-  e->comm2 = nullptr;
+  e->dist.comm2 = nullptr;
 }
 
 }  // namespace bae
@@ -207,12 +207,12 @@ int ba_hip_comm_init(ba_hip_engine* h, const void* id128, int rank, int nranks) 
   e->comm = comm;
   // side communicator of the distributed solve (the bulk of every panel travels on its own stream, beside
   // the chain's messages): a duplicate of the first one.  Collective over all ranks, like the init itself.
-  e->comm2 = nullptr;
+  e->dist.comm2 = nullptr;
   if (a->CommSplit && !getenv("BA_HIP_ONE_COMM")) {
     ncclComm_t c2 = nullptr;
     const ncclResult_t r2 = a->CommSplit(comm, 0, rank, &c2, nullptr);
     if (r2 != ncclSuccess) return rccl_fail(e, "ncclCommSplit", r2);
-    e->comm2 = c2;
+    e->dist.comm2 = c2;
   }
   e->allreduce = native_allreduce; e->allreduce_ctx = e;
   e->coll = native_collective; e->coll_ctx = e;

@@ -1,7 +1,8 @@
-// Ownership map and message plan of the distributed reduced solve — plain
-// host C++, no device code: the engine (k_chol.hip) executes the plan, ba_hip_dist_plan_stats and the CPU
-// tests only count its bytes.  Replaces nothing in the reference (arpg/ba is single-process); what is
-// distributed is CalculateGn, /root/reference/src/BundleAdjuster.cpp:748-833.
+// Ownership map, message plan and every derived table of the distributed reduced solve
+// — plain host C++, no device code: dist_solve.hip uploads the tables and executes the plan, ba_hip_dist_plan_stats
+// only counts its bytes, hostcheck.cpp evaluates the same functions on the CPU (tests/test_dist_plan.py,
+// tests/test_dist_tables.py).  Replaces nothing in the reference (arpg/ba is single-process); what is distributed is
+// CalculateGn, /root/reference/src/BundleAdjuster.cpp:748-833.
 //
 // The lower triangle of S is cut into BLOCKS of G x G 64-tiles (G = the outer panel width KOUT of the
 // single-GPU factorisation, so a column of blocks is one outer panel).  Block row / column b has the
@@ -266,5 +267,222 @@ inline DistPlanStats dist_plan_stats(const DistPlan& p) {
   }
   return s;
 }
+
+// ---- the derived tables: everything dist_solve.hip uploads or sizes a buffer by ------------------------------------
+// The enumeration orders are part of the result: they fix the order of the transfers and of the sums.
+static const uint32_t kDistTile = 64;                    // NB of the kernels
+struct DistPair { uint32_t bi, bc; };                    // as uint2 on the device
+struct DistRect { uint32_t row, col, width, off; };      // as uint4: row tile, first column (doubles), columns, staging offset
+
+// Block pairs (bi >= bc) the plan's rank owns, by block column then block row; pair_first[J] = first pair with
+// bc >= J + 2 (what the bulk update of panel J touches).
+struct DistOwnedPairs {
+  std::vector<DistPair> pairs;
+  std::vector<uint32_t> pair_first;   // [nb + 1]
+};
+inline DistOwnedPairs dist_owned_pairs(const DistPlan& pl) {
+  const OwnMap& map = pl.map;
+  DistOwnedPairs o;
+  o.pair_first.assign(pl.nb + 1, 0);
+  for (uint32_t bc = 0; bc < pl.nb; ++bc) {
+    if (bc >= 2) o.pair_first[bc - 2] = (uint32_t)o.pairs.size();
+    for (uint32_t bi = bc; bi < pl.nb; ++bi)
+      if (map.n <= 1 || map.tbl[bi % map.T][bc % map.T] == map.rank) o.pairs.push_back({bi, bc});
+  }
+  for (uint32_t J = (pl.nb >= 2 ? pl.nb - 2 : 0); J <= pl.nb; ++J) o.pair_first[J] = (uint32_t)o.pairs.size();
+  return o;
+}
+
+// Row list of every square: per panel its tiles, then the rhs row (row lists of the chain kernels).
+inline std::vector<uint32_t> dist_square_rows(const DistPlan& pl) {
+  std::vector<uint32_t> h;
+  for (const DistPanel& pn : pl.panels) {
+    for (uint32_t t = pn.c0; t < pn.c1; ++t) h.push_back(t);
+    h.push_back(pl.nblk);
+  }
+  return h;
+}
+
+// Dense reduce-scatter of S.  Chunk of destination rank r: for every panel p, the row tiles of that panel whose
+// block r owns and that hold a tile of nzS in it (nblk x nblk bytes; null: all of them) — rows[off[p N + r] ..
+// off[p N + r + 1]), at chunk_off[p N + r] doubles into the chunk, panels in order.  chunk: the longest chunk, padded
+// to a multiple of 64 doubles.
+struct DistDenseRows {
+  std::vector<uint32_t> rows, off;    // off: [npanels N + 1]
+  std::vector<size_t> chunk_off;      // [npanels N]
+  size_t chunk = 0;
+};
+inline DistDenseRows dist_dense_scatter_rows(const DistPlan& pl, const uint8_t* nzS) {
+  const uint32_t nblk = pl.nblk, npanels = pl.nb, N = std::max(pl.map.n, 1u);
+  DistDenseRows d;
+  d.off.assign((size_t)npanels * N + 1, 0);
+  d.chunk_off.assign((size_t)npanels * N, 0);
+  std::vector<size_t> used(N, 0);
+  for (uint32_t p = 0; p < npanels; ++p) {
+    const uint32_t J = pl.panels[p].c0, Jend = pl.panels[p].c1;
+    for (uint32_t r = 0; r < N; ++r) {
+      OwnMap m = pl.map;
+      m.rank = r;
+      const size_t k = (size_t)p * N + r, before = d.rows.size();
+      for (uint32_t i = J; i < nblk; ++i) {
+        if (!own_tile(m, i, J, nblk)) continue;
+        bool on = !nzS || i < Jend;
+        for (uint32_t kb = J; kb < Jend && !on; ++kb) on = nzS[(size_t)i * nblk + kb] != 0;
+        if (on) d.rows.push_back(i);
+      }
+      d.off[k + 1] = (uint32_t)d.rows.size();
+      d.chunk_off[k] = used[r];
+      used[r] += (d.rows.size() - before) * kDistTile * (size_t)(Jend - J) * kDistTile;
+    }
+  }
+  for (size_t u : used) d.chunk = std::max(d.chunk, u);
+  d.chunk = (d.chunk + 63) / 64 * 64;
+  return d;
+}
+
+// Sparse exchange of S.  `all`: the local lower tile patterns of all ranks, bit i nblk + k of the `words` 64-bit words
+// of rank s (dist_pack_pattern).  A rank sends a (row tile x panel) rectangle to its owner only if its own pattern
+// has a tile in it.  send: the rectangles this rank sends, by destination (send_first[peer] .. send_first[peer + 1]),
+// then panel, then row tile; recv: those it receives, by source, in the same order — the list a sends to b IS the
+// list b receives from a.  *_off[peer]: where the peer's rectangles start in the staging half, in doubles (what the
+// rectangles' 32-bit offsets count too: refused when a half exceeds `limit` doubles).
+struct DistSparseRects {
+  std::vector<DistRect> send, recv;
+  std::vector<uint32_t> send_first, recv_first;   // [N + 1]
+  std::vector<size_t> send_off, recv_off;         // [N + 1]
+  std::string refused;
+};
+inline void dist_pack_pattern(const uint8_t* tile_nz, uint32_t nblk, unsigned long long* bits) {
+  for (uint32_t i = 0; i < nblk; ++i)
+    for (uint32_t k = 0; k <= i; ++k)
+      if (tile_nz[(size_t)i * nblk + k]) {
+        const size_t b = (size_t)i * nblk + k;
+        bits[b >> 6] |= 1ull << (b & 63);
+      }
+}
+inline size_t dist_pattern_words(uint32_t nblk) { return ((size_t)nblk * nblk + 63) / 64; }
+inline DistSparseRects dist_sparse_rects(const DistPlan& pl, uint32_t rank, const unsigned long long* all, size_t words,
+                                         uint64_t limit = 0xffffffffull) {
+  const uint32_t nblk = pl.nblk, N = std::max(pl.map.n, 1u), NB = kDistTile;
+  auto has = [&](uint32_t s_, uint32_t i, uint32_t c0, uint32_t c1) {
+    for (uint32_t kb = c0; kb < c1 && kb <= i; ++kb) {
+      const size_t b = (size_t)i * nblk + kb;
+      if (all[(size_t)s_ * words + (b >> 6)] >> (b & 63) & 1ull) return true;
+    }
+    return false;
+  };
+  DistSparseRects t;
+  t.send_first.assign(N + 1, 0); t.recv_first.assign(N + 1, 0);
+  t.send_off.assign(N + 1, 0); t.recv_off.assign(N + 1, 0);
+  size_t soff = 0, roff = 0;
+  bool too_big = false;
+  auto add = [&](std::vector<DistRect>& list, size_t& off, uint32_t i, uint32_t c0, uint32_t w) {
+    too_big |= off + (size_t)NB * w > limit;
+    list.push_back({i, c0 * NB, w, (uint32_t)off});
+    off += (size_t)NB * w;
+  };
+  for (uint32_t peer = 0; peer < N; ++peer) {
+    t.send_first[peer] = (uint32_t)t.send.size(); t.recv_first[peer] = (uint32_t)t.recv.size();
+    t.send_off[peer] = soff; t.recv_off[peer] = roff;
+    if (peer == rank) continue;
+    OwnMap mp = pl.map, mr = pl.map;
+    mp.rank = peer; mr.rank = rank;
+    for (uint32_t p = 0; p < pl.nb; ++p) {
+      const uint32_t c0 = pl.panels[p].c0, c1 = pl.panels[p].c1, w = (c1 - c0) * NB;
+      for (uint32_t i = c0; i < nblk; ++i) {
+        if (own_tile(mp, i, c0, nblk) && has(rank, i, c0, c1)) add(t.send, soff, i, c0, w);   // mine -> peer
+        if (own_tile(mr, i, c0, nblk) && has(peer, i, c0, c1)) add(t.recv, roff, i, c0, w);   // peer -> me
+      }
+    }
+  }
+  t.send_first[N] = (uint32_t)t.send.size(); t.recv_first[N] = (uint32_t)t.recv.size();
+  t.send_off[N] = soff; t.recv_off[N] = roff;
+  if (too_big) t.refused = "sparse exchange of S: more than 2^32 doubles to one side (use BA_HIP_DENSE_SCATTER=1)";
+  return t;
+}
+
+// Which tiles of the factor's pattern nzL a rank's assembly has to write when S is exchanged sparsely: the tiles it
+// OWNS (they receive the other shards' rectangles and the factorisation's updates: they must start from its own
+// partial or from zero) and the tiles of every rectangle it SENDS, i.e. where its local pattern tile_nz has a tile (a
+// rectangle travels whole: tiles of it that the shard does not touch must be zeros, not last iteration's leftovers).
+// Every other tile is neither read nor sent by this rank.  nblk x nblk bytes, lower triangle.
+inline std::vector<uint8_t> dist_assembly_need(const DistPlan& pl, uint32_t rank, const uint8_t* tile_nz, const uint8_t* nzL) {
+  const uint32_t nt = pl.nblk;
+  OwnMap me = pl.map;
+  me.rank = rank;
+  std::vector<uint8_t> need((size_t)nt * nt, 0);
+  for (uint32_t p = 0; p < pl.nb; ++p) {
+    const uint32_t c0 = pl.panels[p].c0, c1 = pl.panels[p].c1;
+    for (uint32_t i = c0; i < nt; ++i) {
+      bool touch = own_tile(me, i, c0, nt);
+      for (uint32_t kb = c0; kb < c1 && kb <= i && !touch; ++kb) touch = tile_nz[(size_t)i * nt + kb] != 0;
+      if (!touch) continue;
+      for (uint32_t kb = c0; kb < c1 && kb <= i; ++kb)
+        if (nzL[(size_t)i * nt + kb]) need[(size_t)i * nt + kb] = 1;
+    }
+  }
+  return need;
+}
+
+// Doubles of the point-to-point staging buffers of `rank`: the urgent / side messages it sends / receives in its
+// busiest panel (at least 1).
+struct DistStagingCaps { size_t usend = 1, urecv = 1, ssend = 1, srecv = 1; };
+inline DistStagingCaps dist_staging_caps(const DistPlan& pl, uint32_t rank) {
+  DistStagingCaps c;
+  for (const DistPanel& pn : pl.panels) {
+    size_t us = 0, ur = 0, ss = 0, sr = 0;
+    const size_t w = (size_t)(pn.c1 - pn.c0) * kDistTile;
+    for (uint32_t mi : pn.msgs) {
+      const DistMsg& m = pl.msgs[mi];
+      const size_t cnt = (size_t)m.count * kDistTile * w;
+      const bool recv = std::find(m.dst.begin(), m.dst.end(), rank) != m.dst.end();
+      if (m.src == rank) (m.urgent ? us : ss) += cnt;
+      if (recv) (m.urgent ? ur : sr) += cnt;
+    }
+    c.usend = std::max(c.usend, us); c.urecv = std::max(c.urecv, ur);
+    c.ssend = std::max(c.ssend, ss); c.srecv = std::max(c.srecv, sr);
+  }
+  return c;
+}
+
+// Tile products one bulk update forms on `rank` (flop accounting of the profiled launches): per tile column kb of
+// the panel [c0, c1) the tiles (i, c), i >= c >= first, the rank owns and whose two operand tiles (i, kb), (c, kb)
+// are in nzL (null: dense), plus the rhs row's; per row class a suffix count of the nonzero tiles of the column.
+// Summed over the ranks — or with own_map_single() — that is sum over kb of m (m + 1) / 2 + m, m = the nonzero
+// tiles of column kb from row `first` on.
+inline double bulk_update_tile_products(const OwnMap& own, uint32_t rank, uint32_t nblk, uint32_t first, uint32_t c0,
+                                        uint32_t c1, const uint8_t* nzL) {
+  double tiles = 0.0;
+  std::vector<double> suffix((size_t)own.T * (nblk + 1));
+  for (uint32_t kb = c0; kb < c1; ++kb) {
+    for (uint32_t a = 0; a < own.T; ++a) suffix[(size_t)a * (nblk + 1) + nblk] = 0.0;
+    for (uint32_t r = nblk; r-- > first;)
+      for (uint32_t a = 0; a < own.T; ++a)
+        suffix[(size_t)a * (nblk + 1) + r] = suffix[(size_t)a * (nblk + 1) + r + 1] +
+            (((r / own.G) % own.T == a && (!nzL || nzL[(size_t)r * nblk + kb])) ? 1.0 : 0.0);
+    for (uint32_t c = first; c < nblk; ++c) {
+      if (nzL && !nzL[(size_t)c * nblk + kb]) continue;
+      const uint32_t cc = (c / own.G) % own.T;
+      for (uint32_t a = 0; a < own.T; ++a)
+        if (own.n <= 1 || own.tbl[a][cc] == rank) tiles += suffix[(size_t)a * (nblk + 1) + c];
+      if (own.n <= 1 || own.tbl[cc][cc] == rank) tiles += 1.0;  // the rhs row
+    }
+  }
+  return tiles;
+}
+
+// What the engine keeps per plan: the tables of the plan alone, and the two that need a further input (the S pattern /
+// the all-gathered local patterns), built by the first exchange that needs them.  A new plan replaces all of them.
+struct DistTables {
+  DistOwnedPairs own;
+  std::vector<uint32_t> square_rows;
+  DistStagingCaps caps;
+  bool have_dense = false, have_sparse = false;
+  DistDenseRows dense;
+  DistSparseRects sparse;
+  DistTables() = default;
+  explicit DistTables(const DistPlan& pl)
+      : own(dist_owned_pairs(pl)), square_rows(dist_square_rows(pl)), caps(dist_staging_caps(pl, pl.map.rank)) {}
+};
 
 }  // namespace bae

@@ -145,7 +145,7 @@ struct Engine {
   DBuf<uint4> tile_desc;                 // per launch entry: (tile, first ref, end ref, row << 16 | column) (k_tile_desc)
   uint32_t n_tile_order = 0;
   uint64_t tile_order_version = ~0ull;
-  uint64_t tile_order_plan = ~0ull;      // distributed solve: the launch list holds the owned + sent tiles of plan version ..
+  uint64_t tile_order_plan = ~0ull;      // distributed solve: the launch list holds the owned + sent tiles of the plan with key ..
   int dbg_assemble_variant = 5;          // k_assemble_tiles<VAR> (ba_hip_debug_set key 1)
   int dbg_host_structure = 0;            // 1: build the static lists on the host (structure.h) (key 5)
   int dbg_linearize_variant = 0;         // 0 LDS-staged factor rows, 1 direct stores (key 4)
@@ -158,38 +158,33 @@ struct Engine {
   DBuf<uint8_t> nzL;                     // tile pattern of the factor L (nt x nt bytes, lower), see k_chol.hip
   std::vector<uint8_t> nzL_host;         // host copy (flop accounting of the profiled launches)
   uint64_t nzL_version = 0;
-  // distributed solve: per panel the row tiles with a structurally nonzero tile (message rows)
   std::vector<uint8_t> nzS_host;         // tile pattern of S itself (union over the shards), before fill
-  DBuf<uint32_t> dist_srows;             // reduce-scatter: row tiles of every panel with a nonzero S tile
-  std::vector<uint32_t> dist_srows_off;
-  uint64_t dist_srows_version = ~0ull;
-  DBuf<uint32_t> dist_rows;
-  std::vector<uint32_t> dist_rows_off;
-  uint64_t dist_rows_version = ~0ull;
-  DBuf<double> dist_msg;                 // square broadcast message (distributed solve)
-  // plan of the distributed solve (dist_plan.h): ownership map, per-panel row lists and messages
-  DistPlan dist_plan;
-  uint64_t dist_plan_version = ~0ull;
+  // Distributed solve (dist_solve.hip).  `key`: the dist_plan_key the plan was built for (~0 = none; the plan also
+  // remembers nblk, the ranks and the rank).  A new plan rebuilds `tab` (dist_plan.h), so every table below lives and
+  // dies with the key; tile_order_plan compares against it.
+  struct Dist {
+    uint64_t key = ~0ull;
+    DistPlan plan;                       // ownership map, per-panel row lists and messages
+    DistTables tab;                      // the tables derived from it
+    // ... on the device
+    DBuf<uint32_t> tiles;                // DistPlan::tiles
+    DBuf<uint2> pairs;                   // tab.own.pairs (k_update128<false, true>)
+    DBuf<uint32_t> square_rows;          // tab.square_rows
+    DBuf<uint32_t> dense_rows;           // tab.dense.rows (reduce-scatter of S)
+    DBuf<uint4> send_rects, recv_rects;  // tab.sparse.send / recv (sparse exchange of S)
+    // staging
+    DBuf<double> msg;                    // square broadcast message
+    DBuf<double> usend, urecv;           // urgent point-to-point staging (chain stream)
+    DBuf<double> ssend, srecv;           // side point-to-point staging (side stream)
+    DBuf<double> back;                   // backward substitution: partial sums of a panel + their reduction
+    hipStream_t stream3 = nullptr;       // bulk trailing updates
+    hipStream_t stream4 = nullptr;       // side communicator
+    void* comm2 = nullptr;               // side communicator (ncclCommSplit of comm)
+    std::vector<hipEvent_t> ev;          // 5 events per panel: urgent, packed, side, next, bulk
+  } dist;
   // who shares the solve changed (ba_hip_set_allreduce, ba_hip_comm_init, ba_hip_comm_destroy)
-  void sharding_changed() { held.sharding_changed(); dist_plan_version = ~0ull; }
+  void sharding_changed() { held.sharding_changed(); dist.key = ~0ull; }
   std::string dist_layout_name;
-  DBuf<uint32_t> dist_tiles;             // DistPlan::tiles on the device
-  // sparse exchange of S (dist_scatter_S_sparse): rectangles per peer (prefix offsets [N + 1]) and their staging offsets
-  uint64_t dist_sp_version = ~0ull;
-  std::vector<uint32_t> dist_sp_send, dist_sp_recv;
-  std::vector<size_t> dist_sp_send_off, dist_sp_recv_off;
-  DBuf<uint4> dist_sp_srect, dist_sp_rrect;
-  DBuf<uint2> dist_pairs;                // block pairs this rank owns, by block column (k_update128<false, true>)
-  std::vector<uint32_t> dist_pair_first; // per panel J: first pair with block column >= J + 2
-  uint32_t dist_npairs = 0;
-  DBuf<uint32_t> dist_sq_list;           // per panel: the tiles of its square, then the rhs row (row lists of the chain kernels)
-  DBuf<double> dist_usend, dist_urecv;   // urgent point-to-point staging (chain stream)
-  DBuf<double> dist_ssend, dist_srecv;   // side point-to-point staging (side stream)
-  DBuf<double> dist_back;                // backward substitution: partial sums of a panel + their reduction
-  hipStream_t stream3 = nullptr;         // distributed solve: bulk trailing updates
-  hipStream_t stream4 = nullptr;         // distributed solve: side communicator
-  void* comm2 = nullptr;                 // side communicator (ncclCommSplit of comm)
-  std::vector<hipEvent_t> ev_dist;       // 5 events per panel: urgent, packed, side, next, bulk
   ba_hip_comm_stats cstats = {};
   DBuf<double> packed;                   // packed lower triangle + rhs row (all-reduce staging)
 
@@ -519,7 +514,7 @@ int dist_reduce_scatter_S(Engine* e);
 int launch_imu_residual_vectors(Engine* e, double* d_r15);
 int build_tile_order(Engine* e);
 int build_tile_desc(Engine* e);   // k_reduce.hip
-int dist_assembly_tiles(Engine* e, std::vector<uint8_t>* need);  // k_chol.hip
+int dist_assembly_tiles(Engine* e, std::vector<uint8_t>* need);  // dist_solve.hip
 // the static lists built on the device (structure_dev.hip); same contents as structure.h's host builder
 int build_lists_device(Engine* e, const std::function<void(const char*)>& stage);
 // Pose ordering of ba_hip_finalize (engine.hip): with e->st.pose_opt holding the natural opt ids, builds the

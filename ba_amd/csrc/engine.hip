@@ -45,15 +45,15 @@ int Engine::fail_msg(const char* what) {
   return -1;
 }
 Engine::~Engine() {
-  for (hipStream_t s : {stream, stream2, stream3, stream4})
+  for (hipStream_t s : {stream, stream2, dist.stream3, dist.stream4})
     if (s) (void)hipStreamSynchronize(s);
-  for (auto* v : {&ev_panel, &ev_bulk, &ev_dist, &timer_events})
+  for (auto* v : {&ev_panel, &ev_bulk, &dist.ev, &timer_events})
     for (hipEvent_t ev : *v) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : {ev_imu_start, ev_imu_done, ev_fork, ev_join})
     if (ev) (void)hipEventDestroy(ev);
   for (auto* v : {&ev_syrk, &ev_gather, &ev_landmarks, &ev_imu, &ev_pose})   // profiling pairs nobody collected
     for (auto& pr : *v) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (hipStream_t s : {stream2, stream3, stream4})
+  for (hipStream_t s : {stream2, dist.stream3, dist.stream4})
     if (s) (void)hipStreamDestroy(s);
   if (own_stream && stream) (void)hipStreamDestroy(stream);   // a caller's stream is only synchronised
 }
@@ -428,11 +428,11 @@ int build_tile_order(Engine* e) {
     if (rc) return rc;
   }
   const uint32_t nt = st.ld / 64;
-  // distributed solve with the sparse exchange of S: only the tiles this rank owns or sends (k_chol.hip)
+  // distributed solve with the sparse exchange of S: only the tiles this rank owns or sends (dist_solve.hip)
   std::vector<uint8_t> need;
   const int restricted = e->dbg_all_tiles ? 0 : dist_assembly_tiles(e, &need);
   if (restricted < 0) return restricted;
-  const uint64_t plan_key = restricted ? e->dist_plan_version : ~0ull;
+  const uint64_t plan_key = restricted ? e->dist.key : ~0ull;
   if (e->tile_order_version == e->nzL_version && e->tile_order.p && e->tile_order_plan == plan_key) return 0;
   const bool pat = !e->dbg_all_tiles && e->nzL_host.size() == (size_t)nt * nt;
   const std::vector<uint8_t>& which = restricted ? need : e->nzL_host;
@@ -1402,7 +1402,7 @@ int ba_hip_set_collectives(ba_hip_engine* h, ba_hip_collective_fn fn, void* ctx)
   if (fn && e->solver_mode == BA_HIP_SOLVER_PCG)
     return e->fail_msg("the collectives hook needs the direct reduced solver (ba_hip_set_reduced_solver selected PCG)");
   e->coll = fn; e->coll_ctx = ctx;
-  e->dist_plan_version = ~0ull;
+  e->dist.key = ~0ull;
   return 0;
 }
 

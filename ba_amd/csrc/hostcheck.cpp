@@ -980,6 +980,89 @@ extern "C" int ba_hostcheck_chol_launch(int op, uint32_t n, const int64_t* in, c
   return 0;
 }
 
+// ---- the derived tables of the distributed solve ---------------------------------------------------------------
+#include "dist_plan.h"
+
+// dist_plan.h on one plan: hdr = nblk G nranks rank, `layout` as BA_HIP_DIST_LAYOUT, nzL the factor pattern the plan
+// is built from (nblk x nblk bytes, null = dense; self messages as the engine sets them).  The result goes to out
+// (cap entries) as integers; returns their count, -1 for an unknown op, -2 when the layout gives no plan, -3 when out
+// is too short.
+//   0  dist_owned_pairs         out: npairs | pair_first[nb + 1] | (bi bc) per pair
+//   1  dist_square_rows         out: the list
+//   2  dist_dense_scatter_rows  nz2: nzS or null; out: chunk nrows | off[nb N + 1] | chunk_off[nb N] | rows
+//   3  dist_sparse_rects        bits: the N local patterns (dist_pattern_words(nblk) words each); arg[0]: the limit, < 0 =
+//                               the default; out: refused nsend nrecv | send_first[N + 1] | recv_first[N + 1] |
+//                               send_off[N + 1] | recv_off[N + 1] | (row col width off) per send, per recv rectangle;
+//                               msg: the refusal
+//   4  dist_assembly_need       nz2: the local pattern (nzL required); out: nblk x nblk marks
+//   5  dist_staging_caps        out: usend urecv ssend srecv
+//   6  bulk_update_tile_products  arg: first c0 c1 single (1: own_map_single(), the plan's map otherwise); out: the count
+//   7  the plan itself          out: nb T nmsgs | tbl[T T] | (c0 c1 diag_owner) per panel | (panel src urgent ntiles
+//                               ndst, the tiles, the receivers) per message
+extern "C" int64_t ba_hostcheck_dist_tables(int op, const uint32_t* hdr, const char* layout, const uint8_t* nzL, const uint8_t* nz2,
+                                            const uint64_t* bits, const int64_t* arg, int64_t* out, uint64_t cap, char* msg,
+                                            uint32_t msg_cap) {
+  using namespace bae;
+  const uint32_t nblk = hdr[0], N = hdr[2], rank = hdr[3];
+  OwnMap map;
+  if (!build_own_map(N, layout, hdr[1], &map, nullptr)) return -2;
+  map.rank = rank;
+  const DistPlan pl = build_dist_plan(nblk, map, nzL, N == 1);
+  std::vector<int64_t> v;
+  auto put = [&](const auto& list) { v.insert(v.end(), list.begin(), list.end()); };
+  if (op == 0) {
+    const DistOwnedPairs o = dist_owned_pairs(pl);
+    v.push_back((int64_t)o.pairs.size());
+    put(o.pair_first);
+    for (const DistPair& p : o.pairs) { v.push_back(p.bi); v.push_back(p.bc); }
+  } else if (op == 1) {
+    put(dist_square_rows(pl));
+  } else if (op == 2) {
+    const DistDenseRows d = dist_dense_scatter_rows(pl, nz2);
+    v.push_back((int64_t)d.chunk); v.push_back((int64_t)d.rows.size());
+    put(d.off); put(d.chunk_off); put(d.rows);
+  } else if (op == 3) {
+    const size_t words = dist_pattern_words(nblk);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "pattern words");
+    const unsigned long long* all = reinterpret_cast<const unsigned long long*>(bits);
+    const DistSparseRects t = arg[0] < 0 ? dist_sparse_rects(pl, rank, all, words)
+                                         : dist_sparse_rects(pl, rank, all, words, (uint64_t)arg[0]);
+    v.push_back(!t.refused.empty()); v.push_back((int64_t)t.send.size()); v.push_back((int64_t)t.recv.size());
+    put(t.send_first); put(t.recv_first); put(t.send_off); put(t.recv_off);
+    for (const std::vector<DistRect>* l : {&t.send, &t.recv})
+      for (const DistRect& r : *l) { v.push_back(r.row); v.push_back(r.col); v.push_back(r.width); v.push_back(r.off); }
+    if (msg && msg_cap) {
+      const size_t k = std::min<size_t>(t.refused.size(), msg_cap - 1);
+      std::copy(t.refused.begin(), t.refused.begin() + k, msg);
+      msg[k] = 0;
+    }
+  } else if (op == 4) {
+    if (!nzL || !nz2) return -2;
+    put(dist_assembly_need(pl, rank, nz2, nzL));
+  } else if (op == 5) {
+    const DistStagingCaps c = dist_staging_caps(pl, rank);
+    for (size_t x : {c.usend, c.urecv, c.ssend, c.srecv}) v.push_back((int64_t)x);
+  } else if (op == 6) {
+    v.push_back((int64_t)bulk_update_tile_products(arg[3] ? own_map_single() : pl.map, arg[3] ? 0 : rank, nblk, (uint32_t)arg[0],
+                                                   (uint32_t)arg[1], (uint32_t)arg[2], nzL));
+  } else if (op == 7) {
+    v.push_back(pl.nb); v.push_back(map.T); v.push_back((int64_t)pl.msgs.size());
+    for (uint32_t a = 0; a < map.T; ++a)
+      for (uint32_t b = 0; b < map.T; ++b) v.push_back(N > 1 ? map.tbl[a][b] : 0);
+    for (const DistPanel& pn : pl.panels) { v.push_back(pn.c0); v.push_back(pn.c1); v.push_back(pn.diag_owner); }
+    for (const DistMsg& m : pl.msgs) {
+      v.push_back(m.panel); v.push_back(m.src); v.push_back(m.urgent); v.push_back(m.count); v.push_back((int64_t)m.dst.size());
+      v.insert(v.end(), pl.tiles.begin() + m.first, pl.tiles.begin() + m.first + m.count);
+      put(m.dst);
+    }
+  } else {
+    return -1;
+  }
+  if (v.size() > cap) return -3;
+  std::copy(v.begin(), v.end(), out);
+  return (int64_t)v.size();
+}
+
 // ---- panel PCG (pcg_panel.h) --------------------------------------------------------------------------------
 #include "pcg_panel.h"
 

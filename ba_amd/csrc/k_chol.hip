@@ -30,8 +30,9 @@
 // matrix, so the forward substitution L y = b is a by-product.  Masked parameters carry 1e6
 // on the diagonal; a zero / NaN / Inf pivot raises the status flag (-> FactorizationError,
 // BundleAdjuster.cpp:756-759).  With the collectives hook the factorisation is distributed
-// over the ranks (cholesky_solve_dist).
+// over the ranks (cholesky_solve_dist, dist_solve.hip).
 #include "engine.h"
+#include "chol_kernels.h"
 #include <cstdlib>
 #include <algorithm>
 #include <vector>
@@ -1608,8 +1609,8 @@ k_backward2(double* __restrict__ A, uint32_t ld, uint32_t i, uint32_t nblk,
 
 // the backward substitution over the block rows [lo, hi), last first, updating the columns from tile lo on:
 // pairs of block rows, a single one first if the count is odd.  (0, nblk) is the whole substitution.
-static void launch_backward(hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, const double* linvT, double* dx,
-                            const uint8_t* nz, uint32_t lo = 0, uint32_t hi = 0xffffffffu) {
+void launch_backward(hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, const double* linvT, double* dx,
+                     const uint8_t* nz, uint32_t lo, uint32_t hi) {
   uint32_t ii = std::min(hi, nblk);
   const uint32_t col0 = lo * NB;
   if ((ii - lo) & 1u) {
@@ -1662,48 +1663,6 @@ int factor_tile_pattern(Engine* e) {
 
 uint32_t choose_kout(uint32_t nblk) { return kout_from_env(nblk); }
 
-// ---------------------------------------------------------------------------------
-// Distributed reduced solve (replaces CalculateGn,
-// /root/reference/src/BundleAdjuster.cpp:748-833, across the GPUs of a node).  Ownership of the tile blocks
-// and the message plan: dist_plan.h.  Per iteration:
-//   * reduce-scatter: the partial S of every landmark shard is summed onto the owners of its tile blocks
-//     (dist_reduce_scatter_S), instead of an all-reduce of the whole matrix;
-//   * panel J, four streams per rank:
-//       chain  (e->stream,  chain communicator)  the owner of block (J, J) factorises the SQUARE and broadcasts it
-//              with its factor packets; the owner of block (J+1, J) substitutes those rows and sends them to the
-//              ranks that multiply their class (URGENT: the next square needs them); the owner of block
-//              (J+1, J+1) applies panel J to it and factorises its first diagonal tile in the same launch;
-//       panel  (e->stream2) substitution + in-panel updates of the other row tiles this rank owns in panel J,
-//              packing of their messages, then panel J applied to the tiles it owns in column block J+1;
-//       side   (e->stream4, side communicator)   those messages, point to point, and their unpacking;
-//       bulk   (e->stream3) panel J applied to the tiles it owns right of column block J+1 (k_update128).
-//     Only the square and one block row per panel travel on the chain stream; everything else has until the
-//     step its block row reaches the diagonal.
-//   * forward substitution rides along (the rhs row is a row of every square); the backward substitution
-//     walks the panels from the last: partial sums over the own tiles of the panel, one small all-reduce,
-//     then the square's own rows (every rank holds every square) — the step is bitwise equal on all ranks.
-// Enabled when the caller installed the collectives hook (ba_hip_set_collectives) or the native
-// communicator, more than one rank takes part, and the reduced system need not stay readable
-// (keep_reduced_system).  BA_HIP_DIST_LAYOUT = tri | grid | col | row overrides the layout.
-bool dist_solve_enabled(const Engine* e) {
-  return e->coll && e->sharded() && !e->opt.keep_reduced_system && !chol_process_switches().no_dist_solve;
-}
-
-// a list of 64-row tiles (then, if the grid says so, the rhs row = row n_pad) x columns [c0, c0 + w) of A
-// <->  dense row-major block in buf: messages carry no structurally zero tiles
-__global__ void __launch_bounds__(256)
-k_copy_panel_rows(double* __restrict__ A, uint32_t ld, const uint32_t* __restrict__ tiles, uint32_t ntiles,
-                  uint32_t n_pad, uint32_t c0, uint32_t w, double* __restrict__ buf, int unpack) {
-  const uint32_t r = blockIdx.x;
-  const uint32_t arow = (r < ntiles * NB) ? tiles[r >> 6] * NB + (r & 63u) : n_pad;
-  double* row = A + (size_t)arow * ld + c0;
-  double* brow = buf + (size_t)r * w;
-  for (uint32_t cc = threadIdx.x; cc < w; cc += 256) {
-    if (unpack) row[cc] = brow[cc];
-    else brow[cc] = row[cc];
-  }
-}
-
 // The serial chain of one outer panel [J, Jend) on stream s.
 // Two-level inside the panel: sub-panels of KIN tile columns are factorised right-looking, one
 // K = 64 update of the rest of the sub-panel per tile column; at the end of a sub-panel the
@@ -1714,10 +1673,9 @@ k_copy_panel_rows(double* __restrict__ A, uint32_t ld, const uint32_t* __restric
 // from the panel down; rl_square: the list starts with the panel's own tiles J .. Jend-1 (the square — its
 // diagonal tiles are factorised here); otherwise all its rows lie below the panel and the factor packets
 // of the diagonal tiles are already there (received with the square).
-static void launch_panel_chain(const CholSwitches& sw, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
-                               uint32_t J, uint32_t Jend, double* dsgn, double* opbuf, int* colneg, int* flags,
-                               const uint8_t* nz, const uint32_t* rl = nullptr, uint32_t rl_n = 0,
-                               bool rl_square = false, bool sq = false) {
+void launch_panel_chain(const CholSwitches& sw, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk, uint32_t J,
+                        uint32_t Jend, double* dsgn, double* opbuf, int* colneg, int* flags, const uint8_t* nz,
+                        const uint32_t* rl, uint32_t rl_n, bool rl_square, bool sq) {
   const ChainShape cs = chain_shape(nblk, sw);
   const bool left = cs.left;
   const uint32_t KINv = cs.kin, SW = sw.sq_w;
@@ -1775,9 +1733,9 @@ static void launch_panel_chain(const CholSwitches& sw, hipStream_t s, double* dA
 // (0,0) — stays a k_step_update launch; the rectangle below the panel goes to 128x128 blocks when
 // it is big enough.
 // The rectangle below the tile columns [c0, c0 + ncols) in 128x128 blocks (rect128_shape said use128).
-static void launch_rect128(const CholSwitches& sw, const Rect128Shape& r, hipStream_t s, double* dA, uint32_t ld,
-                           uint32_t nblk, uint32_t c0, uint32_t ncols, uint32_t kb0, uint32_t kb1, const double* dsgn,
-                           const int* colneg, const uint8_t* nz, const OwnMap& own) {
+void launch_rect128(const CholSwitches& sw, const Rect128Shape& r, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
+                    uint32_t c0, uint32_t ncols, uint32_t kb0, uint32_t kb1, const double* dsgn, const int* colneg,
+                    const uint8_t* nz, const OwnMap& own) {
   auto kernel = sw.c_rmw ? k_update128<true, false, true> : k_update128<true>;
   hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(256), 0, s, dA, ld, nblk, c0, r.m2, kb0, kb1, dsgn, colneg,
                      0u, nz, own, r.nrow64, c0 + ncols, r.rect_cols);
@@ -1797,13 +1755,23 @@ static void launch_next_panel_update(const CholSwitches& sw, hipStream_t s, doub
                      opbuf, colneg, flags, nz, nblk + 1u, (const uint32_t*)nullptr);
 }
 
+// for dist_solve.hip (chol_kernels.h): the two kernels it runs beside the launchers above and below
+void launch_step_update(hipStream_t s, dim3 grid, double* dA, uint32_t ld, uint32_t nblk, uint32_t c0, uint32_t kb0,
+                        uint32_t kb1, double* dsgn, double* opbuf, int* colneg, int* flags, const uint8_t* nz,
+                        const uint32_t* rl) {
+  hipLaunchKernelGGL(k_step_update<true>, grid, dim3(256), 0, s, dA, ld, nblk, c0, kb0, kb1, dsgn, opbuf, colneg, flags, nz,
+                     nblk + 1u, rl);
+}
+void launch_linvT(hipStream_t s, uint32_t nblk, const double* opbuf, const double* dsgn, double* linvT) {
+  hipLaunchKernelGGL(k_linvT, dim3(nblk), dim3(256), 0, s, opbuf, dsgn, linvT);
+}
+
 // Bulk trailing update of the tile rows / columns >= a_end (and the rhs row) with the tile columns
 // [J, Jend): the kernel and its grid are bulk_shape's.  `own`: the tiles this rank updates, `pairs`: the block
 // pairs it owns (distributed solve).  One launch, bracketed by the profiling events.
-static void launch_bulk_update(const CholSwitches& sw, Engine* e, hipStream_t s, double* dA, uint32_t ld,
-                               uint32_t nblk, uint32_t a_end, uint32_t J, uint32_t Jend, const double* dsgn,
-                               const int* colneg, const uint8_t* nz, bool full, const OwnMap& own,
-                               const uint2* pairs = nullptr, uint32_t npairs = 0) {
+void launch_bulk_update(const CholSwitches& sw, Engine* e, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
+                        uint32_t a_end, uint32_t J, uint32_t Jend, const double* dsgn, const int* colneg,
+                        const uint8_t* nz, bool full, const OwnMap& own, const uint2* pairs, uint32_t npairs) {
   const BulkShape b = bulk_shape(nblk, a_end, full, own.n, own.G, pairs != nullptr, npairs, sw);
   const dim3 grid(b.grid), wg(256);
   e->prof_begin(e->ev_syrk, s);
@@ -1833,296 +1801,6 @@ static void launch_bulk_update(const CholSwitches& sw, Engine* e, hipStream_t s,
   e->prof_end(e->ev_syrk, s);
 }
 
-// ---- the plan of the distributed solve for the current pattern / communicator ------------------------
-static int ensure_dist_plan(const CholSwitches& sw, Engine* e, uint32_t nblk, bool pat) {
-  const uint32_t KOUT = sw.kout;
-  const char* lay_env = sw.dist_layout;
-  const uint64_t want = dist_plan_key(e->nzL_version, KOUT, pat, lay_env, sw.dense_scatter);
-  if (e->dist_plan_version == want && e->dist_plan.nblk == nblk && e->dist_plan.map.n == (uint32_t)e->nranks &&
-      e->dist_plan.map.rank == (uint32_t)e->rank)
-    return 0;
-  OwnMap map;
-  std::string why;
-  if (!build_own_map((uint32_t)e->nranks, lay_env, KOUT, &map, &e->dist_layout_name, &why)) {
-    e->err = "distributed solve: " + why;
-    return -1;
-  }
-  map.rank = (uint32_t)e->rank;
-  // one rank with the native communicator (comm_force): the rank sends its rows to itself — every pack /
-  // transfer / unpack path runs on a one-GPU box
-  e->dist_plan = build_dist_plan(nblk, map, pat ? e->nzL_host.data() : nullptr, e->nranks == 1);
-  BAE_HIP(e->dist_tiles.alloc(std::max<size_t>(e->dist_plan.tiles.size(), 1)));
-  if (!e->dist_plan.tiles.empty())
-    BAE_HIP(hipMemcpy(e->dist_tiles.p, e->dist_plan.tiles.data(), e->dist_plan.tiles.size() * sizeof(uint32_t),
-                      hipMemcpyHostToDevice));
-  {
-    // block pairs (bi >= bc) this rank owns, by block column then block row; pair_first[J] = first pair with
-    // bc >= J + 2 (what the bulk update of panel J touches)
-    const DistPlan& pl = e->dist_plan;
-    std::vector<uint2> pairs;
-    e->dist_pair_first.assign(pl.nb + 1, 0);
-    for (uint32_t bc = 0; bc < pl.nb; ++bc) {
-      if (bc >= 2) e->dist_pair_first[bc - 2] = (uint32_t)pairs.size();
-      for (uint32_t bi = bc; bi < pl.nb; ++bi)
-        if (map.n <= 1 || map.tbl[bi % map.T][bc % map.T] == map.rank) pairs.push_back(make_uint2(bi, bc));
-    }
-    for (uint32_t J = (pl.nb >= 2 ? pl.nb - 2 : 0); J <= pl.nb; ++J) e->dist_pair_first[J] = (uint32_t)pairs.size();
-    e->dist_npairs = (uint32_t)pairs.size();
-    BAE_HIP(e->dist_pairs.alloc(std::max<size_t>(pairs.size(), 1)));
-    if (!pairs.empty())
-      BAE_HIP(hipMemcpy(e->dist_pairs.p, pairs.data(), pairs.size() * sizeof(uint2), hipMemcpyHostToDevice));
-  }
-  {
-    std::vector<uint32_t> h;
-    for (const DistPanel& pn : e->dist_plan.panels) {
-      for (uint32_t t = pn.c0; t < pn.c1; ++t) h.push_back(t);
-      h.push_back(nblk);
-    }
-    BAE_HIP(e->dist_sq_list.alloc(std::max<size_t>(h.size(), 1)));
-    BAE_HIP(hipMemcpy(e->dist_sq_list.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  e->dist_plan_version = want;
-  e->dist_srows_version = ~0ull;
-  e->dist_sp_version = ~0ull;
-  return 0;
-}
-
-// Reduce-scatter of S onto the owners of its tile blocks.  Only the row tiles of a panel that hold a
-// structurally nonzero tile of S on SOME shard travel (the union pattern of factor_tile_pattern, identical
-// on every rank; S itself is half as dense as its factor): the other tiles are zero on every rank already.
-// Chunk of destination rank r: for every panel, the row tiles of that panel whose block r owns.
-static int dist_scatter_S_sparse(const CholSwitches& sw, Engine* e);
-int dist_reduce_scatter_S(Engine* e) {
-  const uint32_t ld = e->st.ld, nblk = ld / NB, N = (uint32_t)e->nranks, rank = (uint32_t)e->rank;
-  const CholSwitches sw = chol_switches(nblk);
-  // default: the sparse point-to-point exchange (below); BA_HIP_DENSE_SCATTER=1: one reduce-scatter of the union pattern
-  if (!sw.dense_scatter && e->nranks > 1) return dist_scatter_S_sparse(sw, e);
-  const bool pat = e->nzS_host.size() == (size_t)nblk * nblk;
-  { const int prc = ensure_dist_plan(sw, e, nblk, pat && e->nzL_host.size() == (size_t)nblk * nblk); if (prc) return prc; }
-  const DistPlan& pl = e->dist_plan;
-  const uint32_t npanels = pl.nb;
-  const uint64_t want = e->dist_plan_version;
-  if (e->dist_srows_version != want || e->dist_srows_off.size() != (size_t)npanels * N + 1) {
-    std::vector<uint32_t> list;
-    e->dist_srows_off.assign((size_t)npanels * N + 1, 0);
-    for (uint32_t p = 0; p < npanels; ++p) {
-      const uint32_t J = pl.panels[p].c0, Jend = pl.panels[p].c1;
-      for (uint32_t r = 0; r < N; ++r) {
-        OwnMap m = pl.map;
-        m.rank = r;
-        for (uint32_t i = J; i < nblk; ++i) {
-          if (!own_tile(m, i, J, nblk)) continue;
-          bool on = !pat || i < Jend;
-          for (uint32_t kb = J; kb < Jend && !on; ++kb) on = e->nzS_host[(size_t)i * nblk + kb] != 0;
-          if (on) list.push_back(i);
-        }
-        e->dist_srows_off[(size_t)p * N + r + 1] = (uint32_t)list.size();
-      }
-    }
-    BAE_HIP(e->dist_srows.alloc(std::max<size_t>(list.size(), 1)));
-    if (!list.empty())
-      BAE_HIP(hipMemcpy(e->dist_srows.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    e->dist_srows_version = want;
-  }
-  // offsets inside the chunks: panels in order
-  std::vector<size_t> off((size_t)npanels * N, 0), used(N, 0);
-  for (uint32_t p = 0; p < npanels; ++p)
-    for (uint32_t r = 0; r < N; ++r) {
-      const size_t k = (size_t)p * N + r;
-      const size_t rows = (size_t)(e->dist_srows_off[k + 1] - e->dist_srows_off[k]) * NB;
-      off[k] = used[r];
-      used[r] += rows * (size_t)(pl.panels[p].c1 - pl.panels[p].c0) * NB;
-    }
-  size_t chunk = 0;
-  for (size_t u : used) chunk = std::max(chunk, u);
-  chunk = (chunk + 63) / 64 * 64;
-  BAE_HIP(e->packed.alloc(chunk * N));
-  // the padding behind the shorter chunks is summed too: keep it finite
-  BAE_HIP(hipMemsetAsync(e->packed.p, 0, chunk * N * sizeof(double), e->stream));
-  for (uint32_t p = 0; p < npanels; ++p)
-    for (uint32_t r = 0; r < N; ++r) {
-      const size_t k = (size_t)p * N + r;
-      const uint32_t ntl = e->dist_srows_off[k + 1] - e->dist_srows_off[k];
-      if (ntl == 0) continue;
-      hipLaunchKernelGGL(k_copy_panel_rows, dim3(ntl * NB), dim3(256), 0, e->stream, e->A.p, ld,
-                         (const uint32_t*)(e->dist_srows.p + e->dist_srows_off[k]), ntl, nblk * NB, pl.panels[p].c0 * NB,
-                         (pl.panels[p].c1 - pl.panels[p].c0) * NB, e->packed.p + (size_t)r * chunk + off[k], 0);
-    }
-  BAE_HIP(hipGetLastError());
-  BAE_HIP(hipStreamSynchronize(e->stream));
-  e->cstats.reduce_scatter_bytes += 8.0 * (double)chunk * N;
-  if (e->coll(e->coll_ctx, 2, e->packed.p, chunk, 0) != 0) return e->fail_msg("reduce-scatter hook failed");
-  for (uint32_t p = 0; p < npanels; ++p) {
-    const size_t k = (size_t)p * N + rank;
-    const uint32_t ntl = e->dist_srows_off[k + 1] - e->dist_srows_off[k];
-    if (ntl == 0) continue;
-    hipLaunchKernelGGL(k_copy_panel_rows, dim3(ntl * NB), dim3(256), 0, e->stream, e->A.p, ld,
-                       (const uint32_t*)(e->dist_srows.p + e->dist_srows_off[k]), ntl, nblk * NB, pl.panels[p].c0 * NB,
-                       (pl.panels[p].c1 - pl.panels[p].c0) * NB, e->packed.p + (size_t)rank * chunk + off[k], 1);
-  }
-  BAE_HIP(hipGetLastError());
-  return 0;
-}
-
-// ---- sparse exchange of S: only the tiles a shard really has ------------------------------------------------------
-// rects[b >> 6] = (row tile, first column in doubles, columns, offset of the 64 x columns block in buf);
-// mode 0: buf <- A (pack), mode 1: A += buf (sum at the owner)
-__global__ void __launch_bounds__(256)
-k_copy_rects(double* __restrict__ A, uint32_t ld, const uint4* __restrict__ rects, double* __restrict__ buf, int mode) {
-  const uint4 rc = rects[blockIdx.x >> 6];
-  const uint32_t r = blockIdx.x & 63u;
-  double* row = A + ((size_t)rc.x * NB + r) * ld + rc.y;
-  double* brow = buf + (size_t)rc.w + (size_t)r * rc.z;
-  for (uint32_t cc = threadIdx.x; cc < rc.z; cc += 256) {
-    if (mode) row[cc] += brow[cc];
-    else brow[cc] = row[cc];
-  }
-}
-
-// Every rank holds a partial S over its landmark shard; the owner of a tile block needs the SUM.  The dense
-// reduce-scatter (dist_reduce_scatter_S) moves every tile of the UNION pattern from every rank.  Here a rank sends a
-// (row tile x panel) rectangle to its owner only if its OWN pattern (Structure::tile_nz: the tiles its shard, its
-// pose-pose residuals and the diagonal touch) has a tile in it; the owner adds what arrives in ascending rank order
-// (deterministic).  With shards dealt along the trajectory a shard touches a band of S and sends a fraction of what
-// the dense exchange does; with shards that touch everything the volume is the dense one.  The local patterns are
-// all-gathered once per structure (one u64 all-reduce with every rank's bits in its own slot).
-static int dist_scatter_S_sparse(const CholSwitches& sw, Engine* e) {
-  const uint32_t ld = e->st.ld, nblk = ld / NB, N = (uint32_t)e->nranks, rank = (uint32_t)e->rank;
-  { const int prc = ensure_dist_plan(sw, e, nblk, e->nzL_host.size() == (size_t)nblk * nblk); if (prc) return prc; }
-  const DistPlan& pl = e->dist_plan;
-  if (e->st.tile_nz.size() != (size_t)nblk * nblk) return e->fail_msg("sparse exchange of S: no local tile pattern");
-  if (e->dist_sp_version != e->dist_plan_version) {
-    // --- all-gather of the local patterns (lower triangle, bit per tile)
-    const size_t bits = (size_t)nblk * nblk, words = (bits + 63) / 64;
-    std::vector<unsigned long long> all(words * N, 0ull);
-    for (uint32_t i = 0; i < nblk; ++i)
-      for (uint32_t k = 0; k <= i; ++k)
-        if (e->st.tile_nz[(size_t)i * nblk + k]) {
-          const size_t b = (size_t)i * nblk + k;
-          all[(size_t)rank * words + (b >> 6)] |= 1ull << (b & 63);
-        }
-    {
-      DBuf<unsigned long long> d;
-      BAE_HIP(d.alloc(all.size()));
-      hipError_t err = hipMemcpy(d.p, all.data(), all.size() * 8, hipMemcpyHostToDevice);
-      int rc = 0;
-      if (err != hipSuccess) rc = e->fail(err, "hipMemcpy");
-      if (!rc && shard_allreduce(e, d.p, all.size(), 1) != 0) rc = e->fail_msg("allreduce hook failed");
-      if (!rc && (err = hipMemcpy(all.data(), d.p, all.size() * 8, hipMemcpyDeviceToHost)) != hipSuccess) rc = e->fail(err, "hipMemcpy");
-      if (rc) return rc;
-    }
-    auto has = [&](uint32_t s_, uint32_t i, uint32_t c0, uint32_t c1) {
-      for (uint32_t kb = c0; kb < c1 && kb <= i; ++kb) {
-        const size_t b = (size_t)i * nblk + kb;
-        if (all[(size_t)s_ * words + (b >> 6)] >> (b & 63) & 1ull) return true;
-      }
-      return false;
-    };
-    // --- rectangles this rank sends (by destination) and receives (by source), enumerated identically on both sides
-    std::vector<uint4> srect, rrect;
-    e->dist_sp_send.assign(N + 1, 0); e->dist_sp_recv.assign(N + 1, 0);
-    e->dist_sp_send_off.assign(N + 1, 0); e->dist_sp_recv_off.assign(N + 1, 0);
-    size_t soff = 0, roff = 0;
-    bool too_big = false;
-    for (uint32_t peer = 0; peer < N; ++peer) {
-      e->dist_sp_send[peer] = (uint32_t)srect.size(); e->dist_sp_recv[peer] = (uint32_t)rrect.size();
-      e->dist_sp_send_off[peer] = soff; e->dist_sp_recv_off[peer] = roff;
-      if (peer == rank) continue;
-      OwnMap mp = pl.map, mr = pl.map;
-      mp.rank = peer; mr.rank = rank;
-      for (uint32_t p = 0; p < pl.nb; ++p) {
-        const uint32_t c0 = pl.panels[p].c0, c1 = pl.panels[p].c1, w = (c1 - c0) * NB;
-        for (uint32_t i = c0; i < nblk; ++i) {
-          if (own_tile(mp, i, c0, nblk) && has(rank, i, c0, c1)) {   // mine -> peer
-            too_big |= soff > 0xffffffffull - (size_t)NB * w;
-            srect.push_back(make_uint4(i, c0 * NB, w, (uint32_t)soff));
-            soff += (size_t)NB * w;
-          }
-          if (own_tile(mr, i, c0, nblk) && has(peer, i, c0, c1)) {   // peer -> me
-            too_big |= roff > 0xffffffffull - (size_t)NB * w;
-            rrect.push_back(make_uint4(i, c0 * NB, w, (uint32_t)roff));
-            roff += (size_t)NB * w;
-          }
-        }
-      }
-    }
-    e->dist_sp_send[N] = (uint32_t)srect.size(); e->dist_sp_recv[N] = (uint32_t)rrect.size();
-    e->dist_sp_send_off[N] = soff; e->dist_sp_recv_off[N] = roff;
-    if (too_big) return e->fail_msg("sparse exchange of S: more than 2^32 doubles to one side (use BA_HIP_DENSE_SCATTER=1)");
-    BAE_HIP(e->dist_sp_srect.alloc(std::max<size_t>(srect.size(), 1)));
-    BAE_HIP(e->dist_sp_rrect.alloc(std::max<size_t>(rrect.size(), 1)));
-    if (!srect.empty()) BAE_HIP(hipMemcpy(e->dist_sp_srect.p, srect.data(), srect.size() * sizeof(uint4), hipMemcpyHostToDevice));
-    if (!rrect.empty()) BAE_HIP(hipMemcpy(e->dist_sp_rrect.p, rrect.data(), rrect.size() * sizeof(uint4), hipMemcpyHostToDevice));
-    e->dist_sp_version = e->dist_plan_version;
-  }
-  const size_t stot = e->dist_sp_send_off[N], rtot = e->dist_sp_recv_off[N];
-  // staging: the send half and the receive half of `packed`
-  BAE_HIP(e->packed.alloc(std::max<size_t>(stot + rtot, 1)));
-  double* sbuf = e->packed.p;
-  double* rbuf = e->packed.p + stot;
-  std::vector<DistXfer> xf;
-  for (uint32_t peer = 0; peer < N; ++peer) {
-    if (peer == rank) continue;
-    const uint32_t ns = e->dist_sp_send[peer + 1] - e->dist_sp_send[peer];
-    const size_t slen = e->dist_sp_send_off[peer + 1] - e->dist_sp_send_off[peer];
-    if (ns) {
-      hipLaunchKernelGGL(k_copy_rects, dim3(ns * 64), dim3(256), 0, e->stream, e->A.p, ld,
-                         (const uint4*)(e->dist_sp_srect.p + e->dist_sp_send[peer]), sbuf, 0);
-      xf.push_back({sbuf + e->dist_sp_send_off[peer], slen, (int)peer, true});
-    }
-    const size_t rlen = e->dist_sp_recv_off[peer + 1] - e->dist_sp_recv_off[peer];
-    if (rlen) xf.push_back({rbuf + e->dist_sp_recv_off[peer], rlen, (int)peer, false});
-  }
-  BAE_HIP(hipGetLastError());
-  e->cstats.reduce_scatter_bytes += 8.0 * (double)stot;
-  {
-    // (counted as the S exchange, not as chain traffic: undo dist_exchange's own bookkeeping)
-    const ba_hip_comm_stats keep = e->cstats;
-    const int xrc = dist_exchange(e, xf, false, e->stream);
-    const double rs = e->cstats.reduce_scatter_bytes;
-    e->cstats = keep;
-    e->cstats.reduce_scatter_bytes = rs;
-    if (xrc) return xrc;
-  }
-  for (uint32_t peer = 0; peer < N; ++peer) {   // ascending rank order: the sums are reproducible
-    if (peer == rank) continue;
-    const uint32_t nr = e->dist_sp_recv[peer + 1] - e->dist_sp_recv[peer];
-    if (nr)
-      hipLaunchKernelGGL(k_copy_rects, dim3(nr * 64), dim3(256), 0, e->stream, e->A.p, ld,
-                         (const uint4*)(e->dist_sp_rrect.p + e->dist_sp_recv[peer]), rbuf, 1);
-  }
-  BAE_HIP(hipGetLastError());
-  return 0;
-}
-
-// Which tiles of the factor's pattern this rank's assembly has to write when S is exchanged sparsely: the tiles it OWNS
-// (they receive the other shards' rectangles and the factorisation's updates: they must start from its own partial or
-// from zero) and the tiles of every rectangle it SENDS (a rectangle travels whole: tiles of it that the shard does not
-// touch must be zeros, not last iteration's leftovers).  Every other tile is neither read nor sent by this rank.  need:
-// nt x nt bytes, lower triangle.  Returns 1 if the restriction applies (distributed solve with the sparse exchange).
-int dist_assembly_tiles(Engine* e, std::vector<uint8_t>* need) {
-  const uint32_t nt = e->st.ld / NB;
-  const CholSwitches sw = chol_switches(nt);
-  if (!dist_solve_enabled(e) || e->nranks <= 1 || sw.dense_scatter) return 0;
-  if (e->nzL_host.size() != (size_t)nt * nt || e->st.tile_nz.size() != (size_t)nt * nt) return 0;
-  if (ensure_dist_plan(sw, e, nt, true)) return -1;
-  const DistPlan& pl = e->dist_plan;
-  OwnMap me = pl.map;
-  me.rank = (uint32_t)e->rank;
-  need->assign((size_t)nt * nt, 0);
-  for (uint32_t p = 0; p < pl.nb; ++p) {
-    const uint32_t c0 = pl.panels[p].c0, c1 = pl.panels[p].c1;
-    for (uint32_t i = c0; i < nt; ++i) {
-      bool touch = own_tile(me, i, c0, nt);
-      for (uint32_t kb = c0; kb < c1 && kb <= i && !touch; ++kb) touch = e->st.tile_nz[(size_t)i * nt + kb] != 0;
-      if (!touch) continue;
-      for (uint32_t kb = c0; kb < c1 && kb <= i; ++kb)
-        if (e->nzL_host[(size_t)i * nt + kb]) (*need)[(size_t)i * nt + kb] = 1;
-    }
-  }
-  return 1;
-}
-
 // pivot floors tol * |A_jj| of the matrix about to be factorised (rank-deficiency guard)
 __global__ void k_pivot_floor(uint32_t n_pad, uint32_t ld, const double* __restrict__ A, double tol,
                               double* __restrict__ out) {
@@ -2131,7 +1809,7 @@ __global__ void k_pivot_floor(uint32_t n_pad, uint32_t ld, const double* __restr
 }
 
 // status block: int 0 = factorisation status, ints 2..3 = device pointer of the pivot floors (or null)
-static int setup_status_block(Engine* e, const double* dA, uint32_t ld, hipStream_t s0) {
+int setup_status_block(Engine* e, const double* dA, uint32_t ld, hipStream_t s0) {
   BAE_HIP(hipMemsetAsync(e->flags.p, 0, 4 * sizeof(int), s0));
   const double tol = e->opt.pivot_rel_tolerance;
   if (tol > 0.0) {
@@ -2142,298 +1820,6 @@ static int setup_status_block(Engine* e, const double* dA, uint32_t ld, hipStrea
     BAE_HIP(hipMemcpyAsync(e->flags.p + 2, &ptr, sizeof(ptr), hipMemcpyHostToDevice, s0));
     BAE_HIP(hipStreamSynchronize(s0));  // `ptr` is a stack variable
   }
-  return 0;
-}
-
-// Backward substitution of the distributed solve, panel [c0, c1): partial sums over the row tiles this rank
-// owns below the square,  part[g][col] = sum over its tiles t = g, g + NG, ... of  L[t-rows, col]^T x[t-rows].
-__global__ void __launch_bounds__(256)
-k_back_partial(const double* __restrict__ A, uint32_t ld, uint32_t nblk, const uint32_t* __restrict__ tiles,
-               uint32_t ntiles, uint32_t c0, uint32_t w, const double* __restrict__ x,
-               const uint8_t* __restrict__ nz, double* __restrict__ part) {
-  __shared__ double xs[NB];
-  const uint32_t col = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y, ng = gridDim.y;
-  double s = 0.0;
-  for (uint32_t t = g; t < ntiles; t += ng) {
-    const uint32_t i = tiles[t];
-    __syncthreads();
-    if (threadIdx.x < NB) xs[threadIdx.x] = x[(size_t)i * NB + threadIdx.x];
-    __syncthreads();
-    if (col < w && (!nz || nz[(size_t)i * nblk + c0 + (col >> 6)])) {
-      const double* L = A + ((size_t)i * NB) * ld + (size_t)c0 * NB + col;
-#pragma unroll 16
-      for (int r = 0; r < NB; ++r) s += L[(size_t)r * ld] * xs[r];
-    }
-  }
-  if (col < w) part[(size_t)g * w + col] = s;
-}
-
-// out[col] = sum over g (fixed order) of part[g][col]
-__global__ void k_back_sum(const double* __restrict__ part, uint32_t ng, uint32_t w, double* __restrict__ out) {
-  const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= w) return;
-  double s = 0.0;
-  for (uint32_t g = 0; g < ng; ++g) s += part[(size_t)g * w + col];
-  out[col] = s;
-}
-
-// y[c0*64 + col] -= p[col]   (y = the rhs row of A)
-__global__ void k_back_apply(double* __restrict__ yrow, const double* __restrict__ p, uint32_t w) {
-  const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
-  if (col < w) yrow[col] -= p[col];
-}
-
-int cholesky_solve_dist(Engine* e, double* dA, uint32_t ld, double* dx, int* status, const uint8_t* nz) {
-  const uint32_t nblk = ld / NB, rank = (uint32_t)e->rank;
-  const CholSwitches sw = chol_switches(nblk);
-  const FactorWork fw(nblk);
-  BAE_HIP(e->invdiag.alloc(fw.total));
-  double* dsgn = e->invdiag.p + fw.dsgn;
-  double* linvT = e->invdiag.p + fw.linvT;
-  double* opbuf = e->invdiag.p + fw.opbuf;
-  int* colneg = reinterpret_cast<int*>(e->invdiag.p + fw.colneg);
-  const bool pat = nz && e->nzL_host.size() == (size_t)nblk * nblk;
-  { const int prc = ensure_dist_plan(sw, e, nblk, pat); if (prc) return prc; }
-  const DistPlan& pl = e->dist_plan;
-  const OwnMap& own = pl.map;
-  const uint32_t KOUT = own.G, npanels = pl.nb, n_pad = nblk * NB;
-  const uint32_t* dtiles = e->dist_tiles.p;
-  // streams: chain, panel, bulk, side
-  if (!e->stream3) {
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    BAE_HIP(hipStreamCreateWithPriority(&e->stream3, hipStreamNonBlocking, lo));
-    BAE_HIP(hipStreamCreateWithPriority(&e->stream4, hipStreamNonBlocking, hi));
-  }
-  // (a native communicator without its duplicate — librccl lacks ncclCommSplit, or BA_HIP_ONE_COMM — carries the
-  // side transfers too: they are then ordered into the chain stream, one communicator is never used on two streams)
-  hipStream_t s0 = e->stream, s1 = e->stream2, s2 = e->stream3, s3 = (e->comm && !e->comm2) ? e->stream : e->stream4;
-  // staging buffers: the square message; urgent / side messages of the busiest panel
-  const size_t wmax = (size_t)KOUT * NB;
-  BAE_HIP(e->dist_msg.alloc(dist_square_doubles(KOUT)));
-  size_t cap_us = 1, cap_ur = 1, cap_ss = 1, cap_sr = 1;
-  for (const DistPanel& pn : pl.panels) {
-    size_t us = 0, ur = 0, ss = 0, sr = 0;
-    const size_t w = (size_t)(pn.c1 - pn.c0) * NB;
-    for (uint32_t mi : pn.msgs) {
-      const DistMsg& m = pl.msgs[mi];
-      const size_t cnt = (size_t)m.count * NB * w;
-      const bool recv = std::find(m.dst.begin(), m.dst.end(), rank) != m.dst.end();
-      if (m.src == rank) (m.urgent ? us : ss) += cnt;
-      if (recv) (m.urgent ? ur : sr) += cnt;
-    }
-    cap_us = std::max(cap_us, us); cap_ur = std::max(cap_ur, ur);
-    cap_ss = std::max(cap_ss, ss); cap_sr = std::max(cap_sr, sr);
-  }
-  BAE_HIP(e->dist_usend.alloc(cap_us)); BAE_HIP(e->dist_urecv.alloc(cap_ur));
-  BAE_HIP(e->dist_ssend.alloc(cap_ss)); BAE_HIP(e->dist_srecv.alloc(cap_sr));
-  const uint32_t NG = 32;
-  BAE_HIP(e->dist_back.alloc((size_t)(NG + 1) * wmax));
-  while (e->ev_dist.size() < (size_t)npanels * 5) {
-    hipEvent_t a;
-    BAE_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-    e->ev_dist.push_back(a);
-  }
-  auto EV = [&](uint32_t J, int k) { return e->ev_dist[(size_t)J * 5 + k]; };  // 0 urgent 1 packed 2 side 3 next 4 bulk
-  e->cstats.factorisations++;
-  { const int src = setup_status_block(e, dA, ld, s0); if (src) return src; }
-  // everything queued on the chain stream so far (assembly, reduce-scatter unpack) precedes the other streams' work
-  BAE_HIP(hipEventRecord(e->ev_dist[1], s0));
-  BAE_HIP(hipStreamWaitEvent(s1, e->ev_dist[1], 0));
-  BAE_HIP(hipStreamWaitEvent(s2, e->ev_dist[1], 0));
-  BAE_HIP(hipStreamWaitEvent(s3, e->ev_dist[1], 0));
-  if (rank == pl.panels[0].diag_owner)  // factor packet of tile 0
-    hipLaunchKernelGGL(k_step_update<true>, dim3(1, 1), dim3(256), 0, s0, dA, ld, nblk, 0u, 0u, 0u, dsgn, opbuf,
-                       colneg, e->flags.p, nz, nblk + 1u, (const uint32_t*)nullptr);
-  // row list of a square: its tiles, then the rhs row — one small device array per plan (ensure_dist_plan)
-  DBuf<uint32_t>& sq_list = e->dist_sq_list;
-  int rc = 0;
-  size_t sq_off = 0;
-  for (uint32_t J = 0; J < npanels && !rc; ++J) {
-    const DistPanel& pn = pl.panels[J];
-    const uint32_t c0 = pn.c0, c1 = pn.c1, wt = c1 - c0, w = wt * NB;
-    const uint32_t* sq = sq_list.p + sq_off;
-    sq_off += wt + 1;
-    const bool last = c1 >= nblk;
-    // ---- chain stream: the square ----------------------------------------------------------------------
-    double* msg = e->dist_msg.p;
-    const size_t n_cols = (size_t)(w + 1) * w;
-    double* m_sgn = msg + n_cols;
-    double* m_neg = m_sgn + w;
-    double* m_op = m_neg + wt;
-    const size_t msg_len = n_cols + w + wt + (size_t)wt * kPacketStride;
-    if (rank == pn.diag_owner) {
-      // (its updates by the earlier panels: bulk of steps <= J-2 and the chain-stream update of step J-1,
-      // both ordered before this point by the waits of step J-1)
-      launch_panel_chain(sw, s0, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, sq, wt + 1, true);
-      hipLaunchKernelGGL(k_copy_panel_rows, dim3(w + 1), dim3(256), 0, s0, dA, ld, sq, wt, n_pad, c0 * NB, w, msg, 0);
-      BAE_HIP(hipMemcpyAsync(m_sgn, dsgn + (size_t)c0 * NB, w * sizeof(double), hipMemcpyDeviceToDevice, s0));
-      BAE_HIP(hipMemcpyAsync(m_neg, colneg + c0, wt * sizeof(int), hipMemcpyDeviceToDevice, s0));
-      BAE_HIP(hipMemcpyAsync(m_op, opbuf + (size_t)c0 * kPacketStride, (size_t)wt * kPacketStride * sizeof(double),
-                             hipMemcpyDeviceToDevice, s0));
-    }
-    BAE_HIP(hipGetLastError());
-    if ((rc = dist_broadcast(e, msg, msg_len, (int)pn.diag_owner, s0))) break;
-    if (rank != pn.diag_owner) {
-      hipLaunchKernelGGL(k_copy_panel_rows, dim3(w + 1), dim3(256), 0, s0, dA, ld, sq, wt, n_pad, c0 * NB, w, msg, 1);
-      BAE_HIP(hipMemcpyAsync(dsgn + (size_t)c0 * NB, m_sgn, w * sizeof(double), hipMemcpyDeviceToDevice, s0));
-      BAE_HIP(hipMemcpyAsync(colneg + c0, m_neg, wt * sizeof(int), hipMemcpyDeviceToDevice, s0));
-      BAE_HIP(hipMemcpyAsync(opbuf + (size_t)c0 * kPacketStride, m_op, (size_t)wt * kPacketStride * sizeof(double),
-                             hipMemcpyDeviceToDevice, s0));
-    }
-    if (last) break;
-    // ---- chain stream: the urgent block row (block J+1 of panel J) -------------------------------------
-    // its tiles took the updates of the panels < J on the panel stream (step J-1: column block J)
-    if (pn.own_u_count[rank]) {
-      if (J > 0) BAE_HIP(hipStreamWaitEvent(s0, EV(J - 1, 3), 0));
-      launch_panel_chain(sw, s0, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, dtiles + pn.own_u_first[rank],
-                         pn.own_u_count[rank], false);
-    }
-    auto run_messages = [&](bool urgent, hipStream_t sp, hipStream_t sc, double* sendbuf, double* recvbuf,
-                            hipEvent_t packed_ev) -> int {
-      // pack on `sp` (the stream that computed the rows), transfer + unpack on `sc`
-      std::vector<DistXfer> xf;
-      struct Unp { const uint32_t* tl; uint32_t n; double* buf; };
-      std::vector<Unp> unp;
-      size_t so = 0, ro = 0;
-      for (uint32_t mi : pn.msgs) {
-        const DistMsg& m = pl.msgs[mi];
-        if (m.urgent != urgent) continue;
-        const size_t cnt = (size_t)m.count * NB * w;
-        if (m.src == rank) {
-          hipLaunchKernelGGL(k_copy_panel_rows, dim3(m.count * NB), dim3(256), 0, sp, dA, ld, dtiles + m.first, m.count,
-                             n_pad, c0 * NB, w, sendbuf + so, 0);
-          for (uint32_t q : m.dst) xf.push_back({sendbuf + so, cnt, (int)q, true});
-          so += cnt;
-        }
-        if (std::find(m.dst.begin(), m.dst.end(), rank) != m.dst.end()) {
-          xf.push_back({recvbuf + ro, cnt, (int)m.src, false});
-          unp.push_back({dtiles + m.first, m.count, recvbuf + ro});
-          ro += cnt;
-        }
-      }
-      BAE_HIP(hipGetLastError());
-      if (sp != sc) {
-        BAE_HIP(hipEventRecord(packed_ev, sp));
-        BAE_HIP(hipStreamWaitEvent(sc, packed_ev, 0));
-      }
-      const int xrc = dist_exchange(e, xf, !urgent, sc);
-      if (xrc) return xrc;
-      for (const Unp& u : unp)
-        hipLaunchKernelGGL(k_copy_panel_rows, dim3(u.n * NB), dim3(256), 0, sc, dA, ld, u.tl, u.n, n_pad, c0 * NB, w,
-                           u.buf, 1);
-      BAE_HIP(hipGetLastError());
-      return 0;
-    };
-    if ((rc = run_messages(true, s0, s0, e->dist_usend.p, e->dist_urecv.p, nullptr))) break;
-    BAE_HIP(hipEventRecord(EV(J, 0), s0));
-    // ---- chain stream: panel J applied to the next square (and its rhs segment) + its first diagonal tile
-    const uint32_t n1 = std::min(c1 + KOUT, nblk);  // end of column block J+1
-    if (rank == pl.panels[J + 1].diag_owner) {
-      if (J > 0) BAE_HIP(hipStreamWaitEvent(s0, EV(J - 1, 4), 0));  // the bulk updates of its tiles by the panels < J
-      hipLaunchKernelGGL(k_step_update<true>, dim3(n1 - c1 + 1, n1 - c1), dim3(256), 0, s0, dA, ld, nblk, c1, c0, c1, dsgn, opbuf,
-                         colneg, e->flags.p, nz, nblk + 1u, (const uint32_t*)(sq_list.p + sq_off));
-    }
-    // ---- panel stream: the other own rows of panel J, their messages -----------------------------------
-    BAE_HIP(hipStreamWaitEvent(s1, EV(J, 0), 0));
-    if (J > 0) BAE_HIP(hipStreamWaitEvent(s1, EV(J - 1, 2), 0));  // the side staging buffers are free again
-    if (pn.own_r_count[rank])
-      launch_panel_chain(sw, s1, dA, ld, nblk, c0, c1, dsgn, opbuf, colneg, e->flags.p, nz, dtiles + pn.own_r_first[rank],
-                         pn.own_r_count[rank], false);
-    if ((rc = run_messages(false, s1, s3, e->dist_ssend.p, e->dist_srecv.p, EV(J, 1)))) break;
-    BAE_HIP(hipEventRecord(EV(J, 2), s3));
-    // ---- panel stream: panel J applied to the own tiles of column block J+1 below its square ------------
-    if (pn.next_needs_side[rank] || own.n <= 1) BAE_HIP(hipStreamWaitEvent(s1, EV(J, 2), 0));  // rows received on the side stream
-    if (J > 0) BAE_HIP(hipStreamWaitEvent(s1, EV(J - 1, 4), 0));
-    if (n1 < nblk) {
-      const uint32_t ncols = n1 - c1;
-      OwnMap o1 = own;
-      o1.skip_rhs = 1;  // the rhs segment of column block J+1 went with the square's update on the chain stream
-      const Rect128Shape r = rect128_shape(kRectDist, nblk, c1, ncols, own.G, sw);
-      if (r.use128) {
-        launch_rect128(sw, r, s1, dA, ld, nblk, c1, ncols, c0, c1, dsgn, colneg, nz, o1);
-      } else {
-        // 64-tiles: exactly the row tiles this rank owns below the square of panel J+1 (its two row lists are
-        // adjacent) — a structurally zero tile of L takes no update, so the lists are complete
-        const DistPanel& pq = pl.panels[J + 1];
-        const uint32_t cnt = pq.own_u_count[rank] + pq.own_r_count[rank];
-        if (cnt)
-          hipLaunchKernelGGL(k_step_update<true>, dim3(cnt, ncols), dim3(256), 0, s1, dA, ld, nblk, c1, c0, c1, dsgn, opbuf,
-                             colneg, e->flags.p, nz, nblk + 1u, dtiles + pq.own_u_first[rank]);
-      }
-    }
-    BAE_HIP(hipEventRecord(EV(J, 3), s1));
-    // ---- bulk stream: panel J applied to the own tiles right of column block J+1 -----------------------
-    if (n1 < nblk) {
-      BAE_HIP(hipStreamWaitEvent(s2, EV(J, 2), 0));
-      BAE_HIP(hipStreamWaitEvent(s2, EV(J, 0), 0));
-      launch_bulk_update(sw, e, s2, dA, ld, nblk, n1, c0, c1, dsgn, colneg, nz, true, own,
-                         e->dist_pairs.p + e->dist_pair_first[J], e->dist_npairs - e->dist_pair_first[J]);
-      if (e->profiling) {
-        // tile products formed by THIS rank: tiles (i, c), i >= c >= n1, it owns, both operand tiles of the
-        // panel column structurally nonzero; per row class a suffix count of the nonzero tiles of the column
-        double tiles = 0.0;
-        std::vector<double> suffix((size_t)own.T * (nblk + 1));
-        for (uint32_t kb = c0; kb < c1; ++kb) {
-          for (uint32_t a = 0; a < own.T; ++a) suffix[(size_t)a * (nblk + 1) + nblk] = 0.0;
-          for (uint32_t r = nblk; r-- > n1;)
-            for (uint32_t a = 0; a < own.T; ++a)
-              suffix[(size_t)a * (nblk + 1) + r] = suffix[(size_t)a * (nblk + 1) + r + 1] +
-                  (((r / own.G) % own.T == a && (!pat || e->nzL_host[(size_t)r * nblk + kb])) ? 1.0 : 0.0);
-          for (uint32_t c = n1; c < nblk; ++c) {
-            if (pat && !e->nzL_host[(size_t)c * nblk + kb]) continue;
-            const uint32_t cc = (c / own.G) % own.T;
-            for (uint32_t a = 0; a < own.T; ++a)
-              if (own.n <= 1 || own.tbl[a][cc] == rank) tiles += suffix[(size_t)a * (nblk + 1) + c];
-            if (own.n <= 1 || own.tbl[cc][cc] == rank) tiles += 1.0;  // the rhs row
-          }
-        }
-        e->kstats.syrk_flops += tiles * 2.0 * NB * NB * NB;
-      }
-    }
-    BAE_HIP(hipEventRecord(EV(J, 4), s2));
-  }
-  if (rc) return rc;
-  BAE_HIP(hipGetLastError());
-  // every stream has drained into the chain stream's view before the backward substitution
-  BAE_HIP(hipStreamSynchronize(s1));
-  BAE_HIP(hipStreamSynchronize(s2));
-  BAE_HIP(hipStreamSynchronize(s3));
-  hipLaunchKernelGGL(k_linvT, dim3(nblk), dim3(256), 0, s0, (const double*)opbuf, (const double*)dsgn, linvT);
-  // ---- backward substitution, panels from the last -------------------------------------------------------
-  double* yrow = dA + (size_t)n_pad * ld;
-  double* part = e->dist_back.p;
-  double* psum = part + (size_t)NG * wmax;
-  for (uint32_t J = npanels; J-- > 0 && !rc;) {
-    const DistPanel& pn = pl.panels[J];
-    const uint32_t c0 = pn.c0, c1 = pn.c1, w = (c1 - c0) * NB;
-    if (c1 < nblk) {
-      const uint32_t nt = pn.own_u_count[rank] + pn.own_r_count[rank];  // (the two lists are adjacent)
-      const uint32_t ng = std::min(NG, std::max(nt, 1u));
-      if (nt) {
-        hipLaunchKernelGGL(k_back_partial, dim3((w + 255) / 256, ng), dim3(256), 0, s0, (const double*)dA, ld, nblk,
-                           dtiles + pn.own_u_first[rank], nt, c0, w, (const double*)dx, nz, part);
-        hipLaunchKernelGGL(k_back_sum, dim3((w + 255) / 256), dim3(256), 0, s0, (const double*)part, ng, w, psum);
-      } else {
-        BAE_HIP(hipMemsetAsync(psum, 0, (size_t)w * sizeof(double), s0));
-      }
-      BAE_HIP(hipGetLastError());
-      if ((rc = dist_allreduce_stream(e, psum, w, s0))) break;
-      hipLaunchKernelGGL(k_back_apply, dim3((w + 255) / 256), dim3(256), 0, s0, yrow + (size_t)c0 * NB, (const double*)psum, w);
-    }
-    launch_backward(s0, dA, ld, nblk, (const double*)linvT, dx, nz, c0, c1);
-  }
-  if (rc) return rc;
-  BAE_HIP(hipGetLastError());
-  // the pivot status of every diagonal owner
-  int st = 0;
-  BAE_HIP(hipMemcpyAsync(&st, e->flags.p, sizeof(int), hipMemcpyDeviceToHost, s0));
-  BAE_HIP(hipStreamSynchronize(s0));
-  double sd = (double)st;
-  BAE_HIP(hipMemcpy(e->scalars_out.p, &sd, sizeof(double), hipMemcpyHostToDevice));
-  if (shard_allreduce(e, e->scalars_out.p, 1, 0) != 0) return e->fail_msg("allreduce hook failed");
-  BAE_HIP(hipMemcpy(&sd, e->scalars_out.p, sizeof(double), hipMemcpyDeviceToHost));
-  *status = sd > 0.5 ? 1 : 0;
   return 0;
 }
 
@@ -2584,18 +1970,11 @@ int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, i
       BAE_HIP(hipEventRecord(e->ev_bulk[pj], s1));
       prev_bulk = (int)pj;
       if (e->profiling) {
-        // algorithmic flops of this launch: per panel column kb the tiles (i, c), i >= c >= a_end,
-        // whose two operand tiles are structurally nonzero, plus the rhs row
-        double tiles = 0.0;
-        for (uint32_t kb = J; kb < Jend; ++kb) {
-          double mk = (double)(nblk - a_end);
-          if (nz && e->nzL_host.size() == (size_t)nblk * nblk) {
-            mk = 0.0;
-            for (uint32_t r = a_end; r < nblk; ++r) mk += e->nzL_host[(size_t)r * nblk + kb];
-          }
-          tiles += mk * (mk + 1) / 2 + mk;
-        }
-        e->kstats.syrk_flops += tiles * 2.0 * NB * NB * NB;
+        // algorithmic flops of this launch (dist_plan.h): the tiles (i, c), i >= c >= a_end, whose two operand
+        // tiles are structurally nonzero, plus the rhs row
+        const bool pat = nz && e->nzL_host.size() == (size_t)nblk * nblk;
+        e->kstats.syrk_flops += bulk_update_tile_products(own_map_single(), 0, nblk, a_end, J, Jend,
+                                                          pat ? e->nzL_host.data() : nullptr) * 2.0 * NB * NB * NB;
       }
     }
   }
