@@ -18,11 +18,12 @@ void launch_step_update(hipStream_t s, dim3 grid, double* dA, uint32_t ld, uint3
 void launch_rect128(const CholSwitches& sw, const Rect128Shape& r, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
                     uint32_t c0, uint32_t ncols, uint32_t kb0, uint32_t kb1, const double* dsgn, const int* colneg,
                     const uint8_t* nz, const OwnMap& own);
-// bulk trailing update of the tile rows / columns >= a_end with the tile columns [J, Jend) (bulk_shape)
+// bulk trailing update of the tile rows / columns >= a_end with the tile columns [J, Jend) (bulk_shape); blocks /
+// nblocks: the launch's slice of the list of non-empty blocks (bulk_lists.h), sentinels included
 void launch_bulk_update(const CholSwitches& sw, Engine* e, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
                         uint32_t a_end, uint32_t J, uint32_t Jend, const double* dsgn, const int* colneg,
                         const uint8_t* nz, bool full, const OwnMap& own, const uint2* pairs = nullptr,
-                        uint32_t npairs = 0);
+                        uint32_t npairs = 0, const uint2* blocks = nullptr, uint32_t nblocks = 0);
 // L_JJ^-T of every diagonal tile from its factor packet
 void launch_linvT(hipStream_t s, uint32_t nblk, const double* opbuf, const double* dsgn, double* linvT);
 // the backward substitution over the block rows [lo, hi), last first

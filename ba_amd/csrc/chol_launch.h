@@ -28,6 +28,7 @@ struct CholSwitches {
   uint32_t rect_min_rows = 128;   //   max(16, v): tile rows below the next panel from which its rectangle goes to k_update128
   uint32_t bulk_full_m = 128;     //   v: trailing tile rows from which the bulk update runs uncapped
   bool c_rmw = false;             // BA_HIP_C_RMW: k_update128 reads, subtracts and stores C (default: memory-side FP64 adds)
+  bool bulk_grid = false;         // BA_HIP_BULK_GRID: the bulk update covers the whole block triangle (default: bulk_lists.h)
   // --- read on every call (tests vary them inside one process)
   uint32_t kout = 4;              // BA_HIP_KOUT: tiles per outer panel; 0 / unset: by nblk
   uint32_t left_min_tiles = 512;  // BA_HIP_LEFT_MIN_TILES: left-looking sub-panels from this many tiles on
@@ -36,6 +37,7 @@ struct CholSwitches {
   const char* dist_layout = nullptr;  // BA_HIP_DIST_LAYOUT
   bool dense_scatter = false;     // BA_HIP_DENSE_SCATTER
   const char* trace_file = nullptr;   // BA_HIP_TRACE_FILE (BAE_TIME128 builds)
+  bool lists_report = false;      // BA_HIP_BULK_LISTS_REPORT: one line on stderr per build of the bulk block lists
 };
 
 // The parsing, on the variables' values (null = unset).
@@ -45,7 +47,8 @@ inline uint32_t parse_kout(const char* v, uint32_t nblk) {
 }
 inline void parse_process_switches(CholSwitches* sw, const char* no128, const char* no_lookahead, const char* bulk_full,
                                    const char* dense, const char* no_dist_solve, const char* sbl,
-                                   const char* bulk_full_m, const char* c_rmw = nullptr) {
+                                   const char* bulk_full_m, const char* c_rmw = nullptr,
+                                   const char* bulk_grid = nullptr) {
   sw->no128 = no128 != nullptr;
   sw->no_lookahead = no_lookahead != nullptr;
   sw->bulk_full = bulk_full != nullptr;
@@ -55,10 +58,12 @@ inline void parse_process_switches(CholSwitches* sw, const char* no128, const ch
   sw->rect_min_rows = bulk_full_m ? (uint32_t)std::max(16, atoi(bulk_full_m)) : 128u;
   sw->bulk_full_m = bulk_full_m ? (uint32_t)atoi(bulk_full_m) : 128u;
   sw->c_rmw = c_rmw != nullptr;
+  sw->bulk_grid = bulk_grid != nullptr;
 }
 inline void parse_call_switches(CholSwitches* sw, uint32_t nblk, const char* kout, const char* left_min_tiles,
                                 const char* square, const char* sq_w, const char* dist_layout,
-                                const char* dense_scatter, const char* trace_file) {
+                                const char* dense_scatter, const char* trace_file,
+                                const char* lists_report = nullptr) {
   sw->kout = parse_kout(kout, nblk);
   sw->left_min_tiles = left_min_tiles ? (uint32_t)std::max(1, atoi(left_min_tiles)) : 512u;
   sw->square = nblk < 512 && square && atoi(square) != 0;
@@ -66,6 +71,7 @@ inline void parse_call_switches(CholSwitches* sw, uint32_t nblk, const char* kou
   sw->dist_layout = dist_layout;
   sw->dense_scatter = dense_scatter != nullptr;
   sw->trace_file = trace_file;
+  sw->lists_report = lists_report != nullptr;
 }
 
 inline const CholSwitches& chol_process_switches() {
@@ -73,7 +79,7 @@ inline const CholSwitches& chol_process_switches() {
     CholSwitches sw;
     parse_process_switches(&sw, getenv("BA_HIP_NO128"), getenv("BA_HIP_NO_LOOKAHEAD"), getenv("BA_HIP_BULK_FULL"),
                            getenv("BA_HIP_DENSE"), getenv("BA_HIP_NO_DIST_SOLVE"), getenv("BA_HIP_SBL"),
-                           getenv("BA_HIP_BULK_FULL_M"), getenv("BA_HIP_C_RMW"));
+                           getenv("BA_HIP_BULK_FULL_M"), getenv("BA_HIP_C_RMW"), getenv("BA_HIP_BULK_GRID"));
     return sw;
   }();
   return once;
@@ -83,7 +89,7 @@ inline CholSwitches chol_switches(uint32_t nblk) {
   CholSwitches sw = chol_process_switches();
   parse_call_switches(&sw, nblk, getenv("BA_HIP_KOUT"), getenv("BA_HIP_LEFT_MIN_TILES"), getenv("BA_HIP_SQUARE"),
                       getenv("BA_HIP_SQ_W"), getenv("BA_HIP_DIST_LAYOUT"), getenv("BA_HIP_DENSE_SCATTER"),
-                      getenv("BA_HIP_TRACE_FILE"));
+                      getenv("BA_HIP_TRACE_FILE"), getenv("BA_HIP_BULK_LISTS_REPORT"));
   return sw;
 }
 inline uint32_t kout_from_env(uint32_t nblk) { return parse_kout(getenv("BA_HIP_KOUT"), nblk); }
@@ -127,11 +133,13 @@ inline Rect128Shape rect128_shape(RectRule rule, uint32_t nblk, uint32_t c0, uin
 // Bulk trailing update of the tile rows / columns >= a_end.  Big trailing matrices: 128x128 blocks over the even
 // part (k_update128, XCD-aware 4x4 super-blocks = the footprint of the 64-tile kernel's 8x8; the rhs row and an odd
 // last tile row ride along as 64-tiles) — all of the triangle, or with have_pairs the npairs ownership blocks of
-// this rank; otherwise the 64-tile kernel over its 2^sbl super-blocks, capped (`full` = false) to leave the chain room.
-enum BulkKernel { kBulkU128, kBulkU128List, kBulkU2Full, kBulkU2Capped };
+// this rank, or with list_len >= 0 the list_len entries (8 x the longest per-XCD sub-list, sentinels included) of
+// the launch's list of non-empty blocks (bulk_lists.h); otherwise the 64-tile kernel over its 2^sbl super-blocks,
+// capped (`full` = false) to leave the chain room.
+enum BulkKernel { kBulkU128, kBulkU128List, kBulkU2Full, kBulkU2Capped, kBulkU128Blocks };
 struct BulkShape { BulkKernel kernel; uint32_t grid, nrow64, m2, sbl; int swzf; };
 inline BulkShape bulk_shape(uint32_t nblk, uint32_t a_end, bool full, uint32_t own_n, uint32_t own_G, bool have_pairs,
-                            uint32_t npairs, const CholSwitches& sw) {
+                            uint32_t npairs, const CholSwitches& sw, int64_t list_len = -1) {
   const uint32_t m = nblk - a_end;
   if (full && !sw.no128 && m >= 16 && (a_end % 2u) == 0 && (own_n <= 1 || own_G % 2u == 0)) {
     const uint32_t m2 = m / 2, sbl2 = 2, sbe2 = 1u << sbl2;
@@ -139,6 +147,8 @@ inline BulkShape bulk_shape(uint32_t nblk, uint32_t a_end, bool full, uint32_t o
     const uint32_t nrow64 = (m * (1 + (m & 1u)) + 7) / 8 * 8;
     if (have_pairs && own_n > 1 && a_end % own_G == 0)
       return {kBulkU128List, nrow64 + npairs * (own_G / 2) * (own_G / 2), nrow64, m2, sbl2, 0};
+    if (list_len >= 0 && own_n <= 1 && !sw.bulk_grid)
+      return {kBulkU128Blocks, nrow64 + (uint32_t)list_len, nrow64, m2, sbl2, 0};
     return {kBulkU128, nrow64 + ((nsb + 7) / 8) * 8 * sbe2 * sbe2, nrow64, m2, sbl2, 0};
   }
   // 1-D XCD-aware launch over the super-blocks of the (m + 1) x m lower-triangular tile region

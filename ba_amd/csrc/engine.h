@@ -16,6 +16,7 @@
 #include "dist_plan.h"
 #include "lifecycle.h"
 #include "chol_launch.h"
+#include "bulk_lists.h"
 
 namespace bae {
 
@@ -49,6 +50,24 @@ struct DBuf {
     n = 0;
   }
   size_t bytes() const { return n * sizeof(T); }
+};
+
+// bulk_lists.h on the device: all launches of a solve in one buffer of (block row, block column) in absolute
+// 128-block coordinates, ~0 for a sentinel; the per-launch slices stay on the host.
+struct BulkDeviceLists {
+  BulkListsKey key;
+  bool built = false;                     // false: grid launches (no pattern, over the budget, BA_HIP_BULK_GRID)
+  std::vector<BulkLaunchList> launches;
+  DBuf<uint2> blocks;
+  uint64_t total_blocks = 0;
+  double build_ms = 0.0;                  // host time of the last build and upload
+  uint32_t builds = 0;
+  const BulkLaunchList* find(uint32_t a_end) const {
+    if (!built) return nullptr;
+    for (const BulkLaunchList& l : launches)
+      if (l.a_end == a_end) return &l;
+    return nullptr;
+  }
 };
 
 // Rigid transform in matrix form as stored on the device: R row-major (9) then t (3).
@@ -158,6 +177,9 @@ struct Engine {
   DBuf<uint8_t> nzL;                     // tile pattern of the factor L (nt x nt bytes, lower), see k_chol.hip
   std::vector<uint8_t> nzL_host;         // host copy (flop accounting of the profiled launches)
   uint64_t nzL_version = 0;
+  // The non-empty 128-blocks of the bulk updates of cholesky_solve on nzL (bulk_lists.h): rebuilt when `key` (the
+  // pattern version and the inputs of the set of launches) moves, as the other version-counted plans.
+  BulkDeviceLists bulk_lists;
   std::vector<uint8_t> nzS_host;         // tile pattern of S itself (union over the shards), before fill
   // Distributed solve (dist_solve.hip).  `key`: the dist_plan_key the plan was built for (~0 = none; the plan also
   // remembers nblk, the ranks and the rank).  A new plan rebuilds `tab` (dist_plan.h), so every table below lives and
@@ -505,8 +527,12 @@ int launch_imu_early(Engine* e, double c_huber_proj);
 int launch_posepose_build(Engine* e, double c_huber_proj, double* h3);
 int launch_posepose_eval(Engine* e, double* h3);
 int launch_posepose_jrhs(Engine* e, double* out);
+// lists: the block lists of the bulk updates for this pattern (ensure_bulk_lists), null = grid launches
 int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, int* status,
-                   const uint8_t* nz_tiles);
+                   const uint8_t* nz_tiles, const BulkDeviceLists* lists = nullptr);
+// Builds and uploads the lists of a solve of nblk tiles on the host pattern nz_host unless `lists` already holds them
+// for (version, nblk, switches); version ~0: a pattern of its own, always rebuilt.
+int ensure_bulk_lists(Engine* e, uint32_t nblk, const uint8_t* nz_host, uint64_t version, BulkDeviceLists* lists);
 int factor_tile_pattern(Engine* e);
 uint32_t choose_kout(uint32_t nblk);
 bool dist_solve_enabled(const Engine* e);

@@ -1120,7 +1120,12 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
     if (!e->held.nzL_valid && (rc = factor_tile_pattern(e))) return rc;
     if (dist_solve_enabled(e)) {
       if ((rc = cholesky_solve_dist(e, e->A.p, st.ld, e->gn_p.p, &status, e->nzL.p))) return rc;
-    } else if ((rc = cholesky_solve(e, e->A.p, st.n, st.ld, e->gn_p.p, &status, e->nzL.p))) return rc;
+    } else {
+      const uint32_t nt = st.ld / 64;
+      const bool pat = e->nzL_host.size() == (size_t)nt * nt;
+      if ((rc = ensure_bulk_lists(e, nt, pat ? e->nzL_host.data() : nullptr, e->nzL_version, &e->bulk_lists))) return rc;
+      if ((rc = cholesky_solve(e, e->A.p, st.n, st.ld, e->gn_p.p, &status, e->nzL.p, &e->bulk_lists))) return rc;
+    }
     e->held.solved_directly();
   }
   e->timers.solve = t.stop_ms();

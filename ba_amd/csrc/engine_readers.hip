@@ -741,9 +741,12 @@ static int tile_factorise(Engine* e, const char* who, uint32_t n, const double* 
   BAE_HIP(hipMemcpy(dA.p, sys.A.data(), sys.A.size() * 8, hipMemcpyHostToDevice));
   BAE_HIP(hipMemcpy(dnz.p, nz.data(), nz.size(), hipMemcpyHostToDevice));
   e->held.standalone_factorisation();
-  int rc = cholesky_solve(e, dA.p, n, ld, dx.p, status, dnz.p);
+  BulkDeviceLists lists;            // of this pattern alone: temporary, as dnz
+  int rc = ensure_bulk_lists(e, nt, nz.data(), ~0ull, &lists);
   if (rc) return rc;
-  BAE_HIP(hipDeviceSynchronize());  // both streams of the factorisation (dnz goes with this scope)
+  rc = cholesky_solve(e, dA.p, n, ld, dx.p, status, dnz.p, &lists);
+  if (rc) return rc;
+  BAE_HIP(hipDeviceSynchronize());  // both streams of the factorisation (dnz and lists go with this scope)
   return 0;
 }
 int ba_hip_tile_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, const uint8_t* tile_map,

@@ -933,6 +933,9 @@ extern "C" int ba_hostcheck_lifecycle(uint32_t n, const int32_t* events, uint32_
 //   4  FactorWork       in: nblk; out: dsgn linvT opbuf colneg total packet_stride
 //   5  dist_plan_key    in: nzL_version kout pat dense_scatter; str: layout; out: key
 //   7  the epilogue switch of k_update128   str: C_RMW; out: c_rmw   (6 stays unknown: tests/test_chol_launch.py)
+//   8  the launch switch of the bulk update   str: BULK_GRID; out: bulk_grid
+//   9  bulk_shape with a block list   in: nblk a_end full own_n own_G have_pairs npairs no128 sbl list_len bulk_grid
+//                                     (list_len < 0: no list); out: as 3
 extern "C" int ba_hostcheck_chol_launch(int op, uint32_t n, const int64_t* in, const char* const* str, int64_t* out) {
   using namespace bae;
   for (uint32_t i = 0; i < n; ++i) {
@@ -973,11 +976,45 @@ extern "C" int ba_hostcheck_chol_launch(int op, uint32_t n, const int64_t* in, c
     } else if (op == 7) {
       parse_process_switches(&sw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, str[0]);
       out[0] = sw.c_rmw;
+    } else if (op == 8) {
+      parse_process_switches(&sw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, str[0]);
+      out[0] = sw.bulk_grid;
+    } else if (op == 9) {
+      const int64_t* a = in + (size_t)i * 11;
+      sw.no128 = a[7] != 0; sw.sbl = (uint32_t)a[8]; sw.bulk_grid = a[10] != 0;
+      const BulkShape b = bulk_shape((uint32_t)a[0], (uint32_t)a[1], a[2] != 0, (uint32_t)a[3], (uint32_t)a[4], a[5] != 0,
+                                     (uint32_t)a[6], sw, a[9]);
+      const int64_t v[6] = {b.kernel, b.grid, b.nrow64, b.m2, b.sbl, b.swzf};
+      std::copy(v, v + 6, out + (size_t)i * 6);
     } else {
       return -1;
     }
   }
   return 0;
+}
+
+// ---- the block lists of the bulk updates (bulk_lists.h) ----------------------------------------------------------
+#include "bulk_lists.h"
+
+// build_bulk_lists on the pattern nz (nblk x nblk bytes, lower; null = none).  hdr = nblk kout no128 bulk_full_m
+// full_always (BA_HIP_NO_LOOKAHEAD or BA_HIP_BULK_FULL) bulk_grid dense; budget: bytes on the device, < 0 = the default.
+// out (cap entries): built nlaunches total_blocks nentries | (a_end J Jend first len blocks xcd_blocks[8]) per launch |
+// (R C mask) per entry, sentinels as R = C = 2^32 - 1.  Returns the count, or -3 when out is too short.
+extern "C" int64_t ba_hostcheck_bulk_lists(const uint32_t* hdr, const uint8_t* nz, int64_t budget, int64_t* out, uint64_t cap) {
+  using namespace bae;
+  CholSwitches sw;
+  sw.no128 = hdr[2] != 0; sw.bulk_full_m = hdr[3]; sw.bulk_full = hdr[4] != 0; sw.bulk_grid = hdr[5] != 0; sw.dense = hdr[6] != 0;
+  const BulkLists l = budget < 0 ? build_bulk_lists(hdr[0], hdr[1], nz, sw) : build_bulk_lists(hdr[0], hdr[1], nz, sw, (size_t)budget);
+  const size_t need = 4 + 14 * l.launches.size() + 3 * l.entries.size();
+  if (need > cap) return -3;
+  int64_t* o = out;
+  *o++ = l.built; *o++ = (int64_t)l.launches.size(); *o++ = (int64_t)l.total_blocks; *o++ = (int64_t)l.entries.size();
+  for (const BulkLaunchList& b : l.launches) {
+    *o++ = b.a_end; *o++ = b.J; *o++ = b.Jend; *o++ = b.first; *o++ = b.len; *o++ = b.blocks;
+    for (uint32_t x = 0; x < 8; ++x) *o++ = b.xcd_blocks[x];
+  }
+  for (const BulkEntry& b : l.entries) { *o++ = b.R; *o++ = b.C; *o++ = (int64_t)b.mask; }
+  return (int64_t)need;
 }
 
 // ---- the derived tables of the distributed solve ---------------------------------------------------------------

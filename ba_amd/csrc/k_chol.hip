@@ -35,6 +35,7 @@
 #include "chol_kernels.h"
 #include <cstdlib>
 #include <algorithm>
+#include <chrono>
 #include <vector>
 
 namespace bae {
@@ -1771,11 +1772,25 @@ void launch_linvT(hipStream_t s, uint32_t nblk, const double* opbuf, const doubl
 // pairs it owns (distributed solve).  One launch, bracketed by the profiling events.
 void launch_bulk_update(const CholSwitches& sw, Engine* e, hipStream_t s, double* dA, uint32_t ld, uint32_t nblk,
                         uint32_t a_end, uint32_t J, uint32_t Jend, const double* dsgn, const int* colneg,
-                        const uint8_t* nz, bool full, const OwnMap& own, const uint2* pairs, uint32_t npairs) {
-  const BulkShape b = bulk_shape(nblk, a_end, full, own.n, own.G, pairs != nullptr, npairs, sw);
+                        const uint8_t* nz, bool full, const OwnMap& own, const uint2* pairs, uint32_t npairs,
+                        const uint2* blocks, uint32_t nblocks) {
+  const BulkShape b = bulk_shape(nblk, a_end, full, own.n, own.G, pairs != nullptr, npairs, sw,
+                                 blocks ? (int64_t)nblocks : -1);
   const dim3 grid(b.grid), wg(256);
   e->prof_begin(e->ev_syrk, s);
   switch (b.kernel) {
+    case kBulkU128Blocks: {
+      // the launch's list of non-empty blocks through the pair mode: one 128-block per "pair" (G = 2), entries in
+      // absolute block coordinates, so R and C come out as the grid launch's; a sentinel gives R >= m2
+      OwnMap ol = own;
+      ol.G = 2;
+      ol.pairs_lo = (uint32_t)(reinterpret_cast<unsigned long long>(blocks) & 0xffffffffull);
+      ol.pairs_hi = (uint32_t)(reinterpret_cast<unsigned long long>(blocks) >> 32);
+      auto kernel = sw.c_rmw ? k_update128<false, true, true> : k_update128<false, true>;
+      hipLaunchKernelGGL(kernel, grid, wg, 0, s, dA, ld, nblk, a_end, b.m2, J, Jend, dsgn, colneg, b.sbl, nz, ol,
+                         b.nrow64, a_end, 0u);
+      break;
+    }
     case kBulkU128List: {
       OwnMap ol = own;
       ol.pairs_lo = (uint32_t)(reinterpret_cast<unsigned long long>(pairs) & 0xffffffffull);
@@ -1898,8 +1913,47 @@ static int time128_write(Engine* e, const CholSwitches& sw) {
 }
 #endif
 
+// The block lists of the bulk updates (bulk_lists.h) for a solve of nblk tiles on the host pattern nz_host, uploaded:
+// a one-off per pattern, outside every timed region (build_ms keeps its host time).
+int ensure_bulk_lists(Engine* e, uint32_t nblk, const uint8_t* nz_host, uint64_t version, BulkDeviceLists* L) {
+  const CholSwitches sw = chol_switches(nblk);
+  const BulkListsKey key = bulk_lists_key(version, nblk, sw);
+  if (version != ~0ull && L->key == key) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  L->key = BulkListsKey();
+  L->built = false;
+  L->launches.clear();
+  L->total_blocks = 0;
+  const BulkLists lists = build_bulk_lists(nblk, sw.kout, nz_host, sw);
+  if (lists.built) {
+    // on the device an entry is (block row, block column) in absolute 128-block coordinates, as the owned pairs of the
+    // distributed solve (k_update128<false, true> with one block per pair); the kernel forms the K mask itself
+    std::vector<uint2> dev(lists.entries.size());
+    size_t at = 0;
+    for (const BulkLaunchList& l : lists.launches)
+      for (uint32_t k = 0; k < l.len; ++k, ++at) {
+        const BulkEntry& b = lists.entries[at];
+        dev[at] = b.R == kBulkSentinel ? make_uint2(kBulkSentinel, kBulkSentinel)
+                                       : make_uint2(l.a_end / 2 + b.R, l.a_end / 2 + b.C);
+      }
+    BAE_HIP(L->blocks.alloc(std::max<size_t>(dev.size(), 1)));   // (an empty list is a list: the pointer says so)
+    if (!dev.empty()) BAE_HIP(hipMemcpy(L->blocks.p, dev.data(), dev.size() * sizeof(uint2), hipMemcpyHostToDevice));
+  }
+  L->built = lists.built;
+  L->launches = lists.launches;
+  L->total_blocks = lists.total_blocks;
+  L->key = key;
+  L->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  L->builds++;
+  if (sw.lists_report)
+    fprintf(stderr, "bulk lists: nblk %u kout %u built %d launches %zu blocks %llu entries %zu build_ms %.3f\n",
+            nblk, sw.kout, (int)L->built, L->launches.size(), (unsigned long long)L->total_blocks,
+            lists.entries.size(), L->build_ms);
+  return 0;
+}
+
 int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, int* status,
-                   const uint8_t* nz) {
+                   const uint8_t* nz, const BulkDeviceLists* lists) {
   (void)n;
   const uint32_t nblk = ld / NB;
   const CholSwitches sw = chol_switches(nblk);
@@ -1964,9 +2018,10 @@ int cholesky_solve(Engine* e, double* dA, uint32_t n, uint32_t ld, double* dx, i
       BAE_HIP(hipStreamWaitEvent(s1, e->ev_panel[pj], 0));
       // large trailing matrices (the serial chain is negligible beside them): full occupancy;
       // otherwise the capped variant leaves the chain room
-      const uint32_t m = nblk - a_end;
-      launch_bulk_update(sw, e, s1, dA, ld, nblk, a_end, J, Jend, dsgn, colneg, nz,
-                         sw.no_lookahead || sw.bulk_full || m >= sw.bulk_full_m, own_map_single());
+      const BulkLaunchList* bl = nz && lists && lists->key.nblk == nblk ? lists->find(a_end) : nullptr;
+      if (bl && (bl->J != J || bl->Jend != Jend)) bl = nullptr;   // (built for another panel width: grid launch)
+      launch_bulk_update(sw, e, s1, dA, ld, nblk, a_end, J, Jend, dsgn, colneg, nz, bulk_launch_full(nblk, a_end, sw),
+                         own_map_single(), nullptr, 0, bl ? lists->blocks.p + bl->first : nullptr, bl ? bl->len : 0);
       BAE_HIP(hipEventRecord(e->ev_bulk[pj], s1));
       prev_bulk = (int)pj;
       if (e->profiling) {

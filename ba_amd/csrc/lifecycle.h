@@ -2,8 +2,8 @@
 // One record (Engine::held), one method per event; the body of an event lists what it drops or establishes and
 // why.  Nothing else assigns these flags (DESIGN.md "What the engine holds and what drops it").  Host only: no HIP
 // include, hostcheck.cpp replays event lists on a fresh record (ba_hostcheck_lifecycle).
-// The version counters (sig_plan_version, pcg_plan_version, tile_order_version, dist.key, nzL_version)
-// compare against each other and are a different mechanism: they stay on the engine.
+// The version counters (sig_plan_version, pcg_plan_version, tile_order_version, dist.key, bulk_lists.key,
+// nzL_version) compare against each other and are a different mechanism: they stay on the engine.
 #pragma once
 
 namespace bae {
