@@ -26,6 +26,8 @@
 //   visual_ba_demo --pcg [tol] --joint-cov A,B   after the solve: the joint covariance of the poses A and B without a
 //                                           factor (GetJointPoseCovarianceIterative: the panel PCG on the twelve unit
 //                                           columns), printed as a 12 x 12 block with the passes and the time
+//   visual_ba_demo --lm [lambda0]           Options::use_levenberg_marquardt (initial damping lambda0, default 1e-4): damped
+//                                           steps accepted by gain ratio; prints lambda and rho of every iteration
 //   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
 //                                           GetLandmarkCovariance: selected inverse of the reduced system), then
@@ -53,7 +55,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false; double pcg_tol = 1e-6; unsigned pcg_coarse = 0, weakest_modes = 0; int joint_a = -1, joint_b = -1; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false, lm = false; double pcg_tol = 1e-6, lm_lambda0 = 1e-4; unsigned pcg_coarse = 0, weakest_modes = 0; int joint_a = -1, joint_b = -1; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -83,6 +85,11 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   options.error_change_threshold = 1e-5;
   options.device = shard.device;
   if (shard.order_auto) options.pose_ordering = ba::PoseOrdering::Auto;
+  if (shard.lm) { options.use_levenberg_marquardt = true; options.use_dogleg = false; options.lm_initial_damping = shard.lm_lambda0; }
+  auto print_lm = [&](int step) {
+    std::printf("step %d: lambda %.3e rho %.4f rejected %u proj error %.4f\n", step, adjuster.damping(), adjuster.last_gain_ratio(),
+                adjuster.rejected_steps(), adjuster.GetSolutionSummary().post_solve_norm);
+  };
   if (shard.pcg) { options.reduced_solver = ba::ReducedSolver::Pcg; options.pcg_tolerance = shard.pcg_tol; options.pcg_coarse_aggregate = shard.pcg_coarse; }
   auto print_pcg = [&](int step) {
     ba_hip_pcg_stats ps;
@@ -210,6 +217,7 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   std::printf("poses %u landmarks %u residuals %d\n", adjuster.GetNumPoses(), adjuster.GetNumLandmarks(), n_res);
   adjuster.Solve(1);
   if (shard.pcg) print_pcg(1);
+  if (shard.lm) print_lm(1);
   if (shard.order_auto) {
     ba_hip_ordering_stats os;
     if (ba_hip_get_pose_ordering(adjuster.engine(), nullptr, &os) != 0) { std::printf("no pose ordering\n"); return 2; }
@@ -223,10 +231,11 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   double e0, eu, eb, ei;
   adjuster.GetErrors(e0, eu, eb, ei);
   if (!adjuster.GetSolutionSummary().IsResultGood()) { std::printf("Solve failed\n"); return 2; }
-  if (shard.pcg) {  // one Gauss-Newton step per call, to print the solver's statistics of each
+  if (shard.pcg || shard.lm) {  // one step per call, to print the solver's statistics of each
     for (int it = 0; it < 8; ++it) {
       adjuster.Solve(1);
-      print_pcg(it + 2);
+      if (shard.pcg) print_pcg(it + 2);
+      if (shard.lm) print_lm(it + 2);
       if (adjuster.GetSolutionSummary().result != ba::Success) break;
     }
   } else {
@@ -385,6 +394,12 @@ int main(int argc, char** argv) {
   for (int i = 1; i < argc; i += 2) {
     if (std::strcmp(argv[i], "--covariances") == 0) { shard.covariances = true; --i; continue; }
     if (std::strcmp(argv[i], "--leverages") == 0) { shard.leverages = true; --i; continue; }
+    if (std::strcmp(argv[i], "--lm") == 0) {
+      shard.lm = true;
+      if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.lm_lambda0 = std::atof(argv[i + 1]);
+      else --i;
+      continue;
+    }
     if (std::strcmp(argv[i], "--pcg") == 0) {
       shard.pcg = true;
       if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.pcg_tol = std::atof(argv[i + 1]);

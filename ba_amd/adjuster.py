@@ -79,6 +79,7 @@ SYMBOLS = [
     "ba_adjuster_get_pose_pose_leverages", "ba_adjuster_get_pose_pose_leverage",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
+    "ba_adjuster_set_levenberg_marquardt", "ba_adjuster_get_damping", "ba_adjuster_get_levenberg_marquardt_state",
 ]
 
 _lib = None
@@ -97,6 +98,7 @@ def lib():
         L.ba_adjuster_engine.restype = C.c_void_p
         L.ba_adjuster_landmark_outlier_ratio.restype = C.c_double
         L.ba_adjuster_get_camera_fov.restype = C.c_double
+        L.ba_adjuster_get_damping.restype = C.c_double
         for n in ("ba_adjuster_add_camera", "ba_adjuster_add_pose", "ba_adjuster_add_landmark",
                   "ba_adjuster_add_projection_residual", "ba_adjuster_add_unary_constraint",
                   "ba_adjuster_add_binary_constraint", "ba_adjuster_add_imu_residual",
@@ -236,6 +238,21 @@ class BundleAdjuster:
     def Solve(self, max_iter, gn_damping=1.0, error_increase_allowed=False):
         self.L.ba_adjuster_solve(self.h, int(max_iter), C.c_double(gn_damping),
                                  int(error_increase_allowed))
+
+    def SetLevenbergMarquardt(self, on, lambda0=1e-4):
+        """Options::use_levenberg_marquardt / lm_initial_damping between Solve() calls: damped steps accepted by gain
+        ratio; the damping starts again at lambda0."""
+        self.L.ba_adjuster_set_levenberg_marquardt(self.h, int(bool(on)), C.c_double(lambda0))
+
+    def damping(self):
+        """the Levenberg-Marquardt damping the next iteration starts with"""
+        return float(self.L.ba_adjuster_get_damping(self.h))
+
+    def levenberg_marquardt_state(self):
+        """(gain ratio of the last step judged, steps the last Solve() rolled back and re-linearised)"""
+        rho, rej = C.c_double(), C.c_uint32()
+        self.L.ba_adjuster_get_levenberg_marquardt_state(self.h, C.byref(rho), C.byref(rej))
+        return rho.value, int(rej.value)
 
     def GetNumPoses(self):
         return self.L.ba_adjuster_num_poses(self.h)

@@ -28,6 +28,8 @@ struct Iface {
   virtual void regularize(uint32_t p, int t, int g, int b, int r) = 0;
   virtual void set_root(uint32_t id) = 0;
   virtual void solve(uint32_t it, double damping, int allow) = 0;
+  virtual void set_levenberg_marquardt(int on, double lambda0) = 0;
+  virtual void lm_state(double* lambda, double* rho, uint32_t* rejected) const = 0;
   virtual uint32_t num_poses() const = 0;
   virtual uint32_t num_landmarks() const = 0;
   virtual uint32_t num_proj() const = 0;
@@ -161,6 +163,10 @@ struct Impl : Iface {
   void regularize(uint32_t p, int t, int g, int b, int r) override { ba.RegularizePose(p, t != 0, g != 0, b != 0, r != 0); }
   void set_root(uint32_t id) override { ba.SetRootPoseId(id); }
   void solve(uint32_t it, double damping, int allow) override { ba.Solve(it, damping, allow != 0); }
+  void set_levenberg_marquardt(int on, double lambda0) override { ba.SetLevenbergMarquardt(on != 0, lambda0); }
+  void lm_state(double* lambda, double* rho, uint32_t* rejected) const override {
+    *lambda = ba.damping(); *rho = ba.last_gain_ratio(); *rejected = ba.rejected_steps();
+  }
   uint32_t num_poses() const override { return ba.GetNumPoses(); }
   uint32_t num_landmarks() const override { return ba.GetNumLandmarks(); }
   uint32_t num_proj() const override { return ba.GetNumProjResiduals(); }
@@ -460,6 +466,17 @@ double ba_adjuster_landmark_outlier_ratio(const ba_adjuster* a, uint32_t id) { r
 void ba_adjuster_get_projection_residual(const ba_adjuster* a, uint32_t id, double* out11) { a->p->proj_residual(id, out11); }
 uint32_t ba_adjuster_get_imu_residual(const ba_adjuster* a, uint32_t id, double* out19) { return a->p->imu_residual(id, out19); }
 void ba_adjuster_get_summary(const ba_adjuster* a, ba_summary* s) { a->p->summary(s); }
+void ba_adjuster_set_levenberg_marquardt(ba_adjuster* a, int on, double lambda0) { a->p->set_levenberg_marquardt(on, lambda0); }
+double ba_adjuster_get_damping(const ba_adjuster* a) {
+  double lambda, rho;
+  uint32_t rejected;
+  a->p->lm_state(&lambda, &rho, &rejected);
+  return lambda;
+}
+void ba_adjuster_get_levenberg_marquardt_state(const ba_adjuster* a, double* gain_ratio, uint32_t* rejected_steps) {
+  double lambda;
+  a->p->lm_state(&lambda, gain_ratio, rejected_steps);
+}
 void ba_adjuster_get_timers(const ba_adjuster* a, ba_hip_timers* t) { a->p->timers(t); }
 ba_hip_engine* ba_adjuster_engine(ba_adjuster* a) { return a->p->engine(); }
 void ba_adjuster_get_camera_pose(const ba_adjuster* a, uint32_t cam_id, double t_vs[7]) { a->p->camera_pose(cam_id, t_vs); }

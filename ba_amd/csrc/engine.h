@@ -17,6 +17,7 @@
 #include "lifecycle.h"
 #include "chol_launch.h"
 #include "bulk_lists.h"
+#include "damping.h"
 
 namespace bae {
 
@@ -369,6 +370,19 @@ struct Engine {
   ba_hip_pcg_panel_stats pcgp_stats = {};
   std::vector<PcgState> pcgp_cols;
 
+  // Levenberg-Marquardt damping (ba_hip_set_damping, damping.h, k_damp.hip).  lambda_next: what the next
+  // ba_hip_linearize takes; lambda_lin: what the linearisation on the device was built with (GuardFacts::damped).
+  // The buffers exist only once a linearisation was damped: d_p [n] (engine rows, 0 on masked parameters), d_l
+  // [L][lm], schur [Pact][6] the Schur part of the pose diagonals, part / out the sums of k_damp_terms
+  // (pred | delta^T D delta | min d | max d), terms_h their host copy while terms_valid.
+  struct Damp {
+    double lambda_next = 0.0, lambda_lin = 0.0;
+    DBuf<double> d_p, d_l, schur, part, out;
+    double terms_h[4] = {0, 0, 0, 0};
+    bool terms_valid = false;
+    double poses_ms = 0.0, terms_ms = 0.0;   // k_damp_poses of the last linearisation, k_damp_terms of the last solve
+  } damp;
+
   // optional per-kernel timing (ba_hip_set_profiling)
   bool profiling = false;
   ba_hip_kernel_stats kstats = {};
@@ -503,6 +517,11 @@ int launch_backsub(Engine* e);                         // delta_l
 int launch_compose_step(Engine* e, double coef_rhs, double coef_gn, double* norms2_host);
 int launch_apply_step(Engine* e);                      // state[cur] -> state[1-cur]
 int launch_dogleg(Engine* e, int gn_available, double* h7, bool skip_jrhs);
+// damping (k_damp.hip), each a no-op unless the linearisation is damped (e->damp.lambda_lin > 0):
+int damp_prepare(Engine* e);             // buffers of a damped linearisation, before launch_landmarks
+int launch_pose_schur_diag(Engine* e);   // Schur part of the pose diagonals, on stream2 behind k_pose_blocks
+int launch_damp_poses(Engine* e);        // d_p, S_jj += lambda d_p: once A holds the complete S
+int launch_damp_terms(Engine* e);        // predicted decrease and delta^T D delta of gn_p / gn_l into damp.terms_h
 int select_kth(Engine* e, const double* d_values, uint32_t n_local, uint64_t k, double* out);
 int sum_partials(Engine* e, uint32_t nparts, uint32_t ncomp, double* host_out, bool cross_shard = true);
 void defer_begin(Engine* e);   // k_reduce.hip

@@ -975,7 +975,12 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   const Structure& st = e->st;
   ba_hip_errors errs = {0, 0, 0, 0};
   int rc;
+  if (e->damp.lambda_next > 0.0) BA_ASK(damping_refusal(e));
   e->held.linearize_begins();
+  e->damp.lambda_lin = e->damp.lambda_next;   // the rows, V^-1 and S written below are those of H + lambda D
+  e->damp.terms_valid = false;
+  e->damp.poses_ms = e->damp.terms_ms = 0.0;
+  if ((rc = damp_prepare(e))) return rc;
   // projection errors at the linearisation point -> Huber sigma
   EventTimer t_j(e);
   if ((rc = launch_pose_prep(e))) return rc;
@@ -1027,6 +1032,13 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   if ((rc = launch_gather_S(e)) || (rc = launch_posepose_build(e, c_huber, hs + 1))) return rc;
   // dense priors after k_pp_scatter, in prior order; their E_p is folded into unary_error
   if ((rc = launch_priors(e, 1, &e->prior_err_h))) return rc;
+  // A holds the complete S: the pose part of the damping, before anything reads or copies it
+  std::unique_ptr<EventTimer> t_d;
+  if (e->damp.lambda_lin > 0.0) {
+    t_d.reset(new EventTimer(e));
+    if ((rc = launch_damp_poses(e))) return rc;
+    t_d->mark();
+  }
   if (e->prob.num_unary + e->prob.num_binary + e->prob.num_imu)  // kept for ba_hip_marginalize (the dogleg reuses pp_err)
     BAE_HIP(hipMemcpyAsync(e->pp_err_lin.p, e->pp_err.p, (size_t)(e->prob.num_unary + e->prob.num_binary + e->prob.num_imu) *
                            sizeof(double), hipMemcpyDeviceToDevice, e->stream));
@@ -1067,6 +1079,7 @@ int ba_hip_linearize(ba_hip_engine* h, ba_hip_errors* out) {
   e->timers.j_evaluation = t_j.read_ms() + t_l.read_ms();
   e->timers.robust_weights = t_r.read_ms();
   e->timers.jtj_schur = t_s.read_ms();
+  if (t_d) e->damp.poses_ms = t_d->read_ms();
   errs.proj_error = hs[0]; errs.unary_error = hs[1] + e->prior_err_h; errs.binary_error = hs[2]; errs.inertial_error = hs[3];
   e->held.linearize_succeeded();
   if (out) *out = errs;
@@ -1132,11 +1145,20 @@ int ba_hip_solve_gn(ba_hip_engine* h) {
   EventTimer tb(e);
   if ((rc = launch_backsub(e))) return rc;
   e->timers.back_substitution = tb.stop_ms();
+  e->damp.terms_valid = false;
+  if (e->damp.lambda_lin > 0.0 && !status) {
+    EventTimer td(e);
+    if ((rc = launch_damp_terms(e))) return rc;
+    e->damp.terms_ms = td.stop_ms();
+  }
   return status ? BA_HIP_FACTORIZATION_ERROR : 0;
 }
 
 int ba_hip_dogleg_terms(ba_hip_engine* h, int gn_available, ba_hip_dogleg_scalars* out) {
   BA_ENTRY_FINAL(h);
+  if (e->damp.lambda_lin > 0.0)
+    return e->fail_msg("ba_hip_dogleg_terms: the linearisation the device holds is damped (ba_hip_set_damping); the dogleg "
+                       "step is not combined with damping");
   // every sum of this call stays on the device until ONE copy at the end (sums.flush())
   memset(out, 0, sizeof(*out));
   double* dh = e->dog_h;
@@ -1154,6 +1176,58 @@ int ba_hip_dogleg_terms(ba_hip_engine* h, int gn_available, ba_hip_dogleg_scalar
   out->rhs_l_sq = dh[3]; out->gn_l_sq = dh[4]; out->rhs_gn_l = dh[5];
   out->j_rhs_sq = dh[6] + dh[7] + e->prior_jrhs_h;
   return e->st.K ? launch_calib_dogleg(e, gn_available, out) : 0;
+}
+
+// ---- Levenberg-Marquardt damping (damping.h, k_damp.hip) ----------------------------------------------------------
+int ba_hip_set_damping(ba_hip_engine* h, double lambda) {
+  BA_ENTRY_HOST(h);
+  if (!(lambda >= 0.0) || !std::isfinite(lambda)) return e->fail_msg("ba_hip_set_damping: lambda must be finite and >= 0");
+  if (lambda > 0.0) BA_ASK(damping_refusal(e));
+  e->damp.lambda_next = lambda;
+  return 0;
+}
+
+int ba_hip_damping_update(ba_hip_engine* h, double* lambda, double* nu, double rho) {
+  BA_ENTRY_HOST(h);
+  if (!lambda || !nu) return e->fail_msg("ba_hip_damping_update: NULL argument");
+  DampState s = {*lambda, *nu};
+  const bool accepted = damp_update(&s, rho);
+  *lambda = s.lambda;
+  *nu = s.nu;
+  return accepted ? 1 : 0;
+}
+
+int ba_hip_get_damping_terms(ba_hip_engine* h, ba_hip_damping_terms* out) {
+  BA_ENTRY_FINAL(h);
+  if (!out) return e->fail_msg("ba_hip_get_damping_terms: NULL argument");
+  memset(out, 0, sizeof(*out));
+  out->lambda = e->damp.lambda_lin;
+  if (!(e->damp.lambda_lin > 0.0)) return 0;
+  if (!e->damp.terms_valid)
+    return e->fail_msg("ba_hip_get_damping_terms: needs a finished ba_hip_solve_gn of the damped linearisation");
+  const double* t = e->damp.terms_h;
+  out->predicted_decrease = t[0]; out->step_scaled_sq = t[1];
+  out->diag_min = t[2]; out->diag_max = t[3];
+  out->device_ms = e->damp.poses_ms + e->damp.terms_ms;
+  return 0;
+}
+
+int ba_hip_get_damping_diagonal(ba_hip_engine* h, double* d_p, double* d_l) {
+  BA_ENTRY_FINAL(h);
+  const Structure& st = e->st;
+  if (!(e->damp.lambda_lin > 0.0))
+    return e->fail_msg("ba_hip_get_damping_diagonal: the linearisation the device holds is not damped (ba_hip_set_damping)");
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  if (d_p && st.np) BAE_HIP(hipMemcpy(d_p, e->damp.d_p.p, (size_t)st.np * 8, hipMemcpyDeviceToHost));
+  unpermute_vec(e, st.np ? d_p : nullptr);
+  if (d_l && st.Lact) {
+    std::vector<double> dl((size_t)st.L * e->lm_dim);
+    BAE_HIP(hipMemcpy(dl.data(), e->damp.d_l.p, dl.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t l = 0; l < st.L; ++l)
+      if (st.lm_opt[l] >= 0)
+        for (int k = 0; k < e->lm_dim; ++k) d_l[(size_t)st.lm_opt[l] * e->lm_dim + k] = dl[(size_t)l * e->lm_dim + k];
+  }
+  return 0;
 }
 
 int ba_hip_compose_step(ba_hip_engine* h, double coef_rhs, double coef_gn, ba_hip_step_norms* out) {
@@ -1309,6 +1383,8 @@ int ba_hip_set_calibration(ba_hip_engine* h, int calib_size, int do_tvs) {
                        "columns it shares an entry with (BundleAdjuster.cpp:1775-1783)");
   if ((do_tvs || calib_size) && e->lm_dim != 1)
     return e->fail_msg("calibration columns need LmSize 1 (parallel_algos.h:102-131)");
+  if ((do_tvs || calib_size) && e->damp.lambda_next > 0.0)
+    return e->fail_msg("ba_hip_set_calibration: damping is set (ba_hip_set_damping) and is not offered with calibration unknowns");
   e->calib_dim = do_tvs ? 6 : calib_size;
   e->calib_tvs = do_tvs != 0;
   e->held.calibration_changed();

@@ -26,7 +26,13 @@ namespace bae {
 
 inline GuardFacts guard_facts(const Engine* e) {
   return {dist_solve_enabled(e), e->sharded(), e->pcg_refused(), e->opt.keep_reduced_system && e->A_keep.p,
-          e->pcg_plan.nt == e->st.ld / 64 && e->pcg_blk.size() == (size_t)2 * e->st.ld};
+          e->pcg_plan.nt == e->st.ld / 64 && e->pcg_blk.size() == (size_t)2 * e->st.ld, e->damp.lambda_lin > 0.0};
+}
+// why ba_hip_set_damping(lambda > 0) is refused on this engine, or nothing
+inline std::string damping_refusal(const Engine* e) {
+  if (e->calib_dim) return "ba_hip_set_damping: not offered with calibration unknowns";
+  if (e->allreduce || e->coll || e->comm) return "ba_hip_set_damping: not offered on sharded engines or with the distributed solve";
+  return "";
 }
 inline StructureView structure_view(const Engine* e) {
   const Structure& st = e->st;

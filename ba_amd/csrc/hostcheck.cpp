@@ -1175,7 +1175,7 @@ static int put_message(const std::string& m, char* msg, uint32_t cap) {
 }
 
 // The events replayed on a fresh record as ba_hostcheck_lifecycle does, then one named guard of requests.h.
-// facts: bit 0 distributed solve, 1 sharded, 2 hooked, 3 kept copy, 4 the PCG plan fits.  flags: bit 0 foreign_ok
+// facts: bit 0 distributed solve, 1 sharded, 2 hooked, 3 kept copy, 4 the PCG plan fits, 5 (value 32) damped.  flags: bit 0 foreign_ok
 // (kept_factor), bit 1 landmarks (kept_factor, marginals), bit 2 the caller passed PCG options (pcg_panel), bit 3
 // calibration unknowns (marginalize).  noun: kept_factor only, null for the calibration wording.
 // Returns 0 (served), 1 (refused, the message in msg), -(i + 1) at the first unknown event code, -1000 for an
@@ -1187,7 +1187,8 @@ extern "C" int ba_hostcheck_guard(uint32_t n, const int32_t* events, const char*
   Held h;
   for (uint32_t i = 0; i < n; ++i)
     if (!held_apply(h, events[i])) return -(int)(i + 1);
-  const GuardFacts f = {(facts & 1) != 0, (facts & 2) != 0, (facts & 4) != 0, (facts & 8) != 0, (facts & 16) != 0};
+  const GuardFacts f = {(facts & 1) != 0, (facts & 2) != 0, (facts & 4) != 0, (facts & 8) != 0, (facts & 16) != 0,
+                        (facts & 32) != 0};
   const PcgAsk ask = {rel_tolerance, coarse_aggregate};
   const std::string g = guard;
   if (g == "kept_factor") return put_message(guard_kept_factor(h, f, who, noun, flags & 1, (flags & 2) != 0), msg, cap);
@@ -1246,4 +1247,33 @@ extern "C" void ba_hostcheck_rowmaps(uint32_t np, uint32_t K, uint32_t D, uint32
   const std::vector<uint32_t> a = natural_rowmap(v), b = identity_rowmap(np + K, ld);
   std::copy(a.begin(), a.end(), natural_out);
   std::copy(b.begin(), b.end(), identity_out);
+}
+
+#include "damping.h"
+// The damping rules of damping.h.  op 0: damp_clamp(in[0]) -> out[0].  1: damp_update on (lambda, nu) = in[0 .. 1]
+// with rho = in[2] -> out = (lambda, nu, accepted).  2: damp_terms_host on n parameters, in = delta | g | d -> out =
+// (delta^T D delta, predicted decrease).  3: damp_v<n> on the unique entries in[0 ..] of V (n = 1 | 3) -> out = the
+// damped entries, then d_l.  4: damp_pose_diag(in[0], in[1]) -> out[0].  5: damp_keep_lambda(in[0]) -> out[0].
+// 6: damp_gain_ratio(in[0], in[1], in[2]) -> out[0].  Returns 0, -1000 for an unknown op.
+extern "C" int ba_hostcheck_damping(int op, uint32_t n, const double* in, double lambda, double* out) {
+  using namespace bae;
+  if (op == 0) { out[0] = damp_clamp(in[0]); return 0; }
+  if (op == 1) {
+    DampState s = {in[0], in[1]};
+    const bool ok = damp_update(&s, in[2]);
+    out[0] = s.lambda; out[1] = s.nu; out[2] = ok ? 1.0 : 0.0;
+    return 0;
+  }
+  if (op == 2) { damp_terms_host(n, in, in + n, in + 2 * (size_t)n, lambda, out, out + 1); return 0; }
+  if (op == 3 && (n == 1 || n == 3)) {
+    const uint32_t nv = n * (n + 1) / 2;
+    std::copy(in, in + nv, out);
+    if (n == 1) damp_v<1>(out, lambda, out + nv);
+    else damp_v<3>(out, lambda, out + nv);
+    return 0;
+  }
+  if (op == 4) { out[0] = damp_pose_diag(in[0], in[1]); return 0; }
+  if (op == 5) { out[0] = damp_keep_lambda(in[0]); return 0; }
+  if (op == 6) { out[0] = damp_gain_ratio(in[0], in[1], in[2]); return 0; }
+  return -1000;
 }

@@ -473,7 +473,9 @@ __device__ __forceinline__ void store_landmark(uint32_t l, uint32_t O, uint32_t 
 // CAL (calibration instantiations, LM == 1): additionally the calibration rows `crow` (engine.h) —
 // sqrt(w) dz_dtvs of the observation at 2a, 2a+1 and the landmark's E_l = sum w J_l^T J_k at 2O + l
 // (six more components of the segmented sums).
-template <int LM, int WAVES, bool BIG, bool STAGE, int CAL = 0, bool FOV = false>
+// DAMP (ba_hip_set_damping, damping.h): V <- V + lambda diag(d_l) before the inverse, d_l to lm_dl; an instantiation
+// of its own, so that the undamped kernels stay the code they were.
+template <int LM, int WAVES, bool BIG, bool STAGE, int CAL = 0, bool FOV = false, bool DAMP = false>
 __global__ void __launch_bounds__(64 * WAVES)
 k_linearize(uint32_t n_chunks, int C, uint32_t O, uint32_t lrow_base, double c_huber, int use_robust,
             const uint2* __restrict__ wave_rng, const uint32_t* __restrict__ lm_ptr,
@@ -488,7 +490,7 @@ k_linearize(uint32_t n_chunks, int C, uint32_t O, uint32_t lrow_base, double c_h
             double* __restrict__ lm_vinv, double* __restrict__ lm_bl, double* __restrict__ obs_jl,
             double* __restrict__ partials, const int32_t* __restrict__ pose_opt, double* __restrict__ crow,
             const double* __restrict__ lm_zref, const double* __restrict__ state,
-            const double* __restrict__ cam_cache) {
+            const double* __restrict__ cam_cache, double lambda, double* __restrict__ lm_dl) {
   constexpr int R = LM == 1 ? 6 : 8, RD = R * 6;   // rows / doubles per observation
   constexpr int STRIDE = RD + 2;                    // LDS stride per lane (even: 16-byte reads; odd multiple of 2 banks)
   constexpr int NS = LmSums<LM, CAL>::N, NV = LmSums<LM, CAL>::NV, NE = LmSums<LM, CAL>::NE;
@@ -544,7 +546,8 @@ k_linearize(uint32_t n_chunks, int C, uint32_t O, uint32_t lrow_base, double c_h
     double tot[NS];
 #pragma unroll
     for (int i = 0; i < NS; ++i) tot[i] = __shfl(v[i], s1, 64);
-    double Vi[LM * LM];
+    double Vi[LM * LM], dl[LM];
+    if constexpr (DAMP) damp_v<LM>(tot, lambda, dl);
     invert_v<LM>(tot, Vi);
     if constexpr (STAGE) {
       double* st = stage[wave] + lane * STRIDE;
@@ -572,6 +575,10 @@ k_linearize(uint32_t n_chunks, int C, uint32_t O, uint32_t lrow_base, double c_h
       if (lane == s1 && lm_act) {
         store_landmark<LM>(l, O, lrow_base, tot, Vi, lm_vinv, lm_bl, scal, frow);
         store_calib_lm(l, tot);
+        if constexpr (DAMP) {
+#pragma unroll
+          for (int i = 0; i < LM; ++i) lm_dl[(size_t)l * LM + i] = dl[i];
+        }
       }
     }
     // LDS image -> one contiguous span of the factor rows (16 bytes per lane per store)
@@ -611,7 +618,8 @@ k_linearize(uint32_t n_chunks, int C, uint32_t O, uint32_t lrow_base, double c_h
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) tot[i] += __shfl_xor(tot[i], off, 64);
     }
-    double Vi[LM * LM];
+    double Vi[LM * LM], dl[LM];
+    if constexpr (DAMP) damp_v<LM>(tot, lambda, dl);
     invert_v<LM>(tot, Vi);
     for (uint32_t a = a0 + lane; a < a1; a += 64) {
       ObsLin<LM, CAL> q;
@@ -632,6 +640,10 @@ k_linearize(uint32_t n_chunks, int C, uint32_t O, uint32_t lrow_base, double c_h
     if (lane == 0 && lm_act) {
       store_landmark<LM>(l, O, lrow_base, tot, Vi, lm_vinv, lm_bl, scal, frow);
       store_calib_lm(l, tot);
+      if constexpr (DAMP) {
+#pragma unroll
+        for (int i = 0; i < LM; ++i) lm_dl[(size_t)l * LM + i] = dl[i];
+      }
     }
   }
 #undef BAE_LIN_ARGS
@@ -639,14 +651,22 @@ k_linearize(uint32_t n_chunks, int C, uint32_t O, uint32_t lrow_base, double c_h
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) err += __shfl_xor(err, off, 64);
   if (lane == 0) partials[chunk] = err;
-  (void)NV; (void)NE;
+  (void)NV; (void)NE; (void)lambda; (void)lm_dl;
 }
 
 // one launch of k_linearize: the FOV instantiation when the rig holds a FovCamera
-#define BAE_LIN_LAUNCH(LMv, WAVESv, BIGv, STAGEv, CALv, grid_, block_, shm_, stream_, ...)                        \
+#define BAE_LIN_LAUNCH_D(LMv, WAVESv, BIGv, STAGEv, CALv, DAMPv, grid_, block_, shm_, stream_, ...)              \
   do {                                                                                                          \
-    if (e->has_fov) hipLaunchKernelGGL((k_linearize<LMv, WAVESv, BIGv, STAGEv, CALv, true>), grid_, block_, shm_, stream_, __VA_ARGS__); \
-    else hipLaunchKernelGGL((k_linearize<LMv, WAVESv, BIGv, STAGEv, CALv, false>), grid_, block_, shm_, stream_, __VA_ARGS__);           \
+    if (e->has_fov) hipLaunchKernelGGL((k_linearize<LMv, WAVESv, BIGv, STAGEv, CALv, true, DAMPv>), grid_, block_, shm_, stream_, __VA_ARGS__); \
+    else hipLaunchKernelGGL((k_linearize<LMv, WAVESv, BIGv, STAGEv, CALv, false, DAMPv>), grid_, block_, shm_, stream_, __VA_ARGS__);           \
+  } while (0)
+#define BAE_LIN_LAUNCH(LMv, WAVESv, BIGv, STAGEv, CALv, ...) BAE_LIN_LAUNCH_D(LMv, WAVESv, BIGv, STAGEv, CALv, false, __VA_ARGS__)
+// ... without calibration unknowns: the damped instantiation while this linearisation is damped (ba_hip_set_damping
+// refuses calibration unknowns)
+#define BAE_LIN_LAUNCH_L(LMv, WAVESv, BIGv, STAGEv, ...)                                                         \
+  do {                                                                                                          \
+    if (e->damp.lambda_lin > 0.0) BAE_LIN_LAUNCH_D(LMv, WAVESv, BIGv, STAGEv, 0, true, __VA_ARGS__);            \
+    else BAE_LIN_LAUNCH_D(LMv, WAVESv, BIGv, STAGEv, 0, false, __VA_ARGS__);                                     \
   } while (0)
 
 int launch_landmarks(Engine* e, double c_huber, int use_robust) {
@@ -662,7 +682,7 @@ int launch_landmarks(Engine* e, double c_huber, int use_robust) {
       e->lm_ref_pose.p, e->lm_ref_cam.p, e->cam.p, e->pose_cam_ptr(), e->tsw.p, e->tws.p, e->twp.p,     \
       e->obs_w.p, e->frow.p, e->scal.p, e->lm_vinv.p, e->lm_bl.p, e->obs_jl.p, e->partials.p + (first),  \
       (const int32_t*)e->pose_opt.p, e->crow.p, (const double*)e->lm_zref.p,                           \
-      (const double*)e->pose_state[e->cur].p, e->cam_eval_ptr()
+      (const double*)e->pose_state[e->cur].p, e->cam_eval_ptr(), e->damp.lambda_lin, e->damp.d_l.p
   e->prof_begin(e->ev_landmarks);
   if (st.K) {  // calibration instantiations (LmSize 1): the CAL kernels, same launch shapes
     // T_vs calibration with the tables of k_pose_prep built for another T_vs than the rig's (after a
@@ -699,22 +719,24 @@ int launch_landmarks(Engine* e, double c_huber, int use_robust) {
   if (n_small) {
     if (e->dbg_linearize_variant == 0) {
       const dim3 grid((n_small + WAVES - 1) / WAVES), block(64 * WAVES);
-      if (e->lm_dim == 1) BAE_LIN_LAUNCH(1, WAVES, false, true, 0, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
-      else BAE_LIN_LAUNCH(3, WAVES, false, true, 0, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
+      if (e->lm_dim == 1) BAE_LIN_LAUNCH_L(1, WAVES, false, true, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
+      else BAE_LIN_LAUNCH_L(3, WAVES, false, true, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
     } else {
       const dim3 grid((n_small + 3) / 4), block(256);
-      if (e->lm_dim == 1) BAE_LIN_LAUNCH(1, 4, false, false, 0, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
-      else BAE_LIN_LAUNCH(3, 4, false, false, 0, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
+      if (e->lm_dim == 1) BAE_LIN_LAUNCH_L(1, 4, false, false, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
+      else BAE_LIN_LAUNCH_L(3, 4, false, false, grid, block, 0, e->stream, BAE_ARGS(0, n_small));
     }
   }
   if (st.n_big_chunks) {
     const dim3 grid((st.n_big_chunks + WAVES - 1) / WAVES), block(64 * WAVES);
-    if (e->lm_dim == 1) BAE_LIN_LAUNCH(1, WAVES, true, false, 0, grid, block, 0, e->stream, BAE_ARGS(n_small, st.n_big_chunks));
-    else BAE_LIN_LAUNCH(3, WAVES, true, false, 0, grid, block, 0, e->stream, BAE_ARGS(n_small, st.n_big_chunks));
+    if (e->lm_dim == 1) BAE_LIN_LAUNCH_L(1, WAVES, true, false, grid, block, 0, e->stream, BAE_ARGS(n_small, st.n_big_chunks));
+    else BAE_LIN_LAUNCH_L(3, WAVES, true, false, grid, block, 0, e->stream, BAE_ARGS(n_small, st.n_big_chunks));
   }
   e->prof_end(e->ev_landmarks);
 #undef BAE_ARGS
 #undef BAE_LIN_LAUNCH
+#undef BAE_LIN_LAUNCH_L
+#undef BAE_LIN_LAUNCH_D
   BAE_HIP(hipGetLastError());
   return 0;
 }

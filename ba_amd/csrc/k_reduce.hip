@@ -572,6 +572,10 @@ int launch_gather_S(Engine* e) {
                          e->frow.p, e->crow.p, e->border_blocks.p);
       BAE_HIP(hipGetLastError());
     }
+    {
+      int rc = launch_pose_schur_diag(e);   // (a damped linearisation only)
+      if (rc) return rc;
+    }
     BAE_HIP(hipEventRecord(e->ev_join, e->stream2));
   }
   e->prof_begin(e->ev_gather);

@@ -22,7 +22,13 @@ struct GuardFacts {
   bool hooked;         // an all-reduce hook, a collectives hook or a communicator is set
   bool kept_copy;      // keep_reduced_system is set and A_keep holds a copy of S
   bool pcg_plan_fits;  // the plan of the last PCG solve has the tile count and row blocks of the system
+  bool damped;         // the linearisation the device holds was built with lambda > 0 (ba_hip_set_damping)
 };
+// The kept factor, the factor rows and the S of a damped linearisation belong to H + lambda D: what would read a
+// covariance, a leverage, a mode or a prior out of them refuses.  ba_hip_get_S and ba_hip_check_solve keep serving:
+// they read the damped S, which is what ba_hip_solve_gn solved.
+static const char* const kDamped =
+    "the linearisation the device holds is damped (ba_hip_set_damping), linearise and solve once with damping 0";
 static const char* const kNotFinalized = "ba_hip_finalize has not been called";
 
 // Is the factor that the last ba_hip_solve_gn left in A there to be read?  `who` starts the message, `noun` names what
@@ -36,6 +42,7 @@ inline std::string guard_kept_factor(const Held& h, const GuardFacts& f, const c
   if (landmarks && f.sharded && !f.dist_solve)   // (the distributed solve refuses first, for every block)
     return m + "landmark blocks are not available on sharded engines (each rank holds one landmark shard)";
   if (noun && f.dist_solve) return m + "not available with the distributed solve";
+  if (noun && f.damped) return m + kDamped;   // (calibration marginals cannot meet damping: it refuses calibration unknowns)
   if (!h.factored && h.pcg_solved)
     return w + ": the last ba_hip_solve_gn ran the PCG solver (BA_HIP_SOLVER_PCG), which leaves no factor" +
            (noun ? std::string("; ") + noun + " need a direct solve (ba_hip_set_reduced_solver)" : "");
@@ -74,6 +81,7 @@ inline std::string guard_pcg_panel(const Held& h, const GuardFacts& f, const cha
   const std::string m = std::string(who) + ": ";
   if (f.hooked || f.dist_solve) return m + "not available on a sharded engine (all-reduce hook, collectives hook or communicator set)";
   if (!h.finalized) return m + kNotFinalized;
+  if (f.damped) return m + kDamped;
   if (!h.pcg_solved) {
     if (h.factored)
       return m + "the last ba_hip_solve_gn ran the direct solver, A holds its factor and not S; panel solves need "
@@ -110,6 +118,7 @@ inline std::string guard_marginalize(const Held& h, const GuardFacts& f, bool ca
   if (!h.finalized) return kNotFinalized;
   if (calibration) return "marginalize: not offered with calibration unknowns";
   if (f.hooked) return "marginalize: not offered on sharded engines or with the distributed solve";
+  if (f.damped) return std::string("marginalize: ") + kDamped;
   if (!h.lin_valid)
     return "marginalize: needs the linearisation of the current state (ba_hip_linearize, no step, rollback or "
            "new masks since)";

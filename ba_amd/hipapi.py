@@ -185,6 +185,12 @@ class PcgPanelStats(C.Structure):
 PCG_PANEL_MAX_COLUMNS = 512  # BA_HIP_PCG_PANEL_MAX_COLUMNS
 
 
+class DampingTerms(C.Structure):
+    """ba_hip_damping_terms"""
+    _fields_ = [("lambda_", C.c_double), ("predicted_decrease", C.c_double), ("step_scaled_sq", C.c_double),
+                ("diag_min", C.c_double), ("diag_max", C.c_double), ("device_ms", C.c_double)]
+
+
 def _pcg_stats_dict(st):
     return {k: getattr(st, k) for k, _ in type(st)._fields_ if k != "reserved"}
 
@@ -226,6 +232,8 @@ SYMBOLS = [
     "ba_hip_get_weakest_modes", "ba_hip_get_mode_stats",
     "ba_hip_pcg_panel_solve_system", "ba_hip_get_joint_marginals_pcg", "ba_hip_get_pcg_panel_stats",
     "ba_hip_get_pcg_panel_columns", "ba_hip_pcg_panel_solve",
+    "ba_hip_set_damping", "ba_hip_get_damping_terms", "ba_hip_get_damping_diagonal",
+    "ba_hip_damping_update",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -401,6 +409,25 @@ class Engine:
         s = DoglegScalars()
         self._chk(self.L.ba_hip_dogleg_terms(self.h, int(gn_available), C.byref(s)))
         return s
+
+    def set_damping(self, lam):
+        """Levenberg-Marquardt damping of the next linearize(): (H + lam diag(d)) delta = g; 0 = off."""
+        self._chk(self.L.ba_hip_set_damping(self.h, C.c_double(lam)))
+
+    def damping_terms(self):
+        """dict of ba_hip_damping_terms: lambda of the held linearisation, predicted_decrease and step_scaled_sq of the
+        last solve_gn, diag_min / diag_max of the damping diagonal, device_ms of the damping kernels."""
+        t = DampingTerms()
+        self._chk(self.L.ba_hip_get_damping_terms(self.h, C.byref(t)))
+        return {"lambda": t.lambda_, "predicted_decrease": t.predicted_decrease, "step_scaled_sq": t.step_scaled_sq,
+                "diag_min": t.diag_min, "diag_max": t.diag_max, "device_ms": t.device_ms}
+
+    def damping_diagonal(self):
+        """(d_p, d_l) of the damped linearisation: pose rows in the caller's order, landmarks by optimisation index."""
+        n, nl = self.num_pose_params(), self.num_lm_params()
+        a, c = np.zeros(max(n, 1)), np.zeros(max(nl, 1))
+        self._chk(self.L.ba_hip_get_damping_diagonal(self.h, _p(a, dp), _p(c, dp)))
+        return a[:n], c[:nl]
 
     def compose_step(self, coef_rhs, coef_gn):
         n = StepNorms()

@@ -116,6 +116,15 @@ struct Options {  // reference BundleAdjuster.h:72-107, same names and defaults
   // Pcg only: g >= 1 adds the coarse-space correction over aggregates of g consecutive active poses to the
   // block-Jacobi preconditioner (ba_hip_pcg_options.coarse_aggregate); 0 = block-Jacobi alone.
   uint32_t pcg_coarse_aggregate = 0;
+  // extension: Levenberg-Marquardt steps (include/ba_hip.h: ba_hip_set_damping).  Every
+  // iteration solves (H + lambda diag(H)) delta = g, the damping acting inside the landmark elimination, and the
+  // step is accepted by its gain ratio (Nielsen's rule); a rejected step is rolled back and the system linearised
+  // again with a larger lambda, up to lm_max_inner_iterations times, then ErrorIncreased.  lambda starts at
+  // lm_initial_damping and lives across Solve() calls like the trust region (damping()).  Together with use_dogleg:
+  // reported by Init, Levenberg-Marquardt wins.  Ignored, with a warning, by the calibration instantiations.
+  bool use_levenberg_marquardt = false;
+  Scalar lm_initial_damping = 1e-4;
+  uint32_t lm_max_inner_iterations = 100;
 };
 
 // A dense Gaussian prior on poses (extension; include/ba_hip.h, ba_hip_marginalize): pose_ids (k), x0 (k x 16:
@@ -188,6 +197,7 @@ class BundleAdjuster {
             uint32_t num_landmarks = 0, const SE3t& t_vs = SE3t()) {
     options_ = options;
     trust_region_size_ = options_.trust_region_size;
+    SetLevenbergMarquardt(options_.use_levenberg_marquardt, options_.lm_initial_damping);
     root_pose_id_ = 0;
     num_active_poses_ = 0;
     num_active_landmarks_ = 0;
@@ -796,6 +806,28 @@ class BundleAdjuster {
   Scalar GetBinaryLeverage(uint32_t id) { return PosePoseLeverage(BA_HIP_RES_BINARY, id); }
   Scalar GetImuLeverage(uint32_t id) { return PosePoseLeverage(BA_HIP_RES_IMU, id); }
   Scalar trust_region_size() const { return trust_region_size_; }
+  // Options::use_levenberg_marquardt: the damping the next iteration starts with, the gain ratio of the last
+  // accepted or finally rejected step, and the steps rejected (rolled back and re-linearised) by the last Solve()
+  Scalar damping() const { return lm_lambda_; }
+  // ... switched on or off between Solve() calls; the damping starts again at lambda0
+  void SetLevenbergMarquardt(bool on, Scalar lambda0) {
+    options_.use_levenberg_marquardt = on;
+    options_.lm_initial_damping = lambda0;
+    lm_lambda_ = lambda0;
+    lm_nu_ = 2;
+    lm_rho_ = 0;
+    lm_rejections_ = 0;
+    if (on && kCalibDim > 0) {
+      std::cerr << "ba::BundleAdjuster: use_levenberg_marquardt is not offered with calibration unknowns, ignored" << std::endl;
+      options_.use_levenberg_marquardt = false;
+    }
+    if (options_.use_levenberg_marquardt && options_.use_dogleg) {
+      std::cerr << "ba::BundleAdjuster: use_dogleg and use_levenberg_marquardt are both set, Levenberg-Marquardt steps are taken" << std::endl;
+      options_.use_dogleg = false;
+    }
+  }
+  Scalar last_gain_ratio() const { return lm_rho_; }
+  uint32_t rejected_steps() const { return lm_rejections_; }
   const ba_hip_timers& GetLastTimers() const { return last_timers_; }
   uint32_t iterations_run() const { return iterations_run_; }
   // multi-GPU: every rank holds all poses and its landmark shard; sums over shards go
@@ -912,6 +944,8 @@ class BundleAdjuster {
   Options<Scalar> options_;
   SolutionSummary<Scalar> summary_;
   Scalar trust_region_size_ = kTrustRegionAuto;
+  Scalar lm_lambda_ = 1e-4, lm_nu_ = 2, lm_rho_ = 0;
+  uint32_t lm_rejections_ = 0;
   Scalar proj_error_ = 0, binary_error_ = 0, unary_error_ = 0, inertial_error_ = 0;
   uint32_t root_pose_id_ = 0, num_active_poses_ = 0, num_active_landmarks_ = 0;
   uint32_t iterations_run_ = 0;
@@ -1324,7 +1358,48 @@ bool BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::SolveInternal(
     proj_error_ = e.proj_error; unary_error_ = e.unary_error;
     binary_error_ = e.binary_error; inertial_error_ = e.inertial_error;
   };
-  if (use_dogleg) {
+  if (options_.use_levenberg_marquardt) {
+    // One pass: solve the damped system, compose (0, 1), evaluate before, apply, evaluate after, gain ratio.  A
+    // rejected step is rolled back, lambda grows by Nielsen's rule and the system is linearised again with it.
+    for (uint32_t inner = 0;; ++inner) {
+      if (num_active_poses_ > 0) summary_.result = Success;
+      const int rc = ba_hip_solve_gn(engine_);
+      if (rc < 0) { Check(rc, "ba_hip_solve_gn"); return false; }
+      if (rc == BA_HIP_FACTORIZATION_ERROR) { summary_.result = FactorizationError; return false; }
+      if (rc == BA_HIP_SOLVER_ERROR) { summary_.result = SolverError; return false; }
+      ba_hip_damping_terms terms;
+      if (!Check(ba_hip_get_damping_terms(engine_, &terms), "ba_hip_get_damping_terms")) return false;
+      if (!Check(ba_hip_compose_step(engine_, 0.0, 1.0, &norms), "ba_hip_compose_step")) return false;
+      if (!Check(ba_hip_eval_residuals(engine_, &pre), "ba_hip_eval_residuals")) return false;
+      summary_.pre_solve_norm = total(pre);
+      if (!options_.apply_results) {   // nothing moves: there is no gain to judge
+        summary_.post_solve_norm = summary_.pre_solve_norm;
+        return true;
+      }
+      summary_.delta_norm = norms.step_l_norm + norms.step_p_norm;
+      if (!Check(ba_hip_apply_step(engine_), "ba_hip_apply_step")) return false;
+      if (!Check(ba_hip_eval_residuals(engine_, &post), "ba_hip_eval_residuals")) return false;
+      summary_.post_solve_norm = total(post);
+      lm_rho_ = (summary_.pre_solve_norm - summary_.post_solve_norm) / terms.predicted_decrease;
+      double lambda = lm_lambda_, nu = lm_nu_;
+      const bool accepted = ba_hip_damping_update(engine_, &lambda, &nu, lm_rho_) == 1;
+      lm_lambda_ = lambda;
+      lm_nu_ = nu;
+      if (accepted) {
+        accept(post);
+        return true;
+      }
+      if (!Check(ba_hip_rollback(engine_), "ba_hip_rollback")) return false;
+      lm_rejections_++;
+      if (inner + 1 >= options_.lm_max_inner_iterations) {
+        summary_.result = ErrorIncreased;
+        return false;
+      }
+      ba_hip_errors built;
+      if (!Check(ba_hip_set_damping(engine_, lm_lambda_), "ba_hip_set_damping")) return false;
+      if (!Check(ba_hip_linearize(engine_, &built), "ba_hip_linearize")) return false;
+    }
+  } else if (use_dogleg) {
     bool gn_computed = false;
     ba_hip_dogleg_scalars s;
     if (!Check(ba_hip_dogleg_terms(engine_, 0, &s), "ba_hip_dogleg_terms")) return false;
@@ -1434,6 +1509,7 @@ void BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::Solve(
   // already holds the current state
   if (!SyncEngine()) return;
   iterations_run_ = 0;
+  lm_rejections_ = 0;
   if (!Check(ba_hip_begin_solve(engine_), "ba_hip_begin_solve")) return;  // :288-296
   const bool host_was_stale = host_state_stale_;
   host_state_stale_ = true;  // from here on the device holds the state; getters fetch it lazily (:666-678)
@@ -1452,6 +1528,7 @@ void BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::Solve(
       masks_uploaded_ = masks;
     }
     ba_hip_errors built;
+    if (options_.use_levenberg_marquardt && !Check(ba_hip_set_damping(engine_, lm_lambda_), "ba_hip_set_damping")) return;
     if (!Check(ba_hip_linearize(engine_, &built), "ba_hip_linearize")) return;  // BuildProblem .. Schur
     proj_error_ = built.proj_error; binary_error_ = built.binary_error;
     unary_error_ = built.unary_error; inertial_error_ = built.inertial_error;
@@ -1471,6 +1548,9 @@ void BundleAdjuster<Scalar, LmSize, PoseSize, CalibSize, DoTvs>::Solve(
       break;
     }
   }
+  // the damping goes back to 0: what reads the kept factor after this Solve() meets the "re-linearised since"
+  // refusals it already handles at the next undamped linearisation, never a factor of H + lambda D served as H's
+  if (options_.use_levenberg_marquardt && !Check(ba_hip_set_damping(engine_, 0.0), "ba_hip_set_damping")) return;
   if (!Check(ba_hip_end_solve(engine_), "ba_hip_end_solve")) return;  // :672-678
   if (DoTvs && rig_->NumCams() > 0) {
     // :72-83 moved the rig's camera 0 on every applied step (host-side copy in the engine: no transfer)

@@ -109,6 +109,13 @@ void ba_adjuster_get_projection_residual(const ba_adjuster* a, uint32_t id, doub
  * first PoseSize entries are used); returns the number of measurements (0 for a bad id) */
 uint32_t ba_adjuster_get_imu_residual(const ba_adjuster* a, uint32_t id, double* out19);
 void ba_adjuster_get_summary(const ba_adjuster* a, ba_summary* s);
+/* Options::use_levenberg_marquardt and lm_initial_damping, between Solve() calls (the damping starts again at lambda0;
+ * together with use_dogleg Levenberg-Marquardt wins; ignored with a warning by the calibration instantiations);
+ * BundleAdjuster::damping(): the lambda the next iteration starts with; last_gain_ratio() and rejected_steps(): rho
+ * of the last step judged and the steps the last Solve() rolled back and re-linearised. */
+void ba_adjuster_set_levenberg_marquardt(ba_adjuster* a, int on, double lambda0);
+double ba_adjuster_get_damping(const ba_adjuster* a);
+void ba_adjuster_get_levenberg_marquardt_state(const ba_adjuster* a, double* gain_ratio, uint32_t* rejected_steps);
 /* SolutionSummary::cond_proj_error, cond_inertial_error (reference BundleAdjuster.cpp:680-704) */
 void ba_adjuster_get_cond_errors(const ba_adjuster* a, double out2[2]);
 void ba_adjuster_get_timers(const ba_adjuster* a, ba_hip_timers* t);

@@ -247,6 +247,39 @@ int ba_hip_linearize(ba_hip_engine* e, ba_hip_errors* out);
 int ba_hip_solve_gn(ba_hip_engine* e);
 /* BundleAdjuster.cpp:858-925 + the norms/dots of :971-1004 */
 int ba_hip_dogleg_terms(ba_hip_engine* e, int gn_available, ba_hip_dogleg_scalars* out);
+
+/* ---- Levenberg-Marquardt damping (ba_amd/csrc/damping.h) ----------------------------
+ * With lambda > 0 the next ba_hip_linearize builds, and ba_hip_solve_gn solves, (H + lambda diag(d)) delta = g
+ * instead of H delta = g: H = J^T Lambda J the full normal matrix, d_j = min(max(H_jj, 1e-6), 1e32) for every free
+ * parameter (masked pose parameters keep their 1e6 and get no damping).  Inside the landmark elimination:
+ * V + lambda diag(d_l) is inverted (d_l from diag V after the 1e-6 guard), so the factor rows, V^-1, the Schur part
+ * of S and of the right-hand side and the back-substitution are those of the damped system; the pose diagonal of H,
+ * recovered as S_jj minus its Schur part, is clamped into d_p and lambda d_p is added to S_jj.
+ * lambda = 0 (the default) is the undamped engine: no damping kernel runs, no damping buffer is allocated, and the
+ * results are bitwise those of an engine that never saw the call.  lambda > 0 is refused with calibration unknowns
+ * (ba_hip_set_calibration) and on an engine that is sharded, hooked or runs the distributed solve.
+ * While the linearisation the device holds is damped, ba_hip_dogleg_terms and every reader of the kept factor, of the
+ * factor rows or of S for covariances, leverages, modes, panel solves or marginalisation priors refuses: linearise
+ * and solve once with damping 0.  ba_hip_get_S and ba_hip_check_solve serve the damped S. */
+int ba_hip_set_damping(ba_hip_engine* e, double lambda);   /* >= 0; 0 = off (default); used from the next ba_hip_linearize */
+typedef struct {
+  double lambda;               /* of the linearisation the device holds */
+  /* of the last ba_hip_solve_gn, in the units of ba_hip_errors: E(0) - E_model(delta) = delta^T (lambda D delta + g),
+   * and delta^T D delta.  The gain ratio of a step is (E_before - E_after) / predicted_decrease. */
+  double predicted_decrease, step_scaled_sq;
+  double diag_min, diag_max;   /* over d_p and d_l of the free parameters, after the clamp */
+  double device_ms;            /* k_damp_poses of the linearisation + k_damp_terms of the solve */
+} ba_hip_damping_terms;
+/* zeros (lambda = 0) for an undamped linearisation; needs a finished ba_hip_solve_gn for a damped one */
+int ba_hip_get_damping_terms(ba_hip_engine* e, ba_hip_damping_terms* out);
+/* test / report access: d_p (ba_hip_num_pose_params, the caller's row order, 0 on masked parameters) and d_l
+ * (ba_hip_num_lm_params, by landmark optimisation index) of the damped linearisation; either may be NULL */
+int ba_hip_get_damping_diagonal(ba_hip_engine* e, double* d_p, double* d_l);
+/* The control rule of the damped step (Nielsen), on the host; the engine's state is not touched: with the gain ratio
+ * rho = (E_before - E_after) / predicted_decrease of a step, accepted (returns 1) when rho > 0: lambda <- lambda
+ * max(1/3, 1 - (2 rho - 1)^3), nu <- 2; otherwise (returns 0; a NaN ratio included) lambda <- lambda nu, nu <- 2 nu.
+ * lambda is kept in [1e-12, 1e12].  nu starts at 2.  Returns -1 for a NULL argument. */
+int ba_hip_damping_update(ba_hip_engine* e, double* lambda, double* nu, double rho);
 /* step = coef_rhs * (rhs_p_, rhs_l_) + coef_gn * delta_gn  (BundleAdjuster.cpp:923-925,
  * 947-950, 985, 1015-1017, 1108-1110) */
 int ba_hip_compose_step(ba_hip_engine* e, double coef_rhs, double coef_gn, ba_hip_step_norms* out);
