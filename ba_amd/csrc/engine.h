@@ -79,10 +79,8 @@ static const int kPoseState = 16;
 // one factor row: 6 doubles (see DESIGN.md "factor rows")
 static const int kRow = 6;
 
-// Host-built structure (ba_hip_finalize): the lists of structure.h + the pose-pose scatter count
-struct Structure : Lists {
-  uint32_t n_pp_entries = 0;  // (pose, residual side) entries of the pose-pose scatter
-};
+// The static structure of the current graph (ba_hip_finalize): the lists of structure.h
+using Structure = Lists;
 
 struct Engine {
   int lm_dim = 1, pose_dim = 6, device = 0;

@@ -58,8 +58,13 @@ Engine::~Engine() {
   if (own_stream && stream) (void)hipStreamDestroy(stream);   // a caller's stream is only synchronised
 }
 
-template <typename T>
-static int upload(Engine* e, DBuf<T>& buf, const std::vector<T>& v, size_t min_count = 0) {
+static_assert(sizeof(U2) == sizeof(uint2) && sizeof(U3) == 3 * sizeof(uint32_t) && sizeof(U4) == sizeof(uint4),
+              "list records are plain words");
+
+// S: T itself, or the host record of structure.h with its layout (U4 for uint4)
+template <typename T, typename S>
+static int upload(Engine* e, DBuf<T>& buf, const std::vector<S>& v, size_t min_count = 0) {
+  static_assert(sizeof(S) == sizeof(T), "host record and device element differ in size");
   const size_t n = std::max(v.size(), min_count);
   BAE_HIP(buf.alloc(std::max<size_t>(n, 1)));
   if (!v.empty()) {
@@ -151,20 +156,10 @@ int order_poses(Engine* e, std::vector<uint64_t>* proj_edges, double device_ms) 
   } else {
     const int D = e->pose_dim;
     const uint32_t G = pose_group_size(D), ng = (Pact + G - 1) / G;
-    // the pose-pose residuals couple their two poses (unary residuals couple none)
+    // the projection part's group pairs, then those of the binary and inertial residuals and the dense priors
     std::vector<uint64_t> edges(proj_edges ? *proj_edges : std::vector<uint64_t>());
-    auto pair = [&](uint32_t p1, uint32_t p2) {
-      if (p1 >= pb.num_poses || p2 >= pb.num_poses || nat[p1] < 0 || nat[p2] < 0) return;
-      const uint32_t a = (uint32_t)nat[p1] / G, b = (uint32_t)nat[p2] / G;
-      if (a != b) edges.push_back((uint64_t)std::min(a, b) << 32 | std::max(a, b));
-    };
-    for (uint32_t i = 0; i < pb.num_binary; ++i) pair(pb.bin_p1[i], pb.bin_p2[i]);
-    for (uint32_t i = 0; i < pb.num_imu; ++i) pair(pb.imu_p1[i], pb.imu_p2[i]);
-    // a dense prior couples every pair of its poses
     const DensePriors& pr = e->dpri;
-    for (uint32_t q = 0; q < pr.count(); ++q)
-      for (uint32_t k = pr.ptr[q]; k < pr.ptr[q + 1]; ++k)
-        for (uint32_t k2 = pr.ptr[q]; k2 < k; ++k2) pair(pr.pose[k], pr.pose[k2]);
+    coupling_group_edges(pb, pr.count(), pr.ptr.data(), pr.pose.data(), nat, G, edges);
     group_graph_csr(ng, std::move(edges), e->group_ptr, e->group_adj);
     OrderingResult r;
     choose_pose_ordering(Pact, D, (uint32_t)e->calib_dim, e->group_ptr, e->group_adj, e->opt_of_natural, &r);
@@ -178,8 +173,157 @@ int order_poses(Engine* e, std::vector<uint64_t>* proj_edges, double device_ms) 
   return 0;
 }
 
+// ---- ba_hip_finalize: the steps of build_structure ---------------------------------------------------
+// a buffer of at least one element, cleared in stream order
+template <typename T>
+static hipError_t alloc_zeroed(Engine* e, DBuf<T>& buf, size_t count) {
+  const hipError_t err = buf.alloc(std::max<size_t>(count, 1));
+  return err != hipSuccess ? err : hipMemsetAsync(buf.p, 0, buf.bytes(), e->stream);
+}
+
+#define UP(buf, vec) if ((rc = upload(e, e->buf, vec))) return rc
+
+// the lists of build_lists (the device builder leaves its own on the device); frees the big host copies
+static int upload_host_lists(Engine* e) {
+  const Problem& pb = e->prob;
+  Structure& st = e->st;
+  int rc;
+  UP(pose_opt, st.pose_opt); UP(lm_opt, st.lm_opt);
+  UP(lm_ref_pose, pb.lm_ref_pose); UP(lm_ref_cam, pb.lm_ref_cam);
+  UP(lm_ptr, st.lm_ptr); UP(obs_z, st.obs_z); UP(obs_pose, st.obs_pose); UP(obs_cam, st.obs_cam);
+  UP(obs_lm, st.obs_lm); UP(obs_rid, st.obs_rid); UP(obs_w0, st.obs_w0);
+  UP(tile_ptr, st.tile_ptr); UP(pose_ptr, st.pose_ptr); UP(pose_mid, st.pose_mid);
+  BAE_HIP(e->pair_ent.alloc(std::max<size_t>(st.n_pair_entries, 1)));
+  if (st.n_pair_entries)
+    BAE_HIP(hipMemcpyAsync(e->pair_ent.p, st.pair_ent.get(), st.n_pair_entries * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+  BAE_HIP(e->wave_rng.alloc(std::max<size_t>(st.n_chunks, 1)));
+  if (st.n_chunks)
+    BAE_HIP(hipMemcpyAsync(e->wave_rng.p, st.wave_rng.data(), (size_t)st.n_chunks * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+  BAE_HIP(e->tile_ref.alloc(std::max<size_t>(st.n_tile_refs, 1)));
+  if (st.n_tile_refs)
+    BAE_HIP(hipMemcpyAsync(e->tile_ref.p, st.tile_ref.data(), st.n_tile_refs * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+  BAE_HIP(e->pose_ent.alloc(std::max<size_t>(3 * st.n_pose_entries, 1)));
+  if (st.n_pose_entries)
+    BAE_HIP(hipMemcpyAsync(e->pose_ent.p, st.pose_ent.data(), st.n_pose_entries * sizeof(U3), hipMemcpyHostToDevice, e->stream));
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  // the big host lists are only needed on the device from here on
+  st.pair_ent.reset();
+  std::vector<U2>().swap(st.tile_ref);
+  std::vector<U3>().swap(st.pose_ent);
+  std::vector<double>().swap(st.obs_z);
+  // conditioning residuals (BundleAdjuster.h:503-510): flags in sorted order
+  std::vector<uint8_t> is_cond(st.O, 0), cond_sorted(std::max<uint32_t>(st.O, 1), 0);
+  for (uint32_t id : pb.proj_cond) if (id < st.O) is_cond[id] = 1;
+  for (uint32_t s = 0; s < st.O; ++s) cond_sorted[s] = is_cond[st.obs_rid[s]];
+  UP(obs_cond, cond_sorted);
+  return 0;
+}
+
+// the unary / binary / inertial residuals, their scatter lists and per-slot buffers, the cameras
+static int upload_pose_pose(Engine* e, const PosePoseLists& pp) {
+  const Problem& pb = e->prob;
+  int rc;
+  UP(pose_active, pb.pose_active);
+  UP(un_pose, pb.un_pose); UP(un_t, pb.un_t); UP(un_cov_inv, pb.un_cov_inv); UP(un_rot, pb.un_rot);
+  UP(bin_p1, pb.bin_p1); UP(bin_p2, pb.bin_p2); UP(bin_t, pb.bin_t); UP(bin_cov_inv, pb.bin_cov_inv);
+  UP(bin_cov_inv_sqrt, pb.bin_cov_inv_sqrt); UP(bin_w, pb.bin_w); UP(bin_rot, pb.bin_rot);
+  UP(imu_p1, pb.imu_p1); UP(imu_p2, pb.imu_p2); UP(imu_ptr, pb.imu_ptr); UP(imu_meas, pb.imu_meas);
+  UP(pp_ptr, pp.pp_ptr); UP(pp_ent, pp.pp_ent); UP(pp_res_p1, pp.res_p1); UP(pp_res_p2, pp.res_p2);
+  const std::vector<double> ones(std::max<uint32_t>(pb.num_unary, 1), 1.0);
+  UP(un_scale, ones);
+  if ((rc = upload_imu_consts(e))) return rc;
+  const size_t nr1 = std::max<size_t>(pp.res_p1.size(), 1);
+  BAE_HIP(e->pp_h.alloc(nr1 * 3 * 225)); BAE_HIP(e->pp_g.alloc(nr1 * 30));
+  BAE_HIP(e->pp_dz.alloc(nr1 * 2 * 225)); BAE_HIP(e->pp_info.alloc(nr1 * 225));
+  BAE_HIP(e->pp_err.alloc(nr1));
+  BAE_HIP(e->pp_err_lin.alloc(nr1));
+  BAE_HIP(alloc_zeroed(e, e->imu_cov_inv, std::max<size_t>(pb.num_imu, 1) * 225));
+  e->tvs_eval = pb.cam_tvs;
+  e->tvs_eval_prev = pb.cam_tvs;
+  return upload_cameras(e, false);
+}
+#undef UP
+
+// the double-buffered state, the transforms derived from it, masks and outlier counts
+static int alloc_state(Engine* e) {
+  const Problem& pb = e->prob;
+  const Structure& st = e->st;
+  int rc;
+  e->cur = 0;
+  e->held.structure_rebuilt();   // (nothing since the new tile pattern has read the old one's flag)
+  for (int b = 0; b < 2; ++b) {
+    BAE_HIP(e->pose_state[b].alloc(std::max<size_t>((size_t)st.P * kPoseState, 1)));
+    BAE_HIP(e->lm_x[b].alloc(std::max<size_t>((size_t)st.L * 4, 1)));
+    BAE_HIP(e->lm_reliable[b].alloc(std::max<size_t>(st.L, 1)));
+  }
+  if (st.P) BAE_HIP(hipMemcpyAsync(e->pose_state[0].p, pb.pose_state.data(),
+                                   (size_t)st.P * kPoseState * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  if ((rc = upload(e, e->lm_xw, pb.lm_xw))) return rc;
+  if (st.L) {
+    BAE_HIP(hipMemcpyAsync(e->lm_x[0].p, pb.lm_xw.data(), (size_t)st.L * 4 * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    BAE_HIP(hipMemsetAsync(e->lm_reliable[0].p, 1, st.L, e->stream));
+  }
+  const size_t PC = std::max<size_t>((size_t)st.P * std::max(st.C, 1u), 1);
+  BAE_HIP(e->tsw.alloc(PC * kRt)); BAE_HIP(e->tws.alloc(PC * kRt));
+  BAE_HIP(e->twp.alloc(std::max<size_t>((size_t)st.P * kRt, 1)));
+  BAE_HIP(alloc_zeroed(e, e->pose_mask, (size_t)st.P + st.Pact));
+  BAE_HIP(e->pose_mask_lin.alloc(std::max<size_t>((size_t)st.P + st.Pact, 1)));
+  e->lin_mask_version = e->mask_version;   // no linearisation yet: nothing reads the copy
+  BAE_HIP(alloc_zeroed(e, e->lm_outliers, st.L));
+  return 0;
+}
+
+// what an iteration writes: residuals and factor rows, the reduced system, steps, reduction scratch
+static int alloc_iteration_buffers(Engine* e, bool host_build) {
+  const Problem& pb = e->prob;
+  const Structure& st = e->st;
+  int rc;
+  const size_t O1 = std::max<size_t>(st.O, 1), L1 = std::max<size_t>(st.L, 1);
+  const int LM1 = std::max(e->lm_dim, 1);
+  BAE_HIP(e->obs_e.alloc(O1)); BAE_HIP(e->obs_w.alloc(O1));
+  BAE_HIP(e->obs_jl.alloc(O1 * 2 * LM1));
+  if (st.O && host_build) BAE_HIP(hipMemcpyAsync(e->obs_w.p, st.obs_w0.data(), (size_t)st.O * sizeof(double),
+                                                 hipMemcpyHostToDevice, e->stream));
+  BAE_HIP(alloc_zeroed(e, e->frow, (size_t)st.n_rows * kRow));
+  BAE_HIP(alloc_zeroed(e, e->scal, std::max<size_t>(st.n_scalars, 2 * O1 + L1 * LM1 + 1)));  // last: the zero scalar
+  if (st.K && !e->calib_tvs) {
+    // parallel_algos.h:115-118 assigns dTransfer_dparams (2 x NumParams) to a 2 x CalibSize block
+    const int nparams = (!pb.cam_model.empty() && pb.cam_model[0] == 1) ? 5 : 4;
+    if ((int)st.K != nparams)
+      return e->fail_msg("CalibSize must equal the parameter count of camera 0 (LinearCamera 4, FovCamera 5)");
+    if (pb.lm_zref.size() != 2 * (size_t)st.L)
+      return e->fail_msg("intrinsics calibration needs the reference pixel of every landmark (ba_hip_set_landmark_ref_pixels)");
+    if ((rc = upload(e, e->lm_zref, pb.lm_zref))) return rc;
+  }
+  e->cam_params_prev = pb.cam_params;
+  e->cam_w_prev = pb.cam_w;
+  if (st.K) {
+    BAE_HIP(alloc_zeroed(e, e->crow, std::max<size_t>(st.n_scalars, 1) * kRow));
+    BAE_HIP(e->border_blocks.alloc(std::max<size_t>((size_t)st.Pact * 36, 1)));
+  }
+  BAE_HIP(alloc_zeroed(e, e->lm_vinv, L1 * LM1 * LM1));
+  BAE_HIP(alloc_zeroed(e, e->lm_bl, L1 * LM1));
+  BAE_HIP(e->A.alloc((size_t)(st.ld + 1) * st.ld));
+  BAE_HIP(e->rhs_p.alloc(st.ld)); BAE_HIP(e->rhs_sc.alloc(st.ld));
+  BAE_HIP(alloc_zeroed(e, e->gn_p, st.ld));
+  BAE_HIP(alloc_zeroed(e, e->step_p, st.ld));
+  const size_t nl = (size_t)st.Lact * LM1;
+  BAE_HIP(alloc_zeroed(e, e->gn_l, nl));
+  BAE_HIP(alloc_zeroed(e, e->step_l, nl));
+  // reduction scratch: block partials of the element-wise kernels (up to 4 components) and one
+  // partial per linearisation wave
+  const size_t nparts = std::max<size_t>({(O1 + 255) / 256, (L1 + 255) / 256, (size_t)(st.ld + 255) / 256, 1});
+  BAE_HIP(e->partials.alloc(std::max<size_t>(4 * nparts, st.n_chunks)));
+  BAE_HIP(e->scalars_out.alloc(128));  // [0,64) results / staging, [64,128) first-level partial sums
+  BAE_HIP(e->hist.alloc(2048 + 8));
+  BAE_HIP(e->flags.alloc(16));
+  return 0;
+}
+
 // Build everything that depends only on the problem graph (not on the state): the lists of
-// structure.h on the host (threads), the pose-pose scatter lists, the tile pattern; then upload.
+// structure.h (on the device, or on host threads), the pose-pose scatter lists, the tile pattern; then
+// upload and size the buffers.
 static int build_structure(Engine* e) {
   Problem& pb = e->prob;
   Structure& st = e->st;
@@ -218,199 +362,22 @@ static int build_structure(Engine* e) {
     const int brc = build_lists_device(e, stage);
     if (brc) return brc;
   }
-  st.n_pp_entries = 0;
-  // ---- pose-pose residuals: slots [unary | binary | imu], scatter lists per active pose ------
-  const uint32_t nu = pb.num_unary, nbn = pb.num_binary, ni = pb.num_imu, nres = nu + nbn + ni;
-  std::vector<uint32_t> res_p1(nres), res_p2(nres, 0xffffffffu);
-  for (uint32_t i = 0; i < nu; ++i) res_p1[i] = pb.un_pose[i];
-  for (uint32_t i = 0; i < nbn; ++i) { res_p1[nu + i] = pb.bin_p1[i]; res_p2[nu + i] = pb.bin_p2[i]; }
-  for (uint32_t i = 0; i < ni; ++i) { res_p1[nu + nbn + i] = pb.imu_p1[i]; res_p2[nu + nbn + i] = pb.imu_p2[i]; }
-  for (uint32_t s = 0; s < nres; ++s)
-    if (res_p1[s] >= st.P || (res_p2[s] != 0xffffffffu && res_p2[s] >= st.P))
-      return e->fail_msg("pose-pose residual references an unknown pose");
-  std::vector<uint32_t> pp_ptr(st.Pact + 1, 0);
-  for (uint32_t s = 0; s < nres; ++s) {
-    const int32_t o1 = st.pose_opt[res_p1[s]];
-    const int32_t o2 = res_p2[s] != 0xffffffffu ? st.pose_opt[res_p2[s]] : -1;
-    if (o1 >= 0) pp_ptr[o1 + 1]++;
-    if (o2 >= 0 && res_p2[s] != res_p1[s]) pp_ptr[o2 + 1]++;
-  }
-  for (uint32_t p = 0; p < st.Pact; ++p) pp_ptr[p + 1] += pp_ptr[p];
-  st.n_pp_entries = st.Pact ? pp_ptr[st.Pact] : 0;
-  std::vector<uint4> pp_ent(st.n_pp_entries);
+  PosePoseLists pp;
   {
-    std::vector<uint32_t> cur(pp_ptr.begin(), pp_ptr.end() - 1);
-    for (uint32_t s = 0; s < nres; ++s) {
-      const int32_t o1 = st.pose_opt[res_p1[s]];
-      const bool two = res_p2[s] != 0xffffffffu && res_p2[s] != res_p1[s];
-      const int32_t o2 = two ? st.pose_opt[res_p2[s]] : -1;
-      if (o1 >= 0) pp_ent[cur[o1]++] = make_uint4(s, 0, o2 >= 0 ? (uint32_t)o2 : 0xffffffffu, 0);
-      if (o2 >= 0) pp_ent[cur[o2]++] = make_uint4(s, 1, o1 >= 0 ? (uint32_t)o1 : 0xffffffffu, 0);
-    }
+    std::string err;
+    if (!build_pose_pose_lists(pb, st, pp, err)) return e->fail_msg(err.c_str());
   }
-
   stage("pose-pose lists");
   int rc;
   if ((rc = priors_upload(e))) return rc;
-  // ---- 64x64-tile pattern of S (for the tile-sparse factorisation): build_lists marked the tiles
-  // of the projection part and the diagonal; add the pose-pose residual blocks ------------------------
-  {
-    const uint32_t nt = st.ld / 64, D = (uint32_t)e->pose_dim;
-    auto mark = [&](uint32_t pi, uint32_t pj) {  // all tiles the D x D block (pi, pj) overlaps
-      const uint32_t r0 = pi * D / 64, r1 = (pi * D + D - 1) / 64;
-      const uint32_t c0 = pj * D / 64, c1 = (pj * D + D - 1) / 64;
-      for (uint32_t r = r0; r <= r1; ++r)
-        for (uint32_t c = c0; c <= c1; ++c) { st.tile_nz[(size_t)r * nt + c] = 1; st.tile_nz[(size_t)c * nt + r] = 1; }
-    };
-    for (uint32_t s = 0; s < nres; ++s) {
-      const int32_t o1 = st.pose_opt[res_p1[s]];
-      const int32_t o2 = res_p2[s] != 0xffffffffu ? st.pose_opt[res_p2[s]] : -1;
-      if (o1 >= 0 && o2 >= 0) mark((uint32_t)o1, (uint32_t)o2);
-    }
-    // dense priors: every block of their clique
-    const DensePriors& pr = e->dpri;
-    for (uint32_t q = 0; q < pr.count(); ++q)
-      for (uint32_t k = pr.ptr[q]; k < pr.ptr[q + 1]; ++k)
-        for (uint32_t k2 = pr.ptr[q]; k2 <= k; ++k2) {
-          const int32_t o1 = st.pose_opt[pr.pose[k]], o2 = st.pose_opt[pr.pose[k2]];
-          if (o1 >= 0 && o2 >= 0) mark((uint32_t)o1, (uint32_t)o2);
-        }
-    // calibration border: rows np .. np + K - 1 are dense (every pose with a projection residual
-    // couples to T_vs, BundleAdjuster.cpp:501-518)
-    if (st.K)
-      for (uint32_t r = st.np / 64; r <= (st.n - 1) / 64; ++r)
-        for (uint32_t c = 0; c <= r; ++c) { st.tile_nz[(size_t)r * nt + c] = 1; st.tile_nz[(size_t)c * nt + r] = 1; }
-  }
-
+  // 64x64-tile pattern of S (for the tile-sparse factorisation): the list builder marked the tiles of the
+  // projection part and the diagonal; add the pose-pose residuals, the dense priors and the calibration border
+  mark_pose_pose_tiles(pb, e->dpri.count(), e->dpri.ptr.data(), e->dpri.pose.data(), e->pose_dim, st);
   stage("tile pattern");
-  // ---- upload ------------------------------------------------------------------------------
-#define UP(buf, vec) if ((rc = upload(e, e->buf, vec))) return rc
-  if (host_build) {
-    UP(pose_opt, st.pose_opt); UP(lm_opt, st.lm_opt);
-    UP(lm_ref_pose, pb.lm_ref_pose); UP(lm_ref_cam, pb.lm_ref_cam);
-    UP(lm_ptr, st.lm_ptr); UP(obs_z, st.obs_z); UP(obs_pose, st.obs_pose); UP(obs_cam, st.obs_cam);
-    UP(obs_lm, st.obs_lm); UP(obs_rid, st.obs_rid); UP(obs_w0, st.obs_w0);
-    UP(tile_ptr, st.tile_ptr); UP(pose_ptr, st.pose_ptr); UP(pose_mid, st.pose_mid);
-    static_assert(sizeof(U2) == sizeof(uint2) && sizeof(U3) == 3 * sizeof(uint32_t), "list records are plain words");
-    BAE_HIP(e->pair_ent.alloc(std::max<size_t>(st.n_pair_entries, 1)));
-    if (st.n_pair_entries)
-      BAE_HIP(hipMemcpyAsync(e->pair_ent.p, st.pair_ent.get(), st.n_pair_entries * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-    BAE_HIP(e->wave_rng.alloc(std::max<size_t>(st.n_chunks, 1)));
-    if (st.n_chunks)
-      BAE_HIP(hipMemcpyAsync(e->wave_rng.p, st.wave_rng.data(), (size_t)st.n_chunks * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-    BAE_HIP(e->tile_ref.alloc(std::max<size_t>(st.n_tile_refs, 1)));
-    if (st.n_tile_refs)
-      BAE_HIP(hipMemcpyAsync(e->tile_ref.p, st.tile_ref.data(), st.n_tile_refs * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-    BAE_HIP(e->pose_ent.alloc(std::max<size_t>(3 * st.n_pose_entries, 1)));
-    if (st.n_pose_entries)
-      BAE_HIP(hipMemcpyAsync(e->pose_ent.p, st.pose_ent.data(), st.n_pose_entries * sizeof(U3), hipMemcpyHostToDevice, e->stream));
-    BAE_HIP(hipStreamSynchronize(e->stream));
-    // the big host lists are only needed on the device from here on
-    st.pair_ent.reset();
-    std::vector<U2>().swap(st.tile_ref);
-    std::vector<U3>().swap(st.pose_ent);
-    std::vector<double>().swap(st.obs_z);
-    {
-      // conditioning residuals (BundleAdjuster.h:503-510): flags in sorted order
-      std::vector<uint8_t> is_cond(st.O, 0), cond_sorted(std::max<uint32_t>(st.O, 1), 0);
-      for (uint32_t id : pb.proj_cond) if (id < st.O) is_cond[id] = 1;
-      for (uint32_t s = 0; s < st.O; ++s) cond_sorted[s] = is_cond[st.obs_rid[s]];
-      UP(obs_cond, cond_sorted);
-    }
-  }
-  UP(pose_active, pb.pose_active);
-  UP(un_pose, pb.un_pose); UP(un_t, pb.un_t); UP(un_cov_inv, pb.un_cov_inv); UP(un_rot, pb.un_rot);
-  UP(bin_p1, pb.bin_p1); UP(bin_p2, pb.bin_p2); UP(bin_t, pb.bin_t); UP(bin_cov_inv, pb.bin_cov_inv);
-  UP(bin_cov_inv_sqrt, pb.bin_cov_inv_sqrt); UP(bin_w, pb.bin_w); UP(bin_rot, pb.bin_rot);
-  UP(imu_p1, pb.imu_p1); UP(imu_p2, pb.imu_p2); UP(imu_ptr, pb.imu_ptr); UP(imu_meas, pb.imu_meas);
-  UP(pp_ptr, pp_ptr); UP(pp_ent, pp_ent); UP(pp_res_p1, res_p1); UP(pp_res_p2, res_p2);
-#undef UP
-  {
-    std::vector<double> ones(std::max<uint32_t>(nu, 1), 1.0);
-    if ((rc = upload(e, e->un_scale, ones))) return rc;
-    if ((rc = upload_imu_consts(e))) return rc;
-    const size_t nr1 = std::max<size_t>(nres, 1);
-    BAE_HIP(e->pp_h.alloc(nr1 * 3 * 225)); BAE_HIP(e->pp_g.alloc(nr1 * 30));
-    BAE_HIP(e->pp_dz.alloc(nr1 * 2 * 225)); BAE_HIP(e->pp_info.alloc(nr1 * 225));
-    BAE_HIP(e->pp_err.alloc(nr1));
-    BAE_HIP(e->pp_err_lin.alloc(nr1));
-    BAE_HIP(e->imu_cov_inv.alloc(std::max<size_t>(ni, 1) * 225));
-    BAE_HIP(hipMemsetAsync(e->imu_cov_inv.p, 0, e->imu_cov_inv.bytes(), e->stream));
-  }
-  e->tvs_eval = pb.cam_tvs;
-  e->tvs_eval_prev = pb.cam_tvs;
-  if ((rc = upload_cameras(e, false))) return rc;
-  // state
-  e->cur = 0;
-  e->held.structure_rebuilt();   // (nothing since the new tile pattern above has read the old one's flag)
-  for (int b = 0; b < 2; ++b) {
-    BAE_HIP(e->pose_state[b].alloc(std::max<size_t>((size_t)st.P * kPoseState, 1)));
-    BAE_HIP(e->lm_x[b].alloc(std::max<size_t>((size_t)st.L * 4, 1)));
-    BAE_HIP(e->lm_reliable[b].alloc(std::max<size_t>(st.L, 1)));
-  }
-  if (st.P) BAE_HIP(hipMemcpyAsync(e->pose_state[0].p, pb.pose_state.data(),
-                                   (size_t)st.P * kPoseState * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  if ((rc = upload(e, e->lm_xw, pb.lm_xw))) return rc;
-  if (st.L) {
-    BAE_HIP(hipMemcpyAsync(e->lm_x[0].p, pb.lm_xw.data(), (size_t)st.L * 4 * sizeof(double),
-                           hipMemcpyHostToDevice, e->stream));
-    BAE_HIP(hipMemsetAsync(e->lm_reliable[0].p, 1, st.L, e->stream));
-  }
-  const size_t PC = std::max<size_t>((size_t)st.P * std::max(st.C, 1u), 1);
-  BAE_HIP(e->tsw.alloc(PC * kRt)); BAE_HIP(e->tws.alloc(PC * kRt));
-  BAE_HIP(e->twp.alloc(std::max<size_t>((size_t)st.P * kRt, 1)));
-  BAE_HIP(e->pose_mask.alloc(std::max<size_t>((size_t)st.P + st.Pact, 1)));
-  BAE_HIP(hipMemsetAsync(e->pose_mask.p, 0, e->pose_mask.bytes(), e->stream));
-  BAE_HIP(e->pose_mask_lin.alloc(std::max<size_t>((size_t)st.P + st.Pact, 1)));
-  e->lin_mask_version = e->mask_version;   // no linearisation yet: nothing reads the copy
-  BAE_HIP(e->lm_outliers.alloc(std::max<size_t>(st.L, 1)));
-  BAE_HIP(hipMemsetAsync(e->lm_outliers.p, 0, e->lm_outliers.bytes(), e->stream));
-  // per-iteration buffers
-  const size_t O1 = std::max<size_t>(st.O, 1), L1 = std::max<size_t>(st.L, 1);
-  const int LM1 = std::max(LM, 1);
-  BAE_HIP(e->obs_e.alloc(O1)); BAE_HIP(e->obs_w.alloc(O1));
-  BAE_HIP(e->obs_jl.alloc(O1 * 2 * LM1));
-  if (st.O && host_build) BAE_HIP(hipMemcpyAsync(e->obs_w.p, st.obs_w0.data(), (size_t)st.O * sizeof(double),
-                                                 hipMemcpyHostToDevice, e->stream));
-  BAE_HIP(e->frow.alloc((size_t)st.n_rows * kRow));
-  BAE_HIP(hipMemsetAsync(e->frow.p, 0, e->frow.bytes(), e->stream));
-  BAE_HIP(e->scal.alloc(std::max<size_t>(st.n_scalars, 2 * O1 + L1 * LM1 + 1)));  // last: the zero scalar
-  BAE_HIP(hipMemsetAsync(e->scal.p, 0, e->scal.bytes(), e->stream));
-  if (st.K && !e->calib_tvs) {
-    // parallel_algos.h:115-118 assigns dTransfer_dparams (2 x NumParams) to a 2 x CalibSize block
-    const int nparams = (!pb.cam_model.empty() && pb.cam_model[0] == 1) ? 5 : 4;
-    if ((int)st.K != nparams)
-      return e->fail_msg("CalibSize must equal the parameter count of camera 0 (LinearCamera 4, FovCamera 5)");
-    if (pb.lm_zref.size() != 2 * (size_t)st.L)
-      return e->fail_msg("intrinsics calibration needs the reference pixel of every landmark (ba_hip_set_landmark_ref_pixels)");
-    if ((rc = upload(e, e->lm_zref, pb.lm_zref))) return rc;
-  }
-  e->cam_params_prev = pb.cam_params;
-  e->cam_w_prev = pb.cam_w;
-  if (st.K) {
-    BAE_HIP(e->crow.alloc((size_t)std::max<size_t>(st.n_scalars, 1) * kRow));
-    BAE_HIP(hipMemsetAsync(e->crow.p, 0, e->crow.bytes(), e->stream));
-    BAE_HIP(e->border_blocks.alloc(std::max<size_t>((size_t)st.Pact * 36, 1)));
-  }
-  BAE_HIP(e->lm_vinv.alloc(L1 * LM1 * LM1)); BAE_HIP(e->lm_bl.alloc(L1 * LM1));
-  BAE_HIP(hipMemsetAsync(e->lm_vinv.p, 0, e->lm_vinv.bytes(), e->stream));
-  BAE_HIP(hipMemsetAsync(e->lm_bl.p, 0, e->lm_bl.bytes(), e->stream));
-  BAE_HIP(e->A.alloc((size_t)(st.ld + 1) * st.ld));
-  BAE_HIP(e->rhs_p.alloc(st.ld)); BAE_HIP(e->rhs_sc.alloc(st.ld));
-  BAE_HIP(e->gn_p.alloc(st.ld)); BAE_HIP(e->step_p.alloc(st.ld));
-  BAE_HIP(hipMemsetAsync(e->gn_p.p, 0, e->gn_p.bytes(), e->stream));
-  BAE_HIP(hipMemsetAsync(e->step_p.p, 0, e->step_p.bytes(), e->stream));
-  const size_t nl = std::max<size_t>((size_t)st.Lact * LM1, 1);
-  BAE_HIP(e->gn_l.alloc(nl)); BAE_HIP(e->step_l.alloc(nl));
-  BAE_HIP(hipMemsetAsync(e->gn_l.p, 0, e->gn_l.bytes(), e->stream));
-  BAE_HIP(hipMemsetAsync(e->step_l.p, 0, e->step_l.bytes(), e->stream));
-  // reduction scratch: block partials of the element-wise kernels (up to 4 components) and one
-  // partial per linearisation wave
-  const size_t nparts = std::max<size_t>({(O1 + 255) / 256, (L1 + 255) / 256, (size_t)(st.ld + 255) / 256, 1});
-  BAE_HIP(e->partials.alloc(std::max<size_t>(4 * nparts, st.n_chunks)));
-  BAE_HIP(e->scalars_out.alloc(128));  // [0,64) results / staging, [64,128) first-level partial sums
-  BAE_HIP(e->hist.alloc(2048 + 8));
-  BAE_HIP(e->flags.alloc(16));
+  if (host_build && (rc = upload_host_lists(e))) return rc;
+  if ((rc = upload_pose_pose(e, pp))) return rc;
+  if ((rc = alloc_state(e))) return rc;
+  if ((rc = alloc_iteration_buffers(e, host_build))) return rc;
   BAE_HIP(hipStreamSynchronize(e->stream));
   stage("upload / device buffers");
   return 0;

@@ -1277,3 +1277,93 @@ extern "C" int ba_hostcheck_damping(int op, uint32_t n, const double* in, double
   if (op == 6) { out[0] = damp_gain_ratio(in[0], in[1], in[2]); return 0; }
   return -1000;
 }
+
+// ---- pose-pose lists and the tile pattern of the non-projection terms (structure.h) -------------------------
+// The finalize steps of a graph without projections, as build_structure runs them: build_lists (opt ids under the
+// optional opt_of_natural, n_perm entries or 0), build_pose_pose_lists, mark_pose_pose_tiles with the prior cliques as
+// CSR.  Then k_pp_scatter restated for the host exactly as the kernel is written: block-row j of the lower storage per
+// active pose, its entries in order, H11 / H22 on the diagonal block, H12 (side 1: transposed) on block (j, other) when
+// other < j, g1 / g2 on the right-hand side (the kernel adds them to rhs_p and rhs_sc alike), rows and columns of masked
+// parameters skipped.  pose_mask: [P] by pose id; pp_h: [nres][3][225] = H11 | H12 | H22 with row stride 15; pp_g:
+// [nres][30] = g1 | g2; slots [unary | binary | imu].  The caller sizes S_lower (ld x ld), rhs (ld) and tile_nz
+// ((ld / 64)^2) with ld = max(64, round_up(Pact D + K, 64)); pp_ptr takes Pact + 1 words, pp_ent 4 words for each of at
+// most 2 nres entries.  counts: Pact, n, ld, n_pp_entries, nres.  Returns 0; 1 with the builder's message in msg; -2
+// when ld is not the structure's.
+extern "C" int ba_hostcheck_pose_pose_lists(
+    int D, int K, uint32_t P, const uint8_t* pose_active, uint32_t n_perm, const uint32_t* opt_of_natural, uint32_t nu,
+    const uint32_t* un_pose, uint32_t nb, const uint32_t* bin_p1, const uint32_t* bin_p2, uint32_t ni, const uint32_t* imu_p1,
+    const uint32_t* imu_p2, uint32_t nq, const uint32_t* prior_ptr, const uint32_t* prior_pose, const uint16_t* pose_mask,
+    const double* pp_h, const double* pp_g, uint32_t ld, double* S_lower, double* rhs, uint8_t* tile_nz, uint32_t* counts,
+    uint32_t* pp_ptr, uint32_t* pp_ent, char* msg, uint32_t cap) {
+  using namespace bae;
+  Problem pb;
+  pb.num_poses = P; pb.num_unary = nu; pb.num_binary = nb; pb.num_imu = ni;
+  pb.pose_active.assign(pose_active, pose_active + P);
+  pb.un_pose.assign(un_pose, un_pose + nu);
+  pb.bin_p1.assign(bin_p1, bin_p1 + nb); pb.bin_p2.assign(bin_p2, bin_p2 + nb);
+  pb.imu_p1.assign(imu_p1, imu_p1 + ni); pb.imu_p2.assign(imu_p2, imu_p2 + ni);
+  const std::vector<uint32_t> perm(opt_of_natural, opt_of_natural + n_perm);
+  Lists st;
+  PosePoseLists pp;
+  std::string err;
+  if (!build_lists(pb, 0, D, st, err, nullptr, K, &perm) || !build_pose_pose_lists(pb, st, pp, err)) return put_message(err, msg, cap);
+  for (uint32_t k = 0; k < (nq ? prior_ptr[nq] : 0); ++k)   // (priors_upload's check)
+    if (prior_pose[k] >= P) return put_message("dense prior on an unknown pose", msg, cap);
+  mark_pose_pose_tiles(pb, nq, prior_ptr, prior_pose, D, st);
+  put_message("", msg, cap);
+  const uint32_t nres = nu + nb + ni;
+  counts[0] = st.Pact; counts[1] = st.n; counts[2] = st.ld; counts[3] = st.n_pp_entries; counts[4] = nres;
+  if (ld != st.ld) return -2;
+  std::copy(st.tile_nz.begin(), st.tile_nz.end(), tile_nz);
+  std::copy(pp.pp_ptr.begin(), pp.pp_ptr.end(), pp_ptr);
+  static_assert(sizeof(U4) == 4 * sizeof(uint32_t), "a scatter entry is four words");
+  if (st.n_pp_entries) std::memcpy(pp_ent, pp.pp_ent.data(), (size_t)st.n_pp_entries * sizeof(U4));
+  std::vector<uint16_t> mask_opt(st.Pact, 0);
+  for (uint32_t p = 0; p < P; ++p)
+    if (st.pose_opt[p] >= 0) mask_opt[st.pose_opt[p]] = pose_mask[p];
+  // ---- k_pp_scatter ----------------------------------------------------------------------------------
+  std::memset(S_lower, 0, sizeof(double) * (size_t)ld * ld);
+  std::fill(rhs, rhs + ld, 0.0);
+  const int kPPH = 225;
+  for (uint32_t j = 0; j < st.Pact; ++j) {
+    const uint16_t mj = mask_opt[j];
+    for (uint32_t e = pp.pp_ptr[j]; e < pp.pp_ptr[j + 1]; ++e) {
+      const U4 en = pp.pp_ent[e];
+      if (en.x >= nres || en.y > 1 || (en.z != kNoPose && en.z >= st.Pact)) return -3;   // what the kernel would read
+      const double* h = pp_h + (size_t)en.x * 3 * kPPH;
+      const double* g = pp_g + (size_t)en.x * 30;
+      for (int r = 0; r < D; ++r)
+        for (int c = 0; c < D; ++c) {
+          if (!(mj & (1u << r)) && !(mj & (1u << c)))
+            S_lower[((size_t)j * D + r) * ld + (size_t)j * D + c] += (en.y == 0 ? h : h + 2 * kPPH)[r * 15 + c];
+          if (en.z != kNoPose && en.z < j && !(mj & (1u << r)) && !(mask_opt[en.z] & (1u << c)))
+            S_lower[((size_t)j * D + r) * ld + (size_t)en.z * D + c] += en.y == 0 ? h[kPPH + r * 15 + c] : h[kPPH + c * 15 + r];
+        }
+      for (int t = 0; t < D; ++t)
+        if (!(mj & (1u << t))) rhs[(size_t)j * D + t] += g[en.y * 15 + t];
+    }
+  }
+  return 0;
+}
+
+// coupling_group_edges of the same graph arguments: the group pairs (a << 32 | b, a < b; natural opt id / group size of
+// PoseSize D) that order_poses adds to the projection part's before group_graph_csr, in enumeration order with
+// duplicates.  Returns their number; fills at most cap.
+extern "C" uint64_t ba_hostcheck_coupling_group_edges(int D, uint32_t P, const uint8_t* pose_active, uint32_t nb,
+                                                      const uint32_t* bin_p1, const uint32_t* bin_p2, uint32_t ni,
+                                                      const uint32_t* imu_p1, const uint32_t* imu_p2, uint32_t nq,
+                                                      const uint32_t* prior_ptr, const uint32_t* prior_pose, uint64_t* edges,
+                                                      uint64_t cap) {
+  using namespace bae;
+  Problem pb;
+  pb.num_poses = P; pb.num_binary = nb; pb.num_imu = ni;
+  pb.pose_active.assign(pose_active, pose_active + P);
+  pb.bin_p1.assign(bin_p1, bin_p1 + nb); pb.bin_p2.assign(bin_p2, bin_p2 + nb);
+  pb.imu_p1.assign(imu_p1, imu_p1 + ni); pb.imu_p2.assign(imu_p2, imu_p2 + ni);
+  std::vector<int32_t> nat;
+  natural_pose_opt(pb, nat);
+  std::vector<uint64_t> out;
+  coupling_group_edges(pb, nq, prior_ptr, prior_pose, nat, pose_group_size(D), out);
+  std::copy(out.begin(), out.begin() + std::min<uint64_t>(out.size(), cap), edges);
+  return out.size();
+}

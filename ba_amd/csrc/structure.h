@@ -3,7 +3,8 @@
 // per graph and reused by every Gauss-Newton iteration and every Solve() call until the graph
 // changes.  Plain C++17, no HIP: the same code runs in the CPU test harness
 // (ba_amd/csrc/hostcheck.cpp, tests/test_structure_lists.py) that checks the lists against a dense
-// brute-force Schur complement.
+// brute-force Schur complement; the pose-pose lists and tile marks at the end of this file the same way
+// through ba_hostcheck_pose_pose_lists, tests/test_pose_pose_lists.py.
 //
 // Replaces the bookkeeping of the reference's BuildProblem: sorted block insertion into j_pr_ /
 // jt_pr / j_l_ (BundleAdjuster.cpp:1552-1802) and the symbolic side of its block-sparse products
@@ -75,6 +76,8 @@ struct Problem {  // host copies, reference ids
 
 struct U2 { uint32_t x, y; };        // same layout as HIP's uint2
 struct U3 { uint32_t a, b, s; };     // 12 bytes
+struct U4 { uint32_t x, y, z, w; };  // same layout as HIP's uint4
+static const uint32_t kNoPose = 0xffffffffu;  // "no second pose" of a residual, "no other pose" of a scatter entry
 
 inline constexpr int rows_per_obs(int LM) { return LM == 1 ? 6 : (LM == 3 ? 8 : 0); }
 inline constexpr int w_row_offset(int LM) { return LM == 1 ? 4 : 2; }  // first W row inside an observation's rows
@@ -96,6 +99,7 @@ struct Lists {
   uint64_t n_pair_entries = 0;
   uint64_t n_tile_refs = 0;
   uint64_t n_pose_entries = 0;
+  uint32_t n_pp_entries = 0;    // (pose, residual side) entries of the pose-pose scatter (build_pose_pose_lists)
   std::vector<int32_t> pose_opt, lm_opt;
   std::vector<uint32_t> obs_perm;           // sorted position -> residual id
   std::vector<uint32_t> lm_ptr;             // [L+1]
@@ -108,7 +112,8 @@ struct Lists {
   std::vector<uint32_t> pose_ptr;           // [Pact+1]
   std::vector<uint32_t> pose_mid;           // [Pact]  first Schur term of the pose
   std::vector<U3> pose_ent;
-  std::vector<uint8_t> tile_nz;             // nt x nt, symmetric: tiles the projection part of S touches (+ diagonal)
+  std::vector<uint8_t> tile_nz;             // nt x nt, symmetric: tiles the projection part of S touches (+ diagonal);
+                                            // mark_pose_pose_tiles adds the rest of the pattern of S
 };
 
 inline unsigned structure_threads() {
@@ -125,6 +130,53 @@ inline uint32_t natural_pose_opt(const Problem& pb, std::vector<int32_t>& pose_o
   for (uint32_t p = 0; p < pb.num_poses; ++p)
     if (pb.pose_active[p]) pose_opt[p] = (int32_t)n++;
   return n;
+}
+
+// ---- tile pattern of S: nt x nt bytes, symmetric ---------------------------------------------------
+// every tile the D x D block (pose opt id pi, pose opt id pj) overlaps, and its mirror image
+inline void mark_block_tiles(std::vector<uint8_t>& tile_nz, uint32_t nt, uint32_t D, uint32_t pi, uint32_t pj) {
+  const uint32_t r0 = pi * D / 64, r1 = (pi * D + D - 1) / 64;
+  const uint32_t c0 = pj * D / 64, c1 = (pj * D + D - 1) / 64;
+  for (uint32_t r = r0; r <= r1; ++r)
+    for (uint32_t c = c0; c <= c1; ++c) { tile_nz[(size_t)r * nt + c] = 1; tile_nz[(size_t)c * nt + r] = 1; }
+}
+// the diagonal D x D blocks and the tile diagonal (padding identity) are always present
+inline void mark_diagonal_tiles(std::vector<uint8_t>& tile_nz, uint32_t nt, uint32_t D, uint32_t Pact) {
+  for (uint32_t p = 0; p < Pact; ++p) mark_block_tiles(tile_nz, nt, D, p, p);
+  for (uint32_t t = 0; t < nt; ++t) tile_nz[(size_t)t * nt + t] = 1;
+}
+// calibration border: rows np .. n - 1 are dense (every pose with a projection residual couples to
+// the calibration unknowns, BundleAdjuster.cpp:501-518); call only with n > np
+inline void mark_calibration_border(std::vector<uint8_t>& tile_nz, uint32_t nt, uint32_t np, uint32_t n) {
+  for (uint32_t r = np / 64; r <= (n - 1) / 64; ++r)
+    for (uint32_t c = 0; c <= r; ++c) { tile_nz[(size_t)r * nt + c] = 1; tile_nz[(size_t)c * nt + r] = 1; }
+}
+
+// The pose couplings that are not projections: fn(pose id a, pose id b) for every binary residual, every
+// inertial residual and every pair k2 <= k (the diagonal included) of every dense-prior clique
+// (prior q: prior_pose[prior_ptr[q] .. prior_ptr[q + 1])).  Unary residuals couple nothing.  Ids come as the
+// caller gave them, unchecked; whether a pose is active, and what a pair of one pose means, is the caller's filter.
+template <class Fn>
+inline void for_each_pose_coupling(const Problem& pb, uint32_t num_priors, const uint32_t* prior_ptr,
+                                   const uint32_t* prior_pose, Fn&& fn) {
+  for (uint32_t i = 0; i < pb.num_binary; ++i) fn(pb.bin_p1[i], pb.bin_p2[i]);
+  for (uint32_t i = 0; i < pb.num_imu; ++i) fn(pb.imu_p1[i], pb.imu_p2[i]);
+  for (uint32_t q = 0; q < num_priors; ++q)
+    for (uint32_t k = prior_ptr[q]; k < prior_ptr[q + 1]; ++k)
+      for (uint32_t k2 = prior_ptr[q]; k2 <= k; ++k2) fn(prior_pose[k], prior_pose[k2]);
+}
+
+// Group pairs (a << 32 | b, a < b) of those couplings, appended to `edges` in enumeration order, duplicates kept:
+// both poses known and active, their groups (natural opt id / G) different.  With host_group_edges / the
+// device's list this is the group graph the pose ordering works on (ordering.h: group_graph_csr).
+inline void coupling_group_edges(const Problem& pb, uint32_t num_priors, const uint32_t* prior_ptr,
+                                 const uint32_t* prior_pose, const std::vector<int32_t>& natural_opt, uint32_t G,
+                                 std::vector<uint64_t>& edges) {
+  for_each_pose_coupling(pb, num_priors, prior_ptr, prior_pose, [&](uint32_t p1, uint32_t p2) {
+    if (p1 >= pb.num_poses || p2 >= pb.num_poses || natural_opt[p1] < 0 || natural_opt[p2] < 0) return;
+    const uint32_t a = (uint32_t)natural_opt[p1] / G, b = (uint32_t)natural_opt[p2] / G;
+    if (a != b) edges.push_back((uint64_t)std::min(a, b) << 32 | std::max(a, b));
+  });
 }
 
 // Group pairs (a << 32 | b, a < b) of the projection part of S: two active poses whose groups
@@ -528,19 +580,76 @@ inline bool build_lists(const Problem& pb, int LM, int D, Lists& st, std::string
       }
     }
   }
-  // the diagonal D x D blocks (and the padding identity) are always present
-  {
-    auto mark = [&](uint32_t pi, uint32_t pj) {
-      const uint32_t r0 = pi * D / 64, r1 = (pi * D + D - 1) / 64;
-      const uint32_t c0 = pj * D / 64, c1 = (pj * D + D - 1) / 64;
-      for (uint32_t r = r0; r <= r1; ++r)
-        for (uint32_t c = c0; c <= c1; ++c) { st.tile_nz[(size_t)r * nt + c] = 1; st.tile_nz[(size_t)c * nt + r] = 1; }
-    };
-    for (uint32_t p = 0; p < st.Pact; ++p) mark(p, p);
-    for (uint32_t t = 0; t < nt; ++t) st.tile_nz[(size_t)t * nt + t] = 1;
-  }
+  mark_diagonal_tiles(st.tile_nz, nt, (uint32_t)D, st.Pact);
   mark_stage("pose terms");
   return true;
+}
+
+// ---- pose-pose residuals ----------------------------------------------------------------------------
+// Residual slots [unary | binary | imu] and, per active pose j, the entries that k_pp_scatter (one workgroup
+// per pose: block-row j of the lower storage of S) walks in slot order:
+//   (slot, side, other, 0)   side 0: j is the residual's first pose (adds H11, g1), side 1: its second (H22, g2);
+//                            other: opt id of the residual's other pose, if that pose is active — the kernel adds
+//                            H12 (side 1: transposed) to block (j, other) when other < j — else kNoPose.
+// A residual with p1 == p2 yields ONE side-0 entry without an other pose (H11 and g1 only), one
+// whose poses are both inactive none.
+struct PosePoseLists {
+  std::vector<uint32_t> res_p1, res_p2;   // [nres] pose ids; res_p2: kNoPose for a unary residual
+  std::vector<uint32_t> pp_ptr;           // [Pact+1]
+  std::vector<U4> pp_ent;                 // [st.n_pp_entries]
+};
+
+// Reads st.P / st.Pact / st.pose_opt (build_lists or the device builder), sets st.n_pp_entries.
+inline bool build_pose_pose_lists(const Problem& pb, Lists& st, PosePoseLists& pp, std::string& err) {
+  const uint32_t nu = pb.num_unary, nbn = pb.num_binary, ni = pb.num_imu, nres = nu + nbn + ni;
+  st.n_pp_entries = 0;
+  pp.res_p1.assign(nres, 0);
+  pp.res_p2.assign(nres, kNoPose);
+  for (uint32_t i = 0; i < nu; ++i) pp.res_p1[i] = pb.un_pose[i];
+  for (uint32_t i = 0; i < nbn; ++i) { pp.res_p1[nu + i] = pb.bin_p1[i]; pp.res_p2[nu + i] = pb.bin_p2[i]; }
+  for (uint32_t i = 0; i < ni; ++i) { pp.res_p1[nu + nbn + i] = pb.imu_p1[i]; pp.res_p2[nu + nbn + i] = pb.imu_p2[i]; }
+  for (uint32_t s = 0; s < nres; ++s)
+    if (pp.res_p1[s] >= st.P || (pp.res_p2[s] != kNoPose && pp.res_p2[s] >= st.P)) {
+      err = "pose-pose residual references an unknown pose";
+      return false;
+    }
+  // opt ids of the two sides of slot s; the second side only if it is another pose
+  auto sides = [&](uint32_t s, int32_t& o1, int32_t& o2) {
+    o1 = st.pose_opt[pp.res_p1[s]];
+    const bool two = pp.res_p2[s] != kNoPose && pp.res_p2[s] != pp.res_p1[s];
+    o2 = two ? st.pose_opt[pp.res_p2[s]] : -1;
+  };
+  pp.pp_ptr.assign((size_t)st.Pact + 1, 0);
+  for (uint32_t s = 0; s < nres; ++s) {
+    int32_t o1, o2;
+    sides(s, o1, o2);
+    if (o1 >= 0) pp.pp_ptr[o1 + 1]++;
+    if (o2 >= 0) pp.pp_ptr[o2 + 1]++;
+  }
+  for (uint32_t p = 0; p < st.Pact; ++p) pp.pp_ptr[p + 1] += pp.pp_ptr[p];
+  st.n_pp_entries = pp.pp_ptr[st.Pact];
+  pp.pp_ent.assign(st.n_pp_entries, U4{0, 0, 0, 0});
+  std::vector<uint32_t> cur(pp.pp_ptr.begin(), pp.pp_ptr.end() - 1);
+  for (uint32_t s = 0; s < nres; ++s) {
+    int32_t o1, o2;
+    sides(s, o1, o2);
+    if (o1 >= 0) pp.pp_ent[cur[o1]++] = {s, 0, o2 >= 0 ? (uint32_t)o2 : kNoPose, 0};
+    if (o2 >= 0) pp.pp_ent[cur[o2]++] = {s, 1, o1 >= 0 ? (uint32_t)o1 : kNoPose, 0};
+  }
+  return true;
+}
+
+// What the non-projection terms add to the tile pattern of S (st.tile_nz as build_lists or the device builder
+// left it): every block between two active poses that for_each_pose_coupling names, and the calibration border.
+// Pose ids must be known (build_pose_pose_lists and the prior upload have checked them).
+inline void mark_pose_pose_tiles(const Problem& pb, uint32_t num_priors, const uint32_t* prior_ptr,
+                                 const uint32_t* prior_pose, int D, Lists& st) {
+  const uint32_t nt = st.ld / 64;
+  for_each_pose_coupling(pb, num_priors, prior_ptr, prior_pose, [&](uint32_t p1, uint32_t p2) {
+    const int32_t o1 = st.pose_opt[p1], o2 = st.pose_opt[p2];
+    if (o1 >= 0 && o2 >= 0) mark_block_tiles(st.tile_nz, nt, (uint32_t)D, (uint32_t)o1, (uint32_t)o2);
+  });
+  if (st.K) mark_calibration_border(st.tile_nz, nt, st.np, st.n);
 }
 
 }  // namespace bae

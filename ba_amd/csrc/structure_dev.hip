@@ -654,13 +654,7 @@ int build_lists_device(Engine* e, const std::function<void(const char*)>& stage)
     BAE_HIP(hipGetLastError());
     BAE_HIP(hipStreamSynchronize(e->stream));
   }
-  // the diagonal D x D blocks (and the padding identity) are always present in the tile pattern
-  for (uint32_t p = 0; p < st.Pact; ++p) {
-    const uint32_t r0 = p * D / 64, r1 = (p * D + D - 1) / 64;
-    for (uint32_t r = r0; r <= r1; ++r)
-      for (uint32_t c = r0; c <= r1; ++c) { st.tile_nz[(size_t)r * nt + c] = 1; st.tile_nz[(size_t)c * nt + r] = 1; }
-  }
-  for (uint32_t t = 0; t < nt; ++t) st.tile_nz[(size_t)t * nt + t] = 1;
+  mark_diagonal_tiles(st.tile_nz, nt, (uint32_t)D, st.Pact);
   if (stage) stage("pose terms");
   return 0;
 }
