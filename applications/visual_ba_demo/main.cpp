@@ -28,6 +28,11 @@
 //                                           columns), printed as a 12 x 12 block with the passes and the time
 //   visual_ba_demo --lm [lambda0]           Options::use_levenberg_marquardt (initial damping lambda0, default 1e-4): damped
 //                                           steps accepted by gain ratio; prints lambda and rho of every iteration
+//   visual_ba_demo --triangulate [iters]    the landmarks start as directions only (w = 0: the bearing of the reference
+//                                           pixel, no depth; with LmSize 3 a point at a fixed wrong range), are
+//                                           triangulated and refined with the poses held fixed (TriangulateLandmarks,
+//                                           at most iters steps per landmark, default 20), the counts per status are
+//                                           printed, then the solve runs as usual
 //   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
 //                                           GetLandmarkCovariance: selected inverse of the reduced system), then
@@ -55,7 +60,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false, lm = false; double pcg_tol = 1e-6, lm_lambda0 = 1e-4; unsigned pcg_coarse = 0, weakest_modes = 0; int joint_a = -1, joint_b = -1; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false, lm = false; double pcg_tol = 1e-6, lm_lambda0 = 1e-4; unsigned pcg_coarse = 0, weakest_modes = 0; int joint_a = -1, joint_b = -1, triangulate = -1; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -205,6 +210,13 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
       apply(gt[ref] * mount0, xs, xw);
       for (int k = 0; k < 3; ++k) Xp[k] = xw[k];
     }
+    if (shard.triangulate >= 0) {
+      // no depth: the bearing from the reference pose's centre (LmSize 1: a pure direction), or 5 units along it
+      double d[3] = {Xp[0] - gt[ref].t[0], Xp[1] - gt[ref].t[1], Xp[2] - gt[ref].t[2]};
+      const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+      for (int k = 0; k < 3; ++k) Xp[k] = BA::kLmDim == 1 ? d[k] / len : gt[ref].t[k] + 5.0 * d[k] / len;
+      Xp[3] = BA::kLmDim == 1 ? 0.0 : 1.0;
+    }
     // landmark shards: every rank draws the same scene, a rank keeps the landmarks l with l mod ranks == rank
     const bool mine = (l % shard.ranks) == shard.rank;
     const uint32_t lm = mine ? adjuster.AddLandmark(ba::Vector4t({Xp[0], Xp[1], Xp[2], Xp[3]}), ref, 0, true) : 0;
@@ -215,6 +227,16 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
     }
   }
   std::printf("poses %u landmarks %u residuals %d\n", adjuster.GetNumPoses(), adjuster.GetNumLandmarks(), n_res);
+  if (shard.triangulate >= 0) {
+    ba::TriangulationOptions to;
+    to.max_iterations = shard.triangulate;
+    std::vector<ba::TriangulationResult> tr;
+    if (!adjuster.TriangulateLandmarks({}, to, &tr)) { std::printf("triangulation refused\n"); return 2; }
+    unsigned count[6] = {0, 0, 0, 0, 0, 0};
+    for (const ba::TriangulationResult& r : tr) count[r.status >= 0 && r.status < 6 ? r.status : 5]++;
+    std::printf("triangulated %zu landmarks: ok %u, not converged %u, too few views %u, low parallax %u, behind a camera %u, failed %u\n",
+                tr.size(), count[0], count[1], count[2], count[3], count[4], count[5]);
+  }
   adjuster.Solve(1);
   if (shard.pcg) print_pcg(1);
   if (shard.lm) print_lm(1);
@@ -397,6 +419,12 @@ int main(int argc, char** argv) {
     if (std::strcmp(argv[i], "--lm") == 0) {
       shard.lm = true;
       if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.lm_lambda0 = std::atof(argv[i + 1]);
+      else --i;
+      continue;
+    }
+    if (std::strcmp(argv[i], "--triangulate") == 0) {
+      shard.triangulate = 20;
+      if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.triangulate = std::atoi(argv[i + 1]);
       else --i;
       continue;
     }

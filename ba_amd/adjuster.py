@@ -78,6 +78,7 @@ SYMBOLS = [
     "ba_adjuster_solve_with_pcg", "ba_adjuster_get_joint_pose_covariance_iterative", "ba_adjuster_get_pcg_panel_stats",
     "ba_adjuster_get_pose_pose_leverages", "ba_adjuster_get_pose_pose_leverage",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
+    "ba_adjuster_triangulate_landmarks",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
     "ba_adjuster_set_levenberg_marquardt", "ba_adjuster_get_damping", "ba_adjuster_get_levenberg_marquardt_state",
 ]
@@ -410,6 +411,24 @@ class BundleAdjuster:
                                                H.ctypes.data_as(dp), b.ctypes.data_as(dp), C.byref(c), C.byref(dr))
         return {"pose_ids": ids[:n], "x0": x0[:n], "H": H[:n * D, :n * D], "b": b[:n * D], "c": c.value,
                 "dropped_projection": dr.value}
+
+    def TriangulateLandmarks(self, ids=None, **options):
+        """ba::BundleAdjuster::TriangulateLandmarks, before or between Solve() calls: ids None = every landmark; options:
+        the fields of hipapi.TriangulationOptions.  Returns (ok, results n x 8); ok False when refused (see stderr)."""
+        o = hipapi.TriangulationOptions(**options)
+        u32p = C.POINTER(C.c_uint32)
+        if ids is None:
+            n, idp = self.GetNumLandmarks(), None
+        else:
+            ida = np.ascontiguousarray(ids, dtype=np.uint32)
+            n, idp = len(ida), ida.ctypes.data_as(u32p)
+        res = np.zeros((max(n, 1), 8))
+        rc = self.L.ba_adjuster_triangulate_landmarks(self.h, n, idp, C.byref(o), res.ctypes.data_as(C.POINTER(C.c_double)))
+        return rc == 0, res[:n]
+
+    def engine_landmarks(self):
+        """ba_hip_get_landmarks of the adjuster's engine"""
+        return self.engine().get_landmarks(self.GetNumLandmarks())
 
     def AddDensePrior(self, pose_ids, prior):
         """ba::BundleAdjuster::AddDensePrior: pose_ids of this problem, in the order of prior["pose_ids"]."""

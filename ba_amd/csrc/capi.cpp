@@ -69,6 +69,7 @@ struct Iface {
   virtual void marginalization(uint32_t* ids, double* x0, double* H, double* b, double* c, uint32_t* dropped) const = 0;
   virtual uint32_t add_dense_prior(uint32_t k, const uint32_t* ids, const double* x0, const double* H, const double* b,
                                    double c) = 0;
+  virtual int triangulate(uint32_t n, const uint32_t* ids, const ba_hip_triangulation_options* o, double* result8) = 0;
 };
 
 template <int LM, int PD, bool TVS = false, int CS = 0>
@@ -254,6 +255,22 @@ struct Impl : Iface {
     if (b) std::copy(marg.b.begin(), marg.b.end(), b);
     if (c) *c = marg.c;
     if (dropped) *dropped = marg.dropped_projection;
+  }
+  int triangulate(uint32_t n, const uint32_t* ids, const ba_hip_triangulation_options* o, double* result8) override {
+    ba::TriangulationOptions t;
+    if (o) {
+      t.linear_init = o->linear_init != 0; t.max_iterations = o->max_iterations; t.write_back = o->write_back != 0;
+      t.lambda0 = o->lambda0; t.gradient_tolerance = o->gradient_tolerance; t.step_tolerance = o->step_tolerance;
+      t.min_parallax = o->min_parallax; t.huber_width = o->huber_width;
+    }
+    std::vector<ba::TriangulationResult> r;
+    if (!ba.TriangulateLandmarks(ids ? std::vector<uint32_t>(ids, ids + n) : std::vector<uint32_t>(), t, &r)) return 1;
+    for (size_t i = 0; result8 && i < r.size(); ++i) {
+      double* q = result8 + 8 * i;
+      q[0] = r[i].status; q[1] = r[i].observations; q[2] = r[i].iterations; q[3] = r[i].cost_start; q[4] = r[i].cost_end;
+      q[5] = r[i].parallax; q[6] = r[i].min_depth; q[7] = r[i].gradient;
+    }
+    return 0;
   }
   uint32_t add_dense_prior(uint32_t k, const uint32_t* ids, const double* x0, const double* H, const double* b,
                            double c) override {
@@ -558,6 +575,11 @@ uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t*
                                      const double* H, const double* b, double c) {
   if (!k || !pose_ids || !x0_16 || !H || !b) return UINT32_MAX;
   return a->p->add_dense_prior(k, pose_ids, x0_16, H, b, c);
+}
+int ba_adjuster_triangulate_landmarks(ba_adjuster* a, uint32_t n, const uint32_t* landmark_ids,
+                                      const ba_hip_triangulation_options* o, double* result8) {
+  if (landmark_ids && !n) return 1;
+  return a->p->triangulate(n, landmark_ids, o, result8);
 }
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) { a->p->set_allreduce(fn, ctx, rank, nranks); }
 void ba_adjuster_set_communicator(ba_adjuster* a, const void* id128, int rank, int nranks, int distributed_solve) { a->p->set_communicator(id128, rank, nranks, distributed_solve); }

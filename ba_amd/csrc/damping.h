@@ -66,15 +66,19 @@ BA_DAMP_HD inline void damp_term(double delta, double g, double d, double lambda
 struct DampState {
   double lambda, nu;
 };
-inline double damp_keep_lambda(double lambda) { return std::min(std::max(lambda, kDampLambdaMin), kDampLambdaMax); }
-inline double damp_gain_ratio(double e_pre, double e_post, double predicted) { return (e_pre - e_post) / predicted; }
+// (std::max and std::min written out, operand for operand, so that the kernels of k_triang.hip can apply the rule too)
+BA_DAMP_HD inline double damp_keep_lambda(double lambda) {
+  const double lo = lambda < kDampLambdaMin ? kDampLambdaMin : lambda;
+  return kDampLambdaMax < lo ? kDampLambdaMax : lo;
+}
+BA_DAMP_HD inline double damp_gain_ratio(double e_pre, double e_post, double predicted) { return (e_pre - e_post) / predicted; }
 // Returns whether the step is accepted.  Accepted (rho > 0): lambda <- lambda max(1/3, 1 - (2 rho - 1)^3), nu <- 2;
 // otherwise (a NaN ratio included) lambda <- lambda nu, nu <- 2 nu.
-inline bool damp_update(DampState* s, double rho) {
+BA_DAMP_HD inline bool damp_update(DampState* s, double rho) {
   const bool accept = rho > 0.0;
   if (accept) {
-    const double t = 2.0 * rho - 1.0;
-    s->lambda = damp_keep_lambda(s->lambda * std::max(1.0 / 3.0, 1.0 - t * t * t));
+    const double t = 2.0 * rho - 1.0, third = 1.0 / 3.0, cube = 1.0 - t * t * t;
+    s->lambda = damp_keep_lambda(s->lambda * (third < cube ? cube : third));
     s->nu = 2.0;
   } else {
     s->lambda = damp_keep_lambda(s->lambda * s->nu);

@@ -18,6 +18,7 @@
 #include "chol_launch.h"
 #include "bulk_lists.h"
 #include "damping.h"
+#include "triang.h"
 
 namespace bae {
 
@@ -381,6 +382,18 @@ struct Engine {
     double poses_ms = 0.0, terms_ms = 0.0;   // k_damp_poses of the last linearisation, k_damp_terms of the last solve
   } damp;
 
+  // Landmark triangulation (ba_hip_triangulate_landmarks, triang.h, k_triang.hip).  in_solve: between
+  // ba_hip_begin_solve and ba_hip_end_solve x_w lags behind x_s (LmSize 1), the call is refused.  The work space exists
+  // only once a call was made (ba_hip_release_marginals frees it): mask [L] the selection, early [n_chunks] the waves
+  // that left at once, res [L][8] and xw [L][4] the results by landmark id.
+  bool in_solve = false;
+  struct Tri {
+    DBuf<uint8_t> mask, early;
+    DBuf<double> res, xw;
+    ba_hip_triangulation_stats stats = {};
+    void release() { mask.release(); early.release(); res.release(); xw.release(); }
+  } tri;
+
   // optional per-kernel timing (ba_hip_set_profiling)
   bool profiling = false;
   ba_hip_kernel_stats kstats = {};
@@ -655,6 +668,8 @@ int pcg_panel_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld,
                            const std::vector<uint8_t>& nz, const std::vector<uint32_t>& blk, const std::vector<uint32_t>& blocks,
                            const uint32_t* rowmap, uint32_t m, const double* B, double* X, const ba_hip_pcg_options& opt,
                            int* status);
+// triangulation (k_triang.hip): the selection in tri.mask is on the device; fills tri.res / tri.xw for every landmark
+int launch_triangulate(Engine* e, const TriOptions& o);
 int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& lmask, double tol, double* dev_ms);
 
 }  // namespace bae

@@ -881,6 +881,7 @@ int ba_hip_set_gravity(ba_hip_engine* h, const double g3[3]) {
 int ba_hip_finalize(ba_hip_engine* h) {
   BA_ENTRY_DEVICE(h);
   e->held.finalize_begins();
+  e->in_solve = false;
   Problem& pb = e->prob;
   if (pb.pose_active.size() != pb.num_poses) pb.pose_active.assign(pb.num_poses, 1);
   if (pb.lm_active.size() != pb.num_lms) pb.lm_active.assign(pb.num_lms, 1);
@@ -910,6 +911,7 @@ int ba_hip_get_conditioning_error(ba_hip_engine* h, double* proj_sq_sum) {
 int ba_hip_begin_solve(ba_hip_engine* h) {
   BA_ENTRY_FINAL(h);
   e->held.solve_begins();
+  e->in_solve = true;   // until ba_hip_end_solve: x_w lags behind x_s (ba_hip_triangulate_landmarks refuses)
   e->err_cache_off = getenv("BA_HIP_NO_ERR_CACHE") != nullptr;
   if (!e->prob.pose_cam_params.empty() && e->prob.pose_cam_params.size() != 4 * (size_t)e->prob.num_poses)
     return e->fail_msg("per-pose camera parameters: one [fx,fy,u0,v0] per pose expected");
@@ -1298,6 +1300,7 @@ int ba_hip_end_solve(ba_hip_engine* h) {
   int rc = launch_end_solve(e);
   if (rc) return rc;
   BAE_HIP(hipStreamSynchronize(e->stream));
+  e->in_solve = false;
   return 0;
 }
 

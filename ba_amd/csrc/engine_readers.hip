@@ -227,6 +227,7 @@ int ba_hip_release_marginals(ba_hip_engine* h) {
   marginals_release(e);
   jointcov_release(e);
   factor_solve_release(e);
+  e->tri.release();
   return 0;
 }
 
@@ -630,6 +631,79 @@ int ba_hip_get_pcg_panel_columns(ba_hip_engine* h, uint32_t m, uint32_t* iterati
     if (rel_residual_true) rel_residual_true[j] = c.bb > 0.0 ? sqrt(c.rr_true / c.bb) : 0.0;
   }
   return 0;
+}
+
+// ---- landmark triangulation and per-landmark refinement, poses held fixed (k_triang.hip, triang.h) ----
+int ba_hip_triangulate_landmarks(ba_hip_engine* h, uint32_t n, const uint32_t* lm_ids, const ba_hip_triangulation_options* o,
+                                 double* result8, double* x_w4) {
+  BA_ENTRY_FINAL(h);
+  BA_ASK(guard_triangulate(e->held, guard_facts(e), e->st.K != 0 || e->calib_dim != 0, e->lm_dim, e->in_solve));
+  // (the cameras as ba_hip_begin_solve takes them)
+  if (!e->prob.pose_cam_params.empty() && e->prob.pose_cam_params.size() != 4 * (size_t)e->prob.num_poses)
+    return e->fail_msg("per-pose camera parameters: one [fx,fy,u0,v0] per pose expected");
+  if (!e->prob.pose_cam_params.empty() && e->has_fov)
+    return e->fail_msg("per-pose camera parameters are offered for LinearCamera rigs only");
+  TriOptions t;   // the defaults of the header
+  if (o) {
+    t.linear_init = o->linear_init != 0; t.max_iterations = o->max_iterations; t.write_back = o->write_back != 0;
+    t.lambda0 = o->lambda0; t.gradient_tolerance = o->gradient_tolerance; t.step_tolerance = o->step_tolerance;
+    t.min_parallax = o->min_parallax; t.huber_width = o->huber_width;
+  }
+  const Structure& st = e->st;
+  const uint32_t L = st.L;
+  BA_ASK(triangulation_ok({t.max_iterations, t.lambda0, t.gradient_tolerance, t.step_tolerance, t.min_parallax, t.huber_width},
+                          L, n, lm_ids));
+  Engine::Tri& w = e->tri;
+  w.stats = ba_hip_triangulation_stats();
+  w.stats.landmarks = n;
+  if (L == 0) return 0;
+  std::vector<uint8_t> mask(L, lm_ids ? 0 : 1);
+  for (uint32_t i = 0; lm_ids && i < n; ++i) mask[lm_ids[i]] = 1;
+  BAE_HIP(w.mask.alloc(L));
+  BAE_HIP(w.early.alloc(std::max<size_t>(st.n_chunks, 1)));
+  BAE_HIP(w.res.alloc((size_t)L * kTriResult));
+  BAE_HIP(w.xw.alloc((size_t)L * 4));
+  Events<2> ev;
+  BAE_HIP(ev.create());
+  BAE_HIP(ev.record(0, e->stream));
+  BAE_HIP(hipMemcpyAsync(w.mask.p, mask.data(), L, hipMemcpyHostToDevice, e->stream));
+  int rc = launch_pose_prep(e);
+  if (!rc) rc = launch_triangulate(e, t);
+  if (rc) return rc;
+  BAE_HIP(ev.record(1, e->stream));
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  std::vector<double> res((size_t)L * kTriResult), xw((size_t)L * 4);
+  std::vector<uint8_t> early(st.n_chunks);
+  BAE_HIP(hipMemcpy(res.data(), w.res.p, res.size() * sizeof(double), hipMemcpyDeviceToHost));
+  BAE_HIP(hipMemcpy(xw.data(), w.xw.p, xw.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (st.n_chunks && st.O) BAE_HIP(hipMemcpy(early.data(), w.early.p, early.size(), hipMemcpyDeviceToHost));
+  w.stats.device_ms = ev.ms(0, 1);
+  w.stats.waves = st.O ? st.n_chunks : 0;
+  for (uint8_t v : early) w.stats.waves_early += v ? 1 : 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const size_t l = lm_ids ? lm_ids[i] : i;
+    const double* r = &res[l * kTriResult];
+    const int status = (int)r[0];
+    if (status >= 0 && status < kTriStatusCount) w.stats.count[status] += 1;
+    // (what tri_accepted decided on the device: OK, or NOT_CONVERGED whose cost fell)
+    if (status == kTriOk || (status == kTriNotConverged && (t.linear_init ? r[4] <= r[3] : r[4] < r[3]))) w.stats.written += 1;
+    if (result8) std::copy(r, r + kTriResult, result8 + (size_t)i * kTriResult);
+    if (x_w4) std::copy(&xw[l * 4], &xw[l * 4] + 4, x_w4 + (size_t)i * 4);
+  }
+  if (!t.write_back) { w.stats.written = 0; return 0; }
+  // accepted rows hold the new coordinates, every other row the bits it had
+  BAE_HIP(hipMemcpyAsync(e->lm_xw.p, w.xw.p, (size_t)L * 4 * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  if (e->lm_dim == 3)
+    BAE_HIP(hipMemcpyAsync(e->lm_x[e->cur].p, w.xw.p, (size_t)L * 4 * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+  else if ((rc = launch_begin_solve(e)))   // x_s from the new x_w
+    return rc;
+  e->held.solve_begins();   // the landmarks moved: the linearisation and the cached errors are those of other coordinates
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  return 0;
+}
+int ba_hip_get_triangulation_stats(ba_hip_engine* h, ba_hip_triangulation_stats* out) {
+  BA_ENTRY_HOST(h);
+  return put_stats(e, __func__, out, e->tri.stats);
 }
 
 int ba_hip_dense_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, double* x) {

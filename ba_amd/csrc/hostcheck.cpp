@@ -1367,3 +1367,155 @@ extern "C" uint64_t ba_hostcheck_coupling_group_edges(int D, uint32_t P, const u
   std::copy(out.begin(), out.begin() + std::min<uint64_t>(out.size(), cap), edges);
   return out.size();
 }
+
+// ---- landmark triangulation (triang.h) --------------------------------------------------------------------------
+#include "triang.h"
+
+// The rules of triang.h on the host, landmark by landmark, sums in observation order.  The tables are built as
+// k_pose_prep builds them: T_ws = T_wp T_vs with the quaternion product renormalised, T_sw its inverse.
+//   poses7 [P][7] (t, q xyzw), cam_params4 [C][4], cam_tvs7 [C][7], cam_model [C] (0 pinhole, 1 FOV; may be NULL),
+//   cam_w [C] (may be NULL), pose_cam4 [P][4] per-pose intrinsics (may be NULL)
+//   lm_ptr [L + 1] over the observations sorted by landmark; obs_pose, obs_cam, obs_z [O][2], obs_w0 [O]
+//   x_w [L][4], ref_pose, ref_cam [L] (read with LM == 1); mask [L] (may be NULL: every landmark)
+//   opts: linear_init, max_iterations, write_back, lambda0, gradient_tolerance, step_tolerance, min_parallax, huber_width
+//   res [L][8] (status -1 in rows the mask leaves out), xw_out [L][4] as ba_hip_triangulate_landmarks fills x_w4,
+//   final (may be NULL) [L][10]: lambda, then the unique entries of V (LM (LM + 1) / 2) and b_l (LM) at the end point
+// Returns 0, 1 with the message of requests.h (triangulation_ok on the ids of the mask's complement is the caller's
+// business: ids / n are checked here when ids is not NULL), -1 for LM other than 1 or 3.
+template <int LM>
+static void hostcheck_triangulate_lm(uint32_t C, const std::vector<bad::Rt>& tsw, const std::vector<bad::Rt>& tws,
+                                     const double* cam_params4, const int32_t* cam_model, const double* cam_w,
+                                     const double* pose_cam4, uint32_t L, const uint32_t* lm_ptr, const uint32_t* obs_pose,
+                                     const uint32_t* obs_cam, const double* obs_z, const double* obs_w0, const double* x_w,
+                                     const uint32_t* ref_pose, const uint32_t* ref_cam, const uint8_t* mask,
+                                     const bae::TriOptions& opt, double* res, double* xw_out, double* final) {
+  using namespace bae;
+  using namespace bad;
+  constexpr int N = TriSums<LM>::N, NL = TriSums<LM>::NL;
+  for (uint32_t l = 0; l < L; ++l) {
+    double* r = res + (size_t)l * kTriResult;
+    for (int i = 0; i < 4; ++i) xw_out[(size_t)l * 4 + i] = x_w[(size_t)l * 4 + i];
+    if (final) for (int i = 0; i < 10; ++i) final[(size_t)l * 10 + i] = 0.0;
+    tri_result_none(r);
+    if (mask && !mask[l]) { r[0] = -1.0; continue; }
+    const uint32_t a0 = lm_ptr[l], a1 = lm_ptr[l + 1], k = a1 - a0;
+    if (k == 0) continue;
+    Rt t_sw_r{}, t_ws_r{};
+    if (LM == 1) { t_sw_r = tsw[(size_t)ref_pose[l] * C + ref_cam[l]]; t_ws_r = tws[(size_t)ref_pose[l] * C + ref_cam[l]]; }
+    std::vector<TriObs> obs(k);
+    for (uint32_t a = a0; a < a1; ++a) {
+      TriObs& o = obs[a - a0];
+      const uint32_t pm = obs_pose[a], cm = obs_cam[a];
+      const double* ip = pose_cam4 ? pose_cam4 + (size_t)pm * 4 : cam_params4 + (size_t)cm * 4;
+      o.cam = {ip[0], ip[1], ip[2], ip[3], cam_w ? cam_w[cm] : 0.0, cam_model && cam_model[cm] ? 1 : 0};
+      const Rt& t_sw_m = tsw[(size_t)pm * C + cm];
+      o.T = LM == 1 ? compose(t_sw_m, t_ws_r) : t_sw_m;
+      o.z[0] = obs_z[2 * (size_t)a]; o.z[1] = obs_z[2 * (size_t)a + 1];
+      o.w0 = obs_w0[a];
+    }
+    double xv[3], rho;
+    tri_held<LM>(x_w + (size_t)l * 4, t_sw_r, xv, &rho);
+    V3 c0 = v3(0.0, 0.0, 0.0), d0 = v3(xv[0], xv[1], xv[2]);
+    if (LM == 3) tri_centre_bearing(obs[0], &c0, &d0);
+    double par = 0.0, base2 = 0.0;
+    for (const TriObs& o : obs) {
+      V3 c, d;
+      tri_centre_bearing(o, &c, &d);
+      par = tri_max(par, tri_angle(d0, d));
+      base2 = tri_max(base2, tri_dist2(c0, c));
+    }
+    if (opt.linear_init) {
+      double lin[NL] = {};
+      for (const TriObs& o : obs) {
+        double v[NL];
+        tri_linear_terms<LM>(o, xv, v);
+        for (int i = 0; i < NL; ++i) lin[i] += v[i];
+      }
+      tri_linear_solve<LM>(lin, xv, &rho);
+    }
+    auto sums_at = [&](const double* txv, double trho, bool guard, double* tot, double* depth) {
+      for (int i = 0; i < N; ++i) tot[i] = 0.0;
+      double dmin = tri_inf();
+      for (const TriObs& o : obs) {
+        double v[N];
+        const double dep = tri_eval<LM>(o, txv, trho, opt.huber_width, guard, v);
+        for (int i = 0; i < N; ++i) tot[i] += v[i];
+        dmin = tri_min(dmin, dep);
+      }
+      if (depth) *depth = dmin;
+    };
+    TriLm<LM> m;
+    double tot[N], depth;
+    sums_at(xv, rho, false, tot, &depth);
+    tri_begin<LM>(&m, opt, LM == 3 ? xv : &rho, tot, depth, par, base2, dot(c0, c0), k);
+    while (m.active) {
+      double txv[3], trho;
+      tri_trial<LM>(m, xv, rho, txv, &trho);
+      sums_at(txv, trho, true, tot, nullptr);
+      tri_step<LM>(&m, opt, tot);
+    }
+    double fxv[3], frho = LM == 3 ? rho : m.x[0];
+    for (int i = 0; i < 3; ++i) fxv[i] = LM == 3 ? m.x[i] : xv[i];
+    double depth_end = m.depth;
+    if (m.status == kTriOk || m.status == kTriNotConverged) {
+      depth_end = tri_inf();
+      for (const TriObs& o : obs) depth_end = tri_min(depth_end, tri_depth<LM>(o, fxv, frho));
+    }
+    tri_result<LM>(m, k, depth_end, r);
+    if (tri_accepted<LM>(m, opt)) tri_world<LM>(fxv, frho, t_ws_r, xw_out + (size_t)l * 4);
+    if (final) {
+      final[(size_t)l * 10] = m.ds.lambda;
+      for (int i = 0; i < N - 1; ++i) final[(size_t)l * 10 + 1 + i] = m.cur[i];
+    }
+  }
+}
+
+extern "C" int ba_hostcheck_triangulate(int LM, uint32_t P, const double* poses7, uint32_t C, const double* cam_params4,
+                                        const double* cam_tvs7, const int32_t* cam_model, const double* cam_w,
+                                        const double* pose_cam4, uint32_t L, const uint32_t* lm_ptr, const uint32_t* obs_pose,
+                                        const uint32_t* obs_cam, const double* obs_z, const double* obs_w0, const double* x_w,
+                                        const uint32_t* ref_pose, const uint32_t* ref_cam, const uint8_t* mask, uint32_t n_ids,
+                                        const uint32_t* ids, const double* opts8, double* res, double* xw_out, double* final,
+                                        char* msg, uint32_t cap) {
+  using namespace bae;
+  using namespace bad;
+  if (LM != 1 && LM != 3) return -1;
+  TriOptions opt;
+  opt.linear_init = opts8[0] != 0.0; opt.max_iterations = (int)opts8[1]; opt.write_back = opts8[2] != 0.0;
+  opt.lambda0 = opts8[3]; opt.gradient_tolerance = opts8[4]; opt.step_tolerance = opts8[5]; opt.min_parallax = opts8[6];
+  opt.huber_width = opts8[7];
+  const std::string bad_request =
+      triangulation_ok({opt.max_iterations, opt.lambda0, opt.gradient_tolerance, opt.step_tolerance, opt.min_parallax,
+                        opt.huber_width}, L, ids ? n_ids : L, ids);
+  if (put_message(bad_request, msg, cap)) return 1;
+  std::vector<Rt> tsw((size_t)P * C), tws((size_t)P * C);
+  for (uint32_t p = 0; p < P; ++p)
+    for (uint32_t c = 0; c < C; ++c) {
+      const double* s = poses7 + (size_t)p * 7;
+      const double* cm = cam_tvs7 + (size_t)c * 7;
+      Rt wp;
+      wp.R = quat_to_rot(s[3], s[4], s[5], s[6]);
+      wp.t = v3(s[0], s[1], s[2]);
+      double qv[4] = {cm[3], cm[4], cm[5], cm[6]}, qp[4] = {s[3], s[4], s[5], s[6]}, q[4];
+      quat_mul(qp, qv, q);
+      quat_normalize(q);
+      Rt ws;
+      ws.R = quat_to_rot(q[0], q[1], q[2], q[3]);
+      ws.t = mul(wp.R, v3(cm[0], cm[1], cm[2])) + wp.t;
+      tws[(size_t)p * C + c] = ws;
+      tsw[(size_t)p * C + c] = inverse(ws);
+    }
+  std::vector<uint8_t> sel;
+  if (ids) {
+    sel.assign(L, 0);
+    for (uint32_t i = 0; i < n_ids; ++i) sel[ids[i]] = 1;
+    mask = sel.data();
+  }
+  if (LM == 1)
+    hostcheck_triangulate_lm<1>(C, tsw, tws, cam_params4, cam_model, cam_w, pose_cam4, L, lm_ptr, obs_pose, obs_cam, obs_z, obs_w0,
+                                x_w, ref_pose, ref_cam, mask, opt, res, xw_out, final);
+  else
+    hostcheck_triangulate_lm<3>(C, tsw, tws, cam_params4, cam_model, cam_w, pose_cam4, L, lm_ptr, obs_pose, obs_cam, obs_z, obs_w0,
+                                x_w, ref_pose, ref_cam, mask, opt, res, xw_out, final);
+  return 0;
+}

@@ -125,6 +125,41 @@ inline std::string guard_marginalize(const Held& h, const GuardFacts& f, bool ca
   return "";
 }
 
+// ba_hip_triangulate_landmarks: the engine facts first (in_solve: between ba_hip_begin_solve and ba_hip_end_solve, where
+// x_w lags behind x_s), then what the caller's options say, then the ids (each below L, each once)
+struct TriAsk {
+  int max_iterations;
+  double lambda0, gradient_tolerance, step_tolerance, min_parallax, huber_width;
+};
+inline std::string guard_triangulate(const Held& h, const GuardFacts& f, bool calibration, int lm_dim, bool in_solve) {
+  static const std::string m = "ba_hip_triangulate_landmarks: ";
+  if (!h.finalized) return m + kNotFinalized;
+  if (lm_dim == 0) return m + "LmSize 0 has no landmark unknowns";
+  if (calibration) return m + "not offered with calibration unknowns";
+  if (f.hooked || f.sharded || f.dist_solve) return m + "not offered on sharded engines or with the distributed solve";
+  if (in_solve)
+    return m + "not offered inside a Solve, where x_w lags behind the state: call ba_hip_end_solve first (or triangulate "
+               "before ba_hip_begin_solve)";
+  return "";
+}
+inline std::string triangulation_ok(const TriAsk& o, uint32_t L, uint32_t n, const uint32_t* ids) {
+  static const std::string m = "ba_hip_triangulate_landmarks: ";
+  if (o.max_iterations < 0 || o.max_iterations > 64)
+    return m + "max_iterations " + std::to_string(o.max_iterations) + " does not lie in 0 .. 64";
+  // (written so that a NaN is refused too)
+  if (!(o.lambda0 >= 0.0) || !(o.gradient_tolerance >= 0.0) || !(o.step_tolerance >= 0.0) || !(o.min_parallax >= 0.0) ||
+      !(o.huber_width >= 0.0))
+    return m + "lambda0, the tolerances, min_parallax and huber_width must not be negative";
+  if (!ids) return n == L ? "" : m + "with NULL ids n must be the landmark count";
+  std::vector<uint8_t> seen(L, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (ids[i] >= L) return m + "id " + std::to_string(ids[i]) + " is not a landmark (there are " + std::to_string(L) + ")";
+    if (seen[ids[i]]) return m + "landmark " + std::to_string(ids[i]) + " is named twice";
+    seen[ids[i]] = 1;
+  }
+  return "";
+}
+
 // ---- the small shared checks ---------------------------------------------------------------------------------------
 // with NULL ids a request means all `count` of them: `count_name` ends the message
 inline std::string ids_or_all(const char* who, const void* ids, uint32_t n, uint32_t count, const std::string& count_name) {

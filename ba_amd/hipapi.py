@@ -191,6 +191,34 @@ class DampingTerms(C.Structure):
                 ("diag_min", C.c_double), ("diag_max", C.c_double), ("device_ms", C.c_double)]
 
 
+class TriangulationOptions(C.Structure):
+    """ba_hip_triangulation_options, with the header's defaults"""
+    _fields_ = [("linear_init", C.c_int32), ("max_iterations", C.c_int32), ("write_back", C.c_int32), ("reserved", C.c_int32),
+                ("lambda0", C.c_double), ("gradient_tolerance", C.c_double), ("step_tolerance", C.c_double),
+                ("min_parallax", C.c_double), ("huber_width", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__(linear_init=1, max_iterations=20, write_back=1, lambda0=1e-3, gradient_tolerance=1e-6,
+                         step_tolerance=1e-12, min_parallax=0.0, huber_width=0.0)
+        for k, v in kw.items():
+            if k not in dict(self._fields_) or k == "reserved":
+                raise TypeError("unknown triangulation option %r" % k)
+            setattr(self, k, v)
+
+
+class TriangulationStats(C.Structure):
+    """ba_hip_triangulation_stats"""
+    _fields_ = [("count", C.c_uint32 * 6), ("landmarks", C.c_uint32), ("waves", C.c_uint32), ("waves_early", C.c_uint32),
+                ("written", C.c_uint32), ("device_ms", C.c_double)]
+
+
+# BA_HIP_TRI_*: the status of a result row of Engine.triangulate_landmarks
+TRI_OK, TRI_NOT_CONVERGED, TRI_TOO_FEW_VIEWS, TRI_LOW_PARALLAX, TRI_BEHIND_CAMERA, TRI_FAILED = range(6)
+TRI_STATUS_NAMES = ("OK", "NOT_CONVERGED", "TOO_FEW_VIEWS", "LOW_PARALLAX", "BEHIND_CAMERA", "FAILED")
+# columns of a result row
+TRI_STATUS, TRI_OBSERVATIONS, TRI_ITERATIONS, TRI_COST_START, TRI_COST_END, TRI_PARALLAX, TRI_MIN_DEPTH, TRI_GRADIENT = range(8)
+
+
 def _pcg_stats_dict(st):
     return {k: getattr(st, k) for k, _ in type(st)._fields_ if k != "reserved"}
 
@@ -234,6 +262,7 @@ SYMBOLS = [
     "ba_hip_get_pcg_panel_columns", "ba_hip_pcg_panel_solve",
     "ba_hip_set_damping", "ba_hip_get_damping_terms", "ba_hip_get_damping_diagonal",
     "ba_hip_damping_update",
+    "ba_hip_triangulate_landmarks", "ba_hip_get_triangulation_stats",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -373,6 +402,7 @@ class Engine:
         rp = np.ascontiguousarray(ref_pose, dtype=np.uint32)
         rc = np.ascontiguousarray(ref_cam, dtype=np.uint32) if ref_cam is not None else None
         a = np.ascontiguousarray(is_active, dtype=np.uint8) if is_active is not None else None
+        self.num_landmarks = x.shape[0]
         self._chk(self.L.ba_hip_set_landmarks(self.h, x.shape[0], _p(x, dp), _p(rp, u32p),
                                               _p(rc, u32p), _p(a, u8p)))
 
@@ -428,6 +458,30 @@ class Engine:
         a, c = np.zeros(max(n, 1)), np.zeros(max(nl, 1))
         self._chk(self.L.ba_hip_get_damping_diagonal(self.h, _p(a, dp), _p(c, dp)))
         return a[:n], c[:nl]
+
+    def triangulate_landmarks(self, ids=None, **options):
+        """Closed-form triangulation and per-landmark Levenberg-Marquardt refinement with the poses held fixed
+        (ba_hip_triangulate_landmarks); outside a Solve.  ids: landmark ids, each once, None = every landmark.  options:
+        the fields of TriangulationOptions.  Returns (results n x 8, x_w n x 4): per landmark the status TRI_*, observations,
+        iterations, cost at the start and the end, parallax, smallest depth, gradient measure; and the world coordinates
+        the call arrived at where it accepts them, the coordinates held elsewhere."""
+        o = TriangulationOptions(**options)
+        if ids is None:
+            n, idp = getattr(self, "num_landmarks", 0), None
+        else:
+            ida = np.ascontiguousarray(ids, dtype=np.uint32)
+            n, idp = ida.shape[0], _p(ida, u32p)
+        res, xw = np.zeros((max(n, 1), 8)), np.zeros((max(n, 1), 4))
+        self._chk(self.L.ba_hip_triangulate_landmarks(self.h, n, idp, C.byref(o), _p(res, dp), _p(xw, dp)))
+        return res[:n], xw[:n]
+
+    def triangulation_stats(self):
+        """dict of ba_hip_triangulation_stats of the last triangulate_landmarks: count per status name, landmarks, waves,
+        waves_early, written, device_ms."""
+        t = TriangulationStats()
+        self._chk(self.L.ba_hip_get_triangulation_stats(self.h, C.byref(t)))
+        return {"count": {TRI_STATUS_NAMES[i]: int(t.count[i]) for i in range(6)}, "landmarks": t.landmarks, "waves": t.waves,
+                "waves_early": t.waves_early, "written": t.written, "device_ms": t.device_ms}
 
     def compose_step(self, coef_rhs, coef_gn):
         n = StepNorms()

@@ -137,6 +137,22 @@ struct DensePosePrior {
   uint32_t dropped_projection = 0;
 };
 
+// Landmark triangulation with the poses held fixed (extension; include/ba_hip.h, ba_hip_triangulate_landmarks): the
+// options with their defaults, and one result per requested landmark (status: BA_HIP_TRI_*).
+struct TriangulationOptions {
+  bool linear_init = true;          // start from the closed-form estimate; false: from the coordinates held
+  int max_iterations = 20;          // refinement steps per landmark, 0..64; 0 = the linear estimate only
+  bool write_back = true;           // accepted landmarks get the new coordinates; false: results only
+  double lambda0 = 1e-3, gradient_tolerance = 1e-6, step_tolerance = 1e-12;
+  double min_parallax = 0.0;        // rad; 0 = report only
+  double huber_width = 0.0;         // pixels; 0 = plain weighted least squares
+};
+struct TriangulationResult {
+  int status = BA_HIP_TRI_FAILED;
+  uint32_t observations = 0, iterations = 0;
+  double cost_start = 0.0, cost_end = 0.0, parallax = 0.0, min_depth = 0.0, gradient = 0.0;
+};
+
 template <typename Scalar = double, int LmSize = 1, int PoseSize = 6, int CalibSize = 0,
           bool DoTvs = false>
 class BundleAdjuster {
@@ -685,6 +701,45 @@ class BundleAdjuster {
     out->dropped_projection = st.dropped_projection;
     return Check(ba_hip_get_marginalization(engine_, out->pose_ids.data(), out->x0.data(), out->H.data(), out->b.data(),
                                             &out->c), "ba_hip_get_marginalization");
+  }
+  // Triangulates and refines landmarks with the poses held fixed (extension; include/ba_hip.h).
+  // ids: landmark ids, each once; empty = every landmark.  Syncs the engine as Solve() does, without solving, so it
+  // works before the first Solve(); the written coordinates are what GetLandmark() returns afterwards.  Refused (false,
+  // reported through Check()) with calibration unknowns, on sharded engines, without landmark unknowns, and for every
+  // refusal of ba_hip_triangulate_landmarks.
+  bool TriangulateLandmarks(const std::vector<uint32_t>& ids, const TriangulationOptions& o,
+                            std::vector<TriangulationResult>* out) {
+    if (kCalibDim > 0) { std::cerr << "ba::BundleAdjuster::TriangulateLandmarks: not offered with calibration unknowns" << std::endl; return false; }
+    if (nranks_ > 1 || comm_set_ || allreduce_ || collectives_) {
+      std::cerr << "ba::BundleAdjuster::TriangulateLandmarks: not offered on sharded engines" << std::endl;
+      return false;
+    }
+    if (LmSize == 0) { std::cerr << "ba::BundleAdjuster::TriangulateLandmarks: LmSize 0 has no landmark unknowns" << std::endl; return false; }
+    if (!SyncEngine()) return false;
+    ba_hip_triangulation_options t;
+    std::memset(&t, 0, sizeof(t));
+    t.linear_init = o.linear_init ? 1 : 0; t.max_iterations = o.max_iterations; t.write_back = o.write_back ? 1 : 0;
+    t.lambda0 = o.lambda0; t.gradient_tolerance = o.gradient_tolerance; t.step_tolerance = o.step_tolerance;
+    t.min_parallax = o.min_parallax; t.huber_width = o.huber_width;
+    const uint32_t n = ids.empty() ? uploaded_landmarks_ : (uint32_t)ids.size();
+    std::vector<double> res(8 * (size_t)n);
+    if (!Check(ba_hip_triangulate_landmarks(engine_, n, ids.empty() ? nullptr : ids.data(), &t, res.data(), nullptr),
+               "ba_hip_triangulate_landmarks"))
+      return false;
+    if (o.write_back) {
+      host_state_stale_ = true;   // landmarks_ take the written coordinates at the next read (EnsureHostState)
+      proj_view_dirty_ = true;
+    }
+    if (out) {
+      out->assign(n, TriangulationResult());
+      for (uint32_t i = 0; i < n; ++i) {
+        const double* r = &res[8 * (size_t)i];
+        TriangulationResult& q = (*out)[i];
+        q.status = (int)r[0]; q.observations = (uint32_t)r[1]; q.iterations = (uint32_t)r[2];
+        q.cost_start = r[3]; q.cost_end = r[4]; q.parallax = r[5]; q.min_depth = r[6]; q.gradient = r[7];
+      }
+    }
+    return true;
   }
   // Carries a prior into this problem: pose_ids are ids of THIS problem, one per pose of the prior, in the
   // prior's order.  Returns the prior's index, or UINT32_MAX when refused (calibration unknowns, sharded

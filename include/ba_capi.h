@@ -191,6 +191,12 @@ void ba_adjuster_get_marginalization(const ba_adjuster* a, uint32_t* pose_ids, d
                                      double* c, uint32_t* dropped_projection);
 uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t* pose_ids, const double* x0_16,
                                      const double* H, const double* b, double c);
+/* ba::BundleAdjuster::TriangulateLandmarks (extension; include/ba_hip.h): triangulates and refines
+ * n landmarks (ids NULL: every landmark, n ignored) with the poses held fixed, before or between solves; o NULL = the
+ * defaults.  result8: 8 doubles per requested landmark as ba_hip_triangulate_landmarks fills them (may be NULL).
+ * Returns 0, or 1 when refused. */
+int ba_adjuster_triangulate_landmarks(ba_adjuster* a, uint32_t n, const uint32_t* landmark_ids,
+                                      const ba_hip_triangulation_options* o, double* result8);
 /* ba::BundleAdjuster::GetPcgStats: 1 and *out filled when the last reduced solve ran PCG, 0 otherwise */
 int ba_adjuster_get_pcg_stats(const ba_adjuster* a, ba_hip_pcg_stats* out);
 /* ba::BundleAdjuster::GetPcgCoarseStats: 1 and *out filled when the last reduced solve used the coarse space */

@@ -980,6 +980,59 @@ int ba_hip_tile_factor_solve(ba_hip_engine* e, uint32_t n, const double* a_lower
  * the Huber sigma (std::nth_element at floor(N/2), BundleAdjuster.cpp:1356-1358) */
 int ba_hip_select_kth(ba_hip_engine* e, uint32_t n, const double* values, uint32_t k, double* out);
 
+/* ---- Landmark triangulation and per-landmark refinement, poses held fixed (ba_amd/csrc/triang.h) ----
+ * With the poses fixed every landmark is a least-squares problem of its own (3 parameters with LmSize 3, the inverse
+ * depth along the reference ray with LmSize 1).  One launch (k_triang.hip) gives each selected landmark a closed-form
+ * linear estimate from its observations and refines it by Levenberg-Marquardt to convergence, on the pose state the
+ * engine holds, with the cameras of the rig (pinhole and FOV), the per-pose intrinsics when set, and the original
+ * weights of the observations.  The active flag of a landmark is not consulted: the id list decides.
+ * LmSize 1 reads the ray as unit(T_sw(ref) x_w): a landmark uploaded as a pure direction (w = 0) is valid input.
+ * Uses: landmarks uploaded as directions only; re-triangulation after tracking; with write_back = 0 an audit of the
+ * map (parallax, cheirality and cost per landmark) that changes nothing.
+ * Placement: after ba_hip_finalize, outside a Solve (before ba_hip_begin_solve or after ba_hip_end_solve).  Refused with
+ * LmSize 0, with calibration unknowns, on a sharded or hooked engine and between ba_hip_begin_solve and ba_hip_end_solve.
+ * With write_back the accepted coordinates replace the landmarks' (every other landmark keeps its bits), x_s is
+ * re-derived (LmSize 1) and the call then counts as a ba_hip_begin_solve for everything the device holds: the
+ * linearisation and the cached errors are dropped, the kept factor stays readable.  With write_back = 0 nothing the
+ * engine holds changes.  Two identical calls return identical bits.  The work space is allocated by the first call and
+ * freed by ba_hip_release_marginals. */
+enum {
+  BA_HIP_TRI_OK = 0,             /* converged; written back */
+  BA_HIP_TRI_NOT_CONVERGED = 1,  /* iteration limit reached; written back if the cost fell (with linear_init: did not rise) */
+  BA_HIP_TRI_TOO_FEW_VIEWS = 2,  /* fewer than 2 observations, or none with a baseline; not written */
+  BA_HIP_TRI_LOW_PARALLAX = 3,   /* below min_parallax; not written */
+  BA_HIP_TRI_BEHIND_CAMERA = 4,  /* depth <= 0 in an observing sensor at the starting point; not written */
+  BA_HIP_TRI_FAILED = 5          /* non-finite result; not written */
+};
+typedef struct {
+  int32_t linear_init;       /* 1 (default): start from the closed-form estimate; 0: from the coordinates held */
+  int32_t max_iterations;    /* refinement steps per landmark, 0..64; default 20; 0 = linear estimate only */
+  int32_t write_back;        /* 1 (default): accepted landmarks get the new coordinates; 0: results only */
+  int32_t reserved;
+  double lambda0;            /* initial per-landmark damping, default 1e-3 */
+  double gradient_tolerance; /* default 1e-6: converged when max_i |b_i| / sqrt(V_ii E) falls to it (MINPACK's gtol) */
+  double step_tolerance;     /* default 1e-12: converged when an accepted |delta| <= tol (|x| + tol); 0 = off */
+  double min_parallax;       /* rad, default 0 = report only */
+  double huber_width;        /* pixels, 0 (default) = plain weighted least squares */
+} ba_hip_triangulation_options;
+typedef struct {
+  uint32_t count[6];         /* landmarks of the last call per status BA_HIP_TRI_* */
+  uint32_t landmarks;        /* landmarks requested */
+  uint32_t waves;            /* wavefronts launched */
+  uint32_t waves_early;      /* ... that held no requested landmark and left after reading the selection */
+  uint32_t written;          /* landmarks whose coordinates were replaced */
+  double device_ms;          /* event-timed: selection upload to the last kernel */
+} ba_hip_triangulation_stats;
+/* lm_ids: n landmark ids, each once; NULL: every landmark, n must be the landmark count.  o: NULL = the defaults above.
+ * result8 (n x 8, may be NULL), per requested landmark: status, observations used, iterations, cost at the starting
+ * point, cost at the end, parallax (rad; the largest angle between the first bearing and any other, the first being
+ * the reference ray with LmSize 1), smallest depth over the observing sensors, gradient measure c at the end.
+ * x_w4 (n x 4, may be NULL): the world coordinates the call arrived at where it accepts them (whether or not
+ * write_back stores them), the coordinates held elsewhere. */
+int ba_hip_triangulate_landmarks(ba_hip_engine* e, uint32_t n, const uint32_t* lm_ids, const ba_hip_triangulation_options* o,
+                                 double* result8, double* x_w4);
+int ba_hip_get_triangulation_stats(ba_hip_engine* e, ba_hip_triangulation_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
