@@ -33,6 +33,11 @@
 //                                           triangulated and refined with the poses held fixed (TriangulateLandmarks,
 //                                           at most iters steps per landmark, default 20), the counts per status are
 //                                           printed, then the solve runs as usual
+//   visual_ba_demo --refine-poses [iters]   the free poses start 0.3 m off (ten times the plain demo) and are resected
+//                                           against the map with the landmarks held fixed (RefinePoses, at most iters
+//                                           steps per pose, default 20; 0 = the same start without the refinement), the
+//                                           counts per status and the projection cost before and after are printed,
+//                                           then the solve runs as usual; composes with --triangulate
 //   visual_ba_demo --covariances            after the solve: the last pose's covariance (translation and rotation
 //                                           sigmas) and the median landmark sigma (GetPoseCovariance,
 //                                           GetLandmarkCovariance: selected inverse of the reduced system), then
@@ -60,7 +65,7 @@
 #include <string>
 #include <thread>
 
-struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false, lm = false; double pcg_tol = 1e-6, lm_lambda0 = 1e-4; unsigned pcg_coarse = 0, weakest_modes = 0; int joint_a = -1, joint_b = -1, triangulate = -1; };
+struct Shard { int rank = 0, ranks = 1, device = 0; std::string id_file; bool order_auto = false, covariances = false, leverages = false, pcg = false, lm = false; double pcg_tol = 1e-6, lm_lambda0 = 1e-4; unsigned pcg_coarse = 0, weakest_modes = 0; int joint_a = -1, joint_b = -1, triangulate = -1, refine_poses = -1; };
 
 // rank 0 creates the communicator id and publishes it through a file; the other ranks wait for it
 static bool exchange_id(const Shard& sh, unsigned char* id) {
@@ -184,7 +189,7 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
   };
   for (int i = 0; i < kPoses; ++i) {
     ba::SE3 init = gt[i];
-    for (int k = 0; k < 3; ++k) init.t[k] += 0.03 * n01(rng);
+    for (int k = 0; k < 3; ++k) init.t[k] += (shard.refine_poses >= 0 ? 0.3 : 0.03) * n01(rng);
     // two fixed poses pin the gauge (and the scale); self-calibration needs more of them
     const bool fixed = calibrate ? (i % 3 == 0) : (i < 2);
     adjuster.AddPose(fixed ? gt[i] : init, /*is_active=*/!fixed);
@@ -236,6 +241,24 @@ int run(int calibrate, const Shard& shard = Shard()) {  // 0 none, 1 intrinsics,
     for (const ba::TriangulationResult& r : tr) count[r.status >= 0 && r.status < 6 ? r.status : 5]++;
     std::printf("triangulated %zu landmarks: ok %u, not converged %u, too few views %u, low parallax %u, behind a camera %u, failed %u\n",
                 tr.size(), count[0], count[1], count[2], count[3], count[4], count[5]);
+  }
+  if (shard.refine_poses >= 0) {
+    // the free poses start 0.3 m off (ten times the plain demo): resected against the map, the landmarks held fixed
+    ba::PoseRefinementOptions po;
+    po.max_iterations = shard.refine_poses;
+    std::vector<uint32_t> ids;
+    for (int i = 2; i < kPoses; ++i) ids.push_back((uint32_t)i);
+    std::vector<ba::PoseRefinementResult> pr;
+    if (!adjuster.RefinePoses(ids, po, &pr)) { std::printf("pose refinement refused\n"); return 2; }
+    unsigned count[4] = {0, 0, 0, 0};
+    double before = 0.0, after = 0.0;
+    for (const ba::PoseRefinementResult& r : pr) {
+      count[r.status >= 0 && r.status < 4 ? r.status : 3]++;
+      before += r.cost_start; after += r.cost_end;
+    }
+    std::printf("refined %zu poses (%d iterations at most): ok %u, not converged %u, too few observations %u, failed %u; "
+                "projection cost of these poses %.6g -> %.6g\n", pr.size(), shard.refine_poses, count[0], count[1], count[2],
+                count[3], before, after);
   }
   adjuster.Solve(1);
   if (shard.pcg) print_pcg(1);
@@ -425,6 +448,12 @@ int main(int argc, char** argv) {
     if (std::strcmp(argv[i], "--triangulate") == 0) {
       shard.triangulate = 20;
       if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.triangulate = std::atoi(argv[i + 1]);
+      else --i;
+      continue;
+    }
+    if (std::strcmp(argv[i], "--refine-poses") == 0) {
+      shard.refine_poses = 20;
+      if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) shard.refine_poses = std::atoi(argv[i + 1]);
       else --i;
       continue;
     }

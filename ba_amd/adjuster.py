@@ -78,7 +78,7 @@ SYMBOLS = [
     "ba_adjuster_solve_with_pcg", "ba_adjuster_get_joint_pose_covariance_iterative", "ba_adjuster_get_pcg_panel_stats",
     "ba_adjuster_get_pose_pose_leverages", "ba_adjuster_get_pose_pose_leverage",
     "ba_adjuster_marginalize", "ba_adjuster_get_marginalization", "ba_adjuster_add_dense_prior",
-    "ba_adjuster_triangulate_landmarks",
+    "ba_adjuster_triangulate_landmarks", "ba_adjuster_refine_poses",
     "ba_adjuster_get_pcg_stats", "ba_adjuster_get_pcg_coarse_stats",
     "ba_adjuster_set_levenberg_marquardt", "ba_adjuster_get_damping", "ba_adjuster_get_levenberg_marquardt_state",
 ]
@@ -425,6 +425,22 @@ class BundleAdjuster:
         res = np.zeros((max(n, 1), 8))
         rc = self.L.ba_adjuster_triangulate_landmarks(self.h, n, idp, C.byref(o), res.ctypes.data_as(C.POINTER(C.c_double)))
         return rc == 0, res[:n]
+
+    def RefinePoses(self, ids=None, **options):
+        """ba::BundleAdjuster::RefinePoses, before or between Solve() calls: ids None = every pose; options: the fields of
+        hipapi.PoseRefinementOptions.  Returns (ok, results n x 8, t_wp n x 7, info n x 6 x 6); ok False when refused (see
+        stderr)."""
+        o = hipapi.PoseRefinementOptions(**options)
+        u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+        if ids is None:
+            n, idp = self.GetNumPoses(), None
+        else:
+            ida = np.ascontiguousarray(ids, dtype=np.uint32)
+            n, idp = len(ida), ida.ctypes.data_as(u32p)
+        res, t7, info = np.zeros((max(n, 1), 8)), np.zeros((max(n, 1), 7)), np.zeros((max(n, 1), 6, 6))
+        rc = self.L.ba_adjuster_refine_poses(self.h, n, idp, C.byref(o), res.ctypes.data_as(dp), t7.ctypes.data_as(dp),
+                                             info.ctypes.data_as(dp))
+        return rc == 0, res[:n], t7[:n], info[:n]
 
     def engine_landmarks(self):
         """ba_hip_get_landmarks of the adjuster's engine"""

@@ -70,6 +70,8 @@ struct Iface {
   virtual uint32_t add_dense_prior(uint32_t k, const uint32_t* ids, const double* x0, const double* H, const double* b,
                                    double c) = 0;
   virtual int triangulate(uint32_t n, const uint32_t* ids, const ba_hip_triangulation_options* o, double* result8) = 0;
+  virtual int refine_poses(uint32_t n, const uint32_t* ids, const ba_hip_pose_refinement_options* o, double* result8,
+                           double* t_wp7, double* info36) = 0;
 };
 
 template <int LM, int PD, bool TVS = false, int CS = 0>
@@ -269,6 +271,27 @@ struct Impl : Iface {
       double* q = result8 + 8 * i;
       q[0] = r[i].status; q[1] = r[i].observations; q[2] = r[i].iterations; q[3] = r[i].cost_start; q[4] = r[i].cost_end;
       q[5] = r[i].parallax; q[6] = r[i].min_depth; q[7] = r[i].gradient;
+    }
+    return 0;
+  }
+  int refine_poses(uint32_t n, const uint32_t* ids, const ba_hip_pose_refinement_options* o, double* result8, double* t_wp7,
+                   double* info36) override {
+    ba::PoseRefinementOptions t;
+    if (o) {
+      t.max_iterations = o->max_iterations; t.write_back = o->write_back != 0; t.fixed_mask = o->fixed_mask;
+      t.initial_damping = o->initial_damping; t.gradient_tolerance = o->gradient_tolerance;
+      t.step_tolerance = o->step_tolerance; t.huber_width = o->huber_width;
+    }
+    std::vector<ba::PoseRefinementResult> r;
+    if (!ba.RefinePoses(ids ? std::vector<uint32_t>(ids, ids + n) : std::vector<uint32_t>(), t, &r)) return 1;
+    for (size_t i = 0; i < r.size(); ++i) {
+      if (result8) {
+        double* q = result8 + 8 * i;
+        q[0] = r[i].status; q[1] = r[i].observations; q[2] = r[i].iterations; q[3] = r[i].cost_start; q[4] = r[i].cost_end;
+        q[5] = r[i].min_depth; q[6] = r[i].gradient; q[7] = r[i].excluded;
+      }
+      if (t_wp7) std::copy(r[i].t_wp, r[i].t_wp + 7, t_wp7 + 7 * i);
+      if (info36) std::copy(r[i].information, r[i].information + 36, info36 + 36 * i);
     }
     return 0;
   }
@@ -580,6 +603,11 @@ int ba_adjuster_triangulate_landmarks(ba_adjuster* a, uint32_t n, const uint32_t
                                       const ba_hip_triangulation_options* o, double* result8) {
   if (landmark_ids && !n) return 1;
   return a->p->triangulate(n, landmark_ids, o, result8);
+}
+int ba_adjuster_refine_poses(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids, const ba_hip_pose_refinement_options* o,
+                             double* result8, double* t_wp7, double* info36) {
+  if (pose_ids && !n) return 1;
+  return a->p->refine_poses(n, pose_ids, o, result8, t_wp7, info36);
 }
 void ba_adjuster_set_allreduce(ba_adjuster* a, ba_hip_allreduce_fn fn, void* ctx, int rank, int nranks) { a->p->set_allreduce(fn, ctx, rank, nranks); }
 void ba_adjuster_set_communicator(ba_adjuster* a, const void* id128, int rank, int nranks, int distributed_solve) { a->p->set_communicator(id128, rank, nranks, distributed_solve); }

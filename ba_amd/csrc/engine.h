@@ -19,6 +19,7 @@
 #include "bulk_lists.h"
 #include "damping.h"
 #include "triang.h"
+#include "resect.h"
 
 namespace bae {
 
@@ -394,6 +395,26 @@ struct Engine {
     void release() { mask.release(); early.release(); res.release(); xw.release(); }
   } tri;
 
+  // Pose refinement with the landmarks held fixed (ba_hip_refine_poses, resect.h, k_resect.hip).  The work space exists
+  // only once a call was made (ba_hip_release_marginals frees it).  ptr [P + 1] / idx [O]: the per-pose observation list,
+  // built by the first call after a ba_hip_finalize (list_valid; host_ptr its host copy, which sizes the launches);
+  // ids / rows [n]: the requests grouped by launch and their result rows; used [O]: the streaming kernel's used flags;
+  // res [n][8], t7 [n][7], info [n][36]: the results by request.
+  struct Resect {
+    DBuf<uint32_t> ptr, idx, ids, rows;
+    DBuf<uint8_t> used;
+    DBuf<double> res, t7, info;
+    std::vector<uint32_t> host_ptr;
+    std::vector<uint32_t> host_ids, host_rows;   // the source of the last request's asynchronous uploads: never freed early
+    bool list_valid = false;
+    ba_hip_pose_refinement_stats stats = {};
+    void release() {
+      ptr.release(); idx.release(); ids.release(); rows.release(); used.release(); res.release(); t7.release(); info.release();
+      host_ptr = std::vector<uint32_t>();
+      list_valid = false;
+    }
+  } resect;
+
   // optional per-kernel timing (ba_hip_set_profiling)
   bool profiling = false;
   ba_hip_kernel_stats kstats = {};
@@ -670,6 +691,10 @@ int pcg_panel_solve_device(Engine* e, const double* dA, uint32_t n, uint32_t ld,
                            int* status);
 // triangulation (k_triang.hip): the selection in tri.mask is on the device; fills tri.res / tri.xw for every landmark
 int launch_triangulate(Engine* e, const TriOptions& o);
+// pose refinement (k_resect.hip): resect.ids / rows hold the requests grouped as cls counts them (no observations, up
+// to 256, up to 1 024, more); fills resect.res / t7 / info by request row.  launch_resect_store: t7 over the poses held
+int launch_resect(Engine* e, const RsOptions& o, const uint32_t cls[4]);
+int launch_resect_store(Engine* e, uint32_t n);
 int marginalize_run(Engine* e, const MargPlan& pl, const std::vector<uint16_t>& lmask, double tol, double* dev_ms);
 
 }  // namespace bae

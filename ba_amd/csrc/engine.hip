@@ -882,6 +882,7 @@ int ba_hip_finalize(ba_hip_engine* h) {
   BA_ENTRY_DEVICE(h);
   e->held.finalize_begins();
   e->in_solve = false;
+  e->resect.list_valid = false;   // the per-pose observation list belongs to the structure built below
   Problem& pb = e->prob;
   if (pb.pose_active.size() != pb.num_poses) pb.pose_active.assign(pb.num_poses, 1);
   if (pb.lm_active.size() != pb.num_lms) pb.lm_active.assign(pb.num_lms, 1);

@@ -228,6 +228,7 @@ int ba_hip_release_marginals(ba_hip_engine* h) {
   jointcov_release(e);
   factor_solve_release(e);
   e->tri.release();
+  e->resect.release();
   return 0;
 }
 
@@ -704,6 +705,112 @@ int ba_hip_triangulate_landmarks(ba_hip_engine* h, uint32_t n, const uint32_t* l
 int ba_hip_get_triangulation_stats(ba_hip_engine* h, ba_hip_triangulation_stats* out) {
   BA_ENTRY_HOST(h);
   return put_stats(e, __func__, out, e->tri.stats);
+}
+
+// ---- pose refinement with the landmarks held fixed (k_resect.hip, resect.h) ----
+// the per-pose observation list of the structure the device holds (the host copies of the sorted observations are gone
+// after ba_hip_finalize: obs_pose comes back from the device, once per structure)
+static int resect_ensure_lists(Engine* e) {
+  Engine::Resect& w = e->resect;
+  if (w.list_valid) return 0;
+  const Structure& st = e->st;
+  std::vector<uint32_t> obs_pose(st.O), idx;
+  if (st.O) {
+    BAE_HIP(hipStreamSynchronize(e->stream));
+    BAE_HIP(hipMemcpy(obs_pose.data(), e->obs_pose.p, (size_t)st.O * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  if (!build_pose_obs_lists(st.P, st.O, obs_pose.data(), &w.host_ptr, &idx))
+    return e->fail_msg("ba_hip_refine_poses: an observation names a pose that does not exist");
+  BAE_HIP(w.ptr.alloc((size_t)st.P + 1));
+  BAE_HIP(w.idx.alloc(std::max<size_t>(st.O, 1)));
+  BAE_HIP(w.used.alloc(std::max<size_t>(st.O, 1)));
+  BAE_HIP(hipMemcpy(w.ptr.p, w.host_ptr.data(), ((size_t)st.P + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (st.O) BAE_HIP(hipMemcpy(w.idx.p, idx.data(), (size_t)st.O * sizeof(uint32_t), hipMemcpyHostToDevice));
+  w.list_valid = true;
+  return 0;
+}
+
+int ba_hip_refine_poses(ba_hip_engine* h, uint32_t n, const uint32_t* pose_ids, const ba_hip_pose_refinement_options* o,
+                        double* result8, double* t_wp7, double* info36) {
+  BA_ENTRY_FINAL(h);
+  BA_ASK(guard_refine_poses(e->held, guard_facts(e), e->st.K != 0 || e->calib_dim != 0, e->lm_dim, e->in_solve));
+  // (the cameras as ba_hip_begin_solve takes them)
+  if (!e->prob.pose_cam_params.empty() && e->prob.pose_cam_params.size() != 4 * (size_t)e->prob.num_poses)
+    return e->fail_msg("per-pose camera parameters: one [fx,fy,u0,v0] per pose expected");
+  if (!e->prob.pose_cam_params.empty() && e->has_fov)
+    return e->fail_msg("per-pose camera parameters are offered for LinearCamera rigs only");
+  RsOptions t;   // the defaults of the header
+  if (o) {
+    t.max_iterations = o->max_iterations; t.write_back = o->write_back != 0; t.fixed_mask = o->fixed_mask;
+    t.lambda0 = o->initial_damping; t.gradient_tolerance = o->gradient_tolerance; t.step_tolerance = o->step_tolerance;
+    t.huber_width = o->huber_width;
+  }
+  const Structure& st = e->st;
+  const uint32_t P = st.P;
+  BA_ASK(refinement_ok({t.max_iterations, t.fixed_mask, t.lambda0, t.gradient_tolerance, t.step_tolerance, t.huber_width}, P,
+                       n, pose_ids));
+  Engine::Resect& w = e->resect;
+  w.stats = ba_hip_pose_refinement_stats();
+  w.stats.poses = n;
+  int rc = resect_ensure_lists(e);
+  if (rc) return rc;
+  // the requests grouped by launch: no observations | up to 256 | up to 1 024 | more; rows: their place in the request
+  uint32_t cls[4] = {0, 0, 0, 0};
+  auto cls_of = [&](uint32_t p) {
+    const uint32_t k = w.host_ptr[p + 1] - w.host_ptr[p];
+    return k == 0 ? 0 : k <= 256 ? 1 : k <= 1024 ? 2 : 3;
+  };
+  for (uint32_t i = 0; i < n; ++i) cls[cls_of(pose_ids ? pose_ids[i] : i)] += 1;
+  uint32_t at[4] = {0, cls[0], cls[0] + cls[1], cls[0] + cls[1] + cls[2]};
+  // (held by the work space, and kept by its release(): the uploads below are asynchronous, and an error return must
+  // not leave them reading freed memory)
+  std::vector<uint32_t>& ids = w.host_ids;
+  std::vector<uint32_t>& rows = w.host_rows;
+  ids.assign(n, 0); rows.assign(n, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t p = pose_ids ? pose_ids[i] : i, j = at[cls_of(p)]++;
+    ids[j] = p; rows[j] = i;
+  }
+  BAE_HIP(w.ids.alloc(n)); BAE_HIP(w.rows.alloc(n));
+  BAE_HIP(w.res.alloc((size_t)n * kRsResult)); BAE_HIP(w.t7.alloc((size_t)n * 7)); BAE_HIP(w.info.alloc((size_t)n * 36));
+  Events<2> ev;
+  BAE_HIP(ev.create());
+  BAE_HIP(ev.record(0, e->stream));
+  BAE_HIP(hipMemcpyAsync(w.ids.p, ids.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+  BAE_HIP(hipMemcpyAsync(w.rows.p, rows.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+  rc = launch_pose_prep(e);
+  if (!rc) rc = launch_resect(e, t, cls);
+  if (rc) return rc;
+  BAE_HIP(ev.record(1, e->stream));
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  std::vector<double> res((size_t)n * kRsResult);
+  BAE_HIP(hipMemcpy(res.data(), w.res.p, res.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (t_wp7) BAE_HIP(hipMemcpy(t_wp7, w.t7.p, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost));
+  if (info36) BAE_HIP(hipMemcpy(info36, w.info.p, (size_t)n * 36 * sizeof(double), hipMemcpyDeviceToHost));
+  w.stats.device_ms = ev.ms(0, 1);
+  for (uint32_t i = 0; i < n; ++i) {
+    const double* r = &res[(size_t)i * kRsResult];
+    const int status = (int)r[0];
+    if (status >= 0 && status < kRsStatusCount) w.stats.count[status] += 1;
+    if (rs_row_accepted(r)) w.stats.written += 1;   // (what rs_accepted decided on the device)
+    w.stats.observations_used += (uint64_t)r[1];
+    w.stats.observations_excluded += (uint64_t)r[7];
+  }
+  if (result8) std::copy(res.begin(), res.end(), result8);
+  if (!t.write_back) { w.stats.written = 0; return 0; }
+  // accepted rows hold the new pose, every other requested row the bits it had
+  if ((rc = launch_resect_store(e, n))) return rc;
+  if (e->lm_dim == 1) {   // x_s from the x_w that stayed, in the reference sensors that moved
+    if ((rc = launch_pose_prep(e))) return rc;
+    if ((rc = launch_begin_solve(e))) return rc;
+  }
+  e->held.solve_begins();   // the poses moved: the linearisation and the cached errors are those of other poses
+  BAE_HIP(hipStreamSynchronize(e->stream));
+  return 0;
+}
+int ba_hip_get_pose_refinement_stats(ba_hip_engine* h, ba_hip_pose_refinement_stats* out) {
+  BA_ENTRY_HOST(h);
+  return put_stats(e, __func__, out, e->resect.stats);
 }
 
 int ba_hip_dense_solve(ba_hip_engine* h, uint32_t n, const double* a_lower, const double* b, double* x) {

@@ -1519,3 +1519,111 @@ extern "C" int ba_hostcheck_triangulate(int LM, uint32_t P, const double* poses7
                                 x_w, ref_pose, ref_cam, mask, opt, res, xw_out, final);
   return 0;
 }
+
+// ---- pose refinement with the landmarks held fixed (resect.h) ----------------------------------------------------
+#include "resect.h"
+
+// build_pose_obs_lists: ptr [P + 1], idx [O].  Returns 0, or 1 when an observation names a pose >= P.
+extern "C" int ba_hostcheck_pose_obs_lists(uint32_t P, uint32_t O, const uint32_t* obs_pose, uint32_t* ptr, uint32_t* idx) {
+  std::vector<uint32_t> p, i;
+  if (!bae::build_pose_obs_lists(P, O, obs_pose, &p, &i)) return 1;
+  std::copy(p.begin(), p.end(), ptr);
+  std::copy(i.begin(), i.end(), idx);
+  return 0;
+}
+
+// guard_refine_poses on a lifecycle record after `events` (as ba_hostcheck_guard): flags bit 0 calibration, bit 1
+// hooked, bit 2 in_solve, bit 3 sharded, bit 4 distributed solve
+extern "C" int ba_hostcheck_refine_poses_guard(uint32_t n, const int32_t* events, int lm_dim, uint32_t flags, char* msg,
+                                               uint32_t cap) {
+  using namespace bae;
+  Held h;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!held_apply(h, events[i])) return -(int)(i + 1);
+  GuardFacts f = {};
+  f.hooked = (flags & 2) != 0; f.sharded = (flags & 8) != 0; f.dist_solve = (flags & 16) != 0;
+  return put_message(guard_refine_poses(h, f, (flags & 1) != 0, lm_dim, (flags & 4) != 0), msg, cap);
+}
+
+// The rules of resect.h on the host, pose by pose, sums in list order.
+//   poses7 [P][7] (t, q xyzw), cam_params4 [C][4], cam_tvs7 [C][7], cam_model [C] (may be NULL), cam_w [C] (may be
+//   NULL), pose_cam4 [P][4] per-pose intrinsics (may be NULL)
+//   the observations in the engine's sorted order: obs_pose, obs_cam, obs_lm [O], obs_z [O][2], obs_w0 [O]
+//   x_w [L][4] world points; ids [n] (NULL: every pose, n = P)
+//   opts7: max_iterations, write_back, fixed_mask, initial_damping, gradient_tolerance, step_tolerance, huber_width
+//   res [n][8], t_out [n][7], info [n][36] as ba_hip_refine_poses fills them; final (may be NULL) [n][7]: lambda, g
+// Returns 0, or 1 with the message of requests.h.
+extern "C" int ba_hostcheck_refine_poses(uint32_t P, const double* poses7, uint32_t C, const double* cam_params4,
+                                         const double* cam_tvs7, const int32_t* cam_model, const double* cam_w,
+                                         const double* pose_cam4, uint32_t O, const uint32_t* obs_pose,
+                                         const uint32_t* obs_cam, const uint32_t* obs_lm, const double* obs_z,
+                                         const double* obs_w0, const double* x_w, uint32_t n, const uint32_t* ids,
+                                         const double* opts7, double* res, double* t_out, double* info, double* final,
+                                         char* msg, uint32_t cap) {
+  using namespace bae;
+  using namespace bad;
+  RsOptions opt;
+  opt.max_iterations = (int)opts7[0]; opt.write_back = opts7[1] != 0.0; opt.fixed_mask = (unsigned)opts7[2];
+  opt.lambda0 = opts7[3]; opt.gradient_tolerance = opts7[4]; opt.step_tolerance = opts7[5]; opt.huber_width = opts7[6];
+  const std::string bad_request =
+      refinement_ok({opt.max_iterations, opt.fixed_mask, opt.lambda0, opt.gradient_tolerance, opt.step_tolerance,
+                     opt.huber_width}, P, n, ids);
+  if (put_message(bad_request, msg, cap)) return 1;
+  std::vector<uint32_t> ptr, idx;
+  if (!build_pose_obs_lists(P, O, obs_pose, &ptr, &idx)) return put_message("an observation names a pose that does not exist", msg, cap);
+  std::vector<M3> R_sv(C);
+  for (uint32_t c = 0; c < C; ++c) {
+    const double* t = cam_tvs7 + (size_t)c * 7;
+    Rt vs;
+    vs.R = quat_to_rot(t[3], t[4], t[5], t[6]);
+    vs.t = v3(t[0], t[1], t[2]);
+    R_sv[c] = inverse(vs).R;
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t p = ids ? ids[i] : i;
+    const uint32_t a0 = ptr[p], k = ptr[p + 1] - a0;
+    const double* held = poses7 + (size_t)p * 7;
+    std::vector<uint8_t> use(k, 0);
+    auto sums_at = [&](const double* pose7, bool first, double* tot, unsigned* used, double* depth) {
+      for (int j = 0; j < kRsSums; ++j) tot[j] = 0.0;
+      *used = 0;
+      *depth = rs_inf();
+      for (uint32_t j = 0; j < k; ++j) {
+        const uint32_t a = idx[a0 + j], cm = obs_cam[a];
+        Rt wp, sw;
+        rs_sensor(pose7, cam_tvs7 + (size_t)cm * 7, &wp, &sw);
+        const double* X = x_w + (size_t)obs_lm[a] * 4;
+        if (first) use[j] = rs_usable(rs_point(sw, X)) ? 1 : 0;
+        if (!use[j]) continue;
+        const double* ip = pose_cam4 ? pose_cam4 + (size_t)p * 4 : cam_params4 + (size_t)cm * 4;
+        const Cam cam = {ip[0], ip[1], ip[2], ip[3], cam_w ? cam_w[cm] : 0.0, cam_model && cam_model[cm] ? 1 : 0};
+        double v[kRsSums];
+        const double dep = rs_eval(cam, obs_z + 2 * (size_t)a, obs_w0[a], X, wp, sw, R_sv[cm], opt.huber_width, !first, v);
+        for (int q = 0; q < kRsSums; ++q) tot[q] += v[q];
+        *used += 1;
+        *depth = dep < *depth ? dep : *depth;
+      }
+      rs_mask_sums(tot, opt.fixed_mask);
+    };
+    RsPose m;
+    double tot[kRsSums], depth;
+    unsigned used;
+    sums_at(held, true, tot, &used, &depth);
+    rs_begin(&m, opt, held, tot, used, k - used, depth);
+    while (m.active) {
+      double trial[7];
+      rs_apply(m.x, m.delta, opt.fixed_mask, trial);
+      sums_at(trial, false, tot, &used, &depth);
+      rs_step(&m, opt, trial, tot, depth);
+    }
+    rs_result(m, res + (size_t)i * kRsResult);
+    const bool acc = rs_accepted(m);
+    for (int j = 0; j < 7; ++j) t_out[(size_t)i * 7 + j] = acc ? m.x[j] : held[j];
+    rs_info(m, info + (size_t)i * 36);
+    if (final) {
+      final[(size_t)i * 7] = m.ds.lambda;
+      for (int j = 0; j < 6; ++j) final[(size_t)i * 7 + 1 + j] = m.cur[kRsH + j];
+    }
+  }
+  return 0;
+}

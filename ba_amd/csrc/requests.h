@@ -160,6 +160,43 @@ inline std::string triangulation_ok(const TriAsk& o, uint32_t L, uint32_t n, con
   return "";
 }
 
+// ba_hip_refine_poses: the same order as ba_hip_triangulate_landmarks (in_solve: x_w lags behind x_s with LmSize 1, and
+// the poses held are those of a step that may still be rolled back), then the options, then the ids
+struct RefineAsk {
+  int max_iterations;
+  unsigned fixed_mask;
+  double initial_damping, gradient_tolerance, step_tolerance, huber_width;
+};
+inline std::string guard_refine_poses(const Held& h, const GuardFacts& f, bool calibration, int lm_dim, bool in_solve) {
+  static const std::string m = "ba_hip_refine_poses: ";
+  if (!h.finalized) return m + kNotFinalized;
+  if (lm_dim == 0) return m + "LmSize 0 has no landmarks to resect against";
+  if (calibration) return m + "not offered with calibration unknowns";
+  if (f.hooked || f.sharded || f.dist_solve) return m + "not offered on sharded engines or with the distributed solve";
+  if (in_solve)
+    return m + "not offered inside a Solve, where x_w lags behind the state: call ba_hip_end_solve first (or refine "
+               "before ba_hip_begin_solve)";
+  return "";
+}
+inline std::string refinement_ok(const RefineAsk& o, uint32_t P, uint32_t n, const uint32_t* ids) {
+  static const std::string m = "ba_hip_refine_poses: ";
+  if (o.max_iterations < 0 || o.max_iterations > 64)
+    return m + "max_iterations " + std::to_string(o.max_iterations) + " does not lie in 0 .. 64";
+  // (written so that a NaN is refused too)
+  if (!(o.initial_damping >= 0.0) || !(o.gradient_tolerance >= 0.0) || !(o.step_tolerance >= 0.0) || !(o.huber_width >= 0.0))
+    return m + "initial_damping, the tolerances and huber_width must not be negative";
+  if (o.fixed_mask >= 63) return m + "fixed_mask " + std::to_string(o.fixed_mask) + " leaves no free parameter (bits 0 .. 5, not all)";
+  if (n == 0) return m + "no pose requested";
+  if (!ids) return n == P ? "" : m + "with NULL ids n must be the pose count";
+  std::vector<uint8_t> seen(P, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (ids[i] >= P) return m + "id " + std::to_string(ids[i]) + " is not a pose (there are " + std::to_string(P) + ")";
+    if (seen[ids[i]]) return m + "pose " + std::to_string(ids[i]) + " is named twice";
+    seen[ids[i]] = 1;
+  }
+  return "";
+}
+
 // ---- the small shared checks ---------------------------------------------------------------------------------------
 // with NULL ids a request means all `count` of them: `count_name` ends the message
 inline std::string ids_or_all(const char* who, const void* ids, uint32_t n, uint32_t count, const std::string& count_name) {

@@ -219,6 +219,35 @@ TRI_STATUS_NAMES = ("OK", "NOT_CONVERGED", "TOO_FEW_VIEWS", "LOW_PARALLAX", "BEH
 TRI_STATUS, TRI_OBSERVATIONS, TRI_ITERATIONS, TRI_COST_START, TRI_COST_END, TRI_PARALLAX, TRI_MIN_DEPTH, TRI_GRADIENT = range(8)
 
 
+class PoseRefinementOptions(C.Structure):
+    """ba_hip_pose_refinement_options, with the header's defaults"""
+    _fields_ = [("max_iterations", C.c_int32), ("write_back", C.c_int32), ("fixed_mask", C.c_uint32), ("reserved", C.c_int32),
+                ("initial_damping", C.c_double), ("gradient_tolerance", C.c_double), ("step_tolerance", C.c_double),
+                ("huber_width", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__(max_iterations=20, write_back=1, fixed_mask=0, initial_damping=1e-3, gradient_tolerance=1e-6,
+                         step_tolerance=1e-12, huber_width=0.0)
+        for k, v in kw.items():
+            if k not in dict(self._fields_) or k == "reserved":
+                raise TypeError("unknown pose refinement option %r" % k)
+            setattr(self, k, v)
+
+
+class PoseRefinementStats(C.Structure):
+    """ba_hip_pose_refinement_stats"""
+    _fields_ = [("count", C.c_uint32 * 4), ("poses", C.c_uint32), ("written", C.c_uint32),
+                ("observations_used", C.c_uint64), ("observations_excluded", C.c_uint64), ("device_ms", C.c_double)]
+
+
+# BA_HIP_RESECT_*: the status of a result row of Engine.refine_poses
+RESECT_OK, RESECT_NOT_CONVERGED, RESECT_TOO_FEW_OBSERVATIONS, RESECT_FAILED = range(4)
+RESECT_STATUS_NAMES = ("OK", "NOT_CONVERGED", "TOO_FEW_OBSERVATIONS", "FAILED")
+# columns of a result row
+(RESECT_STATUS, RESECT_USED, RESECT_ITERATIONS, RESECT_COST_START, RESECT_COST_END, RESECT_MIN_DEPTH, RESECT_GRADIENT,
+ RESECT_EXCLUDED) = range(8)
+
+
 def _pcg_stats_dict(st):
     return {k: getattr(st, k) for k, _ in type(st)._fields_ if k != "reserved"}
 
@@ -263,6 +292,7 @@ SYMBOLS = [
     "ba_hip_set_damping", "ba_hip_get_damping_terms", "ba_hip_get_damping_diagonal",
     "ba_hip_damping_update",
     "ba_hip_triangulate_landmarks", "ba_hip_get_triangulation_stats",
+    "ba_hip_refine_poses", "ba_hip_get_pose_refinement_stats",
 ]
 
 ORDER_NATURAL, ORDER_AUTO, ORDER_USER = 0, 1, 2  # ba_hip_set_pose_ordering modes
@@ -333,6 +363,7 @@ class Engine:
     def __init__(self, lm_dim=1, pose_dim=6, device=0, stream=None):
         self.L = lib()
         self.lm_dim, self.pose_dim = lm_dim, pose_dim
+        self.num_poses = None   # recorded by set_poses; refine_poses(ids=None) needs it, or its num_poses argument
         self.h = C.c_void_p()
         rc = self.L.ba_hip_create(lm_dim, pose_dim, device, C.c_void_p(stream), C.byref(self.h))
         if rc != 0 or not self.h:
@@ -394,6 +425,7 @@ class Engine:
         v = _d(v_w) if v_w is not None else None
         bb = _d(b) if b is not None else None
         a = np.ascontiguousarray(is_active, dtype=np.uint8) if is_active is not None else None
+        self.num_poses = t.shape[0]
         self._chk(self.L.ba_hip_set_poses(self.h, t.shape[0], _p(t, dp), _p(v, dp), _p(bb, dp),
                                           _p(a, u8p)))
 
@@ -482,6 +514,34 @@ class Engine:
         self._chk(self.L.ba_hip_get_triangulation_stats(self.h, C.byref(t)))
         return {"count": {TRI_STATUS_NAMES[i]: int(t.count[i]) for i in range(6)}, "landmarks": t.landmarks, "waves": t.waves,
                 "waves_early": t.waves_early, "written": t.written, "device_ms": t.device_ms}
+
+    def refine_poses(self, ids=None, num_poses=None, **options):
+        """Per-pose Levenberg-Marquardt refinement (resection) with the landmarks held fixed (ba_hip_refine_poses);
+        outside a Solve.  ids: pose ids, each once, None = every pose (num_poses: their count, for an Engine that did not
+        upload the poses itself; set_poses records it otherwise).  options: the fields of PoseRefinementOptions.
+        Returns (results n x 8, t_wp n x 7, info n x 6 x 6): per pose the status RESECT_*, observations used, iterations,
+        cost at the start and the end, smallest depth, gradient measure, observations excluded; the pose (t, q xyzw) the
+        call arrived at where it accepts it, the pose held elsewhere; the undamped H at the end point."""
+        o = PoseRefinementOptions(**options)
+        if ids is None:
+            n, idp = getattr(self, "num_poses", None) if num_poses is None else int(num_poses), None
+            if n is None:
+                raise ValueError("refine_poses: this Engine did not upload the poses itself, pass ids or num_poses")
+        else:
+            ida = np.ascontiguousarray(ids, dtype=np.uint32)
+            n, idp = ida.shape[0], _p(ida, u32p)
+        res, t7, info = np.zeros((max(n, 1), 8)), np.zeros((max(n, 1), 7)), np.zeros((max(n, 1), 6, 6))
+        self._chk(self.L.ba_hip_refine_poses(self.h, n, idp, C.byref(o), _p(res, dp), _p(t7, dp), _p(info, dp)))
+        return res[:n], t7[:n], info[:n]
+
+    def pose_refinement_stats(self):
+        """dict of ba_hip_pose_refinement_stats of the last refine_poses: count per status name, poses, written,
+        observations_used, observations_excluded, device_ms."""
+        t = PoseRefinementStats()
+        self._chk(self.L.ba_hip_get_pose_refinement_stats(self.h, C.byref(t)))
+        return {"count": {RESECT_STATUS_NAMES[i]: int(t.count[i]) for i in range(4)}, "poses": t.poses, "written": t.written,
+                "observations_used": t.observations_used, "observations_excluded": t.observations_excluded,
+                "device_ms": t.device_ms}
 
     def compose_step(self, coef_rhs, coef_gn):
         n = StepNorms()

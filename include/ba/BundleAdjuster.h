@@ -153,6 +153,23 @@ struct TriangulationResult {
   double cost_start = 0.0, cost_end = 0.0, parallax = 0.0, min_depth = 0.0, gradient = 0.0;
 };
 
+// Pose refinement (resection) with the landmarks held fixed (extension; include/ba_hip.h, ba_hip_refine_poses): the
+// options with their defaults, and one result per requested pose (status: BA_HIP_RESECT_*).
+struct PoseRefinementOptions {
+  int max_iterations = 20;          // refinement steps per pose, 0..64
+  bool write_back = true;           // accepted poses replace the poses held; false: results only
+  unsigned fixed_mask = 0;          // bit i (0..5): parameter i (t xyz, rotation xyz) stays; 63 is refused
+  double initial_damping = 1e-3, gradient_tolerance = 1e-6, step_tolerance = 1e-12;
+  double huber_width = 0.0;         // pixels; 0 = plain weighted least squares
+};
+struct PoseRefinementResult {
+  int status = BA_HIP_RESECT_FAILED;
+  uint32_t observations = 0, iterations = 0, excluded = 0;
+  double cost_start = 0.0, cost_end = 0.0, min_depth = 0.0, gradient = 0.0;
+  double t_wp[7] = {0, 0, 0, 0, 0, 0, 1};   // t, q (xyzw): the pose arrived at where accepted, the pose held elsewhere
+  double information[36] = {};               // the undamped 6 x 6 H at the end point, row-major
+};
+
 template <typename Scalar = double, int LmSize = 1, int PoseSize = 6, int CalibSize = 0,
           bool DoTvs = false>
 class BundleAdjuster {
@@ -737,6 +754,46 @@ class BundleAdjuster {
         TriangulationResult& q = (*out)[i];
         q.status = (int)r[0]; q.observations = (uint32_t)r[1]; q.iterations = (uint32_t)r[2];
         q.cost_start = r[3]; q.cost_end = r[4]; q.parallax = r[5]; q.min_depth = r[6]; q.gradient = r[7];
+      }
+    }
+    return true;
+  }
+  // Refines poses with the landmarks held fixed (extension; include/ba_hip.h): the mirror image
+  // of TriangulateLandmarks.  ids: pose ids, each once; empty = every pose.  Syncs the engine as Solve() does, without
+  // solving, so it works before the first Solve() and between Solve() calls; the written poses are what GetPose()
+  // returns afterwards.  Refused (false, reported through Check()) with calibration unknowns, on sharded engines,
+  // with LmSize 0, and for every refusal of ba_hip_refine_poses.
+  bool RefinePoses(const std::vector<uint32_t>& ids, const PoseRefinementOptions& o, std::vector<PoseRefinementResult>* out) {
+    if (kCalibDim > 0) { std::cerr << "ba::BundleAdjuster::RefinePoses: not offered with calibration unknowns" << std::endl; return false; }
+    if (nranks_ > 1 || comm_set_ || allreduce_ || collectives_) {
+      std::cerr << "ba::BundleAdjuster::RefinePoses: not offered on sharded engines" << std::endl;
+      return false;
+    }
+    if (LmSize == 0) { std::cerr << "ba::BundleAdjuster::RefinePoses: LmSize 0 has no landmarks to resect against" << std::endl; return false; }
+    if (!SyncEngine()) return false;
+    ba_hip_pose_refinement_options t;
+    std::memset(&t, 0, sizeof(t));
+    t.max_iterations = o.max_iterations; t.write_back = o.write_back ? 1 : 0; t.fixed_mask = o.fixed_mask;
+    t.initial_damping = o.initial_damping; t.gradient_tolerance = o.gradient_tolerance; t.step_tolerance = o.step_tolerance;
+    t.huber_width = o.huber_width;
+    const uint32_t n = ids.empty() ? uploaded_poses_ : (uint32_t)ids.size();
+    std::vector<double> res(8 * (size_t)n), t7(7 * (size_t)n), info(36 * (size_t)n);
+    if (!Check(ba_hip_refine_poses(engine_, n, ids.empty() ? nullptr : ids.data(), &t, res.data(), t7.data(), info.data()),
+               "ba_hip_refine_poses"))
+      return false;
+    if (o.write_back) {
+      host_state_stale_ = true;   // poses_ take the written poses at the next read (EnsureHostState)
+      proj_view_dirty_ = true;
+    }
+    if (out) {
+      out->assign(n, PoseRefinementResult());
+      for (uint32_t i = 0; i < n; ++i) {
+        const double* r = &res[8 * (size_t)i];
+        PoseRefinementResult& q = (*out)[i];
+        q.status = (int)r[0]; q.observations = (uint32_t)r[1]; q.iterations = (uint32_t)r[2];
+        q.cost_start = r[3]; q.cost_end = r[4]; q.min_depth = r[5]; q.gradient = r[6]; q.excluded = (uint32_t)r[7];
+        std::copy(&t7[7 * (size_t)i], &t7[7 * (size_t)i] + 7, q.t_wp);
+        std::copy(&info[36 * (size_t)i], &info[36 * (size_t)i] + 36, q.information);
       }
     }
     return true;

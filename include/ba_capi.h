@@ -197,6 +197,12 @@ uint32_t ba_adjuster_add_dense_prior(ba_adjuster* a, uint32_t k, const uint32_t*
  * Returns 0, or 1 when refused. */
 int ba_adjuster_triangulate_landmarks(ba_adjuster* a, uint32_t n, const uint32_t* landmark_ids,
                                       const ba_hip_triangulation_options* o, double* result8);
+/* ba::BundleAdjuster::RefinePoses (extension; include/ba_hip.h): refines n poses (ids NULL: every
+ * pose, n ignored) with the landmarks held fixed, before or between solves; o NULL = the defaults.  result8, t_wp7,
+ * info36: 8, 7 and 36 doubles per requested pose as ba_hip_refine_poses fills them (each may be NULL).
+ * Returns 0, or 1 when refused. */
+int ba_adjuster_refine_poses(ba_adjuster* a, uint32_t n, const uint32_t* pose_ids, const ba_hip_pose_refinement_options* o,
+                             double* result8, double* t_wp7, double* info36);
 /* ba::BundleAdjuster::GetPcgStats: 1 and *out filled when the last reduced solve ran PCG, 0 otherwise */
 int ba_adjuster_get_pcg_stats(const ba_adjuster* a, ba_hip_pcg_stats* out);
 /* ba::BundleAdjuster::GetPcgCoarseStats: 1 and *out filled when the last reduced solve used the coarse space */

@@ -1033,6 +1033,60 @@ int ba_hip_triangulate_landmarks(ba_hip_engine* e, uint32_t n, const uint32_t* l
                                  double* result8, double* x_w4);
 int ba_hip_get_triangulation_stats(ba_hip_engine* e, ba_hip_triangulation_stats* out);
 
+/* ---- Pose refinement (resection), landmarks held fixed (ba_amd/csrc/resect.h) -----------------------
+ * The mirror image of ba_hip_triangulate_landmarks: with the landmarks fixed every pose is a 6-parameter least-squares
+ * problem of its own over EVERY projection residual it measures, E_p = sum w |z - pi(T_sw X)|^2 with X the landmark's
+ * world point.  One launch (k_resect.hip, one workgroup per requested pose) refines each requested pose by
+ * Levenberg-Marquardt to convergence, with the cameras of the rig (pinhole and FOV), the per-pose intrinsics when set
+ * and the original weights of the observations.  Unary, binary and inertial residuals and dense priors of the pose are
+ * NOT part of the cost; the active flags of poses and landmarks are not consulted: the id list decides.  With LmSize 1
+ * an observation taken from the landmark's own reference pose counts like any other.  An observation at depth <= 0 (or
+ * with a non-finite point) at the starting pose is excluded for the whole call and counted.
+ * Uses: a new frame of a window gets its pose from the map (motion-only BA); with write_back = 0 an audit of a
+ * trajectory pose by pose (cost, cheirality, and in info36 how well the map determines each pose) that changes nothing.
+ * Placement: after ba_hip_finalize, outside a Solve.  Refused with LmSize 0, with calibration unknowns, on a sharded or
+ * hooked engine and between ba_hip_begin_solve and ba_hip_end_solve.
+ * With write_back the accepted poses replace parameters 0..6 (t, q) of the poses held; velocities, biases and every
+ * other pose keep their bits; x_s is re-derived (LmSize 1; the world points stay) and the call then counts as a
+ * ba_hip_begin_solve for everything the device holds.  With write_back = 0 nothing the engine holds changes.  Two
+ * identical calls return identical bits.  The work space (with the per-pose observation list, built by the first call
+ * after a ba_hip_finalize) is allocated by the first call and freed by ba_hip_release_marginals. */
+enum {
+  BA_HIP_RESECT_OK = 0,                    /* converged; written back */
+  BA_HIP_RESECT_NOT_CONVERGED = 1,         /* iteration limit reached; written back if the cost fell */
+  BA_HIP_RESECT_TOO_FEW_OBSERVATIONS = 2,  /* 2 x used observations < free parameters; not written */
+  BA_HIP_RESECT_FAILED = 3                 /* non-finite starting pose or cost; not written */
+};
+typedef struct {
+  int32_t max_iterations;    /* refinement steps per pose, 0..64; default 20 */
+  int32_t write_back;        /* 1 (default): accepted poses replace the poses held; 0: results only */
+  uint32_t fixed_mask;       /* bit i (0..5): parameter i (t xyz, rotation xyz) stays; default 0; 63 is refused */
+  int32_t reserved;
+  double initial_damping;    /* initial per-pose lambda, default 1e-3 */
+  double gradient_tolerance; /* default 1e-6: converged when max_i |g_i| / sqrt(H_ii E) falls to it */
+                             /* (always: converged when E <= F = sum w (8 eps)^2 |z|^2, the rounding floor of the cost) */
+  double step_tolerance;     /* default 1e-12: an accepted |dt| <= tol (|t| + tol) and |dw| <= tol; 0 = off */
+  double huber_width;        /* pixels, 0 (default) = plain weighted least squares */
+} ba_hip_pose_refinement_options;
+typedef struct {
+  uint32_t count[4];         /* poses of the last call per status BA_HIP_RESECT_* */
+  uint32_t poses;            /* poses requested */
+  uint32_t written;          /* poses whose parameters were replaced */
+  uint64_t observations_used, observations_excluded;
+  double device_ms;          /* event-timed: request upload to the last kernel */
+} ba_hip_pose_refinement_stats;
+/* pose_ids: n pose ids, each once; NULL: every pose, n must be the pose count.  o: NULL = the defaults above.
+ * result8 (n x 8, may be NULL), per requested pose: status, observations used, iterations, cost at the starting pose,
+ * cost at the end, smallest depth of a used observation at the end, gradient measure c at the end, observations excluded.
+ * t_wp7 (n x 7, may be NULL): t, q (xyzw) of the pose the call arrived at where it accepts it (whether or not write_back
+ * stores it), the pose held elsewhere.
+ * info36 (n x 36, may be NULL): the undamped H = sum w Jm^T Jm at the end point, full symmetric, row-major, in the
+ * engine's parameter order, fixed rows and columns zero (all zero where the refinement did not run).  Scaled by the
+ * pixel variance it is the inverse of the localisation covariance. */
+int ba_hip_refine_poses(ba_hip_engine* e, uint32_t n, const uint32_t* pose_ids, const ba_hip_pose_refinement_options* o,
+                        double* result8, double* t_wp7, double* info36);
+int ba_hip_get_pose_refinement_stats(ba_hip_engine* e, ba_hip_pose_refinement_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
